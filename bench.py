@@ -17,9 +17,15 @@ other than the scalar loss all-reduce.
 GPU; RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT in the children's environment, RCCL rendezvous on
 127.0.0.1).  Started under `python -m torch.distributed.run` (RANK and WORLD_SIZE already set) it is one rank of that job.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel timed live with HIP events
-around each of its launches in an instrumented pass of the same step) and `cpu_baseline` (the CPU oracle timed on this
-box's host cores on a bounded sample).
+Prints ONE JSON line on rank 0.  A plain run does only what that line's headline figure needs:
+set-up, warm-up, the `--steps` timed steps, the outputs (`--dump-outputs DIR`), the line.  `--full` appends everything else
+after the timed region: `roofline` (dominant kernel timed live with HIP events around each of its launches in an instrumented
+pass of the same step), the exact-fp32 leg, the range-check count, `cpu_baseline` (the CPU oracle timed on this box's host
+cores on a bounded sample), the `secondary` workloads and, with N ranks, the multi-rank diagnostics.
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (forward: z, nll; inverse: the samples x;
+train: loss, grad_norm) as DIR/<name>.npy, float32, rank 0's arrays; a fixed, seeded sample where they would exceed 64 MB.
+Inputs, weights and random streams are seeded, so two runs with the same arguments see the same inputs.
 """
 import argparse
 import json
@@ -268,21 +274,27 @@ def setup_workload(G, util, parallel, device, cfg_name, mode, B, rank, world, re
     else:
         torch.set_grad_enabled(False)   # forward+logdet metric: inference path (no activation tape)
 
+    last = wl["last"] = {}      # what the latest step returned to its caller (--dump-outputs)
+
     def step():
         if mode == "checked":   # the DROP-IN call: glow(x) in eval under no_grad, range check on (what infer.py / Trainer validation run)
             z, nll, _ = glow(x)
+            last["z"], last["nll"] = z, nll
             return nll.sum()
         if mode == "train":     # secondary metric: the reference's training step (trainer.py:123-150)
-            loss, _ = loop.step(x)
+            loss, grad_norm = loop.step(x)
+            last["loss"], last["grad_norm"] = loss, grad_norm
             return loss * (world * B)
         if mode == "inverse":   # secondary metric: sampling (eps drawn on device, W^-1 from the in-kernel LU)
             plan.ensure_packed(repack, use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
             xs = glow.reverse_flow(z_top, None, eps_std=0.7)
+            last["x"] = xs
             return xs.sum()
         if wl["graph"] is not None:   # the whole forward (noise draw + pack + launch list) as ONE hipGraph launch
             z, nll = wl["graph"]()
         else:
             z, nll, _ = glow.normal_flow(x, None, repack=repack)
+        last["z"], last["nll"] = z, nll
         return parallel.reduce_loss(nll, world)
     wl["step"] = step
     wl["graph"], wl["launch"] = None, "eager (one C call per forward issuing the kernel list)"
@@ -374,6 +386,29 @@ def secondary_workloads(G, util, parallel, device, steps=3, warmup=3):
     return out
 
 
+DUMP_BUDGET_BYTES = (64 << 20) - (1 << 16)      # 64 MB in all, .npy headers included
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """Write {name: tensor} as outdir/<name>.npy in float32.  When the arrays together would exceed `budget`, each is replaced by
+    a fixed, seeded sample of its flattened elements (sorted indices, the same in every run with the same shapes).  Returns
+    {name: full shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    host = {k: torch.as_tensor(v).detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    share = (budget - 4 * len(host)) / total        # (room for the one element every array keeps at least)
+    shapes = {}
+    for name, a in sorted(host.items()):
+        shapes[name] = list(a.shape)
+        if total > budget:
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=max(1, int(a.size * share)), replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(outdir, name + ".npy"), np.asarray(a, dtype=np.float32))
+    return shapes
+
+
 # ------------------------------------------------------------------------------------------------ rank launcher
 def free_port():
     s = socket.socket()
@@ -442,7 +477,7 @@ def dry_run_cpu(args, rank, world):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     multi = None
-    if world > 1:      # the diagnostics the real N-rank line carries (same helpers, same collective order; tiny buffer, gloo)
+    if world > 1 and args.full:      # the diagnostics the real N-rank line carries (same helpers, same collective order; tiny buffer, gloo)
         from pytorch_glow_amd import parallel
         per_rank = parallel.gather_scalars(1e3 * dt / max(args.steps, 1) + rank, "cpu")
         multi = {"world": dist.get_world_size(), "backend": dist.get_backend(), "per_rank_device_ms_per_step": per_rank,
@@ -498,13 +533,18 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="B", help="BASELINE.json workload: B = configs[1] (headline), "
                     "D = configs[3] (128x128 L=4 K=48), E = configs[4] (256x256 L=6 K=32)")
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default: the config's: 64 / 32 / 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check everything beyond the "
+                    "headline figure: roofline and kernel breakdown, exact-fp32 leg, range-check count, CPU baseline, secondary "
+                    "workloads, multi-rank diagnostics (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned (rank 0) as "
+                    "DIR/<name>.npy, float32, 64 MB at most")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-graph", action="store_true", help="forward mode: issue the kernel list eagerly every step instead of "
                     "replaying the captured hipGraph")
-    ap.add_argument("--no-exact-leg", action="store_true", help="skip the same step on the exact-fp32 MFMA kernels that the headline "
-                    "run times for the record (profiling runs: keeps the kernel table to the product path)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` workloads (configs D / E, sampling, training "
-                    "step) that the default one-GPU headline run appends to its JSON line")
+    ap.add_argument("--no-exact-leg", action="store_true", help="--full: skip the same step on the exact-fp32 MFMA kernels that the "
+                    "headline run times for the record (profiling runs: keeps the kernel table to the product path)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the `secondary` workloads (configs D / E, sampling, "
+                    "training step) that the one-GPU headline run appends to its JSON line")
     ap.add_argument("--no-repack", action="store_true", help="inference mode: keep derived parameter data across steps")
     ap.add_argument("--repack", action="store_true", help="inverse mode: re-derive the parameter data (W^-1, weight images) every step "
                     "as well (default there: once -- sampling from a trained model)")
@@ -596,8 +636,11 @@ def main():
         dt = float(t.item())
     total_images = world * B * args.steps
     value = total_images / dt
+    dumped = None
+    if args.dump_outputs and rank == 0:     # the last timed step's results, before anything below runs the model again
+        dumped = dump_outputs(args.dump_outputs, wl["last"])
     multi = None
-    if world > 1 or forced:
+    if args.full and (world > 1 or forced):
         multi = multi_rank_diagnostics(torch, dist, parallel, device, args, wl, marks, world, rank, forced)
     if "loop" in wl:      # how the timed training steps were launched
         lp = wl["loop"]
@@ -639,6 +682,8 @@ def main():
             "frac_of_fp32_mfma_peak_whole_model": round(value / world * fpi / (PEAK_FP32_MFMA_TFLOPS * 1e12), 4),
             "frac_of_split_f16_peak_whole_model": round(value / world * fpi / (PEAK_SPLIT_TFLOPS * 1e12), 4),
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if multi is not None:
             out["multi_rank"] = multi
         if forced:
@@ -646,6 +691,7 @@ def main():
         if args.mode == "train":
             out.pop("model_tflops"), out.pop("frac_of_fp32_mfma_peak_whole_model"), out.pop("frac_of_split_f16_peak_whole_model")
             out["model_tflops_fwd_bwd"] = round(value * 3 * fpi / 1e12, 2)   # backward ~ 2x forward flops
+        if args.mode == "train" or not args.full:
             print(json.dumps(out), flush=True)
             if world > 1 or forced:
                 dist.barrier()

@@ -248,7 +248,7 @@ def test_bench_line_carries_the_contract_fields_and_the_secondary_workloads():
     """One short default-shaped run: the ONE JSON line has the contract's fields, `roofline` (k_cnet, live HIP events), and the
     `secondary` dict -- configs D / E forward, E sampling and the config-B training step measured in the same process after the
     headline's timed region -- each finite, each on the product kernel family."""
-    d = _run_bench(["--steps", "5", "--warmup", "3", "--no-cpu-baseline"])
+    d = _run_bench(["--steps", "5", "--warmup", "3", "--full", "--no-cpu-baseline"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -273,6 +273,29 @@ def test_bench_line_carries_the_contract_fields_and_the_secondary_workloads():
     assert d["roofline"]["launches"] == 96 and set(d["roofline"]["per_level"]) == {"C12_32x32", "C24_16x16", "C48_8x8"}
 
 
+def test_plain_bench_run_times_only_the_headline_and_dumps_the_same_outputs_every_run(tmp_path):
+    """Without --full the line carries the headline and nothing measured beyond it; --dump-outputs writes what the last timed
+    step returned (z, nll of the graphed forward) as float32 .npy, and a second run with the same arguments writes the same."""
+    runs = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        d = _run_bench(["--steps", "4", "--warmup", "2", "--dump-outputs", str(out)])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 4 and d["value"] > 0 and d["ms_per_step"] > 0
+        for k in ("roofline", "secondary", "cpu_baseline", "breakdown_ms_per_step", "exact_fp32_mfma_kernels", "range_fallbacks"):
+            assert k not in d, k
+        assert d["dumped_outputs"] == {"nll": [64], "z": [64, 48, 8, 8]}, d["dumped_outputs"]
+        arrays = {n: np.load(out / f"{n}.npy") for n in ("z", "nll")}
+        for n, a in arrays.items():
+            assert a.dtype == np.float32 and list(a.shape) == d["dumped_outputs"][n] and np.isfinite(a).all(), n
+        # the line's loss is the sum of the dumped nll over the batch
+        assert abs(float(arrays["nll"].mean()) - d["config"]["loss_mean_nll_bits_per_dim"]) < 1e-4
+        runs.append(arrays)
+    for n in ("z", "nll"):
+        np.testing.assert_allclose(runs[0][n], runs[1][n], rtol=1e-5, atol=1e-5, err_msg=n)
+
+
 def test_bench_multi_rank_diagnostics_over_a_one_rank_rccl_group():
     """VERDICT r5 #7 on a one-GPU box: GLOWHIP_BENCH_FORCE_DIST=1 makes `bench.py --gpus 1` join a ONE-rank RCCL group and run the
     N-rank line's exchange code over it -- per-rank step times gathered, the 176 MB flat gradient all-reduce timed on its own, and in
@@ -284,7 +307,7 @@ def test_bench_multi_rank_diagnostics_over_a_one_rank_rccl_group():
     env = dict(os.environ, GLOWHIP_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     for mode in ("train", "forward"):
         proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "4", "--mode", mode,
-                               "--no-cpu-baseline", "--no-secondary", "--no-exact-leg"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
+                               "--full", "--no-cpu-baseline", "--no-secondary", "--no-exact-leg"], capture_output=True, text=True, timeout=900, cwd=root, env=env)
         assert proc.returncode == 0, proc.stdout[-2000:] + proc.stderr[-4000:]
         d = json.loads([l for l in proc.stdout.splitlines() if l.startswith("{")][0])
         assert d["forced_one_rank_group"] and "diagnostic run" in d["metric"] and d["rccl_world_size"] == 1

@@ -350,3 +350,25 @@ def test_bucket_overlap_report_arithmetic():
     assert r["allreduce_ms_per_step"] == pytest.approx((8.5 + 7.5) / 2) and r["exposed_ms_per_step"] == pytest.approx(1.0)
     assert r["hidden_fraction"] == pytest.approx(1.0 - 1.0 / 8.0)
     assert parallel.bucket_overlap_report([]) is None and parallel.bucket_overlap_report([{"sweep_done": Ev(0), "spans": []}]) is None
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_a_large_output_the_same_way_every_time(tmp_path):
+    """`bench.py --dump-outputs`: every array as <name>.npy in float32; over the size budget each is cut to a fixed, seeded sample
+    of its flattened elements (the same one in every run), within the budget in all."""
+    import bench
+    arrays = {"z": torch.arange(4 * 3 * 5 * 5, dtype=torch.float32).reshape(4, 3, 5, 5), "nll": torch.tensor([1.5, 2.5], dtype=torch.float64),
+              "loss": torch.tensor(3.25)}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), arrays)
+    assert shapes == {"z": [4, 3, 5, 5], "nll": [2], "loss": []}
+    for name, t in arrays.items():
+        a = np.load(tmp_path / "all" / f"{name}.npy")
+        assert a.dtype == np.float32 and np.array_equal(a, t.float().numpy())
+    budget = 40 * 4                                                    # 40 of the 303 elements
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+    z = np.load(tmp_path / "a" / "z.npy")
+    assert z.ndim == 1 and 0 < z.size < 300 and np.all(np.diff(z) > 0)   # sorted distinct elements of arange
+    total = sum(np.load(tmp_path / "a" / f"{n}.npy").nbytes for n in arrays)
+    assert total <= budget
+    for name in arrays:
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy"))

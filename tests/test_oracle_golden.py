@@ -66,10 +66,16 @@ def test_g2_actnorm_batch_variance(golden):
 @pytest.mark.parametrize("c", [12, 24, 48, 96])
 def test_g3_invconv(golden, c):
     g = sub(golden("g3_invconv"), f"c{c}_")
+    # log|det W| and W^-1 are fp32 LAPACK results (torch.det, .inverse()) in the reference and in the oracle alike, and their
+    # rounding depends on the host CPU's code path.  At C = 96 the perturbed W is badly enough conditioned that MKL's AVX-512,
+    # AVX2 and generic kernels (or another vendor's CPU) differ by up to 6e-4 in the log-det and 7e-3 in |W^-1 x| ~ 2e2, so there
+    # the golden values hold only to the bounds the GPU parity test applies to the same numbers
+    lapack = c == 96
+    det_close = (lambda a, b: close(a, b, atol=1e-4, rtol=1e-5)) if lapack else ld_close
     z, ld = O.invconv(g["x"], g["w"], g["logdet"], reverse=False)
-    close(z, g["fwd_z"]); ld_close(ld, g["fwd_logdet"])
+    close(z, g["fwd_z"]); det_close(ld, g["fwd_logdet"])
     z, ld = O.invconv(g["x"], g["w"], g["logdet"], reverse=True)
-    close(z, g["rev_z"], atol=1e-5); ld_close(ld, g["rev_logdet"])
+    close(z, g["rev_z"], atol=2e-5 + 5e-5 * g["rev_z"].abs().max().item() if lapack else 1e-5); det_close(ld, g["rev_logdet"])
 
 
 def test_g4_coupling_net(golden):
