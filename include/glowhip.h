@@ -303,6 +303,55 @@ int glowhip_optim_step_dev(const glowhip_optim_chunk* chunks_dev, int n_chunks, 
                            double beta2, float eps, float weight_decay, float clip_value, float max_norm, double* partial_dev,
                            float* grad_norm_out, int skip_if_nonfinite, glowhip_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Top head: learned / class-conditional top prior + classifier (reference network/model.py:345-348, 362-379, 440-445,
+ * 508-538; LinearZeros network/module.py:152-185: out = (x W^T + b) * exp(3 logs)).  All fp32, in both kernel families.
+ *   prior    h[n, :, p] = base[:] + e[n, :];  e = y_emb(y_onehot) (width 2C);  base[c] = learn_top.bias[c] * exp(3 learn_top.logs[c])
+ *            (learn_top is applied to h_top == 0, network/model.py:372-376) or 0;  mean = h[:, :C], logs = h[:, C:]
+ *   logits   classifier(mean_{H,W} z)
+ * With a head attached, glowhip_glow_forward / _u8 / _forward_train add logp(z | mean, logs) with ONE launch (k_top_head_fwd)
+ * that also writes the logits and, with a criterion, the per-sample classification-loss term and
+ * g_logit = weight_y * d classification / d logits; glowhip_glow_backward produces dL/dz with ONE launch (k_top_head_bwd) and
+ * the head's parameter gradients with one small reduction launch.  The prior_mean / prior_logs arguments of those calls are
+ * added to the head's (a dense base; it gets no gradient).
+ * ---------------------------------------------------------------------------------------------- */
+enum { GLOWHIP_CRIT_NONE = 0, GLOWHIP_CRIT_CE = 1 /* Glow.single_class_loss, network/model.py:508-521 */,
+       GLOWHIP_CRIT_BCE = 2 /* Glow.multi_class_loss, network/model.py:523-538 */ };
+/* Device pointers to the live parameters (NULL = that part is absent): learn_top.{bias,logs} (2C), y_emb.{weight (2C,K), bias,
+ * logs (2C)}, classifier.{weight (K,C), bias, logs (K)} -- the classifier only when weight_y > 0 (network/model.py:441). */
+typedef struct glowhip_head_desc {
+    int32_t K;             /* hps.dataset.num_classes */
+    int32_t criterion;     /* GLOWHIP_CRIT_*: NONE = logits only (the caller's own loss hands g_logit to the backward) */
+    float weight_y;        /* loss = generative + weight_y * classification, network/trainer.py:125-131 */
+    int32_t reserved;
+    const float* lt_bias; const float* lt_logs;
+    const float* ye_w; const float* ye_b; const float* ye_logs;
+    const float* cl_w; const float* cl_b; const float* cl_logs;
+} glowhip_head_desc;
+/* What changes per batch (device pointers).  state: glowhip_plan_head_state_bytes(plan, N) bytes written by the forward and read
+ * by the matching backward.  y_onehot (N,K) fp32; y (N) int64 targets (CE); y_logits (N,K) out; cls_loss (N) out: the per-sample
+ * term whose mean is the classification loss; g_logit (N,K): written by a forward with a criterion, otherwise the caller's
+ * d loss / d logits for the backward (NULL = 0). */
+typedef struct glowhip_head_io {
+    const float* y_onehot; const int64_t* y;
+    float* y_logits; float* cls_loss; float* g_logit; float* state;
+} glowhip_head_io;
+/* Writable gradients of the head's parameters (NULL = not wanted), next to glowhip_layer_grads. */
+typedef struct glowhip_head_grads {
+    float* lt_bias; float* lt_logs; float* ye_w; float* ye_b; float* ye_logs; float* cl_w; float* cl_b; float* cl_logs;
+} glowhip_head_grads;
+/* Attach (head != NULL; copied) or detach a head; clears the bindings below.  HOST bookkeeping, the caller serialises it with
+ * the plan's own calls, as glowhip_plan_set_family. */
+int glowhip_plan_set_head(glowhip_plan* plan, const glowhip_head_desc* head);
+size_t glowhip_plan_head_state_bytes(const glowhip_plan* plan, int N);
+/* Per-call bindings (copied; HOST bookkeeping): the io of the next forward / backward, the gradients of the next backward. */
+int glowhip_plan_bind_head(glowhip_plan* plan, const glowhip_head_io* io);
+int glowhip_plan_bind_head_grads(glowhip_plan* plan, const glowhip_head_grads* grads);
+/* Glow.prior(y_onehot), network/model.py:362-379, as dense tensors: mean, logs (N,C,HW) -- for callers that need them as
+ * tensors (the top sample of Glow.reverse_flow, network/model.py:466-468). */
+int glowhip_top_prior(const glowhip_head_desc* head, const float* y_onehot, int N, int C, int HW, float* mean, float* logs,
+                      glowhip_stream_t stream);
+
 /* Per-launch timing for benchmarks (HIP events recorded on the execution stream around every kernel of
  * the coupling path).  enable=1 creates an event pool (host resource), enable=0 destroys it; while enabled
  * every encode/decode appends records.  glowhip_plan_timing_read synchronises with the recorded events,

@@ -48,6 +48,25 @@ class LayerGrads(ctypes.Structure):
                                         "f2_w", "f2_an_bias", "f2_an_logs", "f4_w", "f4_bias", "f4_logs")]
 
 
+CRIT_NONE, CRIT_CE, CRIT_BCE = 0, 1, 2
+HEAD_PARAMS = ("lt_bias", "lt_logs", "ye_w", "ye_b", "ye_logs", "cl_w", "cl_b", "cl_logs")
+
+
+class HeadDesc(ctypes.Structure):
+    """Mirror of ``glowhip_head_desc``."""
+    _fields_ = [("K", c_int32), ("criterion", c_int32), ("weight_y", c_float), ("reserved", c_int32)] + [(n, c_void_p) for n in HEAD_PARAMS]
+
+
+class HeadIO(ctypes.Structure):
+    """Mirror of ``glowhip_head_io``."""
+    _fields_ = [(n, c_void_p) for n in ("y_onehot", "y", "y_logits", "cls_loss", "g_logit", "state")]
+
+
+class HeadGrads(ctypes.Structure):
+    """Mirror of ``glowhip_head_grads``."""
+    _fields_ = [(n, c_void_p) for n in HEAD_PARAMS]
+
+
 class OptimChunk(ctypes.Structure):
     """Mirror of ``glowhip_optim_chunk``."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int32), ("pad", c_int32)]
@@ -108,6 +127,11 @@ SIGNATURES = {
     "glowhip_plan_backward_marks": (c_int, [_P, POINTER(c_int32), POINTER(c_void_p), c_int]),
     "glowhip_optim_step": (c_int, [_P, c_int, c_int, c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_step_dev": (c_int, [_P, c_int, c_int, _P, ctypes.c_double, ctypes.c_double, c_float, c_float, c_float, c_float, _P, _P, c_int, _P]),
+    "glowhip_plan_set_head": (c_int, [_P, POINTER(HeadDesc)]),
+    "glowhip_plan_head_state_bytes": (c_size_t, [_P, c_int]),
+    "glowhip_plan_bind_head": (c_int, [_P, POINTER(HeadIO)]),
+    "glowhip_plan_bind_head_grads": (c_int, [_P, POINTER(HeadGrads)]),
+    "glowhip_top_prior": (c_int, [POINTER(HeadDesc), _P, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_plan_timing_enable": (c_int, [_P, c_int]),
     "glowhip_plan_timing_read": (c_int, [_P, POINTER(TimingRecord), c_int, POINTER(c_int)]),
 }

@@ -110,6 +110,52 @@ class FlowPlan:
             except Exception:
                 pass
 
+    # ------------------------------------------------------------------ top head (csrc/tophead.hip)
+    def set_head(self, parts, K=0, criterion=_lib.CRIT_NONE, weight_y=0.0) -> None:
+        """Attach the top head (glowhip_plan_set_head): ``parts`` maps the names of `_lib.HEAD_PARAMS` to the live parameters
+        (learn_top.{bias,logs}, y_emb.{weight,bias,logs}, classifier.{weight,bias,logs}); an empty mapping detaches it.  Cheap when
+        nothing changed: the C call is made only for a new parameter address, criterion or weight."""
+        key = (tuple((n, t.data_ptr()) for n, t in parts.items()), int(K), int(criterion), float(weight_y))
+        if key == getattr(self, "_head_key", ((), 0, 0, 0.0)):
+            return
+        names = tuple(parts)
+        if names != tuple(n for n, _ in getattr(self, "_head_parts", ())):
+            # another set of parameters gets gradients: the cached field list, bucket layout and persistent buckets go
+            self._fields = self._bucket_lay = self._pgrad = self._pgrad_bound = None
+        if not parts:
+            check(lib().glowhip_plan_set_head(self._h, None))
+        else:
+            d = _lib.HeadDesc()
+            d.K, d.criterion, d.weight_y = int(K), int(criterion), float(weight_y)
+            for n, t in parts.items():
+                if t.device != self.device or not t.is_contiguous() or t.dtype != torch.float32:
+                    raise _lib.GlowHipError(f"top head parameter {n}: needs contiguous fp32 on {self.device}")
+                setattr(d, n, t.data_ptr())
+            check(lib().glowhip_plan_set_head(self._h, ctypes.byref(d)))
+        self._head_parts = tuple(parts.items())
+        self._head_key = key
+
+    @property
+    def has_head(self) -> bool:
+        return bool(getattr(self, "_head_parts", ()))
+
+    def head_call(self, n, y_onehot=None, y=None):
+        """Per-batch tensors of the head for ONE forward (+ its backward): `HeadCall`."""
+        return HeadCall(self, n, y_onehot, y)
+
+    def _bind_head(self, head, g_logit=None):
+        if not self.has_head:
+            if head is not None:
+                raise _lib.GlowHipError("a head call was given but the plan has no head attached")
+            return
+        if head is None:
+            raise _lib.GlowHipError("the plan has a top head attached: pass head=plan.head_call(...)")
+        io = _lib.HeadIO()
+        io.y_onehot, io.y, io.state = _p(head.y_onehot), _p(head.y), _p(head.state)
+        io.y_logits, io.cls_loss = _p(head.y_logits), _p(head.cls_loss)
+        io.g_logit = _p(head.g_logit if g_logit is None else g_logit)
+        check(lib().glowhip_plan_bind_head(self._h, ctypes.byref(io)))
+
     # ------------------------------------------------------------------ execution
     def _workspace(self, n: int) -> torch.Tensor:
         need = int(lib().glowhip_plan_workspace_bytes(self._h, n))
@@ -247,9 +293,11 @@ class FlowPlan:
                                         n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         return x, ld_out
 
-    def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None):
+    def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None, head=None):
         n = x.shape[0]
         self.ensure_packed(repack)
+        if n:
+            self._bind_head(head)
         if out is None:
             z = torch.empty((n,) + self.out_chw, dtype=torch.float32, device=self.device)
             nll = torch.empty(n, dtype=torch.float32, device=self.device)
@@ -290,6 +338,8 @@ class FlowPlan:
             elif kind == _lib.LAYER_SPLIT2D:
                 cz = layer.conv2d_zeros
                 out += [(i, "f4_w", cz.weight), (i, "f4_bias", cz.bias), (i, "f4_logs", cz.logs)]
+        # the top head's parameters (layer index -1: they go to the glowhip_head_grads struct and the small bucket)
+        out += [(-1, name, p) for name, p in getattr(self, "_head_parts", ())]
         self._fields = out
         self._trainable = [p for _, _, p in out]
         return out
@@ -298,7 +348,7 @@ class FlowPlan:
         self._grad_fields()
         return self._trainable
 
-    def glow_forward_train(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, force_pack=False):
+    def glow_forward_train(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, force_pack=False, head=None):
         """Forward that records the activation tape; returns (z, nll, tape).  ``force_pack``: re-derive the weight images whatever the
         version counters say (a captured training step: every replay follows an update the counters of capture time know nothing of)."""
         n = x.shape[0]
@@ -307,6 +357,7 @@ class FlowPlan:
         nll = torch.empty(n, dtype=torch.float32, device=self.device)
         tape = torch.empty(int(lib().glowhip_plan_tape_bytes(self._h, n)), dtype=torch.uint8, device=self.device)
         ws = self._train_workspace(n)
+        self._bind_head(head)
         check(lib().glowhip_glow_forward_train(self._h, ptr(self.packed), ptr(x), ptr(noise), ptr(prior_mean),
                                                ptr(prior_logs), prior_stride, n_bits, ptr(z), ptr(nll), None, n, ptr(tape),
                                                tape.numel(), ptr(ws), ws.numel(), stream_ptr(self.device)))
@@ -321,12 +372,15 @@ class FlowPlan:
             self._tws = ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ws
 
-    def glow_backward(self, x, tape, nll_grad, z_grad, prior_mean, prior_logs, prior_stride, want_grad_x=False, persistent=False):
+    def glow_backward(self, x, tape, nll_grad, z_grad, prior_mean, prior_logs, prior_stride, want_grad_x=False, persistent=False,
+                      head=None, g_logit=None):
         """Parameter gradients (list aligned with trainable_parameters()) and optionally dL/dx.
         ``persistent``: the flat gradient buckets, the views into them, the pointer table handed to the C sweep and the
         gradient-ready events are created ONCE per plan and reused by every call (the sweep writes every gradient in full) -- the
         per-step host cost of ~1 000 tensor views and ~1 000 ctypes assignments disappears; the caller must have consumed the
-        previous call's gradients (training.TrainLoop: the optimiser step of step N is enqueued before the sweep of step N + 1)."""
+        previous call's gradients (training.TrainLoop: the optimiser step of step N is enqueued before the sweep of step N + 1).
+        ``head``: the `HeadCall` of the matching forward; ``g_logit``: d loss / d y_logits from the caller's own loss (autograd route;
+        None = what the forward's criterion wrote, or zero without one)."""
         n = x.shape[0]
         if (self._version_signature() != getattr(self, "_tape_version", None) or self._packed_version != self._tape_version
                 or not (getattr(self, "_packed_use", 0) & self.PACK_TRAINING)):
@@ -342,17 +396,18 @@ class FlowPlan:
             flats = [torch.empty(nel, dtype=torch.float32, device=self.device) for nel in layout["sizes"]]
             grads = [flats[b][off:off + p.numel()].view_as(p) for (_, _, p), (b, off) in zip(fields, layout["slots"])]
             arr = (_lib.LayerGrads * len(self.layers))()
+            hg = _lib.HeadGrads()
             for (i, name, _), gt in zip(fields, grads):
-                setattr(arr[i], name, gt.data_ptr())
+                setattr(hg if i < 0 else arr[i], name, gt.data_ptr())
             events = [torch.cuda.Event() for _ in layout["marks"]]
             for ev in events:
                 ev.record()                  # (creates the handle; the C sweep records it again where it belongs)
             marks = (ctypes.c_int32 * max(len(events), 1))(*layout["marks"])
             handles = (ctypes.c_void_p * max(len(events), 1))(*[ev.cuda_event for ev in events])
             if persistent:
-                self._pgrad = (flats, grads, arr, events, marks, handles)
+                self._pgrad = (flats, grads, arr, events, marks, handles, hg)
         else:
-            flats, grads, arr, events, marks, handles = cached
+            flats, grads, arr, events, marks, handles, hg = cached
         if not persistent:
             # the sweep rewrites the plan's host-side gradient job tables with THIS call's temporary buffers, and the copy nodes of a
             # captured training step read those tables at replay time: training.GraphedTrainStep sees this epoch move and captures
@@ -360,6 +415,9 @@ class FlowPlan:
             self._grad_table_epoch = getattr(self, "_grad_table_epoch", 0) + 1
         gx = torch.empty_like(x) if want_grad_x else None
         ws = self._train_workspace(n)
+        self._bind_head(head, g_logit)
+        if self.has_head:
+            check(lib().glowhip_plan_bind_head_grads(self._h, ctypes.byref(hg)))
         check(lib().glowhip_plan_backward_marks(self._h, marks, handles, len(events)))
         try:
             check(lib().glowhip_glow_backward(self._h, ptr(self.packed), ptr(x), ptr(tape), tape.numel(), ptr(nll_grad),
@@ -404,6 +462,39 @@ class FlowPlan:
                                               float(actnorm_scale), n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         self._packed_version = self._version_signature()   # the init pass ends with a pack of the inference kernels' data
         self._packed_use = self.PACK_INFERENCE
+
+
+def _p(t):
+    return None if t is None else t.data_ptr()
+
+
+class HeadCall:
+    """What the top head reads and writes for one batch (glowhip_head_io): labels in, ``y_logits`` (N, K), ``cls_loss`` (N: the
+    per-sample term whose mean is the classification loss) and ``g_logit`` out, ``state`` kept for the backward."""
+    __slots__ = ("y_onehot", "y", "y_logits", "cls_loss", "g_logit", "state")
+
+    def __init__(self, plan, n, y_onehot=None, y=None):
+        parts = dict(plan._head_parts)
+        _, K, criterion, _ = plan._head_key
+        dev = plan.device
+        if "ye_w" in parts:
+            assert y_onehot is not None, "y_condition: y_onehot is required"      # reference network/model.py:377
+        if y_onehot is not None:
+            y_onehot = _lib.require_device_tensor(y_onehot.float() if y_onehot.dtype != torch.float32 else y_onehot, "y_onehot")
+            assert tuple(y_onehot.shape) == (n, K), f"y_onehot {tuple(y_onehot.shape)}: expected {(n, K)}"
+        if y is not None:
+            y = y.long().contiguous()
+            assert y.is_cuda and tuple(y.shape) == (n,), f"y {tuple(y.shape)} on {y.device}: expected {(n,)} on the GPU"
+        self.y_onehot, self.y = y_onehot, y
+        self.state = torch.empty(int(lib().glowhip_plan_head_state_bytes(plan._h, n)) // 4 or 1, dtype=torch.float32, device=dev)
+        self.y_logits = self.cls_loss = self.g_logit = None
+        if "cl_w" in parts:
+            self.y_logits = torch.empty((n, K), dtype=torch.float32, device=dev)
+            if criterion != _lib.CRIT_NONE:
+                if criterion == _lib.CRIT_CE:
+                    assert y is not None, "single_class criterion: integer targets y are required"
+                self.cls_loss = torch.empty(n, dtype=torch.float32, device=dev)
+                self.g_logit = torch.empty((n, K), dtype=torch.float32, device=dev)
 
 
 class PlanCache:

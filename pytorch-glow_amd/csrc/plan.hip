@@ -1143,9 +1143,7 @@ int glowhip_glow_forward(glowhip_plan* plan, const void* packed, const float* x,
     RngSpec rng{plan->rng_on && !noise, plan->rng_seed, plan->rng_calls, (float)(1.0 / pow(2.0, n_bits))};
     if (rng.on) ++plan->rng_calls;
     GH_TRY(run_forward(plan, packed, x, noise, z, N, w, s, 0, rng.on ? &rng : nullptr));
-    const int* o = plan->out_shape;
-    GH_TRY(launch_gaussian_logp(z, (long)o[0] * o[1] * o[2], prior_mean, prior_logs, prior_stride, N, o[0], o[1] * o[2],
-                                w.acc, s));
+    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // the sum of the log|det W| terms enters here
     // objective = -ln(n_bins)*CHW + logdet + logp;  nll = -objective / (ln2 * CHW)   (network/model.py:425-450)
     const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
@@ -1177,9 +1175,7 @@ int glowhip_glow_forward_u8(glowhip_plan* plan, const void* packed, const uint8_
     if (rng.on) ++plan->rng_calls;
     (void)d0;
     GH_TRY(run_forward(plan, packed, w.bufA, noise, z, N, w, s, 0, rng.on ? &rng : nullptr, x_u8, divisor));
-    const int* o = plan->out_shape;
-    GH_TRY(launch_gaussian_logp(z, (long)o[0] * o[1] * o[2], prior_mean, prior_logs, prior_stride, N, o[0], o[1] * o[2],
-                                w.acc, s));
+    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
     const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
     return launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, -log(pow(2.0, n_bits)) * chw, -1.0 / (log(2.0) * chw),

@@ -9,6 +9,7 @@
 #include "conv_mfma.h"
 #include "sh.h"
 #include "backward.h"
+#include "tophead.h"
 
 namespace glowhip {
 
@@ -76,6 +77,8 @@ struct glowhip_plan {
     bool rng_on = false; unsigned long long rng_seed = 0, rng_calls = 0;   // in-kernel dequantisation noise (glowhip_plan_set_dequant_rng)
     std::vector<std::pair<int, hipEvent_t>> bwd_marks;   // (layer index, event): glowhip_plan_backward_marks
     int family = GLOWHIP_FAMILY_AUTO;          // kernel family of the coupling networks (glowhip_plan_set_family): a property of the plan
+    // top head (tophead.hip): learned / class-conditional prior + classifier, its per-call io and gradient bindings
+    bool head_on = false; glowhip_head_desc head{}; glowhip_head_io head_io{}; glowhip_head_grads head_grads{};
     std::map<std::string, long> launch_counts; // run-time record of which kernel families this plan launched (glowhip_plan_launch_counts)
 };
 

@@ -643,9 +643,7 @@ int glowhip_glow_forward_train(glowhip_plan* plan, const void* packed, const flo
     GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // the training kernels read the fp32 images from the first layer on
     GH_TRY(forward_train(plan, packed, x, noise, z, N, (char*)tape, tl, w.acc, w.gsh, s));
-    const int* o = plan->out_shape;
-    GH_TRY(launch_gaussian_logp(z, (long)o[0] * o[1] * o[2], prior_mean, prior_logs, prior_stride, N, o[0], o[1] * o[2],
-                                w.acc, s));
+    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));
     const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
     const double offset = -log(pow(2.0, n_bits)) * chw;
     const double scale = -1.0 / (log(2.0) * chw);
@@ -683,9 +681,9 @@ int glowhip_glow_backward(glowhip_plan* plan, const void* packed, const float* x
     GH_TRY(launch_sum_gld(w.gld, N, w.gsum, s));
     // top: dL/dz = z_grad + gld * d logp/dz
     const int* o = plan->out_shape;
-    const long per = (long)o[0] * o[1] * o[2];
     const float* zt = at<float>(tape, tl.back().out);
-    GH_TRY(launch_prior_bwd(zt, prior_mean, prior_logs, prior_stride, w.gld, z_grad, w.gA, N, per, s));
+    GH_REQUIRE(!plan->head_on || 2L * o[0] <= plan->max_chw, "glow_backward: top head scratch does not fit");
+    GH_TRY(launch_top_bwd(plan, zt, prior_mean, prior_logs, prior_stride, w.gld, z_grad, w.gA, w.gB, N, s));
     return backward_sweep(plan, packed, x, (const char*)tape, tl, grads, grad_x, N, w, w.gA, s);
 }
 

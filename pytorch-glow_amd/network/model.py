@@ -5,7 +5,6 @@ state_dict keys and shapes equal the reference's, so its snapshot
 """
 from __future__ import annotations
 
-import numpy as np
 import torch
 import torch.nn as nn
 
@@ -213,39 +212,30 @@ class FlowModel(nn.Module):
 
 class _GlowTrainFn(torch.autograd.Function):
     """Glow.normal_flow as one autograd node: forward records the HIP activation tape, backward runs the HIP reverse
-    sweep (glowhip_glow_backward) and hands the parameter gradients to autograd."""
+    sweep (glowhip_glow_backward) and hands the parameter gradients to autograd.  With a top head on the plan (learned /
+    class-conditional prior, classifier: csrc/tophead.hip) ``y_logits`` is a third, differentiable output: the caller's own
+    classification loss hands d loss / d y_logits back to the head's backward kernel."""
 
     @staticmethod
-    def forward(ctx, plan, x, noise, n_bits, mean, logs, *params):
-        # mean / logs: the top prior's parameters (N, Cz, H, W) when it is LEARNED (ablation.learn_top, network/model.py:375-376),
-        # differentiable inputs of this node; None for the reference profiles' fixed N(0, 1) prior
-        stride = 0 if mean is None else mean.stride(0)
-        z, nll, tape = plan.glow_forward_train(x, noise, mean, logs, stride, n_bits)
-        ctx.plan, ctx.tape, ctx.x_in = plan, tape, x
+    def forward(ctx, plan, x, noise, n_bits, head, *params):
+        z, nll, tape = plan.glow_forward_train(x, noise, None, None, 0, n_bits, head=head)
+        ctx.plan, ctx.tape, ctx.x_in, ctx.head = plan, tape, x, head
         ctx.want_gx = x.requires_grad
-        ctx.prior = None if mean is None else (mean, logs, z)
+        if head is not None and head.y_logits is not None:
+            return z, nll, head.y_logits
         return z, nll
 
     @staticmethod
-    def backward(ctx, gz, gnll):
+    def backward(ctx, gz, gnll, glogit=None):
         plan = ctx.plan
         n = ctx.x_in.shape[0]
         gnll = torch.zeros(n, device=ctx.x_in.device) if gnll is None else gnll.contiguous().float()
         gz = None if gz is None else gz.contiguous().float()
-        mean, logs, z = ctx.prior if ctx.prior is not None else (None, None, None)
-        grads, gx = plan.glow_backward(ctx.x_in, ctx.tape, gnll, gz, mean, logs, 0 if mean is None else mean.stride(0),
-                                       want_grad_x=ctx.want_gx)
+        glogit = None if glogit is None else glogit.contiguous().float()
+        grads, gx = plan.glow_backward(ctx.x_in, ctx.tape, gnll, gz, None, None, 0, want_grad_x=ctx.want_gx, head=ctx.head,
+                                       g_logit=glogit)
         ctx.tape = None
-        gmean = glogs = None
-        if mean is not None:
-            # nll = -(... + logp(z | mean, logs)) / (ln 2 CHW), logp = sum -0.5 (ln 2 pi + 2 logs + (z - mean)^2 exp(-2 logs))
-            # (GaussianDiag, network/module.py:400-467): the prior's own parameters get their gradient here, in a handful of
-            # elementwise launches on the top latent; d nll / d z -- through the flow -- is the sweep's (it takes mean / logs)
-            coef = (-gnll / (float(np.log(2.0)) * ctx.x_in[0].numel())).view(n, 1, 1, 1)
-            d = (z - mean) * torch.exp(-2.0 * logs)
-            gmean = coef * d
-            glogs = coef * (d * (z - mean) - 1.0)
-        return (None, gx, None, None, gmean, glogs) + tuple(grads)
+        return (None, gx, None, None, None) + tuple(grads)
 
 
 # ---- the dequantisation stream of the inference path (network/model.py:421: z = x + U(0, 1/2^n_bits), drawn inside the leading
@@ -290,8 +280,7 @@ class GraphedForward:
         self.glow, self.repack = glow, repack
         self.n_bits = glow.hps.model.n_bits_x
         self.plan = plan = glow.flow.plan_for(x)
-        mean, logs = glow.prior(None)
-        assert mean is None, "capture_forward: learn_top priors are not captured"
+        assert not glow._attach_head(plan), "capture_forward: a learned / class-conditional top prior is not captured"
         self.x = x.clone()
         self.noise = torch.empty_like(self.x)
         n = x.shape[0]
@@ -359,9 +348,10 @@ class Glow(nn.Module):
         if hps.ablation.learn_top:
             nc = self.flow.output_shapes[-1][1]
             self.learn_top = module.Conv2dZeros(in_channels=2 * nc, out_channels=2 * nc)
-        if hps.ablation.y_condition:
-            raise NotImplementedError("class-conditional Glow (y_condition) is outside the flow hot path "
-                                      "(off in every reference profile)")
+        if hps.ablation.y_condition:       # reference network/model.py:345-348
+            nc = self.flow.output_shapes[-1][1]
+            self.y_emb = module.LinearZeros(hps.dataset.num_classes, nc * 2)
+            self.classifier = module.LinearZeros(nc, hps.dataset.num_classes)
         num_device = len(util.get_devices(self.hps.device.graph, verbose=False))
         assert hps.optim.num_batch_train % num_device == 0
         self.register_parameter('h_top', nn.Parameter(torch.zeros([hps.optim.num_batch_train // num_device,
@@ -373,22 +363,60 @@ class Glow(nn.Module):
     def batch_h_top(self):
         return self.h_top.shape[0]
 
+    CRITERIA = {None: _lib.CRIT_NONE, "single_class": _lib.CRIT_CE, "multi_class": _lib.CRIT_BCE}
+
+    def _head_parts(self):
+        """{glowhip_head_desc field: live parameter} of the top head (csrc/tophead.hip): learn_top's bias / logs (its weight
+        multiplies h_top == 0), y_emb under y_condition, the classifier when its logits are asked for (network/model.py:441)."""
+        parts = {}
+        ab = self.hps.ablation
+        if ab.learn_top:
+            parts.update(lt_bias=self.learn_top.bias, lt_logs=self.learn_top.logs)
+        if ab.y_condition:
+            parts.update(ye_w=self.y_emb.weight, ye_b=self.y_emb.bias, ye_logs=self.y_emb.logs)
+            if self.hps.model.weight_y > 0:
+                parts.update(cl_w=self.classifier.weight, cl_b=self.classifier.bias, cl_logs=self.classifier.logs)
+        return parts
+
+    def _attach_head(self, plan, criterion=None):
+        """Make `plan` carry this model's head (host bookkeeping; no C call when nothing changed).  ``criterion``: None (logits
+        only), 'single_class' or 'multi_class' -- the head kernel then also writes the loss term and its gradient."""
+        assert criterion in self.CRITERIA, 'Unsupported criterion: {}'.format(criterion)
+        parts = self._head_parts()
+        if not parts:
+            plan.set_head({})
+            return False
+        K = self.hps.dataset.num_classes if self.hps.ablation.y_condition else 0
+        plan.set_head(parts, K, self.CRITERIA[criterion] if "cl_w" in parts else _lib.CRIT_NONE, float(self.hps.model.weight_y))
+        return True
+
     def prior(self, y_onehot=None):
-        """Top prior parameters (mean, logs).  The reference asserts h_top == 0 with a host sync on every
-        call (network/model.py:373); the sync is not reproduced.  Returns (None, None) for the all-zero
-        prior so the kernels skip the loads."""
-        if not self.hps.ablation.learn_top:
+        """Top prior parameters (mean, logs), reference network/model.py:362-379, as dense tensors from one `k_top_prior`
+        launch.  The reference asserts h_top == 0 with a host sync on every call (:373); the sync is not reproduced.  Returns
+        (None, None) for the all-zero prior.  The forward / training paths do not call this: the head kernels compute the prior
+        themselves."""
+        ab = self.hps.ablation
+        if not (ab.learn_top or ab.y_condition):
             return None, None
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.learn_top.parameters()):
-            # training: h_top is all zeros (the reference asserts it), so the Conv2dZeros output is (0 + bias) exp(3 logs) in every
-            # pixel -- written with torch ops, which makes learn_top.bias / .logs differentiable (its weight multiplies zeros: no
-            # gradient, as under the reference's autograd)
-            lt = self.learn_top
-            h = (lt.bias.view(1, -1, 1, 1) * torch.exp(lt.logs.view(1, -1, 1, 1) * 3.0)).expand(tuple(self.h_top.shape)).contiguous()
+        n = self.batch_h_top
+        if ab.y_condition:
+            assert y_onehot is not None
+            y_onehot = require_device_tensor(y_onehot.float(), "y_onehot")
+            n = y_onehot.shape[0]
         else:
-            h = self.learn_top(self.h_top.detach())
-        nc = h.shape[1]
-        return h[:, :nc // 2, ...], h[:, nc // 2:, ...]
+            y_onehot = None
+        parts = {k: v for k, v in self._head_parts().items() if not k.startswith("cl_")}
+        d = _lib.HeadDesc()
+        d.K = self.hps.dataset.num_classes if ab.y_condition else 0
+        for k, v in parts.items():
+            setattr(d, k, require_device_tensor(v.detach(), k).data_ptr())
+        dev = self.h_top.device
+        c2, h, w = self.h_top.shape[1:]
+        mean = torch.empty((n, c2 // 2, h, w), dtype=torch.float32, device=dev)
+        logs = torch.empty_like(mean)
+        _lib.check(_lib.lib().glowhip_top_prior(d, _lib.ptr(y_onehot), n, c2 // 2, h * w, _lib.ptr(mean), _lib.ptr(logs),
+                                                _lib.stream_ptr(dev)))
+        return mean, logs
 
     def normal_flow(self, x, y_onehot=None, noise=None, repack=False, safe=False):
         """z = x + U(0, 1/2^n_bits); objective = -ln(n_bins)*CHW + logdet + logp(z); nll = -objective/(ln2*CHW).
@@ -418,31 +446,32 @@ class Glow(nn.Module):
         if not in_kernel_rng:
             plan.set_dequant_rng(0, False)
         _maybe_data_dependent_init(self.flow, plan, x, noise, self.flow.actnorm_scale)
-        mean, logs = self.prior(y_onehot)
-        stride = 0
-        if mean is not None:
-            assert mean.shape[0] == x.shape[0], "batch must equal h_top's batch when learn_top is on"
-            stride = mean.stride(0)
-            assert mean[0].is_contiguous() and logs[0].is_contiguous() and logs.stride(0) == stride
+        n = x.shape[0]
+        head = plan.head_call(n, y_onehot) if self._attach_head(plan) else None
         params = plan.trainable_parameters() if torch.is_grad_enabled() else ()     # (a walk over ~1 060 tensors: skipped on the inference path)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
             # training step: one autograd node over the whole flow (HIP forward with tape + HIP backward)
-            z, nll = _GlowTrainFn.apply(plan, x, noise, n_bits, mean, logs, *params)
-            return z, nll, None
-        z, nll, _ = plan.glow_forward(x, noise, mean, logs, stride, n_bits, repack=repack)
+            out = _GlowTrainFn.apply(plan, x, noise, n_bits, head, *params)
+            return out[0], out[1], (out[2] if len(out) > 2 else None)
+        z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, repack=repack, head=head)
         if safe and not bool(torch.isfinite(nll).all()):
             if in_kernel_rng:     # the re-run sees the same dequantisation draw as the flagged run
                 noise = plan.dequant_noise(x.shape, rng_key, rng_call, n_bits)
-            z, nll = self._forward_exact_fp32(plan, x.float() / 255.0 if x.dtype == torch.uint8 else x, noise, mean, logs, stride, n_bits)
-        return z, nll, None
+            z, nll = self._forward_exact_fp32(plan, x.float() / 255.0 if x.dtype == torch.uint8 else x, noise, n_bits, head)
+        return z, nll, (None if head is None else head.y_logits)
 
-    def loss_and_grads(self, x, noise=None, force_pack=False):
+    def loss_and_grads(self, x, noise=None, y_onehot=None, y=None, force_pack=False, criterion=None):
         """mean(nll) of the batch (`generative_loss`) and its gradient for every trainable parameter, WITHOUT an autograd graph:
         the HIP forward with tape and the HIP reverse sweep are called directly, and the gradients land in the plan's persistent
         flat buckets, whose views are the parameters' ``.grad`` (assigned once).  This is `Trainer`'s step (network/trainer.py:123-133:
         forward, `loss.backward()`) minus ~10 ms of per-step host work in autograd's bookkeeping for ~1 060 parameter tensors --
         eight data-parallel ranks share one host.  Same kernels, same bits as ``normal_flow(x)`` + ``loss.backward()``
-        (tests/test_gpu_grad.py).  Returns the loss (a device scalar); gradient buckets: ``flow.pop_grad_buckets()``."""
+        (tests/test_gpu_grad.py).  Returns the loss (a device scalar); gradient buckets: ``flow.pop_grad_buckets()``.
+
+        Class-conditional model (network/trainer.py:100-131): ``y_onehot`` feeds the prior; with ``weight_y > 0`` and a
+        ``criterion`` ('single_class': integer targets ``y``; 'multi_class': multi-hot ``y_onehot``) the head kernel computes the
+        classification term and its gradient itself, and the returned loss is generative + weight_y * classification
+        (``self.last_losses`` holds the two terms)."""
         assert self.training, "loss_and_grads is the training step: call glow.train() first"
         x = require_device_tensor(x, "Glow input", allow_uint8=True)
         if x.dtype == torch.uint8:
@@ -455,16 +484,20 @@ class Glow(nn.Module):
             noise = require_device_tensor(noise, "noise")
         plan.set_dequant_rng(0, False)
         _maybe_data_dependent_init(self.flow, plan, x, noise, self.flow.actnorm_scale)
-        if self.hps.ablation.learn_top:
-            raise NotImplementedError("loss_and_grads: a learned top prior goes through the autograd route (normal_flow + backward)")
+        n = x.shape[0]
+        head = plan.head_call(n, y_onehot, y) if self._attach_head(plan, criterion) else None
         with torch.no_grad():
-            z, nll, tape = plan.glow_forward_train(x, noise, None, None, 0, n_bits, force_pack=force_pack)
-            loss = self.generative_loss(nll)
-            n = x.shape[0]
+            z, nll, tape = plan.glow_forward_train(x, noise, None, None, 0, n_bits, force_pack=force_pack, head=head)
+            loss = loss_generative = self.generative_loss(nll)
+            loss_classes = None
+            if head is not None and head.cls_loss is not None:
+                loss_classes = torch.mean(head.cls_loss)
+                loss = loss_generative + float(self.hps.model.weight_y) * loss_classes
+            self.last_losses = (loss_generative, loss_classes)
             gn = getattr(plan, "_mean_grad", None)
             if gn is None or gn.numel() != n:
                 gn = plan._mean_grad = torch.full((n,), 1.0 / n, dtype=torch.float32, device=x.device)      # d mean(nll) / d nll
-            grads, _ = plan.glow_backward(x, tape, gn, None, None, None, 0, want_grad_x=False, persistent=True)
+            grads, _ = plan.glow_backward(x, tape, gn, None, None, None, 0, want_grad_x=False, persistent=True, head=head)
         # the views ARE the parameters' gradients: bound once per plan -- and again whenever somebody took them away in between
         # (optimizer.zero_grad() sets .grad to None, an autograd backward assigns its own tensors): ~1 060 identity tests, 60 us.  A
         # re-bind hands out a NEW token, so the optimiser rebuilds its chunk table from the gradients that are there now
@@ -486,7 +519,7 @@ class Glow(nn.Module):
 
     _RANGE_FALLBACKS = 0   # how often safe=True had to re-run on the exact-fp32 kernels (diagnostics / tests)
 
-    def _forward_exact_fp32(self, plan, x, noise, mean, logs, stride, n_bits):
+    def _forward_exact_fp32(self, plan, x, noise, n_bits, head=None):
         """The same forward on the exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32): no fp16 range limit.  The kernel family is
         a property of the plan (glowhip_plan_set_family), set for this one call: nothing process-wide is touched, the product
         kernels' weight images stay valid for the next call."""
@@ -494,21 +527,26 @@ class Glow(nn.Module):
         prev = plan.family
         plan.set_family(plan.FAMILY_EXACT_FP32)
         try:
-            z, nll, _ = plan.glow_forward(x, noise, mean, logs, stride, n_bits)
+            z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, head=head)      # (same labels, same head tensors)
         finally:
             plan.set_family(prev)
         return z, nll
 
-    def reverse_flow(self, z, y_onehot=None, eps_std=None, eps=None, safe=False):
+    def reverse_flow(self, z, y_onehot=None, eps_std=None, eps=None, safe=False, eps_top=None):
         """``safe=True``: the decode's range status (glowhip_plan_status: sticky log-det flags | a non-finite pixel) is read back
-        -- one host sync -- and a flagged batch is decoded again on the exact-fp32 kernels with the same eps draws."""
+        -- one host sync -- and a flagged batch is decoded again on the exact-fp32 kernels with the same eps draws.
+        ``z=None``: the top latent is sampled from the (class-conditional) prior, mean + exp(logs) * eps (network/model.py:466-468);
+        ``eps_top`` (beyond the reference signature) injects that draw, already multiplied by its std."""
         with torch.no_grad():
             if z is None:
                 mean, logs = self.prior(y_onehot)
                 if mean is None:
                     c2, h, w = self.h_top.shape[1:]
                     mean = logs = torch.zeros((self.batch_h_top, c2 // 2, h, w), device=self.h_top.device)
-                z = module.GaussianDiag.sample(mean, logs, eps_std)
+                if eps_top is None:
+                    z = module.GaussianDiag.sample(mean, logs, eps_std)
+                else:
+                    z = mean + torch.exp(logs) * require_device_tensor(eps_top, "eps_top")
             return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
 
     # Range policy of ``forward`` -- the call the reference's Trainer / Inferer make (network/trainer.py:113,123,163,171,

@@ -91,6 +91,13 @@ class _ShardSampler(torch.utils.data.Sampler):
 
 
 class Trainer:
+    # reference network/trainer.py:14-17.  Deliberate deviation: the reference maps 'multi_class' to
+    # single_class_loss as well, which raises inside torch for a multi-hot target; here it is Glow.multi_class_loss
+    criterion_dict = {
+        'single_class': lambda y_logits, y: Glow.single_class_loss(y_logits, y),
+        'multi_class': lambda y_logits, y_onehot: Glow.multi_class_loss(y_logits, y_onehot),
+    }
+
     def __init__(self, hps, result_subdir, step, graph, optimizer, scheduler, devices, dataset, data_device,
                  rank=0, world=1):
         self.hps = hps
@@ -116,7 +123,8 @@ class Trainer:
         self.num_epochs = (self.hps.optim.num_epochs + len(self.data_loader) - 1) // len(self.data_loader)
         self.y_condition = self.hps.ablation.y_condition
         if self.y_condition:
-            raise NotImplementedError("class-conditional training (y_condition) is outside the flow hot path")
+            self.y_criterion = self.hps.ablation.y_criterion
+            assert self.y_criterion in self.criterion_dict.keys(), "Unsupported criterion: {}".format(self.y_criterion)
         self.max_grad_clip = self.hps.ablation.max_grad_clip
         self.max_grad_norm = self.hps.ablation.max_grad_norm
         self.writer = _writer(self.result_subdir) if rank == 0 else _ScalarLog(self.result_subdir)   # rank 0 alone writes logs
@@ -133,6 +141,21 @@ class Trainer:
         self.loop.scheduler = scheduler or self.loop.scheduler
         self.loop.global_step = step
         self.last_loss = None
+        self.last_classification_loss = None
+
+    def labels_of(self, batch):
+        """(y, y_onehot) of a batch as the reference extracts them (network/trainer.py:100-109)."""
+        y = None
+        y_onehot = None
+        if self.y_condition:
+            if self.y_criterion == 'single_class':
+                assert 'y' in batch.keys(), 'Single-class criterion needs "y" in batch data'
+                y = batch['y']
+                y_onehot = ops.onehot(y, self.num_classes)
+            else:
+                assert 'y_onehot' in batch.keys(), 'Multi-class criterion needs "y_onehot" in batch data'
+                y_onehot = batch['y_onehot']
+        return y, y_onehot
 
     def _device(self):
         return next(self.graph.parameters()).device
@@ -151,13 +174,25 @@ class Trainer:
                 for i in batch:
                     batch[i] = batch[i].to(self._device())       # the flow runs on this rank's GPU only
                 x = batch['x']                                   # already this rank's shard (_ShardSampler)
-                loss, grad_norm = self.loop.step(x.float().contiguous())
+                y, y_onehot = self.labels_of(batch)               # this rank's shard of the labels, as x
+                if y is not None:
+                    y = y.reshape(-1).long()
+                if y_onehot is not None:
+                    y_onehot = y_onehot.float().contiguous()
+                if self.y_condition:
+                    loss, grad_norm = self.loop.step(x.float().contiguous(), y_onehot=y_onehot, y=y)
+                else:
+                    loss, grad_norm = self.loop.step(x.float().contiguous())
                 lr = self.loop.lr
                 self.last_loss = loss
+                losses = getattr(self.graph, "last_losses", None) if self.y_condition else None
+                self.last_classification_loss = None if losses is None else losses[1]
                 log = self.step % self.interval_scalar == 0 and self.step > 0
                 if log:
                     self.writer.add_scalar('lr/lr', lr, self.step)
-                    self.writer.add_scalar('loss/generative_loss', loss, self.step)
+                    self.writer.add_scalar('loss/generative_loss', loss if not (self.y_condition and losses) else losses[0], self.step)
+                    if self.y_condition and self.last_classification_loss is not None:
+                        self.writer.add_scalar('loss/classification_loss', self.last_classification_loss, self.step)
                     if self.max_grad_norm is not None and self.max_grad_norm > 0:
                         self.writer.add_scalar("grad_norm/grad_norm", grad_norm, self.step)
                 if self.step % self.interval_snapshot == 0 and self.step > 0:
@@ -168,15 +203,15 @@ class Trainer:
                 if self.step % self.interval_valid == 0 and self.step > 0 and self.rank == 0:
                     with torch.no_grad():
                         self.graph.eval()
-                        z, _, _ = self.graph(x=x, y_onehot=None)
-                        img = self.graph(z=z, y_onehot=None, reverse=True)
+                        z, _, _ = self.graph(x=x, y_onehot=y_onehot)
+                        img = self.graph(z=z, y_onehot=y_onehot, reverse=True)
                         self.graph.train()
                     for i in range(min(self.num_sample, img.shape[0])):
                         self.writer.add_image("reconstructed/{}".format(i), ops.cat_channel(img[i], x[i]), self.step)
                 if self.step % self.interval_sample == 0 and self.step > 0 and self.rank == 0:
                     with torch.no_grad():
                         self.graph.eval()
-                        img = self.graph(z=None, y_onehot=None, eps_std=0.5, reverse=True)
+                        img = self.graph(z=None, y_onehot=y_onehot, eps_std=0.5, reverse=True)
                         self.graph.train()
                     for i in range(min(self.num_sample, img.shape[0])):
                         self.writer.add_image("sample/{}".format(i), img[i], self.step)

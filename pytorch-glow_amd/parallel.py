@@ -57,9 +57,10 @@ STEP0 = {}      # timing of the last step-0 exchange on this rank: {"init_ms", "
 
 
 def data_dependent_init(glow, x_local: torch.Tensor, rank: int, world: int,
-                        init_fn: Optional[Callable] = None) -> None:
+                        init_fn: Optional[Callable] = None, y_onehot: Optional[torch.Tensor] = None) -> None:
     """Step-0 exchange: rank 0 initialises every ActNorm from ITS shard, everyone receives the result.
-    `init_fn(glow, x)` defaults to one training-mode forward (which performs the init on the HIP path).
+    `init_fn(glow, x)` defaults to one training-mode forward (which performs the init on the HIP path), with the labels of rank
+    0's shard for a class-conditional model (reference trainer.py:112-115).
     The other ranks have nothing to do while rank 0 runs the init pass (66 ms at config B, 0.3 s at config E, once): they wait in a
     barrier of their own first, so that the wait is visible as such (`STEP0["wait_ms"]`) and the parameter broadcast behind it is
     timed on its own.  What bounds that wait is the timeout of the process group the CALLER created: bench.py creates it with 30
@@ -72,7 +73,7 @@ def data_dependent_init(glow, x_local: torch.Tensor, rank: int, world: int,
         if init_fn is None:
             was_training = glow.training
             glow.train()
-            glow.normal_flow(x_local, None)
+            glow.normal_flow(x_local, y_onehot)
             glow.train(was_training)
         else:
             init_fn(glow, x_local)
@@ -186,7 +187,9 @@ def allreduce_buckets(buckets, world: Optional[int] = None, average: bool = True
 
 def train_step(glow, optimizer, x_local: torch.Tensor, world: int = 1, max_grad_clip: float = 0.0,
                max_grad_norm: float = 0.0, skip_nonfinite: bool = False,
-               before_update: Optional[Callable[[], None]] = None, direct: bool = True) -> Tuple[torch.Tensor, torch.Tensor]:
+               before_update: Optional[Callable[[], None]] = None, direct: bool = True,
+               y_onehot: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
+               criterion: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """One data-parallel training step of the reference's loop (network/trainer.py:123-150) on this rank's shard:
     forward (HIP, with tape) -> loss = mean(nll) -> backward (HIP reverse sweep) -> gradient all-reduce (RCCL) ->
     clip_grad_value_ / clip_grad_norm_ -> optimizer.step().  Returns (global mean loss, gradient norm).
@@ -195,18 +198,26 @@ def train_step(glow, optimizer, x_local: torch.Tensor, world: int = 1, max_grad_
     `loss.backward()` route, kept for comparison and for models the direct call does not take).
     ``before_update``: called after forward, backward and the gradient exchange are enqueued and before the optimiser step is --
     the place where TrainLoop looks at the PREVIOUS step's norm (the device is still a whole forward + backward behind the host).
-    The local loss is mean over the LOCAL shard; averaging the gradients over ranks makes it the global mean."""
-    direct = direct and hasattr(glow, "loss_and_grads") and x_local.is_cuda and not glow.hps.ablation.learn_top
+    The local loss is mean over the LOCAL shard; averaging the gradients over ranks makes it the global mean.
+    Class-conditional model (trainer.py:100-131): ``y_onehot`` / ``y`` are this rank's shard of the labels, ``criterion`` is
+    'single_class' or 'multi_class'; loss = generative + weight_y * classification (the two terms: ``glow.last_losses``)."""
+    direct = direct and hasattr(glow, "loss_and_grads") and x_local.is_cuda
     if direct:
         # HIP forward + reverse sweep called directly (Glow.loss_and_grads): same kernels and bits as the autograd route below,
         # gradients in the plan's persistent buckets (the parameters' .grad are views into them: nothing to zero, nothing to
         # re-assign) -- the per-step host work of autograd over ~1 060 parameter tensors is what eight ranks on one host cannot afford
-        loss = glow.loss_and_grads(x_local)
+        loss = glow.loss_and_grads(x_local, y_onehot=y_onehot, y=y, criterion=criterion)
     else:
         optimizer.zero_grad(set_to_none=True)
         with torch.enable_grad():
-            z, nll, _ = glow.normal_flow(x_local, None)
-            loss = glow.generative_loss(nll)
+            z, nll, y_logits = glow.normal_flow(x_local, y_onehot)
+            loss = loss_generative = glow.generative_loss(nll)
+            loss_classes = None
+            if y_logits is not None and criterion is not None:
+                loss_classes = (glow.single_class_loss(y_logits, y) if criterion == "single_class"
+                                else glow.multi_class_loss(y_logits, y_onehot))
+                loss = loss_generative + loss_classes * glow.hps.model.weight_y
+            glow.last_losses = (loss_generative.detach(), None if loss_classes is None else loss_classes.detach())
             loss.backward()
     buckets = glow.flow.pop_grad_buckets() if hasattr(glow, "flow") and hasattr(glow.flow, "pop_grad_buckets") else None
     if buckets is not None:

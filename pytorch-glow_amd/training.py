@@ -227,26 +227,32 @@ class GraphedTrainStep:
     """One training step of one rank -- dequantisation draw, HIP forward with tape, HIP reverse sweep, both clippings, the Adam /
     Adamax update (reference network/trainer.py:123-150) -- captured in ONE hipGraph: the step's ~1 300 launches cost the host one
     graph launch instead of ~3 ms of Python + launch calls (and the ROCm runtime's helper thread nothing), which is what eight
-    data-parallel ranks sharing a host want.  Single-rank steps only (the gradient exchange of a multi-rank step stays eager), no
-    learned top prior (as `Glow.loss_and_grads`).
+    data-parallel ranks sharing a host want.  Single-rank steps only (the gradient exchange of a multi-rank step stays eager).  A
+    learned or class-conditional top prior and the classifier are inside: the top head is one launch each way (csrc/tophead.hip).
 
-    Static buffers: ``x`` (the batch is copied in), the noise, ``loss``, ``norm``, and ``hyper`` = {lr, 1 - beta1^step, 1 - beta2^step}
+    Static buffers: ``x`` (the batch is copied in), the labels ``y_onehot`` / ``y`` of a class-conditional model beside it, the
+    noise, ``loss``, ``loss_classes``, ``norm``, and ``hyper`` = {lr, 1 - beta1^step, 1 - beta2^step}
     on the device: kernel arguments are frozen in a graph, so the update kernel reads the three values that change from step to step
     from memory (glowhip_optim_step_dev) and __call__ uploads them before each replay.  `glowhip_plan_pack` is inside the graph:
     every replay re-derives the weight images from the live parameters, as the forward after an update must.  Capture executes
     nothing, but it needs the lazy allocations of an eager step behind it: capture after at least one eager step of the same batch
     shape (`TrainLoop(graph=True)` does).  Same kernels, same bits as the eager step (tests/test_gpu_grad.py)."""
 
-    def __init__(self, glow, optimizer, x, max_grad_clip=0.0, max_grad_norm=0.0, skip_nonfinite=False):
-        if not (x.is_cuda and hasattr(optimizer, "fused_step") and hasattr(glow, "loss_and_grads")) or glow.hps.ablation.learn_top:
-            raise _lib.GlowHipError("GraphedTrainStep: the HIP optimisers on a device batch, no learned top prior")
+    def __init__(self, glow, optimizer, x, max_grad_clip=0.0, max_grad_norm=0.0, skip_nonfinite=False, y_onehot=None, y=None,
+                 criterion=None):
+        if not (x.is_cuda and hasattr(optimizer, "fused_step") and hasattr(glow, "loss_and_grads")):
+            raise _lib.GlowHipError("GraphedTrainStep: the HIP optimisers on a device batch")
         self.glow, self.optimizer = glow, optimizer
+        self.criterion = criterion
+        self.y_onehot = None if y_onehot is None else y_onehot.float().clone()
+        self.y = None if y is None else y.long().clone()
         self.clip, self.max_norm, self.skip = max_grad_clip, max_grad_norm, skip_nonfinite
         dev = x.device
         self.x = x.clone()
         self.noise = torch.empty(x.shape, dtype=torch.float32, device=dev)
         self.n_bits = glow.hps.model.n_bits_x
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.loss_classes = torch.zeros((), dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.hyper = torch.zeros(3, dtype=torch.float64, device=dev)
         # A pinned-source H2D copy reads the host words when the STREAM gets to it, not at enqueue time, and the host may run several
@@ -317,32 +323,43 @@ class GraphedTrainStep:
 
     def _body(self):
         self.noise.uniform_(0, 1. / 2 ** self.n_bits)
-        loss = self.glow.loss_and_grads(self.x, noise=self.noise, force_pack=True)
+        loss = self.glow.loss_and_grads(self.x, noise=self.noise, y_onehot=self.y_onehot, y=self.y, criterion=self.criterion,
+                                        force_pack=True)
+        if self.glow.last_losses[1] is not None:
+            self.loss_classes.copy_(self.glow.last_losses[1])
         if hasattr(self.glow.flow, "pop_grad_buckets"):
             self.glow.flow.pop_grad_buckets()            # (one rank: nothing to exchange)
         token = getattr(getattr(self.glow, "_train_plan", None), "_pgrad_bound", None)
         self.optimizer.fused_step(self.clip, self.max_norm, skip_nonfinite=self.skip, grads_token=token, hyper_dev=self.hyper, norm_out=self.norm)
         self.loss.copy_(loss.detach())
 
-    def __call__(self, x, lr):
-        """Replay with this batch and learning rate; returns (loss, gradient norm) as fresh device scalars."""
+    def __call__(self, x, lr, y_onehot=None, y=None):
+        """Replay with this batch (and its labels) and learning rate; returns (loss, gradient norm) as fresh device scalars."""
         if not self.valid():
             raise _lib.GlowHipError("GraphedTrainStep: a parameter or a workspace was re-allocated since the capture -- capture again")
         if x is not self.x:
             self.x.copy_(x, non_blocking=True)
+        if self.y_onehot is not None and y_onehot is not self.y_onehot:
+            self.y_onehot.copy_(y_onehot, non_blocking=True)
+        if self.y is not None and y is not self.y:
+            self.y.copy_(y, non_blocking=True)
         opt = self.optimizer
         opt._steps += 1
         opt._publish_step()
         self._upload_hyper(opt.hyper_values(lr, opt._steps))
         self.graph.replay()
         torch.autograd.graph.increment_version(self._params)      # (the parameters changed behind torch's back, as after fused_step)
-        out = torch.stack((self.loss, self.norm[0]))              # (the static words are overwritten by the next replay)
+        out = torch.stack((self.loss, self.norm[0], self.loss_classes))      # (the static words are overwritten by the next replay)
+        if self.glow.last_losses[1] is not None:
+            self.glow.last_losses = (out[0] - float(self.glow.hps.model.weight_y) * out[2], out[2])
         return out[0], out[1]
 
 
 class TrainLoop:
     """The state the reference's ``Trainer`` carries from step to step, minus its I/O: model, optimiser, schedule, step
-    counter, clipping thresholds (trainer.py:44-60).  ``step(x_local)`` runs one iteration on this rank's shard."""
+    counter, clipping thresholds (trainer.py:44-60).  ``step(x_local)`` runs one iteration on this rank's shard; a
+    class-conditional model takes this shard's labels as ``step(x_local, y_onehot=..., y=...)`` and its criterion from
+    ``hps.ablation.y_criterion`` (trainer.py:64-67, 100-109)."""
 
     GRAPH_AFTER = 3      # graph=True: the first steps run eagerly (data-dependent init, lazy allocations), then the step is captured
 
@@ -375,12 +392,14 @@ class TrainLoop:
         self.max_grad_norm = hps.ablation.get("max_grad_norm", 0)
         self.global_step = 0
         self.lr = None
+        self.criterion = hps.ablation.get("y_criterion", None) if hps.ablation.get("y_condition", False) else None
 
-    def step(self, x_local: torch.Tensor):
+    def step(self, x_local: torch.Tensor, y_onehot: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+        labels = dict(y_onehot=y_onehot, y=y, criterion=self.criterion)
         if self.global_step == 0 and not self.glow.actnorm_inited():
             # data-dependent ActNorm init on rank 0's batch, broadcast to the others (trainer.py:112-115)
             self.glow.train()
-            parallel.data_dependent_init(self.glow, x_local, rank=self.rank, world=self.world)
+            parallel.data_dependent_init(self.glow, x_local, rank=self.rank, world=self.world, y_onehot=y_onehot)
         if not self.glow.training:      # (nn.Module.train() walks all ~6 400 sub-modules: 4.5 ms of host time when called every step)
             self.glow.train()
         self.lr = self.scheduler(global_step=self.global_step)
@@ -388,32 +407,34 @@ class TrainLoop:
             group["lr"] = self.lr
         checked = self.range_check and hasattr(self.optimizer, "undo_step") and x_local.is_cuda
         self._rerun = None
-        graphed = self._graph_for(x_local, checked)
+        graphed = self._graph_for(x_local, checked, y_onehot, y)
         if graphed is not None:
             if checked:
                 self._check_previous()       # (before this step's bias corrections are computed from the step count)
-            loss, grad_norm = graphed(x_local, self.lr)
+            loss, grad_norm = graphed(x_local, self.lr, y_onehot, y)
         else:
             loss, grad_norm = parallel.train_step(self.glow, self.optimizer, x_local, world=self.world,
                                                   max_grad_clip=self.max_grad_clip, max_grad_norm=self.max_grad_norm,
-                                                  skip_nonfinite=checked, before_update=self._check_previous if checked else None)
+                                                  skip_nonfinite=checked, before_update=self._check_previous if checked else None,
+                                                  **labels)
         self.global_step += 1
         if checked:
-            self._pending.append(self._stash(x_local, grad_norm, self.lr))
+            self._pending.append(self._stash(x_local, grad_norm, self.lr, y_onehot, y))
             reruns, self._rerun = self._rerun, None
             for pending in reruns or ():
                 self._run_again(pending)
         return loss, grad_norm
 
-    def _graph_for(self, x_local, checked):
+    def _graph_for(self, x_local, checked, y_onehot=None, y=None):
         """The captured step for this batch, or None (eager): graph=True, one rank, a device batch, the HIP optimiser, past the
         eager warm-up steps; a failed capture is remembered (``graph_error``) and the loop stays eager."""
         if not self.graph or self.world != 1 or not x_local.is_cuda or self.global_step < self.GRAPH_AFTER or self.graph_error:
             return None
-        if not hasattr(self.optimizer, "fused_step") or self.glow.hps.ablation.learn_top:
+        if not hasattr(self.optimizer, "fused_step"):
             return None
         g = self._graphed
-        if g is not None and (g.x.shape != x_local.shape or g.x.dtype != x_local.dtype or g.skip != checked):
+        if g is not None and (g.x.shape != x_local.shape or g.x.dtype != x_local.dtype or g.skip != checked
+                              or (g.y_onehot is None) != (y_onehot is None) or (g.y is None) != (y is None)):
             # another batch shape: its lazy allocations (workspaces, tape, gradient tables) need an eager step behind them before a
             # capture, as the first one had -- this step runs eagerly, the next one captures
             self._graphed = None
@@ -428,21 +449,22 @@ class TrainLoop:
             return None
         if g is None:
             try:
-                g = self._graphed = GraphedTrainStep(self.glow, self.optimizer, x_local, self.max_grad_clip, self.max_grad_norm, checked)
+                g = self._graphed = GraphedTrainStep(self.glow, self.optimizer, x_local, self.max_grad_clip, self.max_grad_norm, checked,
+                                                     y_onehot=y_onehot, y=y, criterion=self.criterion)
             except Exception as e:      # capture is an optimisation of the host side only
                 self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
                 return None
         return g
 
     # ---- deferred range check (no host sync on the step's own work)
-    def _stash(self, x_local, grad_norm, lr):
+    def _stash(self, x_local, grad_norm, lr, y_onehot=None, y=None):
         if self._host is None:       # pinned words, used in turn (one more than checks can be pending)
             self._host = [torch.zeros(1, pin_memory=True) for _ in range(self.MAX_LAG + 1)]
         host = self._host[self.global_step % (self.MAX_LAG + 1)]
         host.copy_(grad_norm.detach().reshape(1), non_blocking=True)
         ev = torch.cuda.Event(blocking=True)       # (a forced wait yields the core instead of spinning: eight ranks share one host)
         ev.record()
-        return x_local, host, ev, lr
+        return x_local, host, ev, lr, y_onehot, y      # (the labels stay with their batch for a re-run)
 
     MAX_LAG = 2      # a check is forced (host sync) once it is this many steps old
 
@@ -484,7 +506,7 @@ class TrainLoop:
         first order in the learning rate.  If step N + 1 is skipped on the device as well, its count is only taken back at N + 2, so
         this re-run's bias correction uses s + 2 instead of s + 1: a relative change of the step size of O(beta^s), nothing after
         warm-up.  The float() conversions below are host syncs on this rare path only."""
-        x_local, _, _, lr = pending
+        x_local, _, _, lr, y_onehot, y = pending
         plan = self.glow.flow.plan_for(x_local)
         prev = plan.family
         plan.set_family(plan.FAMILY_EXACT_FP32)
@@ -493,7 +515,7 @@ class TrainLoop:
         try:
             loss, grad_norm = parallel.train_step(self.glow, self.optimizer, x_local, world=self.world,
                                                   max_grad_clip=self.max_grad_clip, max_grad_norm=self.max_grad_norm,
-                                                  skip_nonfinite=True)
+                                                  skip_nonfinite=True, y_onehot=y_onehot, y=y, criterion=self.criterion)
         finally:
             plan.set_family(prev)
             for group in self.optimizer.param_groups:
