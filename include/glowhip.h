@@ -178,6 +178,15 @@ int glowhip_plan_decode(glowhip_plan* plan, const void* packed, const float* z, 
                         int n_eps, const float* logdet_in, float* x, float* logdet_out, int N,
                         void* workspace, size_t workspace_bytes, glowhip_stream_t stream);
 
+/* Full-latent encode: keep what every Split2d scores and drops (network/module.py:526-536 adds logp(z2 | prior(z1)) to the
+ * log-determinant and returns z1 alone).  eps_out[k] (device buffer, shape of the k-th Split2d's z2 in DECODE order -- deepest
+ * split first, the order glowhip_plan_decode reads, so an encode's output array is a decode's input array) receives
+ * eps = (z2 - mean) * exp(-logs), written by the epilogue of the prior kernel that already holds mean, logs and z2: no extra
+ * launch, no extra pass.  Per-call binding in the pattern of glowhip_plan_bind_head (pointers copied; HOST bookkeeping): honoured
+ * at enqueue time by the next glowhip_plan_encode / glowhip_glow_forward / glowhip_glow_forward_u8 and every one after it until
+ * (NULL, 0) unbinds; the training forward ignores it.  n_eps must equal the plan's Split2d count (GLOWHIP_EINVAL otherwise). */
+int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps);
+
 /* Glow.normal_flow (network/model.py:409-452) in one call: z = x + noise; objective = -ln(2^n_bits)*CHW
  * + encode logdet + logp(z | prior_mean, prior_logs);  nll = -objective / (ln2*CHW).
  * prior_mean/prior_logs: (N,Cz,Hz,Wz) with batch stride prior_stride, NULL = zeros.

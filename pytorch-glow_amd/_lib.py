@@ -131,6 +131,7 @@ SIGNATURES = {
     "glowhip_plan_head_state_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_bind_head": (c_int, [_P, POINTER(HeadIO)]),
     "glowhip_plan_bind_head_grads": (c_int, [_P, POINTER(HeadGrads)]),
+    "glowhip_plan_bind_latents": (c_int, [_P, POINTER(c_void_p), c_int]),
     "glowhip_top_prior": (c_int, [POINTER(HeadDesc), _P, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_plan_timing_enable": (c_int, [_P, c_int]),
     "glowhip_plan_timing_read": (c_int, [_P, POINTER(TimingRecord), c_int, POINTER(c_int)]),

@@ -30,6 +30,7 @@ class FlowPlan:
         self._keep = []  # tensors whose addresses the C plan holds
         descs = (LayerDesc * len(self.layers))()
         c, h, w = self.in_chw
+        split_chw = []   # shape of the z2 half each Split2d drops, in encode order
         for i, layer in enumerate(self.layers):
             d = descs[i]
             d.C, d.H, d.W = c, h, w
@@ -44,7 +45,9 @@ class FlowPlan:
             else:
                 self._fill_split(d, layer)
                 c = c // 2
+                split_chw.append((c, h, w))
         self.out_chw = (c, h, w)
+        self.split_chw = split_chw[::-1]      # DECODE order (deepest first): the order of decode's eps and of bound latents
         self._params = [p for layer in self.layers for p in _param_tensors(layer)]
         for p in self._params:
             if p.device != self.device:
@@ -156,6 +159,24 @@ class FlowPlan:
         io.g_logit = _p(head.g_logit if g_logit is None else g_logit)
         check(lib().glowhip_plan_bind_head(self._h, ctypes.byref(io)))
 
+    # ------------------------------------------------------------------ full-latent encode (glowhip_plan_bind_latents)
+    def latent_buffers(self, n: int) -> List[torch.Tensor]:
+        """Fresh eps buffers for a batch of ``n``: one per Split2d, decode order -- what ``eps_out=`` takes and decode reads."""
+        return [torch.empty((n,) + s, dtype=torch.float32, device=self.device) for s in self.split_chw]
+
+    def _bind_latents(self, eps_out, n: int) -> None:
+        eps_out = list(eps_out)
+        if len(eps_out) != self.n_split:
+            raise _lib.GlowHipError(f"eps_out: {len(eps_out)} buffers given, the plan has {self.n_split} Split2d layers")
+        for k, (e, s) in enumerate(zip(eps_out, self.split_chw)):
+            if e.device != self.device or e.dtype != torch.float32 or not e.is_contiguous() or tuple(e.shape) != (n,) + s:
+                raise _lib.GlowHipError(f"eps_out[{k}]: needs a contiguous fp32 tensor of shape {(n,) + s} on {self.device}")
+        arr = (ctypes.c_void_p * max(len(eps_out), 1))(*[e.data_ptr() for e in eps_out])
+        check(lib().glowhip_plan_bind_latents(self._h, arr, len(eps_out)))
+
+    def _unbind_latents(self) -> None:
+        check(lib().glowhip_plan_bind_latents(self._h, None, 0))
+
     # ------------------------------------------------------------------ execution
     def _workspace(self, n: int) -> torch.Tensor:
         need = int(lib().glowhip_plan_workspace_bytes(self._h, n))
@@ -265,7 +286,9 @@ class FlowPlan:
         check(lib().glowhip_plan_launch_counts(self._h, buf, len(buf), int(reset)))
         return {k: int(v) for k, v in (line.split("=") for line in buf.value.decode().splitlines() if line)}
 
-    def encode(self, x, noise=None, logdet=None, want_logdet=True, repack=False):
+    def encode(self, x, noise=None, logdet=None, want_logdet=True, repack=False, *, eps_out=None):
+        """``eps_out``: optional list of buffers (`latent_buffers`) that receive, per Split2d in decode order, the draw its
+        dropped half implies; bound for this call only."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == self.in_chw, (x.shape, self.in_chw)
         self.ensure_packed(repack)
@@ -274,8 +297,14 @@ class FlowPlan:
         if n == 0:
             return z, ld_out
         ws = self._workspace(n)
-        check(lib().glowhip_plan_encode(self._h, ptr(self.packed), ptr(x), ptr(noise), ptr(logdet), ptr(z), ptr(ld_out), n,
-                                        ptr(ws), ws.numel(), stream_ptr(self.device)))
+        if eps_out is not None:
+            self._bind_latents(eps_out, n)
+        try:
+            check(lib().glowhip_plan_encode(self._h, ptr(self.packed), ptr(x), ptr(noise), ptr(logdet), ptr(z), ptr(ld_out), n,
+                                            ptr(ws), ws.numel(), stream_ptr(self.device)))
+        finally:
+            if eps_out is not None:
+                self._unbind_latents()
         return z, ld_out
 
     def decode(self, z, eps: Sequence[torch.Tensor], logdet=None, want_logdet=False, repack=False):
@@ -293,7 +322,9 @@ class FlowPlan:
                                         n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         return x, ld_out
 
-    def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None, head=None):
+    def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None, head=None, *,
+                     eps_out=None):
+        """``eps_out``: as in `encode`."""
         n = x.shape[0]
         self.ensure_packed(repack)
         if n:
@@ -307,14 +338,20 @@ class FlowPlan:
         if n == 0:
             return z, nll, obj
         ws = self._workspace(n)
-        if x.dtype == torch.uint8:   # 8-bit pixels straight from the data loader: converted inside the leading squeeze
-            check(lib().glowhip_glow_forward_u8(self._h, ptr(self.packed), ptr(x), 255.0, ptr(noise), ptr(prior_mean),
-                                                ptr(prior_logs), prior_stride, n_bits, ptr(z), ptr(nll), ptr(obj), n, ptr(ws),
-                                                ws.numel(), stream_ptr(self.device)))
-            return z, nll, obj
-        check(lib().glowhip_glow_forward(self._h, ptr(self.packed), ptr(x), ptr(noise), ptr(prior_mean), ptr(prior_logs),
-                                         prior_stride, n_bits, ptr(z), ptr(nll), ptr(obj), n, ptr(ws), ws.numel(),
-                                         stream_ptr(self.device)))
+        if eps_out is not None:
+            self._bind_latents(eps_out, n)
+        try:
+            if x.dtype == torch.uint8:   # 8-bit pixels straight from the data loader: converted inside the leading squeeze
+                check(lib().glowhip_glow_forward_u8(self._h, ptr(self.packed), ptr(x), 255.0, ptr(noise), ptr(prior_mean),
+                                                    ptr(prior_logs), prior_stride, n_bits, ptr(z), ptr(nll), ptr(obj), n, ptr(ws),
+                                                    ws.numel(), stream_ptr(self.device)))
+            else:
+                check(lib().glowhip_glow_forward(self._h, ptr(self.packed), ptr(x), ptr(noise), ptr(prior_mean), ptr(prior_logs),
+                                                 prior_stride, n_bits, ptr(z), ptr(nll), ptr(obj), n, ptr(ws), ws.numel(),
+                                                 stream_ptr(self.device)))
+        finally:
+            if eps_out is not None:
+                self._unbind_latents()
         return z, nll, obj
 
     # ------------------------------------------------------------------ training step

@@ -33,7 +33,7 @@ enum TailMode {
     TAIL_AFFINE_REV,     // z2 = z2 / sigmoid(s + 2) - shift,  acc -= sum log sigmoid
     TAIL_ADD_FWD,        // z2 = z2 + h
     TAIL_ADD_REV,        // z2 = z2 - h
-    TAIL_SPLIT_FWD,      // acc += logp(z2 | mean, logs)
+    TAIL_SPLIT_FWD,      // acc += logp(z2 | mean, logs); z2_out (optional) = (z2 - mean) * exp(-logs), the implied draw
     TAIL_SPLIT_REV,      // z2_out = mean + exp(logs) * eps   (eps passed as z2_in)
 };
 struct TailConvArgs {
@@ -70,6 +70,7 @@ size_t conv_mfma_tail_packed_bytes(int Cin, int Cout);
 // paired=1: output channels come in (even, odd) = (shift|mean, scale|logs) pairs (affine coupling, Split2d)
 int conv_mfma_tail_pack(const float* w, int Cin, int Cout, int paired, float* wp, hipStream_t s);
 int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s);
+bool conv_mfma_tail_takes_dma(const TailConvArgs& a);   // which of the two tail kernels launch_conv_mfma_tail picks for `a`
 void conv_mfma_tail_force_tile(int tp);
 void plan_disable_sh(int off);   // testing hook (plan.hip)
 void plan_pack_one_stream(int on);   // testing hook (plan.hip): glowhip_plan_pack without its side-stream fork

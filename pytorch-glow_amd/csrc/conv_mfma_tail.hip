@@ -307,6 +307,13 @@ static int launch_tail_cfg(const TailConvArgs& a, const TailGeom& g, int paired,
     return GLOWHIP_OK;
 }
 
+bool conv_mfma_tail_takes_dma(const TailConvArgs& a) {
+    if (a.N == 0 || !a.zeros || !conv_mfma_tail_supported(a.Cin, a.H, a.W, a.Cout)) return false;
+    const int MTT = tail_mt(a.Cout, tail_paired(a.mode));
+    const TailChoice tc = tail_choose(a.H, a.W, (long)a.N * a.H * a.W, a.Cin, MTT);
+    return tc.tp > 0 && (tc.msplit ? 1 : MTT) == 1 && tp_ok_dma(tc.tp, a.H, a.W, a.Cin);
+}
+
 int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s) {
     GH_REQUIRE(conv_mfma_tail_supported(a.Cin, a.H, a.W, a.Cout), "conv_mfma_tail: unsupported shape");
     if (a.N == 0) return GLOWHIP_OK;

@@ -63,7 +63,10 @@ __device__ __forceinline__ double tail_epilogue(const TailConvArgs& a, const f32
                         a.z2_out[zo] = a.z2_in[zi] / sc - A_;
                         ld -= (double)logf(sc);
                     } else if (a.mode == TAIL_SPLIT_FWD) {
-                        ld += (double)gauss_logp1_(A_, B_, a.z2_in[zi]);
+                        const float z2 = a.z2_in[zi];
+                        ld += (double)gauss_logp1_(A_, B_, z2);
+                        // full-latent encode: the draw this z2 is under the prior, what TAIL_SPLIT_REV takes back as z2_in
+                        if (a.z2_out) a.z2_out[zo] = (z2 - A_) * expf(-B_);
                     } else {  // TAIL_SPLIT_REV
                         a.z2_out[zo] = A_ + expf(B_) * a.z2_in[zi];
                     }

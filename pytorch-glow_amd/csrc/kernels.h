@@ -55,7 +55,7 @@ struct SplitTailArgs {
     const float* h;        // (N, 2*Ch, HW): prior conv output, mean = even, logs = odd channels
     const float* z2; long z2_bs;   // forward: z2 to score
     const float* eps;      // reverse: (N,Ch,HW) injected draw
-    float* z2_out; long z2_out_bs; // reverse: sampled z2
+    float* z2_out; long z2_out_bs; // reverse: sampled z2; forward (optional): the implied draw (z2 - mean) * exp(-logs)
     int N, Ch, HW, reverse;
     unsigned long long* acc;
 };

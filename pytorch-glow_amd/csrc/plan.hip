@@ -298,7 +298,8 @@ static int run_coupling(glowhip_plan* P, const LayerPlan& L, const void* packed,
 }
 
 // Split2d prior conv + tail (network/module.py:498-536).  d.C = channels of the un-split tensor.
-static int run_split(const LayerPlan& L, const void* packed, const float* z1, long z1_bs, const float* z2, long z2_bs,
+// Forward: z2_out (optional) receives the draw z2 implies under the prior, (z2 - mean) * exp(-logs) (glowhip_plan_bind_latents).
+static int run_split(glowhip_plan* P, const LayerPlan& L, const void* packed, const float* z1, long z1_bs, const float* z2, long z2_bs,
                      const float* eps, float* z2_out, long z2_out_bs, int N, int reverse, const Workspace& w,
                      hipStream_t s) {
     const glowhip_layer_desc& d = L.d;
@@ -312,11 +313,13 @@ static int run_split(const LayerPlan& L, const void* packed, const float* z1, lo
         t.z2_in = reverse ? eps : z2; t.z2_in_bs = reverse ? (long)Ch * HW : z2_bs;
         t.z2_out = z2_out; t.z2_out_bs = z2_out_bs; t.acc = w.acc;
         t.zeros = at<float>(packed, 64);
+        count_launch(P, conv_mfma_tail_takes_dma(t) ? "split_prior(k_conv_tail_dma)" : "split_prior(k_conv_tail)");
         GH_TRY(launch_conv_mfma_tail(t, s));
     } else {
         ConvArgs c{z1, z1_bs, d.f4_w, d.f4_bias, nullptr, nullptr, at<float>(packed, L.f4_scale), 0, w.h1,
                    N, Ch, d.H, d.W, L.Cout, 3};
         GH_TRY(launch_conv_direct(c, s));
+        count_launch(P, "split_prior(k_split_tail)");
         SplitTailArgs t{w.h1, z2, z2_bs, eps, z2_out, z2_out_bs, N, Ch, HW, reverse, w.acc};
         GH_TRY(launch_split_tail(t, s));
     }
@@ -469,7 +472,9 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 premixed = false;
             } else {  // SPLIT2D: score z2 under the prior predicted from z1, keep z1
                 GH_TRY(join_legacy(p, s));
-                GH_TRY(run_split(L, packed, cur, chw, cur + (long)Ch * HW, chw, nullptr, nullptr, 0, N, 0, w, s));
+                // bound latents are in DECODE order (deepest split first); contiguous (N, C/2, HW) buffers
+                float* eps_out = p->eps_out.empty() ? nullptr : p->eps_out[p->n_split - 1 - L.split_idx];
+                GH_TRY(run_split(p, L, packed, cur, chw, cur + (long)Ch * HW, chw, nullptr, eps_out, (long)Ch * HW, N, 0, w, s));
                 GH_TRY(launch_copy_strided(cur, chw, dst, (long)Ch * HW, N, (long)Ch * HW, s));
             }
         }
@@ -586,7 +591,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
             GH_TRY(launch_chanmix(m, s));
         } else {  // SPLIT2D reverse: z1 = cur (N, C/2, HW) -> cat(z1, mean + exp(logs)*eps)
             GH_REQUIRE(ke < n_eps && eps && eps[ke], "decode: missing eps draw for Split2d #%d", ke);
-            GH_TRY(run_split(L, packed, cur, (long)Ch * HW, nullptr, 0, eps[ke], dst + (long)Ch * HW, chw, N, 1, w, s));
+            GH_TRY(run_split(p, L, packed, cur, (long)Ch * HW, nullptr, 0, eps[ke], dst + (long)Ch * HW, chw, N, 1, w, s));
             GH_TRY(launch_copy_strided(cur, (long)Ch * HW, dst, chw, N, (long)Ch * HW, s));
             ++ke;
         }
@@ -706,7 +711,7 @@ glowhip_plan* glowhip_plan_create(const glowhip_layer_desc* layers, int n_layers
             L.mfma_last = conv_mfma_tail_supported(C / 2, H, W, C);
             if (L.mfma_last) L.f4_wp = take(off, conv_mfma_tail_packed_bytes(C / 2, C));
             p->max_hidden = std::max(p->max_hidden, (long)C * H * W);
-            p->n_split++;
+            L.split_idx = p->n_split++;
             C /= 2;
         } else {
             return fail("unknown layer kind");
@@ -1066,6 +1071,19 @@ int glowhip_plan_set_family(glowhip_plan* plan, int family) {
 }
 
 int glowhip_plan_get_family(const glowhip_plan* plan) { return plan ? plan->family : GLOWHIP_EINVAL; }
+
+int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps) {
+    GH_REQUIRE(plan, "plan_bind_latents: null plan");
+    if (!eps_out && n_eps == 0) {
+        plan->eps_out.clear();
+        return GLOWHIP_OK;
+    }
+    GH_REQUIRE(n_eps == plan->n_split, "plan_bind_latents: %d latent buffers given, plan has %d Split2d layers", n_eps, plan->n_split);
+    GH_REQUIRE(eps_out, "plan_bind_latents: null buffer list");
+    for (int k = 0; k < n_eps; ++k) GH_REQUIRE(eps_out[k], "plan_bind_latents: null buffer for Split2d #%d", k);
+    plan->eps_out.assign(eps_out, eps_out + n_eps);
+    return GLOWHIP_OK;
+}
 
 int glowhip_plan_status(const glowhip_plan* plan, const void* workspace, size_t workspace_bytes, int N, const float* result,
                         long elems_per_sample, int32_t* status_out, glowhip_stream_t stream) {

@@ -15,6 +15,7 @@ namespace glowhip {
 
 struct LayerPlan {
     glowhip_layer_desc d;
+    int split_idx = -1;  // Split2d: its ordinal in ENCODE order (0 = the shallowest)
     int Cout = 0;  // output channels of f.4 / of the Split2d prior conv
     // byte offsets into the packed buffer
     size_t an_scale = 0, an_inv_scale = 0, winv = 0, logabsdet = 0, konst = 0, lu_scratch = 0;
@@ -71,6 +72,7 @@ struct glowhip_plan {
     long max_chw = 0;      // max over layer inputs/outputs of C*H*W
     long max_hidden = 0;   // max over steps of max(hidden, Cout) * H*W
     int n_split = 0;
+    std::vector<float*> eps_out;               // glowhip_plan_bind_latents: per Split2d in DECODE order, empty = nothing bound
     std::vector<char> tape_has_masks;          // per layer: the last glow_forward_train stored the ReLU sign bits (k_cnet MODE 1)
     std::vector<glowhip::LogsJob> logs_jobs;   // the same for the log-scale gradients derived from dW / db (backward.h)
     std::vector<glowhip::GradJob> grad_jobs;   // host copy of the last backward's finalize table (kept alive for the async copy)

@@ -615,7 +615,9 @@ __global__ void __launch_bounds__(256) k_split_tail(SplitTailArgs a) {
         const float mean = hn[(long)(2 * c) * a.HW + p];
         const float logs = hn[(long)(2 * c + 1) * a.HW + p];
         if (!a.reverse) {
-            lp = (double)gauss_logp1(mean, logs, a.z2[n * a.z2_bs + e]);
+            const float z2 = a.z2[n * a.z2_bs + e];
+            lp = (double)gauss_logp1(mean, logs, z2);
+            if (a.z2_out) a.z2_out[n * a.z2_out_bs + e] = (z2 - mean) * expf(-logs);   // full-latent encode: the implied draw
         } else {
             a.z2_out[n * a.z2_out_bs + e] = mean + expf(logs) * a.eps[n * per + e];
         }

@@ -5,6 +5,7 @@ from . import model as _model
 from . import module as _module
 from .builder import Builder
 from .inferer import Inferer
+from .latents import Latents
 from .trainer import Trainer
 
 _LAYERS = ("ActNorm", "LinearZeros", "Conv2d", "Conv2dZeros", "CouplingNet", "f", "Invertible1x1Conv",
@@ -16,4 +17,4 @@ for _n in _LAYERS:
 for _n in _MODELS:
     globals()[_n] = getattr(_model, _n)
 
-__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer")
+__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Latents")

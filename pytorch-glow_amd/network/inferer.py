@@ -9,12 +9,17 @@ Differences, all deliberate:
   (inferer.py:131): it visits len({'x', 'y_onehot'}) = 2 samples of every batch, not the batch.  `samples_per_batch=None`
   (default) uses every sample -- what the method documents; `samples_per_batch="reference"` reproduces the loop as written
   (the parity tests check both against the oracle).
-* `sample` returns the batch; building an image grid is torchvision's job (`make_grid`), outside the flow path."""
+* `sample` returns the batch; building an image grid is torchvision's job (`make_grid`), outside the flow path.
+* Beyond the reference: the full-latent calls `encode_full` / `decode_full` / `reconstruct` / `interpolate` and
+  `apply_attribute_delta(keep_details=True)`.  The reference's encode keeps the top latent only -- every Split2d's other half
+  is scored and dropped (network/module.py:526-536) -- so its decode re-draws all finer detail; these keep the per-level eps
+  (`Glow.encode_latents`), take batches as they are (no `make_batch` replication) and round-trip an image to rounding."""
 import numpy as np
 import torch
 import torch.distributed as dist
 
 from ..misc import util
+from .latents import Latents
 
 
 class Inferer:
@@ -30,7 +35,8 @@ class Inferer:
         self.device = self.graph.h_top.device
 
     def sample(self, z, y_onehot, eps_std=0.5):
-        """Images drawn from the model (z=None: the top latent is sampled too), inferer.py:41-62."""
+        """Images drawn from the model (z=None: the top latent is sampled too), inferer.py:41-62.  ``eps_std``: one temperature,
+        or one per level in decode order (the top prior's first, then every Split2d's from the deepest)."""
         with torch.no_grad():
             return self.graph(z=z, y_onehot=y_onehot, eps_std=eps_std, reverse=True)
 
@@ -50,6 +56,37 @@ class Inferer:
             if len(z.shape) == 3:
                 z = util.make_batch(z, self.batch_size)
             return self.graph(z=z.to(self.device), y_onehot=None, reverse=True)[0, :, :, :]
+
+    # ---- full latents (beyond the reference): nothing dropped, so decode_full(encode_full(img)) is img
+    def _batch(self, img):
+        if not torch.is_tensor(img):
+            raise TypeError("takes a tensor; image decoding (cv2 / PIL) is outside this package")
+        return (img[None] if img.dim() == 3 else img).to(self.device)
+
+    def encode_full(self, img, y_onehot=None, dequantize=False):
+        """`Latents` of an image (C,H,W) or a batch (N,C,H,W), fp32 in [0, 1] or uint8.  No dequantisation noise by default:
+        the latents then decode to the image itself."""
+        return self.graph.encode_latents(self._batch(img), y_onehot, dequantize=dequantize)
+
+    def decode_full(self, latents):
+        """Images (N,C,H,W) of `Latents`, each Split2d fed the latents' own eps."""
+        return self.graph.decode_latents(latents.to(self.device))
+
+    def reconstruct(self, img):
+        """decode_full(encode_full(img)): the image back, to fp32 rounding; a (C,H,W) input gives a (C,H,W) output."""
+        out = self.decode_full(self.encode_full(img))
+        return out[0] if img.dim() == 3 else out
+
+    def interpolate(self, img_a, img_b, steps):
+        """``steps`` images on the straight line between two images in latent space -- every latent tensor blended, top
+        latent and per-level eps alike -- from ONE decode of a batch of ``steps``; the first is img_a, the last img_b."""
+        assert steps >= 2, "an interpolation has two endpoints"
+        a, b = self._batch(img_a), self._batch(img_b)
+        assert a.shape[0] == 1 and b.shape[0] == 1 and a.shape == b.shape, "interpolate takes two single images of one shape"
+        both = self.encode_full(torch.cat([a, b]))
+        t = torch.linspace(0.0, 1.0, steps, device=self.device)
+        t[-1] = 1.0
+        return self.decode_full(both[0].lerp(both[1], t))
 
     def compute_attribute_delta(self, dataset, samples_per_batch=None, shuffle=True, num_workers=None, world=1, _exact=False):
         """deltaz[c] = mean latent of the images with attribute c - mean latent of those without (inferer.py:104-153).
@@ -104,13 +141,21 @@ class Inferer:
         delta = pos / n_pos.clamp(min=1.0)[:, None] - neg / n_neg.clamp(min=1.0)[:, None]
         return delta.view(self.num_classes, *shape).cpu().numpy()
 
-    def apply_attribute_delta(self, img, deltaz, interpolation):
-        """decode(encode(img) + sum_c interpolation[c] * deltaz[c]), inferer.py:155-188."""
+    def apply_attribute_delta(self, img, deltaz, interpolation, keep_details=False):
+        """decode(encode(img) + sum_c interpolation[c] * deltaz[c]), inferer.py:155-188.  As in the reference, that decode draws
+        every Split2d's half afresh: the result keeps the top-level content of ``img`` and new fine detail.
+        ``keep_details=True``: the shift is applied to the top latent of the image's full latents and the decode reads the image's
+        own eps -- an all-zero ``interpolation`` returns the image; a batch is taken as it is."""
         if isinstance(deltaz, np.ndarray):
             deltaz = torch.as_tensor(deltaz, dtype=torch.float32)
         assert len(interpolation) == self.num_classes
         assert deltaz.shape == torch.Size([self.num_classes, *self.graph.flow.output_shapes[-1][1:]])
-        z = self.encode(img)
         coef = torch.as_tensor(np.asarray(interpolation, dtype=np.float32), device=self.device)
-        z_interpolated = z + (deltaz.to(self.device) * coef.view(-1, 1, 1, 1)).sum(0)
+        shift = (deltaz.to(self.device) * coef.view(-1, 1, 1, 1)).sum(0)
+        if keep_details:
+            lat = self.encode_full(img)
+            out = self.decode_full(Latents(lat.z + shift, lat.eps))
+            return out[0] if img.dim() == 3 else out
+        z = self.encode(img)
+        z_interpolated = z + shift
         return self.decode(z_interpolated)

@@ -13,6 +13,7 @@ from .._lib import require_device_tensor
 from .._plan import PlanCache
 from ..misc import util
 from . import module
+from .latents import Latents
 from .module import _deepcopy_without_plans, _logdet_arg
 
 
@@ -41,6 +42,19 @@ def _maybe_data_dependent_init(owner, plan, x, noise, actnorm_scale):
         m.bias_inited = True
         m.logs_inited = True
     owner._actnorms_all_inited = module.ActNorm.RESET_EPOCH[0]
+
+
+def level_eps_stds(eps_std, L):
+    """Per-level temperature: (std of the top prior's draw, [std per Split2d, decode order]).  ``eps_std`` is a number / None --
+    one temperature everywhere, passed through untouched -- or a sequence of L numbers in decode order: the top prior first, then
+    the deepest Split2d, and so on.  Every entry follows the reference's ``eps_std or 1.`` (network/module.py:419)."""
+    if eps_std is None or isinstance(eps_std, (int, float)) or getattr(eps_std, "ndim", 1) == 0:      # (numpy / 0-dim tensor scalars too)
+        return eps_std, [eps_std] * (L - 1)
+    stds = [float(v) for v in eps_std]
+    if len(stds) != L:
+        raise ValueError(f"eps_std: {len(stds)} entries for a model of L = {L} levels (one per level in decode order: "
+                         "the top prior, then every Split2d from the deepest)")
+    return stds[0] or 1., [v or 1. for v in stds[1:]]
 
 
 class FlowStep(nn.Module):
@@ -147,17 +161,24 @@ class FlowModel(nn.Module):
         """Call after writing parameters through ``.data`` (which torch's version counters do not see)."""
         self._plans.invalidate()
 
-    def encode(self, z, logdet=0.):
+    def encode(self, z, logdet=0., *, return_eps=False):
+        """``return_eps``: also return the list of draws the Split2d layers' dropped halves imply, in decode order -- what
+        ``decode(eps=)`` takes to give the input back."""
         z = require_device_tensor(z, "FlowModel input")
         plan = self.plan_for(z)
         _maybe_data_dependent_init(self, plan, z, None, self.actnorm_scale)
         ld = _logdet_arg(logdet, z.shape[0], z.device)
+        if return_eps:
+            eps_out = plan.latent_buffers(z.shape[0])
+            out, ld_out = plan.encode(z, None, ld, want_logdet=ld is not None, eps_out=eps_out)
+            return out, ld_out, eps_out
         return plan.encode(z, None, ld, want_logdet=ld is not None)
 
     _RANGE_FALLBACKS = 0
 
     def decode(self, z, eps_std=None, eps=None, safe=False):
-        """``eps``: optional list of injected draws, one per Split2d in decode order (deepest first).  ``safe``: see
+        """``eps``: optional list of injected draws, one per Split2d in decode order (deepest first).  ``eps_std``: a number, or
+        one per level (`level_eps_stds`; the first entry belongs to the top prior and is not used here).  ``safe``: see
         Glow.reverse_flow."""
         z = require_device_tensor(z, "FlowModel latent")
         n = z.shape[0]
@@ -198,8 +219,9 @@ class FlowModel(nn.Module):
         return shapes[::-1]
 
     def draw_eps(self, n, plan, eps_std, device):
-        std = eps_std or 1.  # reference network/module.py:419
-        return [torch.randn((n,) + s, dtype=torch.float32, device=device) * std for s in self.split_shapes(plan.in_chw)]
+        stds = [v or 1. for v in level_eps_stds(eps_std, self.L)[1]]  # reference network/module.py:419
+        return [torch.randn((n,) + s, dtype=torch.float32, device=device) * std
+                for s, std in zip(self.split_shapes(plan.in_chw), stds)]
 
     def forward(self, z, logdet=0., eps_std=None, reverse=False):
         if not reverse:
@@ -418,7 +440,7 @@ class Glow(nn.Module):
                                                 _lib.stream_ptr(dev)))
         return mean, logs
 
-    def normal_flow(self, x, y_onehot=None, noise=None, repack=False, safe=False):
+    def normal_flow(self, x, y_onehot=None, noise=None, repack=False, safe=False, *, eps_out=None, dequantize=True):
         """z = x + U(0, 1/2^n_bits); objective = -ln(n_bins)*CHW + logdet + logp(z); nll = -objective/(ln2*CHW).
         ``noise`` (optional, beyond the reference signature) injects the dequantisation draw.
 
@@ -426,14 +448,19 @@ class Glow(nn.Module):
         beyond 4094 becomes inf there where the fp32 reference stays finite.  That never yields a finite wrong answer -- a
         sticky per-sample flag makes the nll NaN -- and ``safe=True`` (inference path; costs one host sync) re-runs such a batch
         on the exact-fp32 MFMA kernels, so the result is the reference's up to fp32 rounding for any input the reference
-        handles."""
+        handles.
+
+        ``eps_out`` / ``dequantize`` (inference path only) serve `encode_latents`: buffers that receive the Split2d draws
+        (FlowPlan.latent_buffers), and ``dequantize=False`` = no noise at all."""
         x = require_device_tensor(x, "Glow input", allow_uint8=True)   # uint8 = pixels as loaded, scaled by 1/255 in-kernel
         if x.dtype == torch.uint8 and (self.training or torch.is_grad_enabled()):
             x = x.float() / 255.0   # the ActNorm init pass and the training step take fp32; inference reads the bytes itself
         n_bits = self.hps.model.n_bits_x
         plan = self.flow.plan_for(x)
         in_kernel_rng = False
-        if noise is None:
+        if not dequantize:
+            assert noise is None, "dequantize=False: no noise is added, so none can be given"
+        elif noise is None:
             if self.training or torch.is_grad_enabled():
                 noise = torch.empty(x.shape, dtype=torch.float32, device=x.device).uniform_(0, 1. / 2 ** n_bits)
             else:     # inference: the leading squeeze draws it (Philox keyed by torch's seed; no noise tensor, no RNG launch)
@@ -450,14 +477,16 @@ class Glow(nn.Module):
         head = plan.head_call(n, y_onehot) if self._attach_head(plan) else None
         params = plan.trainable_parameters() if torch.is_grad_enabled() else ()     # (a walk over ~1 060 tensors: skipped on the inference path)
         if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+            assert eps_out is None and dequantize, "the training forward keeps no latents (use encode_latents)"
             # training step: one autograd node over the whole flow (HIP forward with tape + HIP backward)
             out = _GlowTrainFn.apply(plan, x, noise, n_bits, head, *params)
             return out[0], out[1], (out[2] if len(out) > 2 else None)
-        z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, repack=repack, head=head)
+        z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, repack=repack, head=head, eps_out=eps_out)
         if safe and not bool(torch.isfinite(nll).all()):
             if in_kernel_rng:     # the re-run sees the same dequantisation draw as the flagged run
                 noise = plan.dequant_noise(x.shape, rng_key, rng_call, n_bits)
-            z, nll = self._forward_exact_fp32(plan, x.float() / 255.0 if x.dtype == torch.uint8 else x, noise, n_bits, head)
+            z, nll = self._forward_exact_fp32(plan, x.float() / 255.0 if x.dtype == torch.uint8 else x, noise, n_bits, head,
+                                              eps_out=eps_out)      # (the latents of a flagged batch come from the re-run)
         return z, nll, (None if head is None else head.y_logits)
 
     def loss_and_grads(self, x, noise=None, y_onehot=None, y=None, force_pack=False, criterion=None):
@@ -519,7 +548,7 @@ class Glow(nn.Module):
 
     _RANGE_FALLBACKS = 0   # how often safe=True had to re-run on the exact-fp32 kernels (diagnostics / tests)
 
-    def _forward_exact_fp32(self, plan, x, noise, n_bits, head=None):
+    def _forward_exact_fp32(self, plan, x, noise, n_bits, head=None, eps_out=None):
         """The same forward on the exact-fp32 MFMA kernels (v_mfma_f32_32x32x2_f32): no fp16 range limit.  The kernel family is
         a property of the plan (glowhip_plan_set_family), set for this one call: nothing process-wide is touched, the product
         kernels' weight images stay valid for the next call."""
@@ -527,7 +556,7 @@ class Glow(nn.Module):
         prev = plan.family
         plan.set_family(plan.FAMILY_EXACT_FP32)
         try:
-            z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, head=head)      # (same labels, same head tensors)
+            z, nll, _ = plan.glow_forward(x, noise, None, None, 0, n_bits, head=head, eps_out=eps_out)      # (same labels, same head tensors)
         finally:
             plan.set_family(prev)
         return z, nll
@@ -536,18 +565,42 @@ class Glow(nn.Module):
         """``safe=True``: the decode's range status (glowhip_plan_status: sticky log-det flags | a non-finite pixel) is read back
         -- one host sync -- and a flagged batch is decoded again on the exact-fp32 kernels with the same eps draws.
         ``z=None``: the top latent is sampled from the (class-conditional) prior, mean + exp(logs) * eps (network/model.py:466-468);
-        ``eps_top`` (beyond the reference signature) injects that draw, already multiplied by its std."""
+        ``eps_top`` (beyond the reference signature) injects that draw, already multiplied by its std.
+        ``eps_std``: a number, or one per level in decode order (`level_eps_stds`: the top prior's first)."""
         with torch.no_grad():
+            std_top = level_eps_stds(eps_std, self.flow.L)[0]
             if z is None:
                 mean, logs = self.prior(y_onehot)
                 if mean is None:
                     c2, h, w = self.h_top.shape[1:]
                     mean = logs = torch.zeros((self.batch_h_top, c2 // 2, h, w), device=self.h_top.device)
                 if eps_top is None:
-                    z = module.GaussianDiag.sample(mean, logs, eps_std)
+                    z = module.GaussianDiag.sample(mean, logs, std_top)
                 else:
                     z = mean + torch.exp(logs) * require_device_tensor(eps_top, "eps_top")
             return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
+
+    # ---- full-latent encode: the bijection with nothing dropped
+    def encode_latents(self, x, y_onehot=None, noise=None, dequantize=True, safe=None):
+        """`Latents` of a batch (fp32 in [0, 1] or uint8 pixels): the top latent ``z``, the draw ``eps`` every Split2d's dropped
+        half implies under its prior (the reference scores that half and discards it, network/module.py:526-536), and the nll.
+        ``decode_latents`` of the result is the dequantised input, x + noise, to rounding.  ``noise`` injects the dequantisation
+        draw; ``dequantize=False`` adds none, so the reconstruction is x itself (the nll then is that of the discrete pixels).
+        Runs without autograd.  ``safe`` (None: `range_check` in eval mode, the policy of ``forward``): a batch flagged by a
+        non-finite nll is encoded again on the exact-fp32 kernels, and the returned latents are that run's."""
+        if safe is None:
+            safe = bool(self.range_check) and not self.training
+        with torch.no_grad():
+            x = require_device_tensor(x, "Glow input", allow_uint8=True)
+            eps_out = self.flow.plan_for(x).latent_buffers(x.shape[0])
+            z, nll, _ = self.normal_flow(x, y_onehot, noise=noise, safe=safe, eps_out=eps_out, dequantize=dequantize)
+        return Latents(z, eps_out, nll)
+
+    def decode_latents(self, latents, safe=None):
+        """Images of `Latents`: the decode with every Split2d fed the latents' own eps instead of a fresh draw."""
+        if safe is None:
+            safe = bool(self.range_check) and not self.training
+        return self.reverse_flow(latents.z, eps=latents.eps, safe=safe)
 
     # Range policy of ``forward`` -- the call the reference's Trainer / Inferer make (network/trainer.py:113,123,163,171,
     # inferer.py:55,81,98,133).  Under torch.no_grad() in eval mode (validation, sampling, Inferer) the checked path is the default:

@@ -338,13 +338,19 @@ class Split2d(nn.Module):
         h = self.conv2d_zeros(z)
         return h[:, 0::2, ...], h[:, 1::2, ...]
 
-    def forward(self, x, logdet=0., reverse=False, eps_std=None, eps=None):
-        """``eps`` (optional, beyond the reference signature): inject the N(0,1)*eps_std draw."""
+    def forward(self, x, logdet=0., reverse=False, eps_std=None, eps=None, *, return_eps=False):
+        """``eps`` (optional, beyond the reference signature): inject the N(0,1)*eps_std draw.  ``return_eps`` (forward only):
+        also return, as a one-element list, the draw the dropped half implies, (z2 - mean) * exp(-logs) -- reverse with it as
+        ``eps`` rebuilds x."""
         x = require_device_tensor(x, "Split2d input")
         n, c, h, w = x.shape
         if not reverse:
             assert c == self.num_channels
             plan = self._plans.get([self], (c, h, w), x.device)
+            if return_eps:
+                eps_out = plan.latent_buffers(n)
+                z, ld = plan.encode(x, None, _logdet_arg(logdet, n, x.device), want_logdet=True, eps_out=eps_out)
+                return z, ld, eps_out
             return plan.encode(x, None, _logdet_arg(logdet, n, x.device), want_logdet=True)
         assert c == self.num_channels // 2
         plan = self._plans.get([self], (2 * c, h, w), x.device)
