@@ -378,29 +378,34 @@ typedef struct glowhip_timing_record {
 int glowhip_plan_timing_enable(glowhip_plan* plan, int enable);
 int glowhip_plan_timing_read(glowhip_plan* plan, glowhip_timing_record* out, int max, int* n_out);
 
-/* Testing hook for the fused tail convolution, so every variant can be exercised at any batch size: low byte =
- * pixels per workgroup (16/32/64/128; 0 = automatic, chosen by a cost model), | 0x100 = always split the
- * out-channel tiles over blockIdx.y, | 0x200 = never split, | 0x400 = no LDS-DMA tail kernels.
- * Kernel-family switches (the parity tests of the exact-fp32 kernels, A/B runs): | 0x800 = exact-fp32 MFMA kernels only
- * (split-half f16 path off, training included), | 0x8000 = no fusion around the channel mixer: k_squeeze + k_chanmix + a plain
- * finishing kernel as separate launches (bitwise equal to the fused forms); bits 22..24 = 1, 2 or 4: that many row splits of
- * k_cnet;
- * | 0x2000000 = cnet with 128-pixel tiles only, | 0x4000000 = 64-pixel tiles wherever supported,
- * | 0x10000 = no k_cnet1w (the one-wave-per-SIMD coupling-network kernel of csrc/cnet1w_sh.hip; k_cnet takes its launches: A/B),
- * | 0x80000 = f.2's weight-gradient GEMM on 128-column tiles at every level (no k_wgrad_gemm_ps512: A/B),
- * | 0x40000 = no backward instance of k_cnet1w (the level-1 input-gradient launch back on k_cnet's 64-pixel tiles: A/B),
- * | 0x20000 = the row-split instance of k_cnet1w where it applies (C = 24 levels with 112 .. tiles of 128 pixels; off by default:
- *   measured slower than k_cnet's 64-pixel tiles there; parity tests and A/B),
- * | 0x100000 = FUSED FINISHING on: a k_cnet1w launch finishes its FlowStep itself (arrival counters per tile, the last workgroup
- *   to arrive runs the finishing kernel's code; bit-identical, off by default: measured slower),
- * | 0x200000 = log|det W| of the 12 / 24 / 48-wide invconv matrices on the workgroup-wide LU instead of one wave per matrix (same bits: A/B),
- * | 0x8000000 = the finishing step of a FlowStep runs inside the next FlowStep's k_cnet (off by default: measured slower),
- * | 0x10000000 = the finishing kernel takes its pixel chunks in block order instead of the XCD-affine order (A/B),
- * | 0x20000000 = glowhip_plan_pack entirely on the caller's stream, no side-stream fork (A/B),
- * | 0x40000000 = glowhip_glow_forward_train on the per-layer kernels instead of the taping k_cnet (A/B, parity tests),
- * | 0x80000000 = glowhip_glow_backward's input-gradient chain on the per-layer kernels instead of the backward k_cnet.
- * 0 restores automatic selection.
+/* Testing hook: forces kernel variants so that every one can be exercised at any batch size (parity tests, A/B runs).  The argument
+ * is an OR of the GLOWHIP_DBG_* values below; 0 restores automatic selection.
  * Process-wide, not thread safe: a testing hook, not part of the operator surface. */
+enum {
+    GLOWHIP_DBG_TAIL_TILE_MASK      = 0xff,       /* low byte: pixels per workgroup of the fused tail convolution (16/32/64/128; 0 = cost model) */
+    GLOWHIP_DBG_TAIL_MSPLIT         = 0x100,      /* tail convolution: always split the out-channel tiles over blockIdx.y */
+    GLOWHIP_DBG_TAIL_NO_MSPLIT      = 0x200,      /* ... never split them */
+    GLOWHIP_DBG_TAIL_NO_DMA         = 0x400,      /* ... no LDS-DMA tail kernels */
+    GLOWHIP_DBG_EXACT_FP32          = 0x800,      /* exact-fp32 MFMA kernels only (split-half f16 path off, training included) */
+    GLOWHIP_DBG_NO_MIXER_FUSION     = 0x8000,     /* k_squeeze + k_chanmix + a plain finishing kernel as separate launches (bitwise equal) */
+    GLOWHIP_DBG_NO_CNET1W           = 0x10000,    /* no k_cnet1w (one wave per SIMD, csrc/cnet1w_sh.hip): k_cnet takes its launches (A/B) */
+    GLOWHIP_DBG_CNET1W_ROW_SPLIT    = 0x20000,    /* k_cnet1w's row-split instance where it applies (C = 24 levels from 112 tiles of 128
+                                                     pixels; off by default: measured slower than k_cnet's 64-pixel tiles there) */
+    GLOWHIP_DBG_NO_CNET1W_BWD       = 0x40000,    /* no backward instance of k_cnet1w (level-1 input gradient back on k_cnet: A/B) */
+    GLOWHIP_DBG_WGRAD_NARROW        = 0x80000,    /* f.2's weight-gradient GEMM on 128-column tiles at every level (no k_wgrad_gemm_ps512) */
+    GLOWHIP_DBG_FUSED_FINISH        = 0x100000,   /* a k_cnet1w launch finishes its FlowStep itself (arrival counters per tile; bit-identical,
+                                                     off by default: measured slower) */
+    GLOWHIP_DBG_LU_WORKGROUP        = 0x200000,   /* log|det W| of the 12 / 24 / 48-wide matrices on the workgroup-wide LU (same bits: A/B) */
+    GLOWHIP_DBG_CNET_ROWS_SHIFT     = 22,         /* bits 22..24 = 1, 2 or 4: that many row splits of k_cnet (value << SHIFT) */
+    GLOWHIP_DBG_CNET_128_ONLY       = 0x2000000,  /* k_cnet with 128-pixel tiles only */
+    GLOWHIP_DBG_CNET_64             = 0x4000000,  /* k_cnet with 64-pixel tiles wherever supported */
+    GLOWHIP_DBG_CNET_CHAIN          = 0x8000000,  /* a FlowStep's finishing inside the next FlowStep's k_cnet (off by default: measured slower) */
+    GLOWHIP_DBG_CFINISH_BLOCK_ORDER = 0x10000000, /* the finishing kernel takes its pixel chunks in block order, not the XCD-affine order (A/B) */
+    GLOWHIP_DBG_PACK_ONE_STREAM     = 0x20000000, /* glowhip_plan_pack entirely on the caller's stream, no side-stream fork (A/B) */
+    GLOWHIP_DBG_TRAIN_PER_LAYER_FWD = 0x40000000, /* glowhip_glow_forward_train on the per-layer kernels, no taping k_cnet (A/B, parity tests) */
+    GLOWHIP_DBG_TRAIN_PER_LAYER_BWD = INT32_MIN   /* bit 31 (0x80000000 as the hook's int): glowhip_glow_backward's input-gradient chain on
+                                                     the per-layer kernels, no backward k_cnet */
+};
 void glowhip_debug_force_tail_tile(int pixels_and_flags);
 
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per

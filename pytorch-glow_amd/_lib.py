@@ -6,7 +6,9 @@ entry point raises, so a GPU test can never pass on a silent PyTorch path.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import enum
 import os
 import subprocess
 import threading
@@ -78,6 +80,45 @@ class TimingRecord(ctypes.Structure):
 
 
 K_CHANMIX, K_CONV_F0, K_CONV_F2, K_CONV_F4, K_OTHER = range(5)
+
+
+class DBG(enum.IntFlag):
+    """Mirror of the ``GLOWHIP_DBG_*`` values of include/glowhip.h: the argument of ``glowhip_debug_force_tail_tile`` (through
+    :func:`debug_flags`).  The tail convolution's pixel tile (16 / 32 / 64 / 128) is OR-ed in as a plain integer."""
+    TAIL_MSPLIT = 0x100
+    TAIL_NO_MSPLIT = 0x200
+    TAIL_NO_DMA = 0x400
+    EXACT_FP32 = 0x800
+    NO_MIXER_FUSION = 0x8000
+    NO_CNET1W = 0x10000
+    CNET1W_ROW_SPLIT = 0x20000
+    NO_CNET1W_BWD = 0x40000
+    WGRAD_NARROW = 0x80000
+    FUSED_FINISH = 0x100000
+    LU_WORKGROUP = 0x200000
+    CNET_128_ONLY = 0x2000000
+    CNET_64 = 0x4000000
+    CNET_CHAIN = 0x8000000
+    CFINISH_BLOCK_ORDER = 0x10000000
+    PACK_ONE_STREAM = 0x20000000
+    TRAIN_PER_LAYER_FWD = 0x40000000
+    TRAIN_PER_LAYER_BWD = 0x80000000
+
+
+DBG_CNET_ROWS_SHIFT = 22      # bits 22..24 = 1, 2 or 4 row splits of k_cnet: ``rows << DBG_CNET_ROWS_SHIFT``
+
+
+@contextlib.contextmanager
+def debug_flags(value):
+    """Run a block under ``glowhip_debug_force_tail_tile(value)`` (an OR of :class:`DBG` values, the tail tile and the row-split
+    field); automatic selection is restored on exit, whatever happens.  Process-wide, not thread safe: a testing hook."""
+    value = int(value) & 0xffffffff
+    lib().glowhip_debug_force_tail_tile(value - (1 << 32) if value >= (1 << 31) else value)      # bit 31 into the signed c_int
+    try:
+        yield
+    finally:
+        lib().glowhip_debug_force_tail_tile(0)
+
 
 _P = c_void_p
 # name -> (restype, argtypes); every symbol include/glowhip.h declares (tests/test_abi.py checks the two agree)

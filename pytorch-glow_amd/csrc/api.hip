@@ -3,9 +3,12 @@
 #include <stdio.h>
 
 #include "kernels.h"
-#include "conv_mfma.h"
+#include "debug_switches.h"
 
 namespace glowhip {
+static DebugSwitches g_debug;      // written by glowhip_debug_force_tail_tile alone
+const DebugSwitches& debug_switches() { return g_debug; }
+
 static thread_local char g_err[512] = "";
 void set_error(const char* fmt, ...) {
     va_list ap;
@@ -20,7 +23,30 @@ using namespace glowhip;
 extern "C" {
 
 int glowhip_version(void) { return GLOWHIP_VERSION; }
-void glowhip_debug_force_tail_tile(int pixels) { conv_mfma_tail_force_tile(pixels); }
+void glowhip_debug_force_tail_tile(int v) {
+    auto bit = [v](int flag) { return (v & flag) != 0; };
+    DebugSwitches d;
+    d.tail_tile = v & GLOWHIP_DBG_TAIL_TILE_MASK;
+    d.tail_msplit = bit(GLOWHIP_DBG_TAIL_MSPLIT) ? 1 : (bit(GLOWHIP_DBG_TAIL_NO_MSPLIT) ? 0 : -1);
+    d.tail_no_dma = bit(GLOWHIP_DBG_TAIL_NO_DMA);
+    d.exact_fp32 = bit(GLOWHIP_DBG_EXACT_FP32);
+    d.no_mixer_fusion = bit(GLOWHIP_DBG_NO_MIXER_FUSION);
+    d.no_cnet1w = bit(GLOWHIP_DBG_NO_CNET1W);
+    d.cnet1w_row_split = bit(GLOWHIP_DBG_CNET1W_ROW_SPLIT);
+    d.no_cnet1w_bwd = bit(GLOWHIP_DBG_NO_CNET1W_BWD);
+    d.wgrad_narrow = bit(GLOWHIP_DBG_WGRAD_NARROW);
+    d.fused_finish = bit(GLOWHIP_DBG_FUSED_FINISH);
+    d.lu_workgroup = bit(GLOWHIP_DBG_LU_WORKGROUP);
+    d.cnet_rows = (v >> GLOWHIP_DBG_CNET_ROWS_SHIFT) & 7;
+    d.cnet_128_only = bit(GLOWHIP_DBG_CNET_128_ONLY);
+    d.cnet_64 = bit(GLOWHIP_DBG_CNET_64);
+    d.cnet_chain = bit(GLOWHIP_DBG_CNET_CHAIN);
+    d.cfinish_block_order = bit(GLOWHIP_DBG_CFINISH_BLOCK_ORDER);
+    d.pack_one_stream = bit(GLOWHIP_DBG_PACK_ONE_STREAM);
+    d.train_per_layer_fwd = bit(GLOWHIP_DBG_TRAIN_PER_LAYER_FWD);
+    d.train_per_layer_bwd = bit(GLOWHIP_DBG_TRAIN_PER_LAYER_BWD);
+    g_debug = d;
+}
 const char* glowhip_last_error(void) { return g_err; }
 
 int glowhip_squeeze2d(const float* x, float* y, int N, int C, int H, int W, int factor, int reverse,

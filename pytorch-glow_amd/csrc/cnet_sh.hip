@@ -24,6 +24,7 @@
 #include "conv_mfma.h"
 #include "cnet_fin.h"
 #include "cnet_geo.h"
+#include "debug_switches.h"
 
 GH_STAMPS_DEFINE(cnet)
 GH_WGTIMES_DEFINE(cnet)
@@ -1089,10 +1090,6 @@ __global__ void __launch_bounds__(256) k_cfinish(CfinArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static int g_cnet_ms = 0, g_cnet_flags = 0;
-bool cnet_chain_enabled() { return (g_cnet_flags & 4) != 0; }
-void cnet_force(int ms, int flags) { g_cnet_ms = ms; g_cnet_flags = flags; }
-
 int cnet_g0(int Cin) { return (9 * ((Cin + 7) / 8) + 1) / 2 * 2; }   // 8-wide k groups of f.0, padded to whole k-steps (two groups each)
 int cnet_mpad4(int Cout) { return (9 * Cout + 31) / 32 * 32; }
 
@@ -1197,42 +1194,62 @@ static int launch_cnet_inst(const CnetArgs& a, const CnetGeo& g, hipStream_t s) 
     return GLOWHIP_OK;
 }
 
-// tile size, row split and T units per wave of a launch
-static bool cnet_select(const CnetArgs& a, CnetGeo* gout, int* ms_out, int* upw_out) {
+// 128-pixel tiles are taken from this many tiles on (they alone then give every CU a workgroup); it is also the first count at which
+// k_cnet1w takes a taping / backward launch
+constexpr int CN_TILES_128 = 224;
+// k_cnet1w's row-split instance (debug switch only): 128-pixel tiles from this many tiles on -- the C = 24 levels that otherwise run
+// one 64-pixel k_cnet workgroup per CU
+constexpr int CN1W_SPLIT_TILES = 112;
+// the h2 rows are split over more workgroups per tile while a launch has fewer workgroups than this
+constexpr int CN_MS_FILL_WGS = 160;
+
+// The complete decision for a launch: tile geometry, row split, T units per wave, and whether it goes to k_cnet1w (one wave per
+// SIMD, cnet1w_sh.hip) instead of k_cnet
+struct CnetChoice { CnetGeo g; int ms, upw; bool one_wave; };
+
+static bool cnet_select(const CnetArgs& a, CnetChoice* out) {
+    const DebugSwitches& sw = debug_switches();
     // Tile size and row split.  128-pixel tiles halve the weight bytes per MFMA and are taken whenever they alone give every CU a
     // workgroup.  Below that, 64-pixel tiles double the workgroup count without recomputing anything; splitting the h2 rows over
     // MS workgroups per tile (each recomputing h1) comes last.
-    CnetGeo g128, g64, g;
+    CnetGeo g128, g64;
     const bool ok128 = cnet_geo(a.Cin, a.H, a.W, a.hidden, a.Cout, a.N, 128, &g128);
     const bool ok64 = cnet_geo(a.Cin, a.H, a.W, a.hidden, a.Cout, a.N, 64, &g64);
     if (!ok128 && !ok64) return false;
-    bool use64 = !ok128 || (ok64 && g128.tiles < 224);
-    if (g_cnet_flags & 1) use64 = !ok128;      // testing: 128-pixel tiles wherever they exist
-    if (g_cnet_flags & 2) use64 = ok64;        // testing: 64-pixel tiles wherever they exist
+    bool use64 = !ok128 || (ok64 && g128.tiles < CN_TILES_128);
+    if (sw.cnet_128_only) use64 = !ok128;      // testing: 128-pixel tiles wherever they exist
+    if (sw.cnet_64) use64 = ok64;              // testing: 64-pixel tiles wherever they exist
+    // k_cnet1w (one wave per SIMD, cnet1w_sh.hip): which launches may go to it at all (the shape's say is cnet1w_takes), whether the
+    // 128-pixel tiles it needs may be preferred for it, and its row-split instance only behind its switch
+    const bool c1w_kind = !a.pre_on && !sw.no_cnet1w && !(a.bwd && sw.no_cnet1w_bwd);      // (no_cnet1w_bwd: no backward instance, A/B)
+    const bool c1w_tile = c1w_kind && ok128 && !sw.cnet_64;
+    const bool c1w_split_on = sw.cnet1w_row_split && !sw.cnet_rows;
     // taping / backward launches: the 128-pixel instance is at the register limit and spills once the stores and the sign words
     // are in (184 B); 64-pixel tiles measured 2 % faster on the training step
-    if (a.tape_h1 && ok64 && !(g_cnet_flags & 1)) use64 = true;
+    if (a.tape_h1 && ok64 && !sw.cnet_128_only) use64 = true;
     // ... except where the one-wave-per-SIMD kernel takes the taping forward (cnet1w_sh.hip: its registers hold the 128-pixel tile)
-    const bool c1w_ok = ok128 && !a.pre_on && !(g_cnet_flags & (2 | 16));
-    if (a.tape_h1 && c1w_ok && g128.tiles >= 224 && !(a.bwd && (g_cnet_flags & 64)) && cnet1w_takes(a, g128, 1)) use64 = false;      // (flag 64: no backward instance, A/B)
+    if (a.tape_h1 && c1w_tile && g128.tiles >= CN_TILES_128 && cnet1w_takes(a, g128, 1)) use64 = false;
     // ... and, behind the debug switch 0x20000 only, that kernel's instance with the h2 rows split over two workgroups (128-pixel tiles
     // from 112 tiles on: the C = 24 levels that otherwise run one 64-pixel k_cnet workgroup per CU).  Measured slower than k_cnet
     // where it applies -- 47.0 against 45.5 us per launch at config B's level 2, 176 against 150 us at config E's (DESIGN.md 3.2:
     // each half computes all of f.0 again, 29 % of its MFMAs) -- so it is not selected by default; the parity tests run it.
-    bool c1w_split = false;
-    if (c1w_ok && !a.bwd && !g_cnet_ms && (g_cnet_flags & 32) && g128.tiles >= 112 && cnet1w_takes(a, g128, 2)) { use64 = false; c1w_split = true; }
-    g = use64 ? g64 : g128;
+    const bool c1w_split = c1w_tile && !a.bwd && c1w_split_on && g128.tiles >= CN1W_SPLIT_TILES && cnet1w_takes(a, g128, 2);
+    if (c1w_split) use64 = false;
+    const CnetGeo& g = use64 ? g64 : g128;
     int ms = 1;
     const int ms_max = std::min(CN_MAXMS, a.hidden / (use64 ? 128 : 64));
-    while (ms < ms_max && g.tiles * ms < 160) ms *= 2;
-    if (g_cnet_ms) ms = std::min(g_cnet_ms, ms_max);
+    while (ms < ms_max && g.tiles * ms < CN_MS_FILL_WGS) ms *= 2;
+    if (sw.cnet_rows) ms = std::min(sw.cnet_rows, ms_max);
     // T units per wave: (unit rows of T) x (k parts) over 8 waves.  Two units per wave next to the 128 accumulator registers of
     // a 512-row x 128-pixel h2 block would spill: that combination runs with the rows split in two
     const int upw = g.NU4 * g.KS > 8 ? 2 : 1;
     if (upw == 2 && a.hidden == 512 && ms == 1 && !use64) ms = 2;
     while ((a.hidden / ms / 16) / g.KS < 1 && ms > 1) ms /= 2;
     if (c1w_split) ms = 2;
-    *gout = g; *ms_out = ms; *upw_out = upw;
+    // one wave per SIMD wherever an instance exists for the launch: forward / inverse / taping forward / backward, 128-pixel tiles, no
+    // row split but the one of its row-split instance
+    const bool one_wave = c1w_kind && g.pxt == 128 && cnet1w_takes(a, g, ms) && (ms != 2 || c1w_split_on);
+    *out = CnetChoice{g, ms, upw, one_wave};
     return true;
 }
 
@@ -1245,9 +1262,9 @@ bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N) {
     CnetArgs a{};
     a.Cin = Cin; a.H = H; a.W = W; a.hidden = hidden; a.Cout = Cout; a.N = N;
     a.tape_h1 = reinterpret_cast<float*>(16);      // (selection only: taping launches have their own tile preference)
-    CnetGeo g; int ms, upw;
-    if ((H * W) % 32 != 0 || !cnet_select(a, &g, &ms, &upw)) return false;
-    return cnet_tape_instance(hidden, ms, upw, g.pxt, g.ng);
+    CnetChoice c;
+    if ((H * W) % 32 != 0 || !cnet_select(a, &c)) return false;
+    return cnet_tape_instance(hidden, c.ms, c.upw, c.g.pxt, c.g.ng);
 }
 
 template <int HID, int MS, int PXT, int MODE>
@@ -1263,20 +1280,19 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     GH_REQUIRE(a.mode == TAIL_AFFINE_FWD || a.mode == TAIL_AFFINE_REV || a.mode == TAIL_ADD_FWD || a.mode == TAIL_ADD_REV,
                "cnet: coupling modes only");
     if (a.N == 0) return GLOWHIP_OK;
-    CnetGeo g; int ms, upw;
-    GH_REQUIRE(cnet_select(a, &g, &ms, &upw), "cnet: unsupported shape");
+    CnetChoice c;
+    GH_REQUIRE(cnet_select(a, &c), "cnet: unsupported shape");
+    const CnetGeo& g = c.g;
+    const int ms = c.ms, upw = c.upw;
     GH_REQUIRE(!a.pre_on || a.pre.MS == ms, "cnet: a chained launch needs the previous step's row split");
     const bool tape = a.tape_h1 != nullptr;
     GH_REQUIRE(!tape || (a.tape_h2 && a.mask1 && a.mask2 && !a.pre_on && g.HW % 32 == 0 &&
                          cnet_tape_instance(a.hidden, ms, upw, g.pxt, g.ng)),
                "cnet: no taping / backward instance for this launch");
     int rc = GLOWHIP_EINVAL;
-    // one wave per SIMD (cnet1w_sh.hip) wherever an instance exists for the launch: forward / inverse / taping forward, 128-pixel tiles, no row split
-    bool one_wave = false;
-    if (!a.pre_on && g.pxt == 128 && !(g_cnet_flags & 16) && !(a.bwd && (g_cnet_flags & 64)) && cnet1w_takes(a, g, ms) && !(ms == 2 && (g_cnet_ms || !(g_cnet_flags & 32)))) {
+    if (c.one_wave) {
         GH_TRY(launch_cnet1w(a, g, ms, s));
         rc = GLOWHIP_OK;
-        one_wave = true;
     }
 #define GH_CNT(hid, m, px)                                                                                     \
     if (rc == GLOWHIP_EINVAL && tape && a.hidden == hid && ms == m && g.pxt == px)                             \
@@ -1302,8 +1318,8 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
         out->bias = a.bias; out->scale = a.scale; out->mode = a.mode; out->Cout = a.Cout;
         out->z = a.pre_on ? a.pre_z_new : a.z_in;
         out->z_bs = a.pre_on ? a.pre_z_new_bs : a.z_in_bs;
-        out->one_wave = one_wave ? 1 : 0;
-        out->finished = one_wave && cnet1w_finishes(a, g, ms) ? 1 : 0;      // (launch_cnet1w took the fused-finishing instance)
+        out->one_wave = c.one_wave ? 1 : 0;
+        out->finished = c.one_wave && cnet1w_finishes(a, g, ms) ? 1 : 0;      // (launch_cnet1w took the fused-finishing instance)
     }
     return GLOWHIP_OK;
 }
@@ -1311,7 +1327,7 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
 int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s) {
     if (a.N == 0) return GLOWHIP_OK;
     const int HW = a.H * a.W;
-    CfinArgs f{p, a.mix, a.z_out, a.z_out_bs, a.acc, a.N, a.H, a.W, HW, __builtin_ctz(a.W), (g_cnet_flags & 8) ? 0 : 1, a.tape_hout};
+    CfinArgs f{p, a.mix, a.z_out, a.z_out_bs, a.acc, a.N, a.H, a.W, HW, __builtin_ctz(a.W), debug_switches().cfinish_block_order ? 0 : 1, a.tape_hout};
     const bool paired = p.mode == TAIL_AFFINE_FWD || p.mode == TAIL_AFFINE_REV;
     const int C = 2 * (paired ? p.Cout / 2 : p.Cout);
     GH_REQUIRE(a.mix.C == 0 || a.mix.C == C, "cnet: mixer channel count %d != %d", a.mix.C, C);
@@ -1341,7 +1357,7 @@ int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s) {
 int launch_cnet(const CnetArgs& a, hipStream_t s) {
     CnetPending p{};
     GH_TRY(launch_cnet_main(a, s, &p));
-    if (a.N == 0) return GLOWHIP_OK;
+    if (a.N == 0 || p.finished) return GLOWHIP_OK;      // (a launch that finished the step itself leaves nothing for k_cfinish)
     return launch_cnet_finish(a, p, s);
 }
 

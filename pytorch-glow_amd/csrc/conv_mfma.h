@@ -16,8 +16,6 @@ int launch_conv_mfma_wide(const float* x, long x_bs, const float* wt, const floa
                           float* y, int N, int Cin, int H, int W, int Cout, int ksize, hipStream_t s, int relu = 1,
                           float* splitk_scratch = nullptr, size_t splitk_floats = 0);
 
-void conv_mfma_wide_disable_glds(int off);  // testing hook: 1 = use the register-staged k_conv_wide for 1x1 too
-
 // f.0 with a stationary LDS pixel window (conv_mfma_first.hip): Cin a multiple of 6 (C/2 of every Glow level).
 bool conv_mfma_first_supported(int Cin, int H, int W, int Cout);
 size_t conv_mfma_first_packed_bytes(int Cin, int Cout);
@@ -71,14 +69,7 @@ size_t conv_mfma_tail_packed_bytes(int Cin, int Cout);
 int conv_mfma_tail_pack(const float* w, int Cin, int Cout, int paired, float* wp, hipStream_t s);
 int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s);
 bool conv_mfma_tail_takes_dma(const TailConvArgs& a);   // which of the two tail kernels launch_conv_mfma_tail picks for `a`
-void conv_mfma_tail_force_tile(int tp);
-void plan_disable_sh(int off);   // testing hook (plan.hip)
-void plan_pack_one_stream(int on);   // testing hook (plan.hip): glowhip_plan_pack without its side-stream fork
-void plan_train_disable_sh(int off);   // testing hook (plan_train.hip)
-void plan_train_disable_cnet(int off); // testing hook (plan_train.hip): the training forward without the taping k_cnet
-void wgrad_force_narrow(int on);          // testing hook (wgrad_mfma.hip): f.2's weight-gradient GEMM on 128-column tiles everywhere (A/B)
-void plan_train_disable_cnet_bwd(int off); // testing hook (plan_train.hip): the input-gradient chain without the backward k_cnet
 int launch_tail_dma_narrow(const TailConvArgs& a, int paired, hipStream_t s, int TP, int Y);  // W in {8,16}
-int launch_tail_dma_wide(const TailConvArgs& a, int paired, hipStream_t s, int TP, int Y);    // W in {32,64,128}  // testing hook: 0 = automatic, else 16/32/64/128 pixels per block
+int launch_tail_dma_wide(const TailConvArgs& a, int paired, hipStream_t s, int TP, int Y);    // W in {32,64,128}
 
 }  // namespace glowhip

@@ -355,11 +355,8 @@ k_gemm_glds(const float* __restrict__ X, long x_bs, const float* __restrict__ Wt
     }
 }
 
-static bool g_disable_glds = false;   // testing hook
-void conv_mfma_wide_disable_glds(int off) { g_disable_glds = off != 0; }
-
 static bool gemm_glds_ok(int Cin, int HW, int Cout, long total_px) {
-    return !g_disable_glds && Cout % GL_BM == 0 && Cin % GL_BK == 0 && Cin >= 3 * GL_BK && HW % 4 == 0 &&
+    return Cout % GL_BM == 0 && Cin % GL_BK == 0 && Cin >= 3 * GL_BK && HW % 4 == 0 &&
            total_px % GL_BN == 0;
 }
 

@@ -11,7 +11,7 @@
 // the two 16-lane pixel runs of a ds_read_b32 half-wave fall on disjoint banks.  A tap is an LDS address
 // offset; nothing is expanded (no im2col), each input element is fetched from HBM once per block.
 #include "conv_mfma_tail_dma.h"
-#include "sh.h"
+#include "debug_switches.h"
 
 namespace glowhip {
 
@@ -19,9 +19,6 @@ namespace glowhip {
 // waves are arranged WN (pixel tiles) x WK (K-split: wave wk takes channel groups c4 = wk, wk+WK, ...), partial
 // sums of the WK waves are reduced through LDS before the epilogue.  Smaller tiles + K-split keep >= 2 blocks per
 // CU on the deep levels (8x8 images: 4096 pixels per step) where a 128-pixel tile would occupy 1/4 of the chip.
-static int g_force_tp = 0;      // testing hooks (glowhip_debug_force_tail_tile): pixels per block, 0 = automatic
-static int g_force_msplit = -1; // -1 automatic, 0 never, 1 always split the out-channel tiles over blockIdx.y
-static bool g_disable_tail_dma = false;
 // register-staged kernels: the halo tile must fit the 6-float4 staging registers
 static bool tp_ok_reg(int tp, int H, int W) {
     if (tp % W != 0 || (H * W) % tp != 0) return false;
@@ -29,7 +26,7 @@ static bool tp_ok_reg(int tp, int H, int W) {
 }
 // LDS-DMA kernels: instantiated widths, 16-channel chunks, 3 stages within the 160 KiB LDS
 static bool tp_ok_dma(int tp, int H, int W, int Cin) {
-    if (g_disable_tail_dma || Cin % 16 != 0 || Cin < 32) return false;
+    if (debug_switches().tail_no_dma || Cin % 16 != 0 || Cin < 32) return false;
     if (W != 8 && W != 16 && W != 32 && W != 64 && W != 128) return false;
     if (tp % W != 0 || (H * W) % tp != 0) return false;
     const int xf = (16 * tail_chs(tp / W, W) + 255) / 256 * 256;
@@ -45,9 +42,10 @@ static TailChoice tail_choose(int H, int W, long total_px, int Cin, int mt_total
     const int cand[4] = {128, 64, 32, 16};
     TailChoice best{0, 0};
     double best_cost = 1e30;
+    const int force_tp = debug_switches().tail_tile, force_msplit = debug_switches().tail_msplit;
     for (int ms = 0; ms <= 1; ++ms) {
         if (ms == 1 && mt_total == 1) continue;
-        if (g_force_msplit >= 0 && ms != g_force_msplit && mt_total > 1) continue;
+        if (force_msplit >= 0 && ms != force_msplit && mt_total > 1) continue;
         for (int i = 0; i < 4; ++i) {
             const int tp = cand[i];
             // a DMA-only tile needs the out-channel split (MT == 1 kernels); more than 3 tiles per block do not exist
@@ -55,7 +53,7 @@ static TailChoice tail_choose(int H, int W, long total_px, int Cin, int mt_total
             if (!(reg || dmaok)) continue;
             const int mt_blk = ms ? 1 : mt_total;
             if (mt_blk > 3 || (!reg && mt_blk != 1)) continue;
-            if (g_force_tp && tp != g_force_tp && tp_ok(g_force_tp, H, W, Cin)) continue;
+            if (force_tp && tp != force_tp && tp_ok(force_tp, H, W, Cin)) continue;
             const int wk = tp >= 64 ? 1 : (tp == 32 ? 2 : 4), ntw = tp == 128 ? 2 : 1;
             const int mt_b = ms ? 1 : mt_total;
             const double blocks = (double)(total_px / tp) * (ms ? mt_total : 1);
@@ -346,24 +344,6 @@ int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s) {
 #undef GH_TAIL_TP
     set_error("conv_mfma_tail: no kernel for MT=%d TP=%d", MT, TP);
     return GLOWHIP_EINVAL;
-}
-
-// testing hook: tp = pixels per block (0 automatic); bit 8 set => force msplit on (0x100 | tp), bit 9 => force off
-void conv_mfma_tail_force_tile(int v) {
-    g_force_tp = v & 0xff;
-    g_force_msplit = (v & 0x100) ? 1 : ((v & 0x200) ? 0 : -1);
-    g_disable_tail_dma = (v & 0x400) != 0;   // | 0x400: register-staged kernels only
-    // 0x800: the split-half path off (every coupling network on the exact-fp32 kernels, training included); 0x8000: no mixer of the
-    // next step inside the finishing kernel and no squeeze folded into a mixer (the fused and the separate forms must agree bit for bit)
-    // 0x100000: FUSED finishing on (k_cnet1w finishing the step itself instead of a k_cfinish launch; off by default: measured slower)
-    // 0x200000: log|det W| of the small invconv matrices on the workgroup-wide LU instead of one wave per matrix (lu.hip; same bits)
-    plan_disable_sh(((v & 0x800) ? 1 : 0) | ((v & 0x8000) ? 16 : 0) | ((v & 0x100000) ? 32 : 0) | ((v & 0x200000) ? 64 : 0));
-    cnet_force((v >> 22) & 7, ((v >> 25) & 15) | ((v & 0x10000) ? 16 : 0) | ((v & 0x20000) ? 32 : 0) | ((v & 0x40000) ? 64 : 0));   // 0x40000: no backward instance of k_cnet1w;   // 0x10000: no k_cnet1w (one wave per SIMD); 0x20000: its row-split instance where it applies (off by default: measured slower);   // bits 22..24: row splits; bit 25: 128-pixel tiles only, bit 26: 64-pixel tiles, bit 27: finishing chained into the next k_cnet, bit 28: finishing kernel without the XCD-affine chunk order
-    plan_train_disable_sh((v & 0x800) ? 1 : 0);
-    wgrad_force_narrow((v & 0x80000) ? 1 : 0);           // 0x80000: f.2's weight-gradient GEMM on 128-column tiles everywhere
-    plan_pack_one_stream((v & 0x20000000) ? 1 : 0);      // bit 29: glowhip_plan_pack entirely on the caller's stream (A/B)
-    plan_train_disable_cnet((v & 0x40000000) ? 1 : 0);   // bit 30: training forward on the per-layer kernels (no taping k_cnet)
-    plan_train_disable_cnet_bwd(((unsigned)v & 0x80000000u) ? 1 : 0);   // bit 31: input-gradient chain on the per-layer kernels
 }
 
 }  // namespace glowhip

@@ -75,23 +75,8 @@ static int carve(const glowhip_plan* p, int N, void* ws, size_t bytes, Workspace
 // ---------------------------------------------------------------- coupling network f() (network/module.py:300-319)
 // Runs conv3x3 -> actnorm -> relu -> conv1x1 -> actnorm -> relu -> conv3x3(zeros) and applies the
 // coupling to z2.  x1: first-half channels (batch stride x1_bs).
-static bool g_pack_one_stream = false;     // testing hook: glowhip_plan_pack without the side-stream fork
-void plan_pack_one_stream(int on) { g_pack_one_stream = on != 0; }
-static bool g_sh_disabled = false, g_sh_mix_disabled = false, g_fuse_finish_off = true, g_lu_small_off = false;
-void plan_disable_sh(int off) {
-    g_sh_disabled = (off & 1) != 0;        // the whole split-half path off: every coupling network on the exact-fp32 MFMA kernels
-    g_sh_mix_disabled = (off & 16) != 0;   // no mixer of the next step inside the finishing kernel, no squeeze folded into a mixer
-    // FUSED FINISHING (k_cnet1w finishing the step itself, cnet1w_sh.hip FIN) is OFF unless asked for: built, bit-identical to the
-    // finishing kernel (tests/test_gpu_fused.py), and measured SLOWER -- 7.68 against 6.80 ms per config-B forward, + 27 us per level-1
-    // launch: every workgroup arrives last at about one tile, so every CU pays the finishing's latency chain
-    // (store drain, counter round trip, a read-around-L2 round trip per 64-pixel chunk) twice per launch, one workgroup at a time,
-    // where the finishing kernel runs four workgroups per CU side by side.
-    g_fuse_finish_off = (off & 32) == 0;
-    g_lu_small_off = (off & 64) != 0;      // log|det W| of the small matrices on the workgroup-wide LU (A/B and bitwise test of the one-wave form)
-}
-
 // split-half f16 kernels off for this plan: its own family (glowhip_plan_set_family) or the process-wide testing hook
-static bool sh_off(const glowhip_plan* p) { return g_sh_disabled || (p && p->family == GLOWHIP_FAMILY_EXACT_FP32); }
+static bool sh_off(const glowhip_plan* p) { return debug_switches().exact_fp32 || (p && p->family == GLOWHIP_FAMILY_EXACT_FP32); }
 static bool cnet_runs(const glowhip_plan* p, const LayerPlan& L) { return L.cnet && !sh_off(p); }
 
 // deep levels (dnet_sh.hip): layers k_cnet does not take, with an invertible 1x1 convolution, on the product family
@@ -108,9 +93,6 @@ static int dnet_run_end(const glowhip_plan* p, int li, int dir) {
         lj += dir;
     }
     return lj;
-}
-static int tail_mode(const glowhip_layer_desc& d, int reverse) {
-    return d.coupling == GLOWHIP_COUPLING_AFFINE ? (reverse ? TAIL_AFFINE_REV : TAIL_AFFINE_FWD) : (reverse ? TAIL_ADD_REV : TAIL_ADD_FWD);
 }
 // One level's run of FlowSteps [li .. lj] (encode) on the deep-level kernels: PREP, then MIX -> F0 -> F2 -> F4 -> FIN per step; the
 // result is left in `S` (N, C, H, W).
@@ -194,8 +176,7 @@ static CnetArgs cnet_base(const LayerPlan& L, const void* packed, int N, int rev
     c.N = N; c.Cin = d.C / 2; c.H = d.H; c.W = d.W; c.hidden = d.hidden; c.Cout = L.Cout;
     c.scratch = scratch;
     c.bias = d.f4_bias; c.scale = at<float>(packed, L.f4_scale);
-    c.mode = d.coupling == GLOWHIP_COUPLING_AFFINE ? (reverse ? TAIL_AFFINE_REV : TAIL_AFFINE_FWD)
-                                                   : (reverse ? TAIL_ADD_REV : TAIL_ADD_FWD);
+    c.mode = tail_mode(d, reverse);
     c.acc = w.acc;
     return c;
 }
@@ -205,23 +186,30 @@ static void count_cnet_variant(glowhip_plan* p, const CnetArgs& c, const CnetPen
     snprintf(name, sizeof name, "variant:k_cnet%s<%d,%d,%d>", pend.one_wave ? "1w" : "", c.hidden, pend.MS, 1 << pend.lpxt);
     count_launch(p, name);
 }
-static CnetMixer mixer_fwd(const LayerPlan& L, const void* packed) {      // ActNorm + permutation of step L, forward
-    const glowhip_layer_desc& d = L.d;
-    return CnetMixer{d.C, 0, d.an_bias, at<float>(packed, L.an_scale), d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
-                     d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr};
-}
-static CnetMixer mixer_rev(const LayerPlan& L, const void* packed) {      // permutation^-1 + ActNorm^-1 of step L
-    const glowhip_layer_desc& d = L.d;
-    return CnetMixer{d.C, 1, d.an_bias, at<float>(packed, L.an_inv_scale),
-                     d.permutation == GLOWHIP_PERM_INVCONV ? at<float>(packed, L.winv) : nullptr,
-                     d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr};
+// One FlowStep's k_cnet launch (`pending`: it also finishes the previous step) and, with `finish`, this step's finishing: by the
+// launch itself where it took the offer (fused finishing, sh.h CnetArgs::fin_cnt), by the finishing kernel otherwise.
+static int run_cnet_step(glowhip_plan* p, const CnetArgs& c, bool pending, bool finish, CnetPending* pend, hipStream_t s) {
+    {
+        ScopedTimer t(p, GLOWHIP_K_CNET, 1, s);
+        count_launch(p, pending ? "k_cnet+prev_finish" : "k_cnet");
+        GH_TRY(launch_cnet_main(c, s, pend));
+        count_cnet_variant(p, c, *pend);
+    }
+    if (!finish) return GLOWHIP_OK;
+    if (pend->finished) {
+        count_launch(p, "k_cnet(finishes the step)");
+        return GLOWHIP_OK;
+    }
+    ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
+    count_launch(p, c.mix.C ? "k_cfinish+mixer" : "k_cfinish");
+    return launch_cnet_finish(c, *pend, s);
 }
 // may the finishing step of layer A run inside layer B's k_cnet?  (Off by default: the window-time finishing costs a workgroup
 // ~25 k cycles of dependent global round trips with 8 waves, more than the ~10 us finishing kernel it saves; kept behind
 // glowhip_debug_force_tail_tile(0x8000000) with its bitwise-equality test.)
 static bool cnet_chain(const glowhip_plan* p, const LayerPlan& A, const LayerPlan& B) {
     const glowhip_layer_desc& a = A.d; const glowhip_layer_desc& b = B.d;
-    return cnet_chain_enabled() && !g_sh_mix_disabled && a.kind == GLOWHIP_LAYER_FLOWSTEP && b.kind == GLOWHIP_LAYER_FLOWSTEP &&
+    return debug_switches().cnet_chain && !debug_switches().no_mixer_fusion && a.kind == GLOWHIP_LAYER_FLOWSTEP && b.kind == GLOWHIP_LAYER_FLOWSTEP &&
            cnet_runs(p, A) && cnet_runs(p, B) && a.C == b.C && a.H == b.H && a.W == b.W && a.coupling == b.coupling &&
            cnet_pre_supported(b.C / 2, b.H, b.W, b.hidden, B.Cout, b.C);
 }
@@ -270,8 +258,7 @@ static int run_coupling(glowhip_plan* P, const LayerPlan& L, const void* packed,
         t.x = w.h2; t.x_bs = (long)hid * HW; t.wp = at<float>(packed, L.f4_wp); t.bias = d.f4_bias;
         t.scale = at<float>(packed, L.f4_scale);
         t.N = N; t.Cin = hid; t.H = d.H; t.W = d.W; t.Cout = L.Cout;
-        t.mode = d.coupling == GLOWHIP_COUPLING_AFFINE ? (reverse ? TAIL_AFFINE_REV : TAIL_AFFINE_FWD)
-                                                       : (reverse ? TAIL_ADD_REV : TAIL_ADD_FWD);
+        t.mode = tail_mode(d, reverse);
         t.z2_in = z2_in; t.z2_in_bs = z2_in_bs; t.z2_out = z2_out; t.z2_out_bs = z2_out_bs; t.acc = w.acc;
         t.zeros = at<float>(packed, 64);   // zero block kept by glowhip_plan_pack
         count_launch(P, "k_conv_tail_f32");
@@ -356,7 +343,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
         if (d.kind == GLOWHIP_LAYER_SQUEEZE) {
             const bool u8 = x_u8 != nullptr && li == 0;
             bool foldable = false;
-            if (!g_sh_mix_disabled && li + 1 < nl - 1 && d.W % 2 == 0) {
+            if (!debug_switches().no_mixer_fusion && li + 1 < nl - 1 && d.W % 2 == 0) {
                 const LayerPlan& Ln = p->layers[li + 1];
                 foldable = Ln.d.kind == GLOWHIP_LAYER_FLOWSTEP && !dnet_runs(p, Ln) && chanmix_squeeze_foldable(Ln.d.C);
             }
@@ -400,13 +387,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                     cur = nxt;
                 } else {
                     if (!premixed) {
-                        ChanMixArgs m{};
-                        m.in_a = cur; m.in_a_bs = chw; m.in_b = cur + (long)Ch * HW; m.in_b_bs = chw; m.Ca = Ch;
-                        m.out = dst; m.out_bs = chw;
-                        m.bias = d.an_bias; m.scale = at<float>(packed, L.an_scale);
-                        m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr;
-                        m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr;
-                        m.reverse = 0; m.N = N; m.C = d.C; m.HW = HW;
+                        ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
                         if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; fold = SqueezeFold{}; }
                         ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
                         count_launch(p, "k_chanmix");
@@ -420,7 +401,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 float* out = (li == nl - 1) ? z_out : const_cast<float*>(cur);
                 if (!chain) {   // the step is finished right behind its k_cnet: with the NEXT step's mixer when that is a same-shape FlowStep
                     c.z_out = out; c.z_out_bs = chw;
-                    if (li + 1 < nl - 1 && !g_sh_mix_disabled && d.C <= 96) {
+                    if (li + 1 < nl - 1 && !debug_switches().no_mixer_fusion && d.C <= 96) {
                         const LayerPlan& Ln = p->layers[li + 1];
                         const glowhip_layer_desc& dn = Ln.d;
                         if (dn.kind == GLOWHIP_LAYER_FLOWSTEP && dn.C == d.C && dn.H == d.H && dn.W == d.W) {
@@ -429,38 +410,18 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                         }
                     }
                     // ... by the launch itself where it can (fused finishing, sh.h CnetArgs::fin_cnt; per-launch event timing keeps the two apart)
-                    if (!g_fuse_finish_off && !p->timing) c.fin_cnt = w.fin_cnt;
+                    if (debug_switches().fused_finish && !p->timing) c.fin_cnt = w.fin_cnt;
                 }
-                {
-                    ScopedTimer t(p, GLOWHIP_K_CNET, 1, s);
-                    count_launch(p, pending ? "k_cnet+prev_finish" : "k_cnet");
-                    GH_TRY(launch_cnet_main(c, s, &pend));
-                    count_cnet_variant(p, c, pend);
-                }
+                GH_TRY(run_cnet_step(p, c, pending, !chain, &pend, s));
                 pending = chain;
-                if (!chain) {
-                    if (pend.finished) {
-                        count_launch(p, "k_cnet(finishes the step)");
-                    } else {
-                        ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
-                        count_launch(p, c.mix.C ? "k_cfinish+mixer" : "k_cfinish");
-                        GH_TRY(launch_cnet_finish(c, pend, s));
-                    }
-                    cur = out;
-                }
+                if (!chain) cur = out;
                 continue;
             }
             if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
                 if (premixed) {
                     dst = const_cast<float*>(cur);   // the step runs in place on the already mixed buffer
                 } else {
-                    ChanMixArgs m{};
-                    m.in_a = cur; m.in_a_bs = chw; m.in_b = cur + (long)Ch * HW; m.in_b_bs = chw; m.Ca = Ch;
-                    m.out = dst; m.out_bs = chw;
-                    m.bias = d.an_bias; m.scale = at<float>(packed, L.an_scale);
-                    m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr;
-                    m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr;
-                    m.reverse = 0; m.N = N; m.C = d.C; m.HW = HW;
+                    ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
                     if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; fold = SqueezeFold{}; }
                     ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
                     count_launch(p, "k_chanmix");
@@ -530,25 +491,12 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                 if (!chain && d.C <= 96) {      // (as in run_forward: the finishing's arguments are there at launch time, the launch may do it)
                     fout = (li == 0) ? x_out : other_buf(w, cur);
                     c.z_out = fout; c.z_out_bs = chw; c.mix = mixer_rev(L, packed);
-                    if (!g_fuse_finish_off && !p->timing) c.fin_cnt = w.fin_cnt;
+                    if (debug_switches().fused_finish && !p->timing) c.fin_cnt = w.fin_cnt;
                 }
-                {
-                    ScopedTimer t(p, GLOWHIP_K_CNET, 1, s);
-                    count_launch(p, pending ? "k_cnet+prev_finish" : "k_cnet");
-                    GH_TRY(launch_cnet_main(c, s, &pend));
-                    count_cnet_variant(p, c, pend);
-                }
+                GH_TRY(run_cnet_step(p, c, pending, fout != nullptr, &pend, s));      // (its mixer is set: the finishing counts as "k_cfinish+mixer")
                 pending = chain;
-                if (!chain && d.C <= 96) {
-                    float* out = fout;
-                    if (pend.finished) {
-                        count_launch(p, "k_cnet(finishes the step)");
-                    } else {
-                        ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
-                        count_launch(p, "k_cfinish+mixer");
-                        GH_TRY(launch_cnet_finish(c, pend, s));
-                    }
-                    cur = out;
+                if (fout) {
+                    cur = fout;
                 } else if (!chain) {
                     // wider than the finishing kernel's mixer (additive coupling, 96 < C <= 112: L.cnet holds, the fused mixer
                     // does not): coupling^-1 alone by the finishing kernel, then permutation^-1 + ActNorm^-1 by k_chanmix
@@ -560,13 +508,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                         GH_TRY(launch_cnet_finish(c, pend, s));
                     }
                     float* out = (li == 0) ? x_out : other_buf(w, mid);
-                    ChanMixArgs m{};
-                    m.in_a = mid; m.in_a_bs = chw; m.in_b = mid + (long)Ch * HW; m.in_b_bs = chw; m.Ca = Ch;
-                    m.out = out; m.out_bs = chw;
-                    m.bias = d.an_bias; m.scale = at<float>(packed, L.an_inv_scale);
-                    m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? at<float>(packed, L.winv) : nullptr;
-                    m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr;
-                    m.reverse = 1; m.N = N; m.C = d.C; m.HW = HW;
+                    ChanMixArgs m = chanmix_rev_args(L, packed, N, mid, mid + (long)Ch * HW, chw, out);
                     ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
                     count_launch(p, "k_chanmix");
                     GH_TRY(launch_chanmix(m, s));
@@ -579,13 +521,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
             // over workgroups (config E's 4x4 level: 16 workgroups of 384 outputs each took 350 us per step with the alias)
             if (cur == w.bufA || cur == w.bufB) z2 = const_cast<float*>(cur) + (long)Ch * HW;
             GH_TRY(run_coupling(p, L, packed, cur, chw, cur + (long)Ch * HW, chw, z2, chw, N, 1, w, s));
-            ChanMixArgs m{};
-            m.in_a = cur; m.in_a_bs = chw; m.in_b = z2; m.in_b_bs = chw; m.Ca = Ch;
-            m.out = dst; m.out_bs = chw;
-            m.bias = d.an_bias; m.scale = at<float>(packed, L.an_inv_scale);
-            m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? at<float>(packed, L.winv) : nullptr;
-            m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr;
-            m.reverse = 1; m.N = N; m.C = d.C; m.HW = HW;
+            ChanMixArgs m = chanmix_rev_args(L, packed, N, cur, z2, chw, dst);
             ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
             count_launch(p, "k_chanmix");
             GH_TRY(launch_chanmix(m, s));
@@ -963,7 +899,7 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
     // use bit 8 (internal): the exact-fp32 images of layers that normally run k_cnet / the deep-level kernels -- read by the inference
     // calls only with the split-half path switched off through the debug hook
     // (OR-ed in: the internal bits 16 = init pass' f.0 image and 32 = no LU of the caller's mask survive)
-    if (g_sh_disabled) use |= GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING | 8;
+    if (debug_switches().exact_fp32) use |= GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING | 8;
     // a plan on the exact-fp32 family reads the fp32 MFMA images, which are the training path's
     if (plan->family == GLOWHIP_FAMILY_EXACT_FP32) use |= GLOWHIP_PACK_TRAINING;
     plan->repack_sel.clear();
@@ -1022,7 +958,7 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
     // at config E: +5 % on its forward).  At config B the side stream's workgroups only get in the way of the k_cnet launch that
     // runs beside them (-0.5 %): everything stays on `stream` there.
     hipStream_t side = s;
-    if (!g_pack_one_stream && plan->max_c > 128) {
+    if (!debug_switches().pack_one_stream && plan->max_c > 128) {
         if (!plan->side) {
             if (hipStreamCreateWithFlags(&plan->side, hipStreamNonBlocking) != hipSuccess ||
                 hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -1047,7 +983,7 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
         plan->legacy_pending = true; plan->pending_captured = stream_capturing(s);
     }
     if (!(use & 32)) {      // (32, internal: weight images and scale tables only -- the init pass' first pack)
-        bool all_small = !g_lu_small_off;
+        bool all_small = !debug_switches().lu_workgroup;
         for (const StepPrepJob& pj : plan->prep_jobs) all_small = all_small && step_prepare_small_takes(pj);
         const bool inv = (use & (GLOWHIP_PACK_INVERSE | GLOWHIP_PACK_TRAINING)) != 0;
         count_launch(plan, (all_small && !inv) ? "pack:k_step_prepare_small" : "pack:k_step_prepare_batched");
@@ -1238,12 +1174,7 @@ int glowhip_plan_actnorm_init(glowhip_plan* plan, void* packed, size_t packed_by
             const int hid = d.hidden;
             GH_TRY(launch_actnorm_init(cur, chw, N, d.C, HW, actnorm_scale, (float*)d.an_bias, (float*)d.an_logs, s));
             GH_TRY(pack_scales(d.an_logs, d.C, at<float>(packed, L.an_scale), at<float>(packed, L.an_inv_scale), s));
-            ChanMixArgs m{};
-            m.in_a = cur; m.in_a_bs = chw; m.in_b = cur + (long)Ch * HW; m.in_b_bs = chw; m.Ca = Ch;
-            m.out = dst; m.out_bs = chw; m.bias = d.an_bias; m.scale = at<float>(packed, L.an_scale);
-            m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr;
-            m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr;
-            m.reverse = 0; m.N = N; m.C = d.C; m.HW = HW;
+            ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
             GH_TRY(launch_chanmix(m, s));
             // The statistics of a Conv2d's ActNorm are taken BETWEEN the convolution and the ActNorm (network/module.py:258-259,
             // 86-120), so the init pass needs the un-fused form -- not the slow one: raw convolution on the exact-fp32 MFMA kernels

@@ -10,6 +10,7 @@
 #include "sh.h"
 #include "backward.h"
 #include "tophead.h"
+#include "debug_switches.h"
 
 namespace glowhip {
 
@@ -138,6 +139,42 @@ static inline size_t take(size_t& off, size_t bytes) {
 template <typename T>
 static inline T* at(const void* base, size_t off) {
     return (T*)((char*)base + off);
+}
+
+// ---------------------------------------------------------------- per-FlowStep argument builders of the two executors
+static inline int tail_mode(const glowhip_layer_desc& d, int reverse) {
+    return d.coupling == GLOWHIP_COUPLING_AFFINE ? (reverse ? TAIL_AFFINE_REV : TAIL_AFFINE_FWD) : (reverse ? TAIL_ADD_REV : TAIL_ADD_FWD);
+}
+static inline CnetMixer mixer_fwd(const LayerPlan& L, const void* packed) {      // ActNorm + permutation of step L, forward
+    const glowhip_layer_desc& d = L.d;
+    return CnetMixer{d.C, 0, d.an_bias, at<float>(packed, L.an_scale), d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
+                     d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr};
+}
+static inline CnetMixer mixer_rev(const LayerPlan& L, const void* packed) {      // permutation^-1 + ActNorm^-1 of step L
+    const glowhip_layer_desc& d = L.d;
+    return CnetMixer{d.C, 1, d.an_bias, at<float>(packed, L.an_inv_scale),
+                     d.permutation == GLOWHIP_PERM_INVCONV ? at<float>(packed, L.winv) : nullptr,
+                     d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr};
+}
+// the same mixers as their own k_chanmix launch: channels [0, C/2) from in_a, [C/2, C) from in_b (both with batch stride in_bs),
+// contiguous (N, C, HW) output.  (A folded squeeze -- ChanMixArgs::sq_* -- is set by the caller.)
+static inline ChanMixArgs chanmix_args(const LayerPlan& L, const CnetMixer& mx, int N, const float* in_a, const float* in_b, long in_bs,
+                                       float* out) {
+    const glowhip_layer_desc& d = L.d;
+    const int HW = d.H * d.W;
+    ChanMixArgs m{};
+    m.in_a = in_a; m.in_a_bs = in_bs; m.in_b = in_b; m.in_b_bs = in_bs; m.Ca = d.C / 2;
+    m.out = out; m.out_bs = (long)d.C * HW;
+    m.bias = mx.bias; m.scale = mx.scale; m.matrix = mx.matrix; m.gather = mx.gather;
+    m.reverse = mx.reverse; m.N = N; m.C = d.C; m.HW = HW;
+    return m;
+}
+static inline ChanMixArgs chanmix_fwd_args(const LayerPlan& L, const void* packed, int N, const float* in, long in_bs, float* out) {
+    return chanmix_args(L, mixer_fwd(L, packed), N, in, in + (long)(L.d.C / 2) * L.d.H * L.d.W, in_bs, out);
+}
+static inline ChanMixArgs chanmix_rev_args(const LayerPlan& L, const void* packed, int N, const float* in_a, const float* in_b, long in_bs,
+                                           float* out) {
+    return chanmix_args(L, mixer_rev(L, packed), N, in_a, in_b, in_bs, out);
 }
 
 }  // namespace glowhip

@@ -97,30 +97,25 @@ static size_t max_acc_doubles(const glowhip_plan* p) {
 
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
-static bool g_train_sh = true;   // testing hook: 0 = exact-fp32 kernels for f.2 in the training step too
-// (the plan's own family, glowhip_plan_set_family, decides first: GLOWHIP_FAMILY_EXACT_FP32 keeps the f16 pipe out of the training step)
-static bool train_sh_enabled(const glowhip_plan* p) { return g_train_sh && !(p && p->family == GLOWHIP_FAMILY_EXACT_FP32); }
-void plan_train_disable_sh(int off) { g_train_sh = off == 0; }
-static bool g_train_cnet = true;   // testing hook: 0 = the training forward on the per-layer kernels (no taping k_cnet)
-void plan_train_disable_cnet(int off) { g_train_cnet = off == 0; }
+// the split-half kernels in the training step: off with the plan's own family (glowhip_plan_set_family: GLOWHIP_FAMILY_EXACT_FP32 keeps
+// the f16 pipe out of the training step) or the process-wide testing switch
+static bool train_sh_enabled(const glowhip_plan* p) { return !debug_switches().exact_fp32 && !(p && p->family == GLOWHIP_FAMILY_EXACT_FP32); }
 
 // Does FlowStep L run its training forward as the product path's two launches -- k_cnet storing h1 / h2 from its epilogues, the
 // finishing kernel storing hout and the step output (cnet_sh.hip, TAPE)?  `scratch_floats`: room for the partial sums.
 static bool tape_cnet(const glowhip_plan* p, const LayerPlan& L, int N, size_t scratch_floats);
-static bool g_train_cnet_bwd = true;   // testing hook: 0 = the input-gradient chain on the per-layer kernels
-void plan_train_disable_cnet_bwd(int off) { g_train_cnet_bwd = off == 0; }
 // ... and its input-gradient chain as one backward k_cnet launch?  Needs the taping forward (the sign bits) and all of the
 // coupling network's weight gradients requested (the log-scale gradients are derived from them).
 static bool bwd_cnet(const glowhip_plan* p, const LayerPlan& L, int li, const glowhip_layer_grads& G, int N, size_t scratch_floats) {
     const glowhip_layer_desc& d = L.d;
-    return g_train_cnet_bwd && L.cnet_bwd && tape_cnet(p, L, N, scratch_floats) && G.f0_w && G.f2_w && G.f4_w &&
+    return !debug_switches().train_per_layer_bwd && L.cnet_bwd && tape_cnet(p, L, N, scratch_floats) && G.f0_w && G.f2_w && G.f4_w &&
            li < (int)p->tape_has_masks.size() && p->tape_has_masks[li] &&      // (the forward that filled this tape stored the sign bits)
            cnet_tape_supported(L.Cout, d.H, d.W, d.hidden, d.C / 2, N) &&
            cnet_scratch_floats(N, d.H, d.W, d.C / 2) <= scratch_floats;
 }
 static bool tape_cnet(const glowhip_plan* p, const LayerPlan& L, int N, size_t scratch_floats) {
     const glowhip_layer_desc& d = L.d;
-    return g_train_cnet && train_sh_enabled(p) && d.kind == GLOWHIP_LAYER_FLOWSTEP && L.cnet && d.C <= 96 &&
+    return !debug_switches().train_per_layer_fwd && train_sh_enabled(p) && d.kind == GLOWHIP_LAYER_FLOWSTEP && L.cnet && d.C <= 96 &&
            cnet_tape_supported(d.C / 2, d.H, d.W, d.hidden, L.Cout, N) && cnet_scratch_floats(N, d.H, d.W, L.Cout) <= scratch_floats;
 }
 
@@ -193,12 +188,7 @@ static int forward_train(glowhip_plan* p, const void* packed, const float* x, co
             float* h2 = at<float>(tape, tl[li].h2);
             float* hout = at<float>(tape, tl[li].hout);
             if (!premixed) {
-                ChanMixArgs m{};
-                m.in_a = cur; m.in_a_bs = chw; m.in_b = cur + (long)Ch * HW; m.in_b_bs = chw; m.Ca = Ch;
-                m.out = dst; m.out_bs = chw; m.bias = d.an_bias; m.scale = at<float>(packed, L.an_scale);
-                m.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr;
-                m.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr;
-                m.reverse = 0; m.N = N; m.C = d.C; m.HW = HW;
+                ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
                 GH_TRY(launch_chanmix(m, s));
             }
             premixed = false;
@@ -211,7 +201,7 @@ static int forward_train(glowhip_plan* p, const void* packed, const float* x, co
                 c.N = N; c.Cin = Ch; c.H = d.H; c.W = d.W; c.hidden = hid; c.Cout = L.Cout;
                 c.scratch = sh_scratch;
                 c.bias = d.f4_bias; c.scale = at<float>(packed, L.f4_scale);
-                c.mode = d.coupling == GLOWHIP_COUPLING_AFFINE ? TAIL_AFFINE_FWD : TAIL_ADD_FWD;
+                c.mode = tail_mode(d, 0);
                 c.acc = acc;
                 c.x = dst; c.x_bs = chw; c.z_in = dst; c.z_in_bs = chw;
                 c.z_out = dst; c.z_out_bs = chw;
@@ -222,9 +212,7 @@ static int forward_train(glowhip_plan* p, const void* packed, const float* x, co
                     const LayerPlan& Ln = p->layers[li + 1];
                     const glowhip_layer_desc& dn = Ln.d;
                     if (dn.kind == GLOWHIP_LAYER_FLOWSTEP && dn.C == d.C && dn.H == d.H && dn.W == d.W) {
-                        c.mix = CnetMixer{dn.C, 0, dn.an_bias, at<float>(packed, Ln.an_scale),
-                                          dn.permutation == GLOWHIP_PERM_INVCONV ? dn.invconv_w : nullptr,
-                                          dn.permutation == GLOWHIP_PERM_GATHER ? dn.perm_idx : nullptr};
+                        c.mix = mixer_fwd(Ln, packed);
                         c.z_out = at<float>(tape, tl[li + 1].out);
                         premixed = true;
                     }

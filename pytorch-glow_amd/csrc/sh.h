@@ -178,9 +178,7 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out);       
 int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s);     // the finishing kernel for those sums
 int launch_cnet(const CnetArgs& a, hipStream_t s);                                   // both
 bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N);        // a taping instance of k_cnet exists for the shape
-bool cnet_chain_enabled();   // testing hook (off by default: measured slower)
 bool cnet_pre_supported(int Cin, int H, int W, int hidden, int Cout, int C);         // window-time finishing fits the LDS
-void cnet_force(int ms, int flags);   // testing hook: ms in {0 (automatic), 1, 2, 4}
 
 // ---- FlowSteps of the deep levels (C >= 192, a few hundred pixels per launch): one launch per LAYER, rows split over workgroups,
 // activations between the launches as ready-made SH2 B operands in L2 (dnet_sh.hip) -------------------------------------------

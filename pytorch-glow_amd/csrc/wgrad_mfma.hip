@@ -10,6 +10,7 @@
 // the pixel axis is split over workgroups (split-K), partial tiles go to a scratch buffer and a second kernel adds
 // them in a fixed order (deterministic) while scattering into the reference weight layout.
 #include "backward.h"
+#include "debug_switches.h"
 #include "sh.h"
 #include "wgrad_reduce.h"
 #include <type_traits>
@@ -168,8 +169,6 @@ k_wgrad_gemm(const float* __restrict__ A, long a_bs, const float* __restrict__ B
 // instead of three).  The gradient operand A keeps both planes: it is what needs the range.
 // One GEMM's arguments (the kernel body below is shared by the one-GEMM launch and by the launch that runs f.4's and f.0's GEMMs
 // side by side: k_wgrad_gemm_pair)
-static int g_wgrad_narrow = 0;
-void wgrad_force_narrow(int on) { g_wgrad_narrow = on; }
 struct WgArgs {
     const float* A; long a_bs; const float* B; long b_bs; float* partial;
     int HW, Mpad, Npad, ktiles_total, ktiles_per_split; float a_scale, a_pre; double* rowsum;
@@ -1032,7 +1031,7 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
     const bool bn128 = Npad % 128 == 0;
     const int total = (int)((long)N * HW / 32);
     // f.2 behind the backward k_cnet at a level with enough pixels: 256-column tiles, one eight-wave workgroup per CU (k_wgrad_gemm_ps512)
-    const bool wide = b_half && ps && Npad % 256 == 0 && total >= 512 && !g_wgrad_narrow;
+    const bool wide = b_half && ps && Npad % 256 == 0 && total >= 512 && !debug_switches().wgrad_narrow;
     const int tiles = (Mpad / 128) * (wide ? Npad / 256 : (bn128 ? Npad / 128 : Npad / 64));
     int splits = std::max(1, std::min(total, ((wide ? 256 : 512) + tiles - 1) / tiles));   // 2 workgroups per CU (wide: 1, of twice the waves)
     const int per = (total + splits - 1) / splits;

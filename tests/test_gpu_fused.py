@@ -9,24 +9,19 @@ import pytest
 import torch
 
 import pytorch_glow_amd as G
+from pytorch_glow_amd import _lib
 from oracle import glow_oracle as O
 from test_gpu_parity import close, dev, make_glow
 
 pytestmark = pytest.mark.gpu
-
-EXACT_FP32 = 0x800      # glowhip_debug_force_tail_tile: the split-half path off -> every coupling network on the exact-fp32 kernels
-
 
 @pytest.fixture(params=["cnet", "fp32"])
 def path(request):
     """Both kernel families behind the same tests: the product default (k_cnet: f.0 + f.2 + f.4 in one kernel + finishing
     kernel) and the exact-fp32 MFMA kernels (one launch per layer), the fall-back for out-of-range batches and for shapes the
     product kernels do not take."""
-    G.lib().glowhip_debug_force_tail_tile(EXACT_FP32 if request.param == "fp32" else 0)
-    try:
+    with _lib.debug_flags(_lib.DBG.EXACT_FP32 if request.param == "fp32" else 0):
         yield request.param
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
 
 
 def ncnet(counts):
@@ -36,9 +31,6 @@ def ncnet(counts):
 def nfinish(counts):
     """FlowSteps finished: by a finishing launch, or (round 6) by their own k_cnet1w launch (fused finishing)."""
     return counts.get("k_cfinish", 0) + counts.get("k_cfinish+mixer", 0) + counts.get("k_cnet(finishes the step)", 0)
-
-
-FUSED_FINISH = 0x100000      # glowhip_debug_force_tail_tile: k_cnet1w finishes its step itself (off by default: measured slower)
 
 
 def _case(image, L, K, hidden, batch, seed=5, coup="affine", perm="invconv"):
@@ -105,11 +97,8 @@ def test_level1_runs_on_the_one_wave_per_simd_kernel_and_both_kernels_match_the_
         assert counts.get("variant:k_cnet1w<512,1,128>") == K, counts
         assert counts.get("variant:k_cnet<512,1,64>") == K and counts.get("variant:k_cnet<512,4,64>") == K, counts
         assert ncnet(counts) == 3 * K and nfinish(counts) == 3 * K, counts
-    G.lib().glowhip_debug_force_tail_tile(0x10000)
-    try:
+    with _lib.debug_flags(_lib.DBG.NO_CNET1W):
         plan2, fwd2, rev2 = _case(64, 3, K, 512, 48, seed=12)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     for counts in (fwd2, rev2):
         assert counts.get("variant:k_cnet<512,1,128>") == K and "variant:k_cnet1w<512,1,128>" not in counts, counts
 
@@ -122,11 +111,8 @@ def test_row_split_instance_of_the_one_wave_kernel_matches_the_oracle():
     every element against the oracle (inside _case), the instance asserted from the run-time counters; without the switch the same
     launches run on k_cnet<512,1,64>."""
     K = 2
-    G.lib().glowhip_debug_force_tail_tile(0x20000)
-    try:
+    with _lib.debug_flags(_lib.DBG.CNET1W_ROW_SPLIT):
         plan, fwd, rev = _case(64, 3, K, 512, 64, seed=14)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     for counts in (fwd, rev):
         assert counts.get("variant:k_cnet1w<512,1,128>") == K and counts.get("variant:k_cnet1w<512,2,128>") == K, counts
         assert counts.get("variant:k_cnet<512,4,64>") == K and ncnet(counts) == 3 * K and nfinish(counts) == 3 * K, counts
@@ -193,8 +179,7 @@ def test_fused_finishing_equals_the_finishing_kernel_bitwise(image, L, batch, K)
     zu, nllu, xru, fwdu, revu = run()                  # the default: a finishing launch per step
     for counts in (fwdu, revu):
         assert "k_cnet(finishes the step)" not in counts and nfinish(counts) == L * K, counts
-    G.lib().glowhip_debug_force_tail_tile(FUSED_FINISH)
-    try:
+    with _lib.debug_flags(_lib.DBG.FUSED_FINISH):
         z, nll, xr, fwd, rev = run()
         for counts in (fwd, rev):
             assert counts.get("variant:k_cnet1w<512,1,128>") == K, counts
@@ -203,8 +188,6 @@ def test_fused_finishing_equals_the_finishing_kernel_bitwise(image, L, batch, K)
         for rep in range(10):
             z2, nll2, xr2, _, _ = run()
             assert torch.equal(z, z2) and torch.equal(nll, nll2) and torch.equal(xr, xr2), rep
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     assert torch.equal(z, zu) and torch.equal(nll, nllu) and torch.equal(xr, xru)
     assert torch.isfinite(nll).all() and torch.isfinite(xr).all()
 
@@ -228,11 +211,8 @@ def test_one_wave_per_matrix_logdet_equals_the_workgroup_lu_bitwise():
         sd = O.glow_init_actnorm(x, noise, sd, cfg)
         glow = make_glow(cfg, sd, batch)
         z, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise), repack=True)
-        G.lib().glowhip_debug_force_tail_tile(0x200000)
-        try:
+        with _lib.debug_flags(_lib.DBG.LU_WORKGROUP):
             z2, nll2, _ = glow.normal_flow(dev(x), None, noise=dev(noise), repack=True)
-        finally:
-            G.lib().glowhip_debug_force_tail_tile(0)
         assert torch.isfinite(nll).all() and torch.equal(nll, nll2) and torch.equal(z, z2), perturb
         _, nll_ref, _ = O.glow_forward(x, noise, sd, cfg)
         close(nll, nll_ref, 1e-4, what=f"nll at invconv perturbation {perturb}")
@@ -265,11 +245,8 @@ def test_cnet_every_row_split(ms, image, L, hidden, batch):
     """k_cnet with the h2 rows forced onto 1, 2 and 4 workgroups per pixel tile (the launch heuristic picks by grid size): odd
     batches (a half-filled last tile at the 8x8 level), three hidden widths, tile rows from 16 (8-wide level: two images per
     tile) down to 2 (64-wide level), halo rows between tiles summed by the finishing kernel."""
-    G.lib().glowhip_debug_force_tail_tile(ms << 22)
-    try:
+    with _lib.debug_flags(ms << _lib.DBG_CNET_ROWS_SHIFT):
         plan, fwd, rev = _case(image, L, 2, hidden, batch, seed=30 + ms)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     assert ncnet(fwd) == 2 * L, fwd
     # which instance ran, from the executor's run-time counters: at this batch every level takes 64-pixel tiles, so ms = 1 is the
     # bench's <512, 1, 64> instance (its level 2) and ms = 4 its <512, 4, 64> (level 3), each against the oracle (VERDICT r2 #8)
@@ -285,10 +262,9 @@ def test_cnet_tile_sizes_and_chaining(tile, chained):
     default) and chained into the next FlowStep's launch (0x8000000): the two orders of evaluation must agree BIT FOR BIT -- same arithmetic, log-det terms
     summed as fixed point -- and both match the oracle."""
     outs = []
-    CHAIN = 0x8000000
+    CHAIN = _lib.DBG.CNET_CHAIN
     for flags in [tile | (CHAIN if chained else 0), tile | (0 if chained else CHAIN)]:
-        G.lib().glowhip_debug_force_tail_tile(flags)
-        try:
+        with _lib.debug_flags(flags):
             cfg = O.default_cfg(image_shape=(32, 32, 3), hidden_channels=128, K=3, L=2, batch=5)
             sd = O.seeded_state_dict(cfg, seed=77, invconv_perturb=0.02)
             g = torch.Generator().manual_seed(77)
@@ -299,8 +275,6 @@ def test_cnet_tile_sizes_and_chaining(tile, chained):
             counts = plan.launch_counts(reset=True)
             xr = glow.reverse_flow(z, None, eps=[torch.zeros(5, 6, 16, 16, device=z.device)])
             outs.append((z.clone(), nll.clone(), xr.clone(), counts))
-        finally:
-            G.lib().glowhip_debug_force_tail_tile(0)
     (z0, n0, x0, c0), (z1, n1, x1, c1) = outs
     assert ("k_cnet+prev_finish" in c0) != ("k_cnet+prev_finish" in c1), (c0, c1)
     assert torch.equal(z0, z1) and torch.equal(n0, n1) and torch.equal(x0, x1)
@@ -340,8 +314,7 @@ def test_range_overflow_is_never_a_finite_wrong_answer(flags):
     oracle; and safe=True must recover the reference's answer through the exact-fp32 re-run."""
     cfg, sd, x, noise, z_ref, nll_ref = _range_case(3e5)
     assert torch.isfinite(nll_ref).all()
-    G.lib().glowhip_debug_force_tail_tile(flags)
-    try:
+    with _lib.debug_flags(flags):
         glow = make_glow(cfg, sd, 4)
         z, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
         if flags == 0x800:
@@ -351,8 +324,6 @@ def test_range_overflow_is_never_a_finite_wrong_answer(flags):
         assert not ok.any() or (nll.cpu()[ok] - nll_ref[ok]).abs().max() < 1e-4, "finite AND wrong nll after an fp16-range overflow"
         if flags == 0:
             assert (~ok).any(), "this input is meant to overflow the split-half range"
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     if flags != 0:
         return
     n0 = G.Glow._RANGE_FALLBACKS
@@ -373,12 +344,9 @@ def test_nan_input_gives_nan_nll_on_every_path():
     cfg, sd, x, noise, _, nll_ref = _range_case(1.0)
     x = x.clone(); x[2, 1, 5, 5] = float("nan")
     for flags in (0, 0x800):
-        G.lib().glowhip_debug_force_tail_tile(flags)
-        try:
+        with _lib.debug_flags(flags):
             glow = make_glow(cfg, sd, 4)
             _, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
-        finally:
-            G.lib().glowhip_debug_force_tail_tile(0)
         nll = nll.cpu()
         assert torch.isnan(nll[2]) and torch.isfinite(nll[[0, 1, 3]]).all(), (flags, nll)
         assert (nll[[0, 1, 3]] - nll_ref[[0, 1, 3]]).abs().max() < 1e-4

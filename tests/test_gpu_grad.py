@@ -534,9 +534,8 @@ def test_training_step_runs_on_k_cnet_and_agrees_with_the_per_layer_kernels():
     noise = torch.rand(batch, 3, 64, 64, generator=g) / 256
     sd = O.glow_init_actnorm(x, noise, sd, cfg)
     res = {}
-    try:
-        for flag in (0x40000000, 0x80000000, 0):
-            _lib.lib().glowhip_debug_force_tail_tile(flag - (1 << 32) if flag >= (1 << 31) else flag)
+    for flag in (_lib.DBG.TRAIN_PER_LAYER_FWD, _lib.DBG.TRAIN_PER_LAYER_BWD, 0):
+        with _lib.debug_flags(flag):
             glow = G.Glow(hps_for(cfg, batch))
             glow.load_state_dict(sd)
             glow.set_actnorm_inited()
@@ -547,11 +546,9 @@ def test_training_step_runs_on_k_cnet_and_agrees_with_the_per_layer_kernels():
             counts = glow.flow.plan_for(x.to(DEV)).launch_counts()
             res[flag] = (z.detach().cpu(), nll.detach().cpu(), {n: p.grad.cpu().double() for n, p in glow.named_parameters()
                                                                  if p.grad is not None}, counts)
-    finally:
-        _lib.lib().glowhip_debug_force_tail_tile(0)
-    z0, n0, g0, c0 = res[0x40000000]
+    z0, n0, g0, c0 = res[_lib.DBG.TRAIN_PER_LAYER_FWD]
     assert c0.get("k_cnet(tape)", 0) == 0 and c0.get("k_cnet(bwd)", 0) == 0, c0
-    for flag, want_bwd in ((0x80000000, 0), (0, 3 * K)):
+    for flag, want_bwd in ((_lib.DBG.TRAIN_PER_LAYER_BWD, 0), (0, 3 * K)):
         z1, n1, g1, c1 = res[flag]
         assert c1.get("k_cnet(tape)", 0) == 3 * K and c1.get("k_cnet(bwd)", 0) == want_bwd, (hex(flag), c1)
         assert (z1 - z0).abs().max().item() <= 2e-5 and (n1 - n0).abs().max().item() <= 2e-6
@@ -584,9 +581,8 @@ def test_training_launches_on_the_one_wave_kernel_agree_with_k_cnet(image, L, ba
     noise = torch.rand(batch, 3, image, image, generator=g) / 256
     sd = O.glow_init_actnorm(x, noise, sd, cfg)
     res = {}
-    try:
-        for flag in (0x10000, 0x40000, 0x80000, 0):
-            _lib.lib().glowhip_debug_force_tail_tile(flag)
+    for flag in (_lib.DBG.NO_CNET1W, _lib.DBG.NO_CNET1W_BWD, _lib.DBG.WGRAD_NARROW, 0):
+        with _lib.debug_flags(flag):
             glow = G.Glow(hps_for(cfg, batch))
             glow.load_state_dict(sd)
             glow.set_actnorm_inited()
@@ -599,11 +595,9 @@ def test_training_launches_on_the_one_wave_kernel_agree_with_k_cnet(image, L, ba
             grads = {n: p.grad.cpu().double() for n, p in glow.named_parameters() if p.grad is not None}
             grads["dx"] = xd.grad.cpu().double()
             res[flag] = (z.detach().cpu(), nll.detach().cpu(), grads, counts)
-    finally:
-        _lib.lib().glowhip_debug_force_tail_tile(0)
-    z0, n0, g0, c0 = res[0x10000]
+    z0, n0, g0, c0 = res[_lib.DBG.NO_CNET1W]
     assert c0.get("k_cnet(tape)", 0) == L * K and c0.get("k_cnet1w(tape)", 0) == 0 and c0.get("k_cnet1w(bwd)", 0) == 0, c0
-    for flag, want_bwd in ((0x40000, 0), (0x80000, K), (0, K)):
+    for flag, want_bwd in ((_lib.DBG.NO_CNET1W_BWD, 0), (_lib.DBG.WGRAD_NARROW, K), (0, K)):
         z1, n1, g1, c1 = res[flag]
         assert c1.get("k_cnet(tape)", 0) == L * K and c1.get("k_cnet1w(tape)", 0) == K and c1.get("k_cnet(bwd)", 0) == L * K, c1
         assert c1.get("k_cnet1w(bwd)", 0) == want_bwd, (hex(flag), c1)
@@ -631,9 +625,8 @@ def test_grouped_weight_gradient_launches_agree_with_the_per_layer_kernels():
     noise = torch.rand(batch, 3, 64, 64, generator=g) / 256
     sd = O.glow_init_actnorm(x[:4], noise[:4], sd, cfg)
     res = {}
-    try:
-        for flag in (0x80000000, 0):
-            _lib.lib().glowhip_debug_force_tail_tile(flag - (1 << 32) if flag >= (1 << 31) else flag)
+    for flag in (_lib.DBG.TRAIN_PER_LAYER_BWD, 0):
+        with _lib.debug_flags(flag):
             glow = G.Glow(hps_for(cfg, batch))
             glow.load_state_dict(sd)
             glow.set_actnorm_inited()
@@ -643,9 +636,7 @@ def test_grouped_weight_gradient_launches_agree_with_the_per_layer_kernels():
                 G.Glow.generative_loss(nll).backward()
             counts = glow.flow.plan_for(x.to(DEV)).launch_counts()
             res[flag] = ({n: p.grad.cpu().double() for n, p in glow.named_parameters() if p.grad is not None}, counts)
-    finally:
-        _lib.lib().glowhip_debug_force_tail_tile(0)
-    g0, c0 = res[0x80000000]
+    g0, c0 = res[_lib.DBG.TRAIN_PER_LAYER_BWD]
     g1, c1 = res[0]
     assert c0.get("k_wgrad(trio)", 0) == 0 and c0.get("k_wgrad(pair)", 0) == 0, c0
     assert c1.get("k_wgrad(pair)", 0) == K and c1.get("k_wgrad(trio)", 0) == 2 * K and c1.get("k_cnet(bwd)", 0) == 3 * K, c1

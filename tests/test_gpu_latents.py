@@ -13,6 +13,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import pytorch_glow_amd as G  # noqa: E402
+from pytorch_glow_amd import _lib  # noqa: E402
 from pytorch_glow_amd.misc import util  # noqa: E402
 from pytorch_glow_amd.network import Inferer, Latents  # noqa: E402
 from pytorch_glow_amd.network import model as gmodel  # noqa: E402
@@ -177,11 +178,8 @@ _TILE_CASES = [(tp, c, h, w, ms) for (c, h, w) in [(12, 32, 32), (24, 16, 16), (
 @pytest.mark.parametrize("tp,c,h,w,msplit", _TILE_CASES)
 def test_eps_on_every_tail_wave_layout(tp, c, h, w, msplit):
     """Each pixel-tile / K-split variant of the two MFMA tail kernels, with and without the out-channel split."""
-    G.lib().glowhip_debug_force_tail_tile(tp | msplit)
-    try:
+    with _lib.debug_flags(tp | msplit):
         _check_split_module(c, h, w, 3, 0)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
 
 
 # ------------------------------------------------------------------------------------------------ 2. round trip

@@ -13,6 +13,7 @@ from conftest import sub
 pytestmark = pytest.mark.gpu
 
 import pytorch_glow_amd as G  # noqa: E402
+from pytorch_glow_amd import _lib  # noqa: E402
 from pytorch_glow_amd.misc import util  # noqa: E402
 from oracle import glow_oracle as O  # noqa: E402
 
@@ -276,11 +277,8 @@ def _celeba64_case(batch, perturb, want64):
 @pytest.fixture
 def exact_fp32_kernels():
     """Run a test on the exact-fp32 MFMA kernels only (the split-half f16 path switched off through the debug hook)."""
-    G.lib().glowhip_debug_force_tail_tile(0x800)
-    try:
+    with _lib.debug_flags(_lib.DBG.EXACT_FP32):
         yield
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
 
 
 def _full_tensor_check(expect_sh):
@@ -552,12 +550,9 @@ def test_mfma_tail_every_wave_layout(tp, c, h, w, msplit):
     st, sd = _rand_step(c, 64, "affine", seed=tp + c)
     x = torch.randn(3, c, h, w, generator=torch.Generator().manual_seed(5))
     zr, ldr = O.flowstep(x, torch.zeros(3), sd, "", "invconv", "affine")
-    G.lib().glowhip_debug_force_tail_tile(tp | msplit)
-    try:
+    with _lib.debug_flags(tp | msplit):
         z, ld = st(dev(x), 0.)
         z2, ld2 = st(dev(x), 0.)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     close(z, zr, 2e-5, what=f"tp={tp}"); ld_close(ld, ldr)
     assert torch.equal(z, z2) and torch.equal(ld, ld2)
 
@@ -633,12 +628,9 @@ def test_split_half_stack_every_coupling_and_permutation(coup, perm):
     assert counts.get("k_cfinish+mixer", 0) >= 4 and counts.get("k_conv_direct", 0) == 0, counts
     assert counts.get("squeeze(folded)", 0) == 3, counts
     close(z, z_ref, 1e-4, what="z"); close(nll, nll_ref, 1e-4, what="nll")
-    G.lib().glowhip_debug_force_tail_tile(0x8000)      # the same without the mixer fused into the finishing kernel / the squeeze into the mixer
-    try:
+    with _lib.debug_flags(_lib.DBG.NO_MIXER_FUSION):      # the same without the mixer fused into the finishing kernel / the squeeze into the mixer
         z_u, nll_u, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
         counts_u = plan.launch_counts(reset=True)
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     assert "squeeze(folded)" not in counts_u and "k_cfinish+mixer" not in counts_u, counts_u
     assert torch.equal(z, z_u) and torch.equal(nll, nll_u)
     eps = [torch.randn(batch, *s, generator=torch.Generator().manual_seed(6 + i)) * 0.7
@@ -661,11 +653,8 @@ def test_uint8_pixels_equal_the_float_path_bitwise():
     z8, nll8, _ = glow.normal_flow(u8.to(DEV), None, noise=dev(noise))
     zf, nllf, _ = glow.normal_flow(dev(xf), None, noise=dev(noise))
     assert torch.equal(z8, zf) and torch.equal(nll8, nllf)
-    G.lib().glowhip_debug_force_tail_tile(0x8000)      # ... and the squeeze kernel on the bytes instead of the mixer gathering them
-    try:
+    with _lib.debug_flags(_lib.DBG.NO_MIXER_FUSION):      # ... and the squeeze kernel on the bytes instead of the mixer gathering them
         z8u, nll8u, _ = glow.normal_flow(u8.to(DEV), None, noise=dev(noise))
-    finally:
-        G.lib().glowhip_debug_force_tail_tile(0)
     assert torch.equal(z8, z8u) and torch.equal(nll8, nll8u)
     z_ref, nll_ref, _ = O.glow_forward(xf, noise, sd, cfg)
     close(z8, z_ref, 1e-4, what="z"); close(nll8, nll_ref, 1e-4, what="nll")
