@@ -52,7 +52,17 @@ struct ChanMixBwdArgs {
 };
 struct WgradReduceJobs;
 // reduce != null: the split-K reductions of the FlowStep's weight-gradient GEMMs run in the same launch (k_chanmix_bwd_reduce)
+// C > CHANMIX_BWD_NARROW_C: k_chanmix_bwd_wide (pixel blocks x channel slices) -- gx must not alias gy, add_part is refused
 int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce = nullptr);
+constexpr int CHANMIX_BWD_NARROW_C = 192;      // k_chanmix_bwd's three C x 65 LDS arrays: 150 KB of a CU's 160
+constexpr int CHANMIX_BWD_MAX_C = 512;         // (the forward mixer's limit, launch_chanmix)
+constexpr int CHANMIX_BWD_WIDE_PX = 32;        // pixels of a k_chanmix_bwd_wide workgroup
+constexpr int CHANMIX_BWD_WIDE_COPIES = 8;     // ... whose launch uses one accumulator copy per pixel block, at most this many
+inline bool chanmix_bwd_wide(int C) { return C > CHANMIX_BWD_NARROW_C; }
+inline int chanmix_bwd_wide_copies(long pixels) {
+    const long blocks = (pixels + CHANMIX_BWD_WIDE_PX - 1) / CHANMIX_BWD_WIDE_PX;
+    return (int)(blocks < 1 ? 1 : blocks > CHANMIX_BWD_WIDE_COPIES ? CHANMIX_BWD_WIDE_COPIES : blocks);
+}
 
 int launch_prior_bwd(const float* z, const float* mean, const float* logs, long ml_bs, const float* gld,
                      const float* gz_in, float* gz, int N, long per, hipStream_t s);

@@ -9,6 +9,7 @@
 //   k_split_bwd      Split2d Gaussian log-density gradients (+ Conv2dZeros scale/bias gradients)
 //   k_act_bwd        ReLU mask + ActNorm scale of a hidden layer, with the ActNorm parameter gradients
 //   k_chanmix_bwd    ActNorm + invertible 1x1 conv: input gradient, dW (incl. d log|det W|), d bias, d logs
+//   k_chanmix_bwd_wide   the same for C > 192 (config E's deepest level): pixel blocks x channel slices
 //   k_prior_bwd      top prior: dL/dz of the Gaussian log-density
 //   k_wgrad_direct   dW of a convolution, one workgroup per (out, in) channel pair (generic / cross-check)
 //   k_weight_flipT   w[o][i][tap] -> wT[i][o][8-tap]: the input gradient of a convolution is a convolution with wT
@@ -528,10 +529,161 @@ __global__ void __launch_bounds__(256) k_chanmix_bwd_reduce(ChanMixBwdArgs a, Wg
     wgrad_reduce_body(r.partial, r.dw, r.splits, r.Mpad, r.Npad, r.Mreal, r.Nreal, r.mode, rb - job * rblocks);
 }
 
+// Wide levels (C > 192: three C x 65 arrays no longer fit a CU's LDS; 4x4 / 2x2 pixels per image, so a launch has few pixels and
+// must find its parallelism over the channels): workgroup = 32 pixels x a slice of 32 INPUT channels i, grid = (pixel blocks,
+// C / 32).  A slice needs g_y of ALL channels for its pixels (g_v[i] = sum_o W[o][i] g_y[o]) but only its own 32 columns of W, its
+// own rows of x / v / g_v and its own columns of dW[o][i] = sum_px g_y[o] v[i]: LDS holds W[:, slice] [C][32], g_y [C][33] and
+// v, g_v [32][33] -- 106 KB at C = 384, 138 KB at C = 512.  Other slices read the g_y this one's g_x would overwrite: never in
+// place.  Accumulators as in chanmix_bwd_body: pixel block b adds into copy b % acc_copies, slices own disjoint elements of a copy.
+constexpr int CW_PX = CHANMIX_BWD_WIDE_PX, CW_LD = CW_PX + 1, CW_SL = 32;
+static size_t chanmix_bwd_wide_lds(int C, bool matrix) {
+    return ((matrix ? (size_t)C * CW_SL : 0) + (size_t)C * CW_LD + (size_t)2 * CW_SL * CW_LD) * sizeof(float);
+}
+__global__ void __launch_bounds__(256) k_chanmix_bwd_wide(ChanMixBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float wsm[];
+    const int C = a.C;
+    float* wl = wsm;                                     // [C][32]: W[o][i0 + j]
+    float* gy = wsm + (a.matrix ? C * CW_SL : 0);        // [C][32 (+1)]
+    float* v = gy + C * CW_LD;                           // [32][32 (+1)]
+    float* gv = v + CW_SL * CW_LD;                       // [32][32 (+1)]
+    const int tid = threadIdx.x, px = tid & (CW_PX - 1), g8 = tid >> 5;
+    const int i0 = blockIdx.y * CW_SL, nsl = min(CW_SL, C - i0);
+    const long gp = (long)blockIdx.x * CW_PX + px;
+    const long total = (long)a.N * a.HW;
+    const bool valid = gp < total;
+    const long n = valid ? gp / a.HW : 0;
+    const int p = valid ? (int)(gp - n * a.HW) : 0;
+    // Staging: the slice's x rows, then W's 32 columns and all of g_y in rounds of 16 values per thread -- every load of a round
+    // unconditional from a clamped address and issued before the round's first LDS store (3 + 3 round trips at C = 384, not 96).
+    {
+        float xr[4], bb[4], sc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int c = min(i0 + g8 + 8 * u, C - 1);
+            xr[u] = a.x[n * a.x_bs + (long)c * a.HW + p];
+            bb[u] = a.bias[c]; sc[u] = a.scale[c];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = g8 + 8 * u;
+            v[j * CW_LD + px] = (valid && j < nsl) ? (xr[u] + bb[u]) * sc[u] : 0.f;
+        }
+    }
+    if (a.matrix) {
+        const int ne = C * CW_SL;
+        for (int e0 = tid; e0 < ne; e0 += 256 * 16) {
+            float wv[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int e = min(e0 + 256 * u, ne - 1);
+                wv[u] = a.matrix[(e >> 5) * C + min(i0 + (e & 31), C - 1)];
+            }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const int e = e0 + 256 * u;
+                if (e < ne) wl[e] = (e & 31) < nsl ? wv[u] : 0.f;
+            }
+        }
+    }
+    for (int c0 = g8; c0 < C; c0 += 8 * 16) {
+        float gr[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) gr[u] = a.gy[n * a.g_bs + (long)min(c0 + 8 * u, C - 1) * a.HW + p];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int u = 0; u < 16; ++u) {
+            const int c = c0 + 8 * u;
+            if (c < C) gy[c * CW_LD + px] = valid ? gr[u] : 0.f;
+        }
+    }
+    __syncthreads();
+    // g_v = W^T g_y for the slice (gather: g_v[i] = g_y[inv[i]]): four consecutive channels per thread -- one 16-byte broadcast read
+    // of W[o][i .. i + 3] and one read of g_y[o] per four FMAs, o ascending
+    {
+        const int j0 = 4 * g8;
+        float r[4] = {0.f, 0.f, 0.f, 0.f}, sc[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) sc[u] = a.scale[min(i0 + j0 + u, C - 1)];
+        if (a.matrix) {
+#pragma unroll 4
+            for (int o = 0; o < C; ++o) {
+                const f32x4_t w4 = *reinterpret_cast<const f32x4_t*>(wl + o * CW_SL + j0);
+                const float g = gy[o * CW_LD + px];
+                r[0] = fmaf(w4[0], g, r[0]); r[1] = fmaf(w4[1], g, r[1]); r[2] = fmaf(w4[2], g, r[2]); r[3] = fmaf(w4[3], g, r[3]);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = min(i0 + j0 + u, C - 1);
+                r[u] = gy[(a.gather_inv ? a.gather_inv[i] : i) * CW_LD + px];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int j = j0 + u;
+            gv[j * CW_LD + px] = j < nsl ? r[u] : 0.f;
+            if (valid && j < nsl) a.gx[n * a.g_bs + (long)(i0 + j) * a.HW + p] = r[u] * sc[u];
+        }
+    }
+    __syncthreads();
+    // reductions over the 32 pixels of this workgroup
+    const long aco = (long)(blockIdx.x % a.acc_copies) * a.acc_stride;
+    const bool own = (int)gridDim.x <= a.acc_copies;      // nobody else adds into this copy (zeroed per step): plain stores
+    if (a.matrix) {
+        // dW[o][i0 + j], all o: 2 x 2 blocks of (o, j) -- four LDS reads per four FMAs; the 16 j-pairs of a wave read 16 banks,
+        // its four o-pairs are broadcasts
+        const int nb = ((C + 1) >> 1) * (CW_SL / 2);
+        for (int blk = tid; blk < nb; blk += 256) {
+            const int j = 2 * (blk & (CW_SL / 2 - 1)), o = 2 * (blk / (CW_SL / 2)), o1 = min(o + 1, C - 1);
+            float s00 = 0.f, s01 = 0.f, s10 = 0.f, s11 = 0.f;
+#pragma unroll 8
+            for (int q = 0; q < CW_PX; ++q) {
+                const float g0 = gy[o * CW_LD + q], g1 = gy[o1 * CW_LD + q], v0 = v[j * CW_LD + q], v1 = v[(j + 1) * CW_LD + q];
+                s00 = fmaf(g0, v0, s00); s01 = fmaf(g0, v1, s01); s10 = fmaf(g1, v0, s10); s11 = fmaf(g1, v1, s11);
+            }
+            const float sv[4] = {s00, s01, s10, s11};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int oo = o + (u >> 1), jj = j + (u & 1);
+                if (oo >= C || jj >= nsl) continue;
+                const int pair = oo * C + i0 + jj;
+                if (own) a.acc_w[aco + pair] = (double)sv[u]; else atomic_add_f64(a.acc_w + aco + pair, (double)sv[u]);
+            }
+        }
+    }
+    if (tid < nsl) {
+        const int c = i0 + tid;
+        const float sc = a.scale[c];
+        float sb = 0.f, sl = 0.f;
+        for (int q = 0; q < CW_PX; ++q) {
+            sb = fmaf(gv[tid * CW_LD + q], sc, sb);
+            sl = fmaf(gv[tid * CW_LD + q], v[tid * CW_LD + q], sl);
+        }
+        if (own) { a.acc_b[aco + c] = (double)sb; a.acc_l[aco + c] = (double)sl * 3.0; }
+        else { atomic_add_f64(a.acc_b + aco + c, (double)sb); atomic_add_f64(a.acc_l + aco + c, (double)sl * 3.0); }
+    }
+}
+
 int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce) {
-    GH_REQUIRE(a.C > 0 && a.C <= 192, "chanmix backward: C=%d unsupported (1..192)", a.C);
+    GH_REQUIRE(a.C > 0 && a.C <= CHANMIX_BWD_MAX_C, "chanmix backward: C=%d unsupported (1..%d)", a.C, CHANMIX_BWD_MAX_C);
     const long total = (long)a.N * a.HW;
     if (total == 0) return reduce ? launch_wgrad_reduce_batched(*reduce, s) : GLOWHIP_OK;
+    if (chanmix_bwd_wide(a.C)) {
+        GH_REQUIRE(!a.add_part, "chanmix backward: C=%d has no gather of a backward k_cnet launch's partial sums (C <= %d)", a.C, CHANMIX_BWD_NARROW_C);
+        // (channel slices in separate workgroups: a slice's g_x store would race with another slice's g_y read)
+        const float* g_lo = a.gy; const float* g_hi = a.gy + (long)a.N * a.g_bs;
+        GH_REQUIRE(a.gx + (long)a.N * a.g_bs <= g_lo || a.gx >= g_hi, "chanmix backward: C=%d cannot run in place", a.C);
+        GH_REQUIRE(a.acc_copies >= 1, "chanmix backward: acc_copies=%d", a.acc_copies);
+        if (reduce) GH_TRY(launch_wgrad_reduce_batched(*reduce, s));
+        const size_t lds = chanmix_bwd_wide_lds(a.C, a.matrix != nullptr);
+        if (lds > 32 * 1024)
+            (void)hipFuncSetAttribute((const void*)k_chanmix_bwd_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_chanmix_bwd_wide, dim3(cdiv(total, CW_PX), cdiv(a.C, CW_SL)), dim3(256), lds, s, a);
+        GH_LAUNCH_CHECK("k_chanmix_bwd_wide");
+        return GLOWHIP_OK;
+    }
     size_t lds = (size_t)3 * a.C * CB_LD * sizeof(float);
     ChanMixBwdArgs b = a;
     // (C % 4 == 0: the kernel stages W with 16-byte loads / stores at an offset of 3 C 65 floats -- any other C would run up to three

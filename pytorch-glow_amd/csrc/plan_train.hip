@@ -83,15 +83,21 @@ constexpr int MIX_ACC_COPIES = GH_MIX_ACC_COPIES;     // copies of a FlowStep's 
                                        // (64 copies, one per workgroup of the C = 48 launch and plain stores instead of its 154 k fp64
                                        // atomics, changed nothing in that launch -- it was not waiting for them -- and cost the
                                        // finalize kernel 43 us per step for the 4 x longer sums)
-static size_t layer_acc_doubles(const LayerPlan& L) {
+// (wide levels, C > 192: one copy per pixel block of k_chanmix_bwd_wide's launch, at most 8 -- 16 copies of C = 384's 1.2 MB were
+// 19 MB to zero per FlowStep, 600 MB per sweep of config E's deepest level, nearly all of it never touched by a launch of 8 blocks)
+static int mix_acc_copies(const glowhip_layer_desc& d, int N) {
+    return chanmix_bwd_wide(d.C) ? chanmix_bwd_wide_copies((long)N * d.H * d.W) : MIX_ACC_COPIES;
+}
+static size_t layer_acc_doubles(const LayerPlan& L, int N) {
     const glowhip_layer_desc& d = L.d;
-    if (d.kind == GLOWHIP_LAYER_FLOWSTEP) return MIX_ACC_COPIES * ((size_t)d.C * d.C + 2 * d.C + 2 * L.Cout) + 4 * d.hidden;
+    if (d.kind == GLOWHIP_LAYER_FLOWSTEP)
+        return mix_acc_copies(d, N) * ((size_t)d.C * d.C + 2 * d.C) + MIX_ACC_COPIES * ((size_t)2 * L.Cout) + 4 * d.hidden;
     if (d.kind == GLOWHIP_LAYER_SPLIT2D) return (size_t)2 * L.Cout;
     return 0;
 }
-static size_t max_acc_doubles(const glowhip_plan* p) {
+static size_t max_acc_doubles(const glowhip_plan* p, int N) {
     size_t m = 0;
-    for (const LayerPlan& L : p->layers) m += layer_acc_doubles(L);
+    for (const LayerPlan& L : p->layers) m += layer_acc_doubles(L, N);
     return m + 64;
 }
 
@@ -146,7 +152,7 @@ static size_t train_ws_layout(const glowhip_plan* p, int N, void* base, TrainWs*
     const size_t o_gpre = take(off, (size_t)N * p->max_chw * 4);
     const size_t o_gsh = take(off, (size_t)N * p->max_hidden * 4);
     const size_t o_wT = take(off, max_weight_floats(p) * 4);
-    const size_t nd = max_acc_doubles(p);
+    const size_t nd = max_acc_doubles(p, N);
     const size_t o_dacc = take(off, nd * 8);
     size_t colf, partf;
     wgrad_scratch_floats(p, N, &colf, &partf);
@@ -337,7 +343,7 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
     std::vector<size_t> acc_base(nl, 0);
     {
         size_t o = 0;
-        for (int i = 0; i < nl; ++i) { acc_base[i] = o; o += layer_acc_doubles(p->layers[i]); }
+        for (int i = 0; i < nl; ++i) { acc_base[i] = o; o += layer_acc_doubles(p->layers[i], N); }
         GH_TRY(zero_f64(w.dacc, o, s));
     }
     auto fin = [&](const double* acc, float* out, int n, double add_mul, const float* winv = nullptr, int C = 0, int copies = 1,
@@ -394,7 +400,8 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             // accumulators: [W C*C][an_b C][an_l C][f0_b hid][f0_l hid][f2_b hid][f2_l hid][f4_b Cout][f4_l Cout]
             const long mstride = (long)d.C * d.C + 2 * d.C;       // one copy of the mixer accumulators
             double* aW = w.dacc + acc_base[li]; double* aAb = aW + (size_t)d.C * d.C; double* aAl = aAb + d.C;
-            double* a0b = aW + MIX_ACC_COPIES * mstride; double* a0l = a0b + hid; double* a2b = a0l + hid; double* a2l = a2b + hid;
+            const int mcopies = mix_acc_copies(d, N);
+            double* a0b = aW + mcopies * mstride; double* a0l = a0b + hid; double* a2b = a0l + hid; double* a2l = a2b + hid;
             double* a4b = a2l + hid; double* a4l = a4b + L.Cout;
             // (a) coupling tail: g (second half) becomes g_y2 in place; gpre = gradient of f.4's (conv + bias)
             CouplingBwdArgs cb{hout, out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, g + (long)Ch * HW, w.gpre,
@@ -475,13 +482,13 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                 ChanMixBwdArgs mb{xin, chw, g, g, chw, d.an_bias, at<float>(packed, L.an_scale),
                                   d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
                                   d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr, aW, aAb, aAl, N, d.C, HW};
-                mb.acc_copies = MIX_ACC_COPIES; mb.acc_stride = mstride;
+                mb.acc_copies = mcopies; mb.acc_stride = mstride;      // (C <= 96 here, tape_cnet: never the wide kernel)
                 mb.add_part = pend.scratch; mb.add_scale = 1.0f / sh_grad_scale; mb.add_C = Ch; mb.add_MS = pend.MS;
                 mb.add_tiles = pend.tiles; mb.add_R = pend.R; mb.add_NI = pend.NI; mb.add_lpxt = pend.lpxt; mb.add_H = d.H; mb.add_W = d.W;
                 GH_TRY(launch_chanmix_bwd(mb, s, &rj));
-                if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, MIX_ACC_COPIES, mstride);
-                fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, MIX_ACC_COPIES, mstride);
-                fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, MIX_ACC_COPIES, mstride);
+                if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+                fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
+                fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
                 fin(a0b, G.f0_an_bias, hid, 0.0);
                 fin(a2b, G.f2_an_bias, hid, 0.0);
                 fin(a4b, G.f4_bias, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout); fin(a4l, G.f4_logs, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout);
@@ -550,17 +557,21 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                                    (long)Ch * HW, (long)Ch * HW);
                 GH_LAUNCH_CHECK("k_add_inplace");
             }
-            // (e) ActNorm + invconv / permutation: g (= g_y) -> g_x in place
-            ChanMixBwdArgs mb{xin, chw, g, g, chw, d.an_bias, at<float>(packed, L.an_scale),
+            // (e) ActNorm + invconv / permutation: g (= g_y) -> g_x in place; wide levels (channel slices in separate workgroups, which
+            // all read g_y) into the other gradient buffer
+            const bool wide = chanmix_bwd_wide(d.C);
+            ChanMixBwdArgs mb{xin, chw, g, wide ? gnext : g, chw, d.an_bias, at<float>(packed, L.an_scale),
                               d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
                               d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr, aW, aAb, aAl, N, d.C, HW};
-            mb.acc_copies = MIX_ACC_COPIES; mb.acc_stride = mstride;
-                GH_TRY(launch_chanmix_bwd(mb, s));
+            mb.acc_copies = mcopies; mb.acc_stride = mstride;
+            if (wide) count_launch(p, "k_chanmix_bwd_wide");
+            GH_TRY(launch_chanmix_bwd(mb, s));
+            if (wide) g = gnext;
             // (f) fp64 accumulators -> fp32 gradients (+ the log-det terms that do not depend on the data): queued,
             // converted by ONE launch after the sweep
-            if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, MIX_ACC_COPIES, mstride);
-            fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, MIX_ACC_COPIES, mstride);
-            fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, MIX_ACC_COPIES, mstride);
+            if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+            fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
+            fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
             fin(a0b, G.f0_an_bias, hid, 0.0); fin(a0l, G.f0_an_logs, hid, 0.0);
             fin(a2b, G.f2_an_bias, hid, 0.0); fin(a2l, G.f2_an_logs, hid, 0.0);
             fin(a4b, G.f4_bias, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout); fin(a4l, G.f4_logs, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout);
@@ -661,7 +672,7 @@ int glowhip_glow_backward(glowhip_plan* plan, const void* packed, const float* x
     TrainWs w;
     GH_REQUIRE(workspace_bytes >= train_ws_layout(plan, N, workspace, &w), "glow_backward: workspace too small");
     for (const LayerPlan& L : plan->layers)
-        GH_REQUIRE(L.d.kind != GLOWHIP_LAYER_FLOWSTEP || L.d.C <= 192, "glow_backward: C=%d not supported yet", L.d.C);
+        GH_REQUIRE(L.d.kind != GLOWHIP_LAYER_FLOWSTEP || L.d.C <= CHANMIX_BWD_MAX_C, "glow_backward: C=%d unsupported (the channel mixer's limit is %d)", L.d.C, CHANMIX_BWD_MAX_C);
     hipStream_t s = (hipStream_t)stream;
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
     const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
