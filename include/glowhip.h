@@ -387,6 +387,7 @@ enum {
     GLOWHIP_DBG_TAIL_NO_MSPLIT      = 0x200,      /* ... never split them */
     GLOWHIP_DBG_TAIL_NO_DMA         = 0x400,      /* ... no LDS-DMA tail kernels */
     GLOWHIP_DBG_EXACT_FP32          = 0x800,      /* exact-fp32 MFMA kernels only (split-half f16 path off, training included) */
+    GLOWHIP_DBG_PACK_UNFUSED        = 0x1000,     /* the forward-only pack as its per-kind launches, not the one k_pack_fused launch (same bytes: A/B) */
     GLOWHIP_DBG_NO_MIXER_FUSION     = 0x8000,     /* k_squeeze + k_chanmix + a plain finishing kernel as separate launches (bitwise equal) */
     GLOWHIP_DBG_NO_CNET1W           = 0x10000,    /* no k_cnet1w (one wave per SIMD, csrc/cnet1w_sh.hip): k_cnet takes its launches (A/B) */
     GLOWHIP_DBG_CNET1W_ROW_SPLIT    = 0x20000,    /* k_cnet1w's row-split instance where it applies (C = 24 levels from 112 tiles of 128

@@ -89,6 +89,7 @@ class DBG(enum.IntFlag):
     TAIL_NO_MSPLIT = 0x200
     TAIL_NO_DMA = 0x400
     EXACT_FP32 = 0x800
+    PACK_UNFUSED = 0x1000
     NO_MIXER_FUSION = 0x8000
     NO_CNET1W = 0x10000
     CNET1W_ROW_SPLIT = 0x20000

@@ -43,6 +43,7 @@ void glowhip_debug_force_tail_tile(int v) {
     d.cnet_chain = bit(GLOWHIP_DBG_CNET_CHAIN);
     d.cfinish_block_order = bit(GLOWHIP_DBG_CFINISH_BLOCK_ORDER);
     d.pack_one_stream = bit(GLOWHIP_DBG_PACK_ONE_STREAM);
+    d.pack_unfused = bit(GLOWHIP_DBG_PACK_UNFUSED);
     d.train_per_layer_fwd = bit(GLOWHIP_DBG_TRAIN_PER_LAYER_FWD);
     d.train_per_layer_bwd = bit(GLOWHIP_DBG_TRAIN_PER_LAYER_BWD);
     g_debug = d;

@@ -22,6 +22,7 @@ struct DebugSwitches {
     bool fused_finish = false;
     bool lu_workgroup = false;       // log|det W| of the small matrices on the workgroup-wide LU (A/B and bitwise test of the one-wave form)
     bool pack_one_stream = false;    // glowhip_plan_pack without the side-stream fork
+    bool pack_unfused = false;       // the forward-only pack as its per-kind launch sequence, not k_pack_fused (A/B, byte comparison)
     bool train_per_layer_fwd = false;   // the training forward on the per-layer kernels (no taping k_cnet)
     bool train_per_layer_bwd = false;   // the input-gradient chain on the per-layer kernels (no backward k_cnet)
     // ---- k_cnet / k_cnet1w / k_cfinish (cnet_sh.hip)

@@ -33,6 +33,7 @@ struct ChanMixArgs {
     // dequantisation noise of network/model.py:421 (tensor or in-kernel Philox draw) and the 8-bit scaling of the data loader
     // (dataset/celeba.py:74-86) applied on the way in.  sq_src: float (sq_u8 = 0) or uint8 (sq_u8 = 1) of shape (N, C/4, 2 Ho, sq_W).
     const void* sq_src; int sq_u8; float sq_div; const float* sq_noise; RngSpec sq_rng; int sq_W;
+    long sq_bs;            // batch stride of sq_src in elements, 0 = dense (C/4 * 4 HW); the noise tensor / draw is always dense
 };
 int launch_chanmix(const ChanMixArgs& a, hipStream_t s);
 bool chanmix_squeeze_foldable(int C);      // the squeezed-view input (ChanMixArgs::sq_src) is served for this channel count
@@ -114,6 +115,14 @@ int launch_flipT_batched(const FlipJob* jobs_dev, int n_jobs, const int* max_til
 // first_blocks: workgroups per SH2_FIRST job (32 rows each for the jobs with >= 64 input channels; 2 x 256 rows otherwise)
 int launch_pack_batched(const ScaleJob* sj_dev, int n_scale, const RepackJob* rj_dev, const int* n_kind, int tail_blocks, void* packed,
                         hipStream_t s, hipStream_t s_legacy, int first_blocks = 2);
+// The forward-only pack as one launch (pack.hip k_pack_fused): one PackSeg per workgroup, in this order of kinds -- job = index into
+// the step-prepare (LU: unused, bx walks the table four jobs at a time), repack (sorted as for launch_pack_batched) or scale table
+enum { PACKSEG_LU = 0, PACKSEG_SH2_GEMM, PACKSEG_SH2_FIRST, PACKSEG_SH2_TAIL, PACKSEG_LEGACY, PACKSEG_SCALE, PACKSEG_ZERO };
+struct PackSeg { int kind, job, bx, nbx; };
+int pack_fused_job_blocks(int seg_kind, const RepackJob* r, const ScaleJob* sj);
+// counter_dev: one zero word beside the table (the LU workgroups' arrival counter; left zero)
+int launch_pack_fused(const PackSeg* segs_dev, int n_segs, const StepPrepJob* prep_dev, int n_prep, const RepackJob* rj_dev,
+                      const ScaleJob* sj_dev, unsigned* counter_dev, void* packed, hipStream_t s);
 // n SH2_GEMM jobs on their own (the images of W^-1, after the LU factorisations)
 int launch_repack_sh2_gemm(const RepackJob* rj_dev, int n, void* packed, hipStream_t s);
 

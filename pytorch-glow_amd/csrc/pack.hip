@@ -1,41 +1,46 @@
 // pack.hip -- batched re-derivation of parameter-dependent data (glowhip_plan_pack): ONE launch for all
 // exp(3*logs) tables and ONE for all MFMA weight images of a plan, driven by device-resident job tables
 // (a 96-step Glow has ~390 scale jobs and ~290 repack jobs; launching them one by one cost 11 ms per pack).
+#include <algorithm>
+
 #include "kernels.h"
 #include "conv_mfma.h"
 #include "sh.h"
+#include "lu_wave.h"
 
 namespace glowhip {
 
 __device__ __forceinline__ size_t align_up_dev(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-__global__ void __launch_bounds__(256) k_pack_scales_batched(const ScaleJob* __restrict__ jobs, char* packed) {
-    const ScaleJob j = jobs[blockIdx.y];
+// (every body below is workgroup `bx` of the `nbx` that share its job: the per-kind kernels pass blockIdx.x / gridDim.x, k_pack_fused
+// its segment table's pair)
+__device__ __forceinline__ void pack_scales(const ScaleJob& j, char* packed, int bx, int nbx) {
     float* scale = (float*)(packed + j.scale_off);
     float* inv = j.has_inv ? (float*)(packed + j.inv_off) : nullptr;
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < j.n; i += gridDim.x * 256) {
+    for (int i = bx * 256 + threadIdx.x; i < j.n; i += nbx * 256) {
         const float l3 = j.logs[i] * LOGSCALE;
         scale[i] = expf(l3);
         if (inv) inv[i] = expf(-l3);
     }
 }
+__global__ void __launch_bounds__(256) k_pack_scales_batched(const ScaleJob* __restrict__ jobs, char* packed) {
+    pack_scales(jobs[blockIdx.y], packed, blockIdx.x, gridDim.x);
+}
 
 // wide: wt[k][o] = w[o][k] (k = ci*k*k + tap), zero rows k >= K   -- K-major image for k_conv_wide
 // tail: wp[(((chunk*8 + c4)*9 + tap)*MT + mt)*64 + kq*16 + i] = w[o(mt*16+i)][chunk*32 + c4*4 + kq][tap]
-__global__ void __launch_bounds__(256) k_repack_batched(const RepackJob* __restrict__ jobs, char* packed) {
-    const RepackJob j = jobs[blockIdx.y];
-    if (j.kind >= REPACK_SH2_GEMM) return;   // k_repack_sh2_batched
+__device__ __forceinline__ void repack_legacy(const RepackJob& j, char* packed, int bx, int nbx) {
     float* out = (float*)(packed + j.out_off);
     if (j.kind == REPACK_WIDE) {
         const long total = (long)j.Kpad * j.Cout;
-        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        for (long e = (long)bx * 256 + threadIdx.x; e < total; e += (long)nbx * 256) {
             const int k = (int)(e / j.Cout), o = (int)(e - (long)k * j.Cout);
             out[e] = (k < j.K) ? j.w[(long)o * j.K + k] : 0.f;
         }
     } else if (j.kind == REPACK_FIRST) {
         // wf[(chunk*54 + tap*6 + cl)][o] = w[o][chunk*6 + cl][tap]   -- (6-channel chunk, tap, channel) K order
         const long total = (long)9 * j.Cin * j.Cout;
-        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        for (long e = (long)bx * 256 + threadIdx.x; e < total; e += (long)nbx * 256) {
             const int o = (int)(e % j.Cout);
             const int k = (int)(e / j.Cout);
             const int chunk = k / 54, r = k - chunk * 54;
@@ -44,10 +49,10 @@ __global__ void __launch_bounds__(256) k_repack_batched(const RepackJob* __restr
             const float wv = j.transposed ? j.w[((long)ci * j.Cout + o) * 9 + (8 - tap)] : j.w[((long)o * j.Cin + ci) * 9 + tap];
             out[e] = j.fold_logs ? wv * expf(j.fold_logs[o] * LOGSCALE) : wv;
         }
-        for (long o = (long)blockIdx.x * 256 + threadIdx.x; o < j.Cout; o += (long)gridDim.x * 256)
+        for (long o = (long)bx * 256 + threadIdx.x; o < j.Cout; o += (long)nbx * 256)
             out[total + o] = j.fold_logs ? j.fold_bias[o] * expf(j.fold_logs[o] * LOGSCALE) : 0.f;
     } else {
-        for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < j.total; e += (long)gridDim.x * 256) {
+        for (long e = (long)bx * 256 + threadIdx.x; e < j.total; e += (long)nbx * 256) {
             const int i = (int)(e & 15), kq = (int)((e >> 4) & 3);
             long t = e >> 6;
             const int mt = (int)(t % j.MT); t /= j.MT;
@@ -62,6 +67,11 @@ __global__ void __launch_bounds__(256) k_repack_batched(const RepackJob* __restr
         }
     }
 }
+__global__ void __launch_bounds__(256) k_repack_batched(const RepackJob* __restrict__ jobs, char* packed) {
+    const RepackJob j = jobs[blockIdx.y];
+    if (j.kind >= REPACK_SH2_GEMM) return;   // k_repack_sh2_batched
+    repack_legacy(j, packed, blockIdx.x, gridDim.x);
+}
 
 // SH2 images (sh.h): half [plane][Kp/8][M][8] of w'[r][k] * 2^e[r], then M floats row scale, then M floats bias.  ONE WAVE PER
 // OUTPUT ROW: the row's largest |w'| fixes its exponent e (largest value in [2^12, 2^13)), which needs the whole row first.
@@ -74,7 +84,7 @@ __device__ __forceinline__ const float* repack_src(const RepackJob& j, const cha
 }
 
 template <int KIND>
-__device__ __forceinline__ void repack_sh2_rows(const RepackJob& j, char* packed) {
+__device__ __forceinline__ void repack_sh2_rows(const RepackJob& j, char* packed, int bx, int nbx) {
     const float* jw = repack_src(j, packed);
     // a wave takes EIGHT consecutive rows: lane = (k group within the pass) * 8 + row, so the eight 16-byte groups of one k group
     // are 128 contiguous bytes of the image (a single row per wave wrote 16 bytes every M * 16)
@@ -86,7 +96,7 @@ __device__ __forceinline__ void repack_sh2_rows(const RepackJob& j, char* packed
     float* rowscale = (float*)(packed + j.out_off + (size_t)2 * Kp * M * sizeof(_Float16));
     float* rbias = rowscale + M;
     const int nchunk = (j.Cin + 7) / 8;
-    for (int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 8; r0 < M; r0 += gridDim.x * 32) {
+    for (int r0 = (bx * 4 + (threadIdx.x >> 6)) * 8; r0 < M; r0 += nbx * 32) {
         const int r = r0 + r8;
         const bool rv = r < M;
         float fold = 1.f;
@@ -219,13 +229,13 @@ __device__ __forceinline__ void brick_emit(const float (&b)[72], int tap, float 
 }
 
 // SH2_FIRST: one lane per output row, a loop over the row's bricks (two passes: row maximum, then the split)
-__device__ __forceinline__ void repack_sh2_first(const RepackJob& j, char* packed) {
+__device__ __forceinline__ void repack_sh2_first(const RepackJob& j, char* packed, int bx, int nbx) {
     const int M = j.Cout, G = j.K, Kp = G * 8;
     _Float16* oh = (_Float16*)(packed + j.out_off);
     float* rowscale = (float*)(packed + j.out_off + (size_t)2 * Kp * M * sizeof(_Float16));
     float* rbias = rowscale + M;
     const int nchunk = (j.Cin + 7) / 8;
-    for (int r = blockIdx.x * 256 + threadIdx.x; r < M; r += gridDim.x * 256) {
+    for (int r = bx * 256 + threadIdx.x; r < M; r += nbx * 256) {
         const float fold = j.fold_logs ? expf(j.fold_logs[r] * LOGSCALE) : 1.f;
         const float* row = repack_src(j, packed) + (long)r * j.Cin * 9;
         float mx = 0.f;
@@ -266,14 +276,14 @@ __device__ __forceinline__ void repack_sh2_first(const RepackJob& j, char* packe
 // SH2_FIRST with many input channels (the deep levels' f.4 as a direct 3x3 image: 64 chunks per row; their f.0: 12 / 24): a WAVE takes
 // eight rows, lane = (brick-in-pass) * 8 + row, so a row's bricks are spread over eight lanes (one lane per row walked 64 bricks
 // twice: 0.67 ms per pack at config E).  Same values as repack_sh2_first: the row maximum is a maximum, the split is per element.
-__device__ __forceinline__ void repack_sh2_first_wide(const RepackJob& j, char* packed) {
+__device__ __forceinline__ void repack_sh2_first_wide(const RepackJob& j, char* packed, int bx, int nbx) {
     const int M = j.Cout, G = j.K, Kp = G * 8;
     _Float16* oh = (_Float16*)(packed + j.out_off);
     float* rowscale = (float*)(packed + j.out_off + (size_t)2 * Kp * M * sizeof(_Float16));
     float* rbias = rowscale + M;
     const int nchunk = (j.Cin + 7) / 8;
     const int lane = threadIdx.x & 63, r8 = lane & 7, gl = lane >> 3;
-    for (int r0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 8; r0 < M; r0 += gridDim.x * 32) {
+    for (int r0 = (bx * 4 + (threadIdx.x >> 6)) * 8; r0 < M; r0 += nbx * 32) {
         const int r = r0 + r8;
         const bool rv = r < M;
         const float fold = (rv && j.fold_logs) ? expf(j.fold_logs[r] * LOGSCALE) : 1.f;
@@ -344,14 +354,14 @@ __device__ __forceinline__ void load_brick_kperm(const float* row, int gi, bool 
 
 // SH2_TAIL: a block takes EIGHT output channels (lane = brick-in-pass * 8 + channel, the four waves split the bricks) and emits
 // their 9 x 8 rows; row maxima go through LDS.  Rows beyond 9 Cout (the padding to whole row tiles) are zero-filled.
-__device__ __forceinline__ void repack_sh2_tail(const RepackJob& j, char* packed) {
+__device__ __forceinline__ void repack_sh2_tail(const RepackJob& j, char* packed, int bx, int nbx) {
     __shared__ float s_mx[4][9][8];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, r8 = lane & 7, gl = lane >> 3;
     const int M = j.Kpad, Kp = j.Cin, ngroups = Kp / 8, rows = 9 * j.Cout;
     _Float16* oh = (_Float16*)(packed + j.out_off);
     float* rowscale = (float*)(packed + j.out_off + (size_t)2 * Kp * M * sizeof(_Float16));
     float* rbias = rowscale + M;
-    for (int co0 = blockIdx.x * 8; co0 < j.Cout; co0 += gridDim.x * 8) {
+    for (int co0 = bx * 8; co0 < j.Cout; co0 += nbx * 8) {
         const int co = co0 + r8;
         const bool rv = co < j.Cout;
         const float* row = repack_src(j, packed) + (long)(rv ? co : 0) * j.Cin * 9;
@@ -405,11 +415,11 @@ __device__ __forceinline__ void repack_sh2_tail(const RepackJob& j, char* packed
     h8 z;
 #pragma unroll
     for (int k8 = 0; k8 < 8; ++k8) z[k8] = (_Float16)0.f;
-    for (int el = blockIdx.x * 256 + threadIdx.x; el < pad * 2 * ngroups; el += gridDim.x * 256) {
+    for (int el = bx * 256 + threadIdx.x; el < pad * 2 * ngroups; el += nbx * 256) {
         const int g2 = el / pad, r = rows + (el - g2 * pad);
         *reinterpret_cast<h8*>(oh + ((long)g2 * M + r) * 8) = z;
     }
-    for (int r = rows + blockIdx.x * 256 + threadIdx.x; r < M; r += gridDim.x * 256) {
+    for (int r = rows + bx * 256 + threadIdx.x; r < M; r += nbx * 256) {
         rowscale[r] = SH2_ACT_INV;
         rbias[r] = 0.f;
     }
@@ -419,9 +429,92 @@ template <int KIND>
 __global__ void __launch_bounds__(256) k_repack_sh2_batched(const RepackJob* __restrict__ jobs, char* packed) {
     const RepackJob j = jobs[blockIdx.y];
     if (j.kind != KIND) return;
-    if (KIND == REPACK_SH2_GEMM) repack_sh2_rows<REPACK_SH2_GEMM>(j, packed);
-    else if (KIND == REPACK_SH2_FIRST) { if (j.Cin >= 64) repack_sh2_first_wide(j, packed); else repack_sh2_first(j, packed); }
-    else repack_sh2_tail(j, packed);
+    const int bx = blockIdx.x, nbx = gridDim.x;
+    if (KIND == REPACK_SH2_GEMM) repack_sh2_rows<REPACK_SH2_GEMM>(j, packed, bx, nbx);
+    else if (KIND == REPACK_SH2_FIRST) { if (j.Cin >= 64) repack_sh2_first_wide(j, packed, bx, nbx); else repack_sh2_first(j, packed, bx, nbx); }
+    else repack_sh2_tail(j, packed, bx, nbx);
+}
+
+// ---- the forward-only pack as ONE launch.  Nothing in that pack depends on anything else in it (the mixers apply W itself, the
+// image bodies compute exp(3 logs) themselves, the LU feeds only the log-det total that k_finalize reads at the very end), so
+// one 1-D grid takes every job: a plan-constant table (PackSeg, built by glowhip_plan_pack_for) maps a block to (kind, job, block
+// within the job).  The LU waves hold the lowest block indices -- a 64+ us latency chain that starts at time zero and hides under
+// the bandwidth-bound image blocks behind it.  The bodies are the per-kind kernels' own: the bytes of `packed` are theirs.
+// The plan-wide log-det total (k_sum_konst's) is taken by the LU workgroup that arrives LAST at a counter next to the table -- the
+// classic last-arriver pattern.  The per-step terms are PLAIN stores (step_prepare_small_body); what publishes them is the
+// agent-scope __threadfence() in front of the barrier and the counter increment: it writes this XCD's L2 back (the workgroups sit
+// on different XCDs, each with its own L2).  The last arriver fences again and reads the terms with agent-scope atomic loads,
+// which go around its own L2.  Both fences are load-bearing: without them a term may still sit in another XCD's L2.
+// Nobody waits; the counter is zero when the table is uploaded and the last arriver leaves it zero.
+__global__ void __launch_bounds__(256) k_pack_fused(const PackSeg* __restrict__ segs, const StepPrepJob* __restrict__ prep, int n_prep,
+                                                    const RepackJob* __restrict__ rjobs, const ScaleJob* __restrict__ sjobs,
+                                                    unsigned* counter, int n_lu_blocks, char* packed) {
+    const PackSeg sg = segs[blockIdx.x];
+    switch (sg.kind) {
+    case PACKSEG_LU: {
+        __shared__ double v[256];
+        __shared__ int s_last;
+        step_prepare_small_body(prep, n_prep, packed, sg.bx);
+        __threadfence();                                  // publishes this workgroup's konst words (plain stores) before it counts
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const unsigned old = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            s_last = old + 1 == (unsigned)n_lu_blocks;
+            if (s_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (!s_last) break;
+        __threadfence();
+        // k_sum_konst's sum: fetched in parallel, added in layer order by one thread
+        double t = 0.0;
+        for (int base = 0; base < n_prep; base += 256) {
+            const int i = base + threadIdx.x;
+            v[threadIdx.x] = i < n_prep ? __hip_atomic_load((const double*)(packed + prep[i].konst_off), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+            __syncthreads();
+            if (threadIdx.x == 0)
+                for (int q = 0; q < 256 && base + q < n_prep; ++q) t += v[q];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) *(double*)packed = t;
+        break;
+    }
+    case PACKSEG_SH2_GEMM: repack_sh2_rows<REPACK_SH2_GEMM>(rjobs[sg.job], packed, sg.bx, sg.nbx); break;
+    case PACKSEG_SH2_FIRST: {
+        const RepackJob j = rjobs[sg.job];
+        if (j.Cin >= 64) repack_sh2_first_wide(j, packed, sg.bx, sg.nbx); else repack_sh2_first(j, packed, sg.bx, sg.nbx);
+        break;
+    }
+    case PACKSEG_SH2_TAIL: repack_sh2_tail(rjobs[sg.job], packed, sg.bx, sg.nbx); break;
+    case PACKSEG_LEGACY: repack_legacy(rjobs[sg.job], packed, sg.bx, sg.nbx); break;
+    case PACKSEG_SCALE: pack_scales(sjobs[sg.job], packed, sg.bx, sg.nbx); break;
+    default:            // PACKSEG_ZERO: the 256-byte zero block at the head of `packed` (the log-det total in its first word is the
+                        // last LU workgroup's; a plan without FlowSteps has none, and its total is 0)
+        if (threadIdx.x < 64 && (threadIdx.x >= 2 || n_prep == 0)) reinterpret_cast<float*>(packed)[threadIdx.x] = 0.f;
+        break;
+    }
+}
+
+// blocks of one job inside k_pack_fused: exactly what the job's body can use
+int pack_fused_job_blocks(int seg_kind, const RepackJob* r, const ScaleJob* sj) {
+    switch (seg_kind) {
+    case PACKSEG_SH2_GEMM: return std::max(1, (r->Cout + 31) / 32);                                   // 4 waves x 8 rows
+    case PACKSEG_SH2_FIRST: return std::max(1, r->Cin >= 64 ? std::min(16, (r->Cout + 31) / 32) : (r->Cout + 255) / 256);
+    case PACKSEG_SH2_TAIL: return std::max(1, (r->Cout + 7) / 8);                                     // 8 output channels
+    case PACKSEG_LEGACY: {
+        const long total = r->kind == REPACK_WIDE ? (long)r->Kpad * r->Cout : (r->kind == REPACK_FIRST ? (long)9 * r->Cin * r->Cout : r->total);
+        return (int)std::max(1L, std::min(64L, (total + 255) / 256));
+    }
+    case PACKSEG_SCALE: return std::max(1, std::min(2, (sj->n + 255) / 256));
+    default: return 1;
+    }
+}
+
+int launch_pack_fused(const PackSeg* segs_dev, int n_segs, const StepPrepJob* prep_dev, int n_prep, const RepackJob* rj_dev,
+                      const ScaleJob* sj_dev, unsigned* counter_dev, void* packed, hipStream_t s) {
+    hipLaunchKernelGGL(k_pack_fused, dim3(n_segs), dim3(256), 0, s, segs_dev, prep_dev, n_prep, rj_dev, sj_dev, counter_dev,
+                       (n_prep + 3) / 4, (char*)packed);
+    GH_LAUNCH_CHECK("k_pack_fused");
+    return GLOWHIP_OK;
 }
 
 // dst[i][o][ks-1-tap] = src[o][i][tap]: a workgroup moves a 32 (o) x 32 (i) tile through LDS -- reads are runs of 32 ks floats of

@@ -319,7 +319,7 @@ static float* other_buf(const Workspace& w, const float* cur) { return cur == w.
 // A Squeeze2d layer whose output only the NEXT layer's k_chanmix reads (the first FlowStep of a level on the k_cnet path or the
 // kernel pairs) is not run at all: the mixer gathers the squeezed view itself, dequantisation noise and 8-bit scaling included
 // ("fuse uint8 -> fp32 scaling + noise + first squeeze into the first kernel").
-struct SqueezeFold { const void* src; int u8; float div; const float* noise; RngSpec rng; int W; };
+struct SqueezeFold { const void* src; int u8; float div; const float* noise; RngSpec rng; int W; long bs; };
 // (testing: the mixer-fusion switch glowhip_debug_force_tail_tile(0x8000) also brings the squeeze kernels back -- the two must
 // agree bit for bit)
 
@@ -333,6 +333,13 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
     bool pending = false;    // the previous FlowStep's k_cnet has run, its finishing step has not (cnet_chain)
     CnetPending pend{};
     int scr_i = 0;
+    long cur_bs = 0;         // batch stride of `cur` when it is Split2d's z1 left where it lies (0: dense)
+    // does the Squeeze2d at layer `ls` fold into the next layer's mixer?
+    auto squeeze_folds = [&](int ls) {
+        if (debug_switches().no_mixer_fusion || ls + 1 >= nl - 1 || p->layers[ls].d.W % 2 != 0) return false;
+        const LayerPlan& Ln = p->layers[ls + 1];
+        return Ln.d.kind == GLOWHIP_LAYER_FLOWSTEP && !dnet_runs(p, Ln) && chanmix_squeeze_foldable(Ln.d.C);
+    };
     for (int li = first_layer; li < nl; ++li) {
         const LayerPlan& L = p->layers[li];
         const glowhip_layer_desc& d = L.d;
@@ -342,14 +349,11 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
         const long chw = (long)d.C * HW;
         if (d.kind == GLOWHIP_LAYER_SQUEEZE) {
             const bool u8 = x_u8 != nullptr && li == 0;
-            bool foldable = false;
-            if (!debug_switches().no_mixer_fusion && li + 1 < nl - 1 && d.W % 2 == 0) {
-                const LayerPlan& Ln = p->layers[li + 1];
-                foldable = Ln.d.kind == GLOWHIP_LAYER_FLOWSTEP && !dnet_runs(p, Ln) && chanmix_squeeze_foldable(Ln.d.C);
-            }
+            const bool foldable = squeeze_folds(li);
             if (foldable) {
                 fold = SqueezeFold{u8 ? (const void*)x_u8 : (const void*)cur, u8 ? 1 : 0, u8_div, noise,
-                                   (li == 0 && rng) ? *rng : RngSpec{}, d.W};
+                                   (li == 0 && rng) ? *rng : RngSpec{}, d.W, cur_bs};
+                cur_bs = 0;
                 count_launch(p, "squeeze(folded)");
                 noise = nullptr; rng = nullptr;
                 continue;      // `cur` stays the un-squeezed tensor; the next layer reads it through `fold`
@@ -388,7 +392,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 } else {
                     if (!premixed) {
                         ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
-                        if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; fold = SqueezeFold{}; }
+                        if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; m.sq_bs = fold.bs; fold = SqueezeFold{}; }
                         ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
                         count_launch(p, "k_chanmix");
                         GH_TRY(launch_chanmix(m, s));
@@ -422,7 +426,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                     dst = const_cast<float*>(cur);   // the step runs in place on the already mixed buffer
                 } else {
                     ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
-                    if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; fold = SqueezeFold{}; }
+                    if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; m.sq_bs = fold.bs; fold = SqueezeFold{}; }
                     ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
                     count_launch(p, "k_chanmix");
                     GH_TRY(launch_chanmix(m, s));
@@ -436,6 +440,13 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 // bound latents are in DECODE order (deepest split first); contiguous (N, C/2, HW) buffers
                 float* eps_out = p->eps_out.empty() ? nullptr : p->eps_out[p->n_split - 1 - L.split_idx];
                 GH_TRY(run_split(p, L, packed, cur, chw, cur + (long)Ch * HW, chw, nullptr, eps_out, (long)Ch * HW, N, 0, w, s));
+                // z1 is compacted for the next layer -- unless that is a Squeeze2d that folds into the mixer behind it: the fold
+                // reads z1 where it lies, through the batch stride of the undivided tensor
+                if (li + 1 < nl && p->layers[li + 1].d.kind == GLOWHIP_LAYER_SQUEEZE && squeeze_folds(li + 1)) {
+                    count_launch(p, "split2d:z1 in place");
+                    cur_bs = chw;
+                    continue;
+                }
                 GH_TRY(launch_copy_strided(cur, chw, dst, (long)Ch * HW, N, (long)Ch * HW, s));
             }
         }
@@ -766,6 +777,14 @@ glowhip_plan* glowhip_plan_create(const glowhip_layer_desc* layers, int n_layers
     // rewrites the table a captured graph of another mask launches over
     p->repack_off = take(off, REPACK_SLOTS * p->repack_jobs.size() * sizeof(RepackJob));
     p->flip_off = take(off, p->flip_jobs.size() * sizeof(FlipJob));
+    {   // the one-launch forward pack's table (k_pack_fused): an arrival counter, then at most one PackSeg per block of every job
+        size_t nseg = (p->prep_jobs.size() + 3) / 4 + 1;
+        for (const RepackJob& r : p->repack_jobs)
+            nseg += pack_fused_job_blocks(r.kind < REPACK_SH2_GEMM ? PACKSEG_LEGACY : PACKSEG_SH2_GEMM + (r.kind - REPACK_SH2_GEMM), &r, nullptr);
+        for (const ScaleJob& sj : p->scale_jobs) nseg += pack_fused_job_blocks(PACKSEG_SCALE, nullptr, &sj);
+        p->seg_cap = nseg;
+        p->seg_off = take(off, PACK_SEG_HEAD + nseg * sizeof(PackSeg));
+    }
     p->packed_bytes = align_up(off, 256);
     return p;
 }
@@ -918,8 +937,14 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
                plan->packed_bytes);
     hipStream_t s = (hipStream_t)stream;
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // (a previous pack's side-stream part writes the same buffer)
-    // job tables -> device (plan-constant contents; re-sent because `packed` is caller memory), then 4 launches
-    if (hipMemsetAsync(packed, 0, 256, s) != hipSuccess) {
+    // The forward-only pack of a plan whose LU jobs are all one-wave jobs and that keeps everything on one stream is ONE launch
+    // (pack.hip k_pack_fused); every other pack -- inverse, training, wide plans, the init pass -- is the launch sequence below.
+    // (the debug switch picks the launches only: the table travels either way, so the two routes leave the same bytes in `packed`)
+    bool fusable = use == GLOWHIP_PACK_INFERENCE && plan->max_c <= 128 && n_kind[4] == 0 && !debug_switches().lu_workgroup;
+    for (const StepPrepJob& pj : plan->prep_jobs) fusable = fusable && step_prepare_small_takes(pj);
+    const bool fused = fusable && !debug_switches().pack_unfused;
+    // job tables -> device (plan-constant contents; re-sent because `packed` is caller memory), then the launches
+    if (!fused && hipMemsetAsync(packed, 0, 256, s) != hipSuccess) {
         set_error("plan_pack: hipMemsetAsync failed");
         return GLOWHIP_ELAUNCH;
     }
@@ -939,7 +964,7 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
             set_error("plan_pack: hipMemcpyAsync of the job tables failed");
             return GLOWHIP_ELAUNCH;
         }
-        plan->tables_in = packed; plan->slots_in = 0;
+        plan->tables_in = packed; plan->slots_in = 0; plan->segs_in = false;
     }
     if (!(plan->slots_in & (1u << slot))) {
         // (hipMemcpyAsync from pageable memory stages the source before it returns; the per-slot host copy is kept anyway)
@@ -950,6 +975,47 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
             return GLOWHIP_ELAUNCH;
         }
         plan->slots_in |= 1u << slot;
+    }
+    if (fusable) {
+        // The table holds indices into the repack table of THIS slot (repack_sel of this use mask, sorted by kind group).  Today
+        // `fusable` admits one mask only, so it is a plan constant; it is keyed by the slot all the same: a pack of another slot
+        // rebuilds it and sends it again, and never launches over job indices of another selection.
+        if (plan->pack_segs.empty() || plan->pack_segs_slot != slot) {
+            std::vector<PackSeg>& t = plan->pack_segs;
+            t.clear(); plan->pack_segs_slot = slot; plan->segs_in = false;
+            for (int b = 0; b < ((int)plan->prep_jobs.size() + 3) / 4; ++b) t.push_back(PackSeg{PACKSEG_LU, 0, b, 1});
+            static const int order[4] = {1, 2, 3, 0};      // kind groups of repack_sel: SH2 GEMM, FIRST, TAIL, then the legacy kinds
+            for (int g : order) {
+                int first = 0;
+                for (int q = 0; q < g; ++q) first += n_kind[q];
+                const int kind = g == 0 ? PACKSEG_LEGACY : PACKSEG_SH2_GEMM + (g - 1);
+                for (int jn = first; jn < first + n_kind[g]; ++jn) {
+                    const int nb = pack_fused_job_blocks(kind, &plan->repack_sel[jn], nullptr);
+                    for (int b = 0; b < nb; ++b) t.push_back(PackSeg{kind, jn, b, nb});
+                }
+            }
+            for (int jn = 0; jn < (int)plan->scale_jobs.size(); ++jn) {
+                const int nb = pack_fused_job_blocks(PACKSEG_SCALE, nullptr, &plan->scale_jobs[jn]);
+                for (int b = 0; b < nb; ++b) t.push_back(PackSeg{PACKSEG_SCALE, jn, b, nb});
+            }
+            t.push_back(PackSeg{PACKSEG_ZERO, 0, 0, 1});
+        }
+        GH_REQUIRE(plan->pack_segs.size() <= plan->seg_cap, "plan_pack: segment table larger than its slot");
+        if (!plan->segs_in) {
+            static const char zero_head[PACK_SEG_HEAD] = {0};
+            if (!upload(plan->seg_off, zero_head, PACK_SEG_HEAD) ||
+                !upload(plan->seg_off + PACK_SEG_HEAD, plan->pack_segs.data(), plan->pack_segs.size() * sizeof(PackSeg))) {
+                set_error("plan_pack: hipMemcpyAsync of the segment table failed");
+                return GLOWHIP_ELAUNCH;
+            }
+            plan->segs_in = true;
+        }
+    }
+    if (fused) {
+        count_launch(plan, "pack:k_pack_fused");
+        return launch_pack_fused(at<PackSeg>(packed, plan->seg_off + PACK_SEG_HEAD), (int)plan->pack_segs.size(),
+                                 at<StepPrepJob>(packed, plan->prep_off), (int)plan->prep_jobs.size(), at<RepackJob>(packed, slot_off),
+                                 at<ScaleJob>(packed, plan->scale_off), at<unsigned>(packed, plan->seg_off), packed, s);
     }
     // Fork: the legacy-kind images and the LU factorisations go to the plan's side stream (created on first use; a host resource
     // like the timing events) behind everything enqueued so far; whoever reads their results joins (join_legacy / join_lu).  What
@@ -1042,7 +1108,7 @@ int glowhip_plan_pack_sync(glowhip_plan* plan) {
 
 int glowhip_plan_forget_packed(glowhip_plan* plan) {
     GH_REQUIRE(plan, "plan_forget_packed: null plan");
-    plan->tables_in = nullptr; plan->slots_in = 0;
+    plan->tables_in = nullptr; plan->slots_in = 0; plan->segs_in = false;
     return GLOWHIP_OK;
 }
 

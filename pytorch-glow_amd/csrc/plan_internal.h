@@ -58,6 +58,9 @@ struct glowhip_plan {
     std::vector<FlipJob> flip_jobs; int flip_tiles[3] = {1, 1, 1}; size_t flip_off = 0;      // (tiles: max per member of a (f.4, f.2, f.0) triple)
     std::vector<RepackJob> repack_sel;    // the subset selected by the last glowhip_plan_pack_for (kept alive for the async copy)
     size_t prep_off = 0, scale_off = 0, repack_off = 0;
+    // one-launch forward pack (k_pack_fused): its block table (plan-constant, built by the first such pack), where it lives in
+    // `packed` behind PACK_SEG_HEAD bytes that hold the LU workgroups' arrival counter, and whether tables_in holds it already
+    std::vector<glowhip::PackSeg> pack_segs; int pack_segs_slot = -1; size_t seg_off = 0, seg_cap = 0; bool segs_in = false;
     // glowhip_plan_pack forks onto a side stream what the first kernels of a forward do not wait for: the round-1 / fp32 weight images
     // (read by the deep levels and the Split2d priors) and the LU factorisations (log|det W| enters only the final sum; W^-1 is
     // read by decode / backward).  Consumers join through these events (join_legacy / join_lu).
@@ -103,6 +106,7 @@ struct ScopedTimer {
 };
 
 
+constexpr size_t PACK_SEG_HEAD = 16;
 constexpr int REPACK_SLOTS = 32;
 // slot of a use mask's selected repack jobs: the five bits that select images (1 inference, 2 training, 4 inverse: the W^-1 images
 // of the deep levels, 8 round-1 images of cnet / dnet layers, 16 init pass' f.0 image); 32 (no LU) does not change the table

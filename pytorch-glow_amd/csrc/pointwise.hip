@@ -331,14 +331,16 @@ __global__ void __launch_bounds__(256) k_chanmix(ChanMixArgs a, int stage_matrix
     const bool an = a.bias != nullptr;
     if (a.sq_src) {       // squeezed view of the un-squeezed input (+ dequantisation noise, 8-bit scaling): the squeeze pass is gone
         const int Wo = a.sq_W >> 1, h = p / Wo, w = p - h * Wo, C0 = C >> 2;
-        const long img = (long)n * C0 * (4l * a.HW);
+        const long dense = (long)n * C0 * (4l * a.HW);                       // the element index the noise tensor / draw is keyed by
+        const long img = a.sq_bs ? (long)n * a.sq_bs : dense;               // (a view with a batch stride: Split2d's z1 where it lies)
         for (int c = og; c < C; c += OG) {
             float xv = 0.f;
             if (valid) {
-                const long src = img + ((long)(c >> 2) * (2 * (a.HW / Wo)) + 2 * h + ((c >> 1) & 1)) * a.sq_W + 2 * w + (c & 1);
+                const long rel = ((long)(c >> 2) * (2 * (a.HW / Wo)) + 2 * h + ((c >> 1) & 1)) * a.sq_W + 2 * w + (c & 1);
+                const long src = img + rel;
                 xv = a.sq_u8 ? (float)reinterpret_cast<const uint8_t*>(a.sq_src)[src] / a.sq_div : reinterpret_cast<const float*>(a.sq_src)[src];
-                if (a.sq_noise) xv += a.sq_noise[src];
-                else if (a.sq_rng.on) xv += dequant_noise(a.sq_rng.seed, a.sq_rng.call, (unsigned long long)src, a.sq_rng.scale);
+                if (a.sq_noise) xv += a.sq_noise[dense + rel];
+                else if (a.sq_rng.on) xv += dequant_noise(a.sq_rng.seed, a.sq_rng.call, (unsigned long long)(dense + rel), a.sq_rng.scale);
             }
             if (!a.reverse && an) xv = (xv + a.bias[c]) * a.scale[c];
             v[c * PX + px] = xv;
