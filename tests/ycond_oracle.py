@@ -47,7 +47,7 @@ def classification_loss(y_logits, criterion, y=None, y_onehot=None):
     """network/model.py:508-538 (mean-reduced CrossEntropyLoss / BCEWithLogitsLoss)"""
     if criterion == "ce":
         return torch.nn.functional.cross_entropy(y_logits, y.long())
-    return torch.nn.functional.binary_cross_entropy_with_logits(y_logits, y_onehot.float())
+    return torch.nn.functional.binary_cross_entropy_with_logits(y_logits, y_onehot.to(y_logits.dtype))
 
 
 def glow_sample(sd, cfg, y_onehot, eps_top, eps_list):
@@ -62,6 +62,41 @@ def logit_bound(sd, base):
     """`base` (a bound on |dz|) carried through the classifier: base * max(1, max_k exp(3 logs_k) * sum_c |W[k, c]|)."""
     w, logs = sd["classifier.weight"], sd["classifier.logs"]
     return base * max(1.0, float((torch.exp(3.0 * logs) * w.abs().sum(dim=1)).max()))
+
+
+def seeded_head_state(C, classes, learn_top, seed=7):
+    """Seeded, NON-zero parameters of the top head over a top latent of C channels (LinearZeros / Conv2dZeros initialise to zero,
+    which would hide every head kernel): weights and biases randn * 0.1, every `logs` randn * 0.05; learn_top.weight small but
+    non-zero (it multiplies h_top == 0, so its gradient must stay exactly zero).  Keys and shapes are the modules'."""
+    g = torch.Generator().manual_seed(seed)
+    rn = lambda *shape: torch.randn(*shape, generator=g)
+    sd = {"y_emb.weight": rn(2 * C, classes) * 0.1, "y_emb.bias": rn(2 * C) * 0.1, "y_emb.logs": rn(2 * C) * 0.05,
+          "classifier.weight": rn(classes, C) * 0.1, "classifier.bias": rn(classes) * 0.1, "classifier.logs": rn(classes) * 0.05}
+    if learn_top:
+        sd.update({"learn_top.weight": rn(2 * C, 2 * C, 3, 3) * 0.01, "learn_top.bias": rn(2 * C) * 0.1,
+                   "learn_top.logs": rn(2 * C, 1, 1) * 0.05})
+    return sd
+
+
+def fp64_reference(x, noise, sd, cfg, y_onehot, crit, y=None):
+    """The conditional training step in float64 under O.STABLE_LOGDET (fp32 `det` underflows at C = 384), gradients from
+    autograd: dict(z, nll, y_logits, loss, loss_generative, loss_classes, grad={name: tensor}, dx).  `sd`, `x`, `noise` are the
+    fp32 tensors the HIP path gets; they are widened exactly."""
+    prev, O.STABLE_LOGDET = O.STABLE_LOGDET, True
+    try:
+        with torch.enable_grad():
+            leaf = {k: v.double().requires_grad_(k != "h_top") for k, v in sd.items()}
+            xr = x.double().requires_grad_(True)
+            yo = y_onehot.double()
+            z, nll, y_logits = glow_forward(xr, noise.double(), leaf, cfg, yo)
+            loss_gen = nll.mean()
+            loss_cls = classification_loss(y_logits, crit, y=y, y_onehot=yo)
+            loss = loss_gen + float(cfg["weight_y"]) * loss_cls
+            loss.backward()
+    finally:
+        O.STABLE_LOGDET = prev
+    return dict(z=z.detach(), nll=nll.detach(), y_logits=y_logits.detach(), loss=loss.item(), loss_generative=loss_gen.item(),
+                loss_classes=loss_cls.item(), grad={k: v.grad for k, v in leaf.items() if v.grad is not None}, dx=xr.grad)
 
 
 def case_state(g, lt):
