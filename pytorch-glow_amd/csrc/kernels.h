@@ -87,6 +87,7 @@ struct StepPrepJob {
 };
 int launch_step_prepare_batched(const StepPrepJob* jobs_dev, int n, int max_lds_c, void* packed, hipStream_t s, int want_inverse = 1,
                                 int max_c = 0, int all_small = 0);   // want_inverse = 0: log|det W| only (W^-1 is left stale)
+const char* step_prepare_route_name(int C, int want_inverse);   // launch-counter name of the factorisation k_step_prepare_batched runs on a C x C matrix
 bool step_prepare_small_takes(const StepPrepJob& j);   // all_small = every job of the table passes this (lu.hip k_step_prepare_small)
 
 struct ScaleJob { const float* logs; size_t scale_off, inv_off; int n; int has_inv; };

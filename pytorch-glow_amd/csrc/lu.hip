@@ -1,7 +1,12 @@
-// lu.hip -- in-kernel LU of the invertible 1x1 convolution weight (replaces torch.det and
-// Tensor.inverse at network/module.py:357,365).  One workgroup per matrix runs Gauss-Jordan
-// elimination with partial pivoting in fp64 on the augmented matrix [W | I] held in LDS (C <= 64)
-// or in an L2-resident scratch buffer (larger C): log|det W| = sum log|pivot|, W^-1 = right half.
+// lu.hip -- in-kernel factorisations of the invertible 1x1 convolution weight (replace torch.det and Tensor.inverse at
+// network/module.py:357,365).  One workgroup (or, in lu_wave.h, one wave) per matrix, partial pivoting with the lowest-row
+// tie-break, fp64 arithmetic, fp32 results; log|det W| is always the sum of log|pivot| in pivot order.  Five routes:
+//   lu_logdet_wave<12|24|48> (lu_wave.h)  one wave, the matrix in registers: k_pack_fused, k_step_prepare_small (forward-only packs)
+//   lu_logdet_only       workgroup LU, log-det only: in LDS for C <= 128, in global scratch for C > 448
+//   lu_logdet_blocked    blocked right-looking LU (32-column panels in LDS), log-det only: 128 < C <= 448
+//   lu_gauss_jordan      Gauss-Jordan on [W | I], gives W^-1 as well (decode, backward): in LDS for C <= 64,
+//                        in an L2-resident global scratch buffer above (the ABI accepts C <= 1024)
+// step_prepare_route() is the one place that maps (C, want_inverse) to a route of k_step_prepare_batched.
 #include <algorithm>
 
 #include "kernels.h"
@@ -27,9 +32,13 @@ __device__ __forceinline__ void lu_load_matrix(const float* __restrict__ w, int 
 }
 
 // Workgroup-wide Gauss-Jordan on A = [W | I] (C x 2C doubles, LDS or global).  Returns log|det W| (thread 192).
-// Three barriers per pivot: (1) pivot row and value published by wave 0; (2) rows k and p swapped with the pivot row scaled
-// on the way (two rows, one pass); (3) column k eliminated from every other row.  Column k of the left half is never read
-// again, so it is not cleared.  log|pivot| is summed by a lane of the LAST wave while the others eliminate.
+// Three barriers per pivot: (1) pivot row and value published by wave 0; (2) rows k and p swapped and column k of every other row
+// turned into its multiplier l = a / pivot (one pass); (3) column k eliminated from every other row with fma(-l, pivot row, a).
+// The pivot row is NOT scaled: the left half ends as the diagonal of pivots and W^-1 = right half / diagonal, divided on the way
+// out.  This is the multiplier form of the LU routes: a row equal to the pivot row has l = 1 and cancels EXACTLY (pivot 0 and
+// log 0 = -inf at the end -- never a finite log-det of such a matrix); eliminating with a pre-scaled pivot row leaves the
+// rounding residue of the division instead.  Columns <= k of the left half are dead (they hold multipliers and the diagonal) and
+// are not touched again.  log|pivot| is summed by a lane of the LAST wave while the others eliminate.
 __device__ double lu_gauss_jordan(const float* __restrict__ w, int C, float* __restrict__ winv, double* A) {
     __shared__ int s_piv;
     __shared__ double s_pivval;
@@ -76,19 +85,23 @@ __device__ double lu_gauss_jordan(const float* __restrict__ w, int C, float* __r
         const int pr = s_piv;
         const double piv = s_pivval;
         if (tid == 192) logdet += log(fabs(piv));
-        // rows k <-> pr, the new row k divided by the pivot (each column owned by one thread)
-        for (int c = tid; c < W2; c += 256) {
-            const double tk = A[pr * W2 + c], tp = A[k * W2 + c];
-            A[k * W2 + c] = tk / piv;
-            if (pr != k) A[pr * W2 + c] = tp;
-        }
+        // rows k <-> pr (each column owned by one thread; the row that leaves position k gets its multiplier in column k) ...
+        if (pr != k)
+            for (int c = tid; c < W2; c += 256) {
+                const double tk = A[pr * W2 + c], tp = A[k * W2 + c];
+                A[k * W2 + c] = tk;
+                A[pr * W2 + c] = c == k ? tp / piv : tp;
+            }
+        // ... and the multipliers of all other rows (column k; rows k and pr belong to the loop above)
+        for (int r = tid; r < C; r += 256)
+            if (r != k && r != pr) A[r * W2 + k] = A[r * W2 + k] / piv;
         __syncthreads();
-        // eliminate column k from every other row: A[r][c] -= A[r][k] * A[k][c] for c != k (column k itself is dead)
+        // eliminate column k from every other row: A[r][c] -= l[r] * A[k][c] for c > k (columns <= k of the left half are dead)
         {
             int r = tid / W2, c = tid - r * W2;
             const int dr = 256 / W2, dc = 256 - dr * W2;
             for (int e = tid; e < C * W2; e += 256) {
-                if (r != k && c != k) A[e] = fma(-A[r * W2 + k], A[k * W2 + c], A[e]);
+                if (r != k && c > k) A[e] = fma(-A[r * W2 + k], A[k * W2 + c], A[e]);
                 r += dr; c += dc;
                 if (c >= W2) { c -= W2; ++r; }
             }
@@ -98,7 +111,7 @@ __device__ double lu_gauss_jordan(const float* __restrict__ w, int C, float* __r
     if (winv)
         for (int e = tid; e < C * C; e += 256) {
             int r = e / C, c = e - r * C;
-            winv[e] = (float)A[r * W2 + C + c];
+            winv[e] = (float)(A[r * W2 + C + c] / A[r * W2 + r]);
         }
     __shared__ double s_logdet;
     if (tid == 192) s_logdet = logdet;
@@ -283,7 +296,9 @@ __device__ double lu_logdet_blocked(const float* __restrict__ w, int C, double* 
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
 #pragma unroll
-                    for (int b = 0; b < 4; ++b) acc[a][b] = 0.0;
+                    for (int b = 0; b < 4; ++b)      // the element first, then its updates in panel order: the chain U12's forward
+                                                     // substitution ran on the pivot row, so a row equal to it cancels exactly
+                        acc[a][b] = (r0 + a < m && cc0 + b < cb) ? A[(long)(k0 + r0 + a) * C + c0 + cc0 + b] : 0.0;
                 for (int t = 0; t < nb; ++t) {
                     double l[4], u[4];
 #pragma unroll
@@ -293,7 +308,7 @@ __device__ double lu_logdet_blocked(const float* __restrict__ w, int C, double* 
 #pragma unroll
                     for (int a = 0; a < 4; ++a)
 #pragma unroll
-                        for (int b = 0; b < 4; ++b) acc[a][b] = fma(l[a], u[b], acc[a][b]);
+                        for (int b = 0; b < 4; ++b) acc[a][b] = fma(-l[a], u[b], acc[a][b]);
                 }
 #pragma unroll
                 for (int a = 0; a < 4; ++a)
@@ -301,7 +316,7 @@ __device__ double lu_logdet_blocked(const float* __restrict__ w, int C, double* 
                     for (int b = 0; b < 4; ++b)
                         if (r0 + a < m && cc0 + b < cb) {
                             const long idx = (long)(k0 + r0 + a) * C + c0 + cc0 + b;
-                            A[idx] -= acc[a][b];
+                            A[idx] = acc[a][b];
                         }
             }
             __syncthreads();
@@ -311,6 +326,20 @@ __device__ double lu_logdet_blocked(const float* __restrict__ w, int C, double* 
     if (tid == 192) s_logdet3 = logdet;
     __syncthreads();
     return s_logdet3;
+}
+
+// The route a FlowStep's matrix takes in k_step_prepare_batched: ONE function for the kernel's branch and for the launch counters
+// the host keeps (step_prepare_route_name), so that what a test reads from the counters is what the kernel did.
+enum { LU_ROUTE_GJ_LDS = 0, LU_ROUTE_GJ_GLOBAL, LU_ROUTE_LOGDET_LDS, LU_ROUTE_LOGDET_BLOCKED, LU_ROUTE_LOGDET_GLOBAL };
+__host__ __device__ inline int step_prepare_route(int C, int want_inverse) {
+    if (want_inverse) return C <= LU_LDS_MAX_C ? LU_ROUTE_GJ_LDS : LU_ROUTE_GJ_GLOBAL;
+    if (C > LU_LDS_ONLY_MAX_C && C <= LU_BLOCKED_MAX_C) return LU_ROUTE_LOGDET_BLOCKED;   // forward only, too large for LDS: blocked LU
+    return C <= LU_LDS_ONLY_MAX_C ? LU_ROUTE_LOGDET_LDS : LU_ROUTE_LOGDET_GLOBAL;
+}
+const char* step_prepare_route_name(int C, int want_inverse) {
+    static const char* const names[] = {"pack:lu:gauss_jordan(lds)", "pack:lu:gauss_jordan(global)", "pack:lu:logdet_only(lds)",
+                                        "pack:lu:logdet_blocked", "pack:lu:logdet_only(global)"};
+    return names[step_prepare_route(C, want_inverse)];
 }
 
 template <bool USE_LDS>
@@ -329,14 +358,14 @@ __global__ void __launch_bounds__(256) k_step_prepare_batched(const StepPrepJob*
     const StepPrepJob j = jobs[blockIdx.x];
     double lad = 0.0;
     if (j.w) {
-        if (want_inverse) {
-            double* A = j.C <= LU_LDS_MAX_C ? lds_aug : (double*)(packed + j.scratch_off);
-            lad = lu_gauss_jordan(j.w, j.C, (float*)(packed + j.winv_off), A);
-        } else if (j.C > LU_LDS_ONLY_MAX_C && j.C <= LU_BLOCKED_MAX_C) {   // forward only, too large for LDS: blocked LU
-            lad = lu_logdet_blocked(j.w, j.C, (double*)(packed + j.scratch_off), lds_aug);
+        const int route = step_prepare_route(j.C, want_inverse);
+        double* scratch = (double*)(packed + j.scratch_off);
+        if (route == LU_ROUTE_GJ_LDS || route == LU_ROUTE_GJ_GLOBAL) {
+            lad = lu_gauss_jordan(j.w, j.C, (float*)(packed + j.winv_off), route == LU_ROUTE_GJ_LDS ? lds_aug : scratch);
+        } else if (route == LU_ROUTE_LOGDET_BLOCKED) {
+            lad = lu_logdet_blocked(j.w, j.C, scratch, lds_aug);
         } else {      // forward only: log|det W| without the inverse (C^3/3 instead of 2 C^3 element updates)
-            double* A = j.C <= LU_LDS_ONLY_MAX_C ? lds_aug : (double*)(packed + j.scratch_off);
-            lad = lu_logdet_only(j.w, j.C, A);
+            lad = lu_logdet_only(j.w, j.C, route == LU_ROUTE_LOGDET_LDS ? lds_aug : scratch);
         }
     }
     double acc = 0.0;

@@ -24,6 +24,11 @@ __device__ __forceinline__ double lu_logdet_wave(const float* __restrict__ w, co
 #pragma unroll
     for (int k = 0; k < C; ++k) {
         double best = (lane < C && pos >= k) ? fabs(a[k]) : -1.0;
+        if (best != best) best = __builtin_inf();   // a NaN candidate WINS the search (it compares false with everything: its lane kept
+                                                    // itself while the others never saw it, and lane 0 could end on a position < k --
+                                                    // a row already used -- whose a[k] is finite: a finite log-det of a NaN matrix).
+                                                    // As the pivot it makes every multiplier NaN.  The workgroup kernel reaches NaN its own
+                                                    // way (the row is skipped, poisoned by its NaN multiplier, and is the last candidate).
         int bi = pos;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {       // (butterfly: every lane ends with the same winner -- the largest value, lowest position among equals)

@@ -1053,6 +1053,12 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
         for (const StepPrepJob& pj : plan->prep_jobs) all_small = all_small && step_prepare_small_takes(pj);
         const bool inv = (use & (GLOWHIP_PACK_INVERSE | GLOWHIP_PACK_TRAINING)) != 0;
         count_launch(plan, (all_small && !inv) ? "pack:k_step_prepare_small" : "pack:k_step_prepare_batched");
+        if (!(all_small && !inv)) {      // which factorisation each matrix takes there (tallied first: at most five map updates per pack)
+            std::map<const char*, long> routes;
+            for (const StepPrepJob& pj : plan->prep_jobs)
+                if (pj.w) ++routes[step_prepare_route_name(pj.C, inv ? 1 : 0)];
+            for (const auto& kv : routes) plan->launch_counts[kv.first] += kv.second;
+        }
         GH_TRY(launch_step_prepare_batched(at<StepPrepJob>(packed, plan->prep_off), (int)plan->prep_jobs.size(),
                                            plan->max_lds_c, packed, side, inv, plan->max_c, all_small ? 1 : 0));
         if ((use & GLOWHIP_PACK_INVERSE) && n_kind[4] > 0)
