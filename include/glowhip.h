@@ -361,6 +361,39 @@ int glowhip_plan_bind_head_grads(glowhip_plan* plan, const glowhip_head_grads* g
 int glowhip_top_prior(const glowhip_head_desc* head, const float* y_onehot, int N, int C, int HW, float* mean, float* logs,
                       glowhip_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * LU-parameterised invertible 1x1 convolution (csrc/invconv_lu.hip).  The reference names the option and stops:
+ * Invertible1x1Conv(lu_decomposition=True) raises at network/module.py:336-337.  This is the form of the Glow paper:
+ *   W = P (tril(l, -1) + I) (triu(u, 1) + diag(sign_s * exp(log_s)))
+ * with P a fixed permutation given as its row table perm (C int32: row i of P has its one in column perm[i]), l, u (C,C),
+ * log_s, sign_s (C).  Entries of l on or above and of u on or below the diagonal are never read.  C <= 512.
+ * No factorisation: log|det W| = sum(log_s) in fp64, W^-1 by forward and back substitution.
+ * ---------------------------------------------------------------------------------------------- */
+/* Stand-alone twin of glowhip_invconv_prepare (the determinant and inverse of network/module.py:357,365 for the LU form):
+ * w_out (C*C) <- W, winv_out (C*C, may be NULL) <- W^-1, logabsdet_out (1 float, may be NULL) <- sum(log_s). */
+int glowhip_invconv_lu_prepare(const int32_t* perm, const float* l, const float* u, const float* log_s, const float* sign_s,
+                               int C, float* w_out, float* winv_out, float* logabsdet_out, glowhip_stream_t stream);
+/* Gradients of the factors from dW (C*C), the gradient w.r.t. the assembled matrix WITHOUT any log-det part, and
+ * logdet_term = HW * sum_n dL/dlogdet[n] (the log-det term log|det W| * HW of network/module.py:357 reaches log_s alone):
+ *   dl = strict-lower(P^T dW U_f^T), du = strict-upper(L^T P^T dW), dlog_s[i] = (L^T P^T dW)[i][i] sign_s[i] exp(log_s[i]) + logdet_term.
+ * Masked entries of dl / du are written as exact zeros. */
+int glowhip_invconv_lu_backward(const int32_t* perm, const float* l, const float* u, const float* log_s, const float* sign_s,
+                                int C, const float* dW, double logdet_term, float* dl, float* du, float* dlog_s,
+                                glowhip_stream_t stream);
+/* A FlowStep of a plan in the LU form.  w: writable (C*C) buffer the layer's desc.invconv_w points at -- every pack assembles W
+ * into it first, on the caller's stream, and the layer takes part in no factorisation of the pack (network/module.py:336-337 is
+ * where the reference would have done the same).  Call once after glowhip_plan_create; pointers copied, HOST bookkeeping, in the
+ * pattern of glowhip_plan_bind_head.  W^-1 of such a layer is rebuilt by packs with GLOWHIP_PACK_INVERSE only: the backward
+ * sweep does not read it. */
+typedef struct glowhip_invconv_lu {
+    const int32_t* perm; const float* l; const float* u; const float* log_s; const float* sign_s; float* w;
+} glowhip_invconv_lu;
+int glowhip_plan_bind_invconv_lu(glowhip_plan* plan, int layer, const glowhip_invconv_lu* lu);
+/* Writable gradients of an LU-form layer for the next backward sweeps (copied; NULL unbinds): they take the place of
+ * glowhip_layer_grads.invconv_w, which the sweep ignores for such a layer. */
+typedef struct glowhip_invconv_lu_grads { float* dl; float* du; float* dlog_s; } glowhip_invconv_lu_grads;
+int glowhip_plan_bind_invconv_lu_grads(glowhip_plan* plan, int layer, const glowhip_invconv_lu_grads* grads);
+
 /* Per-launch timing for benchmarks (HIP events recorded on the execution stream around every kernel of
  * the coupling path).  enable=1 creates an event pool (host resource), enable=0 destroys it; while enabled
  * every encode/decode appends records.  glowhip_plan_timing_read synchronises with the recorded events,

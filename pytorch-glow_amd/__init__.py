@@ -15,6 +15,6 @@ from ._lib import GlowHipError, build, lib  # noqa: F401
 from ._plan import FlowPlan  # noqa: F401
 from . import misc, network  # noqa: F401
 from .network import (ActNorm, Conv2d, Conv2dZeros, FlowModel, FlowStep, GaussianDiag, Glow,  # noqa: F401
-                      Invertible1x1Conv, Latents, LinearZeros, Permutation2d, Split2d, Squeeze2d, f)
+                      Invertible1x1Conv, Invertible1x1ConvLU, Latents, LinearZeros, Permutation2d, Split2d, Squeeze2d, f)
 
 __version__ = "0.1.1"

@@ -69,6 +69,16 @@ class HeadGrads(ctypes.Structure):
     _fields_ = [(n, c_void_p) for n in HEAD_PARAMS]
 
 
+class InvconvLU(ctypes.Structure):
+    """Mirror of ``glowhip_invconv_lu``."""
+    _fields_ = [(n, c_void_p) for n in ("perm", "l", "u", "log_s", "sign_s", "w")]
+
+
+class InvconvLUGrads(ctypes.Structure):
+    """Mirror of ``glowhip_invconv_lu_grads``."""
+    _fields_ = [(n, c_void_p) for n in ("dl", "du", "dlog_s")]
+
+
 class OptimChunk(ctypes.Structure):
     """Mirror of ``glowhip_optim_chunk``."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int32), ("pad", c_int32)]
@@ -132,6 +142,10 @@ SIGNATURES = {
     "glowhip_actnorm": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_invconv_scratch_bytes": (c_size_t, [c_int]),
     "glowhip_invconv_prepare": (c_int, [_P, c_int, _P, _P, _P, _P]),
+    "glowhip_invconv_lu_prepare": (c_int, [_P, _P, _P, _P, _P, c_int, _P, _P, _P, _P]),
+    "glowhip_invconv_lu_backward": (c_int, [_P, _P, _P, _P, _P, c_int, _P, ctypes.c_double, _P, _P, _P, _P]),
+    "glowhip_plan_bind_invconv_lu": (c_int, [_P, c_int, POINTER(InvconvLU)]),
+    "glowhip_plan_bind_invconv_lu_grads": (c_int, [_P, c_int, POINTER(InvconvLUGrads)]),
     "glowhip_invconv": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_permute_channels": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "glowhip_conv2d": (c_int, [_P, c_long, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int, _P]),

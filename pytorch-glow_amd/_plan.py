@@ -28,6 +28,7 @@ class FlowPlan:
         self.in_chw = tuple(int(v) for v in in_chw)
         self.device = torch.device(device)
         self._keep = []  # tensors whose addresses the C plan holds
+        self._lu = []    # (layer index, Invertible1x1ConvLU, its assembled-W buffer): bound once the plan exists
         descs = (LayerDesc * len(self.layers))()
         c, h, w = self.in_chw
         split_chw = []   # shape of the z2 half each Split2d drops, in encode order
@@ -41,7 +42,7 @@ class FlowPlan:
                     raise _lib.GlowHipError("flow plans support Squeeze2d(factor=2) only")
                 c, h, w = c * 4, h // 2, w // 2
             elif kind == _lib.LAYER_FLOWSTEP:
-                self._fill_flowstep(d, layer)
+                self._fill_flowstep(d, layer, i)
             else:
                 self._fill_split(d, layer)
                 c = c // 2
@@ -49,6 +50,8 @@ class FlowPlan:
         self.out_chw = (c, h, w)
         self.split_chw = split_chw[::-1]      # DECODE order (deepest first): the order of decode's eps and of bound latents
         self._params = [p for layer in self.layers for p in _param_tensors(layer)]
+        # (the LU modules' buffers decide W like parameters do: a load_state_dict or broadcast into them must re-pack as well)
+        self._params += [b for _, m, _ in self._lu for b in (m.p, m.sign_s)]
         for p in self._params:
             if p.device != self.device:
                 raise _lib.GlowHipError(f"parameter on {p.device}, plan on {self.device}")
@@ -58,6 +61,12 @@ class FlowPlan:
             raise _lib.GlowHipError("glowhip_plan_create: " + lib().glowhip_last_error().decode())
         self._h = ctypes.c_void_p(handle)
         self._descs = descs
+        for i, m, wbuf in self._lu:
+            b = _lib.InvconvLU()
+            b.perm, b.l, b.u, b.log_s, b.sign_s = (self._dev_any(m.perm_table()), self._dev(m.l), self._dev(m.u), self._dev(m.log_s),
+                                                   self._dev(m.sign_s))
+            b.w = wbuf.data_ptr()
+            check(lib().glowhip_plan_bind_invconv_lu(self._h, i, ctypes.byref(b)))
         self.packed_bytes = int(lib().glowhip_plan_packed_bytes(self._h))
         self.packed = torch.empty(max(self.packed_bytes, 256), dtype=torch.uint8, device=self.device)
         self._packed_version = None
@@ -73,13 +82,20 @@ class FlowPlan:
         self._keep.append(t)
         return t.data_ptr()
 
-    def _fill_flowstep(self, d: LayerDesc, step) -> None:
+    def _fill_flowstep(self, d: LayerDesc, step, index: int) -> None:
         d.hidden = step.hidden_channels
         d.coupling = _lib.COUPLING_AFFINE if step.coupling == 'affine' else _lib.COUPLING_ADDITIVE
         d.an_bias, d.an_logs = self._dev(step.actnorm.bias), self._dev(step.actnorm.logs)
         if step.permutation == 'invconv':
             d.permutation = _lib.PERM_INVCONV
-            d.invconv_w = self._dev(step.invconv.weight)
+            if getattr(step.invconv, "lu_decomposition", False):
+                # LU form: the plan owns the buffer every pack assembles W = P L U_f into (csrc/invconv_lu.hip); the layer is bound
+                # to its factors below, once the C plan exists
+                wbuf = torch.empty((d.C, d.C), dtype=torch.float32, device=self.device)
+                d.invconv_w = self._dev(wbuf)
+                self._lu.append((index, step.invconv, wbuf))
+            else:
+                d.invconv_w = self._dev(step.invconv.weight)
         else:
             d.permutation = _lib.PERM_GATHER
             perm = getattr(step, step.permutation)
@@ -90,6 +106,12 @@ class FlowPlan:
         d.f0_w, d.f0_an_bias, d.f0_an_logs = self._dev(f0.weight), self._dev(f0.actnorm.bias), self._dev(f0.actnorm.logs)
         d.f2_w, d.f2_an_bias, d.f2_an_logs = self._dev(f2.weight), self._dev(f2.actnorm.bias), self._dev(f2.actnorm.logs)
         d.f4_w, d.f4_bias, d.f4_logs = self._dev(f4.weight), self._dev(f4.bias), self._dev(f4.logs)
+
+    def _dev_any(self, t: torch.Tensor) -> int:
+        if t.device != self.device or not t.is_contiguous():
+            raise _lib.GlowHipError(f"tensor on {t.device}, plan on {self.device}")
+        self._keep.append(t)
+        return t.data_ptr()
 
     def _fill_split(self, d: LayerDesc, split) -> None:
         cz = split.conv2d_zeros
@@ -216,6 +238,9 @@ class FlowPlan:
         version = self._version_signature()
         if merge and version == self._packed_version:
             use |= getattr(self, "_packed_use", 0)       # same parameters: the images packed earlier stay valid, add to them
+        elif self._lu:
+            for _, m, _ in self._lu:                     # the row tables of p follow a rewritten p (in place: same addresses)
+                m.perm_table()
         check(lib().glowhip_plan_pack_for(self._h, ptr(self.packed), self.packed.numel(), use, stream_ptr(self.device)))
         self._packed_version = version
         self._packed_use = use
@@ -366,7 +391,10 @@ class FlowPlan:
             kind = layer.glowhip_kind
             if kind == _lib.LAYER_FLOWSTEP:
                 out += [(i, "an_bias", layer.actnorm.bias), (i, "an_logs", layer.actnorm.logs)]
-                if layer.permutation == 'invconv':
+                if layer.permutation == 'invconv' and getattr(layer.invconv, "lu_decomposition", False):
+                    # (glowhip_invconv_lu_grads of the layer, not a glowhip_layer_grads field; all three in the small bucket)
+                    out += [(i, "lu_dl", layer.invconv.l), (i, "lu_du", layer.invconv.u), (i, "lu_dlog_s", layer.invconv.log_s)]
+                elif layer.permutation == 'invconv':
                     out.append((i, "invconv_w", layer.invconv.weight))
                 f0, f2, f4 = layer.f[0], layer.f[2], layer.f[4]
                 out += [(i, "f0_w", f0.weight), (i, "f0_an_bias", f0.actnorm.bias), (i, "f0_an_logs", f0.actnorm.logs),
@@ -434,17 +462,25 @@ class FlowPlan:
             grads = [flats[b][off:off + p.numel()].view_as(p) for (_, _, p), (b, off) in zip(fields, layout["slots"])]
             arr = (_lib.LayerGrads * len(self.layers))()
             hg = _lib.HeadGrads()
+            lug = {i: _lib.InvconvLUGrads() for i, _, _ in self._lu}
             for (i, name, _), gt in zip(fields, grads):
-                setattr(hg if i < 0 else arr[i], name, gt.data_ptr())
+                if name.startswith("lu_"):
+                    setattr(lug[i], name[3:], gt.data_ptr())
+                else:
+                    setattr(hg if i < 0 else arr[i], name, gt.data_ptr())
             events = [torch.cuda.Event() for _ in layout["marks"]]
             for ev in events:
                 ev.record()                  # (creates the handle; the C sweep records it again where it belongs)
             marks = (ctypes.c_int32 * max(len(events), 1))(*layout["marks"])
             handles = (ctypes.c_void_p * max(len(events), 1))(*[ev.cuda_event for ev in events])
             if persistent:
-                self._pgrad = (flats, grads, arr, events, marks, handles, hg)
+                self._pgrad = (flats, grads, arr, events, marks, handles, hg, lug)
         else:
-            flats, grads, arr, events, marks, handles, hg = cached
+            flats, grads, arr, events, marks, handles, hg, lug = cached
+        if lug and getattr(self, "_lu_bound", None) is not lug:      # (the persistent set is bound once, not per step)
+            for i, g in lug.items():
+                check(lib().glowhip_plan_bind_invconv_lu_grads(self._h, i, ctypes.byref(g)))
+            self._lu_bound = lug
         if not persistent:
             # the sweep rewrites the plan's host-side gradient job tables with THIS call's temporary buffers, and the copy nodes of a
             # captured training step read those tables at replay time: training.GraphedTrainStep sees this epoch move and captures
@@ -495,6 +531,8 @@ class FlowPlan:
         """Data-dependent init of every ActNorm in the plan from batch x (writes the parameters in place)."""
         n = x.shape[0]
         ws = self._workspace(n)
+        for _, m, _ in self._lu:      # (the init pass packs from C: the row tables of p must be current before it)
+            m.perm_table()
         check(lib().glowhip_plan_actnorm_init(self._h, ptr(self.packed), self.packed.numel(), ptr(x), ptr(noise),
                                               float(actnorm_scale), n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         self._packed_version = self._version_signature()   # the init pass ends with a pack of the inference kernels' data

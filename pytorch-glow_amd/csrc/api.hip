@@ -3,6 +3,7 @@
 #include <stdio.h>
 
 #include "kernels.h"
+#include "invconv_lu.h"
 #include "debug_switches.h"
 
 namespace glowhip {
@@ -102,6 +103,26 @@ int glowhip_invconv_prepare(const float* w, int C, float* winv, float* logabsdet
                             glowhip_stream_t stream) {
     GH_REQUIRE(w, "invconv_prepare: null weight");
     return launch_invconv_prepare(w, C, winv, logabsdet, scratch, (hipStream_t)stream);
+}
+
+int glowhip_invconv_lu_prepare(const int32_t* perm, const float* l, const float* u, const float* log_s, const float* sign_s, int C,
+                               float* w_out, float* winv_out, float* logabsdet_out, glowhip_stream_t stream) {
+    GH_REQUIRE(perm && l && u && log_s && sign_s && w_out, "invconv_lu_prepare: null argument");
+    GH_REQUIRE(C > 0 && C <= INVCONV_LU_MAX_C, "invconv_lu_prepare: C=%d unsupported", C);
+    LuJob j{};
+    j.perm = perm; j.l = l; j.u = u; j.log_s = log_s; j.sign_s = sign_s; j.w = w_out; j.C = C; j.HW = 1;
+    j.winv = winv_out; j.logabsdet = logabsdet_out;
+    GH_TRY(launch_invconv_lu_assemble(nullptr, &j, 1, C, nullptr, (hipStream_t)stream));
+    if (winv_out) GH_TRY(launch_invconv_lu_inverse(nullptr, &j, 1, C, nullptr, (hipStream_t)stream));
+    return GLOWHIP_OK;
+}
+
+int glowhip_invconv_lu_backward(const int32_t* perm, const float* l, const float* u, const float* log_s, const float* sign_s, int C,
+                                const float* dW, double logdet_term, float* dl, float* du, float* dlog_s, glowhip_stream_t stream) {
+    GH_REQUIRE(perm && l && u && log_s && sign_s && dW && dl && du && dlog_s, "invconv_lu_backward: null argument");
+    GH_REQUIRE(C > 0 && C <= INVCONV_LU_MAX_C, "invconv_lu_backward: C=%d unsupported", C);
+    LuGradJob j{perm, l, u, log_s, sign_s, dW, dl, du, dlog_s, C, nullptr, logdet_term};
+    return launch_invconv_lu_backward(nullptr, &j, 1, C, (hipStream_t)stream);
 }
 
 int glowhip_invconv(const float* x, float* y, const float* m, const float* logabsdet, int N, int C, int HW, int reverse,

@@ -84,6 +84,8 @@ struct StepPrepJob {
     const float* an_logs;   // actnorm.logs (C)
     int C, HW;
     size_t winv_off, logabsdet_off, konst_off, scratch_off;
+    int lu_form;            // the step's matrix is kept as P L U factors (invconv_lu.hip wrote the log-det and constant slots
+                            // earlier in the pack): w is null and every step-prepare kernel leaves this job alone
 };
 int launch_step_prepare_batched(const StepPrepJob* jobs_dev, int n, int max_lds_c, void* packed, hipStream_t s, int want_inverse = 1,
                                 int max_c = 0, int all_small = 0);   // want_inverse = 0: log|det W| only (W^-1 is left stale)

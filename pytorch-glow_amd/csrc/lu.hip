@@ -356,6 +356,7 @@ __global__ void __launch_bounds__(256) k_step_prepare_batched(const StepPrepJob*
     extern __shared__ __attribute__((aligned(16))) double lds_aug[];
     __shared__ double red[4];
     const StepPrepJob j = jobs[blockIdx.x];
+    if (j.lu_form) return;
     double lad = 0.0;
     if (j.w) {
         const int route = step_prepare_route(j.C, want_inverse);
@@ -382,7 +383,7 @@ __global__ void __launch_bounds__(256) k_step_prepare_batched(const StepPrepJob*
 __global__ void __launch_bounds__(256) k_step_prepare_small(const StepPrepJob* __restrict__ jobs, int n, char* packed) {
     step_prepare_small_body(jobs, n, packed, blockIdx.x);
 }
-bool step_prepare_small_takes(const StepPrepJob& j) { return j.C <= 64 && (!j.w || j.C == 12 || j.C == 24 || j.C == 48); }
+bool step_prepare_small_takes(const StepPrepJob& j) { return j.lu_form || (j.C <= 64 && (!j.w || j.C == 12 || j.C == 24 || j.C == 48)); }
 
 // plan-wide total of the per-step terms: fetched in parallel, summed in layer order by one thread (deterministic)
 __global__ void __launch_bounds__(256) k_sum_konst(const StepPrepJob* __restrict__ jobs, int n, char* packed) {

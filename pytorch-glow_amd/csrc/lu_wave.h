@@ -77,6 +77,7 @@ __device__ __forceinline__ void step_prepare_small_body(const StepPrepJob* __res
     const int i = bx * 4 + (threadIdx.x >> 6);
     if (i >= n) return;
     const StepPrepJob j = jobs[i];
+    if (j.lu_form) return;
     double lad = 0.0;
     if (j.w) lad = j.C == 12 ? lu_logdet_wave<12>(j.w, lane) : (j.C == 24 ? lu_logdet_wave<24>(j.w, lane) : lu_logdet_wave<48>(j.w, lane));
     // (the same tree as the workgroup kernel's block_sum: its waves 1 - 3 add exact zeros for C <= 64)

@@ -777,6 +777,11 @@ glowhip_plan* glowhip_plan_create(const glowhip_layer_desc* layers, int n_layers
     // rewrites the table a captured graph of another mask launches over
     p->repack_off = take(off, REPACK_SLOTS * p->repack_jobs.size() * sizeof(RepackJob));
     p->flip_off = take(off, p->flip_jobs.size() * sizeof(FlipJob));
+    {   // room for the LU-form job table (glowhip_plan_bind_invconv_lu comes after the caller sized `packed`): one per invconv FlowStep
+        size_t n_inv = 0;
+        for (const StepPrepJob& pj : p->prep_jobs) n_inv += pj.w ? 1 : 0;
+        p->lu_off = take(off, n_inv * sizeof(LuJob));
+    }
     {   // the one-launch forward pack's table (k_pack_fused): an arrival counter, then at most one PackSeg per block of every job
         size_t nseg = (p->prep_jobs.size() + 3) / 4 + 1;
         for (const RepackJob& r : p->repack_jobs)
@@ -960,7 +965,8 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
     if (plan->tables_in != packed) {
         if (!upload(plan->prep_off, plan->prep_jobs.data(), plan->prep_jobs.size() * sizeof(StepPrepJob)) ||
             !upload(plan->scale_off, plan->scale_jobs.data(), plan->scale_jobs.size() * sizeof(ScaleJob)) ||
-            !upload(plan->flip_off, plan->flip_jobs.data(), plan->flip_jobs.size() * sizeof(FlipJob))) {
+            !upload(plan->flip_off, plan->flip_jobs.data(), plan->flip_jobs.size() * sizeof(FlipJob)) ||
+            !upload(plan->lu_off, plan->lu_jobs.data(), plan->lu_jobs.size() * sizeof(LuJob))) {
             set_error("plan_pack: hipMemcpyAsync of the job tables failed");
             return GLOWHIP_ELAUNCH;
         }
@@ -975,6 +981,13 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
             return GLOWHIP_ELAUNCH;
         }
         plan->slots_in |= 1u << slot;
+    }
+    // LU-form layers first, on the caller's stream and ahead of the fork: W = P L U_f into the layer's own buffer (the mixers and the
+    // deep levels' weight images read it) and the layer's log-det and constant slots, which the step-prepare kernels below then
+    // leave alone (StepPrepJob::lu_form) and their totals read
+    if (!plan->lu_jobs.empty()) {
+        plan->launch_counts["pack:invconv_lu"] += (long)plan->lu_jobs.size();
+        GH_TRY(launch_invconv_lu_assemble(at<LuJob>(packed, plan->lu_off), nullptr, (int)plan->lu_jobs.size(), plan->lu_max_c, packed, s));
     }
     if (fusable) {
         // The table holds indices into the repack table of THIS slot (repack_sel of this use mask, sorted by kind group).  Today
@@ -1061,6 +1074,10 @@ int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes,
         }
         GH_TRY(launch_step_prepare_batched(at<StepPrepJob>(packed, plan->prep_off), (int)plan->prep_jobs.size(),
                                            plan->max_lds_c, packed, side, inv, plan->max_c, all_small ? 1 : 0));
+        // W^-1 of the LU-form layers by substitution -- for decode only: the backward sweep does not read it (their GradJob has no
+        // W^-1 term), so a training pack without GLOWHIP_PACK_INVERSE skips it
+        if ((use & GLOWHIP_PACK_INVERSE) && !plan->lu_jobs.empty())
+            GH_TRY(launch_invconv_lu_inverse(at<LuJob>(packed, plan->lu_off), nullptr, (int)plan->lu_jobs.size(), plan->lu_max_c, packed, side));
         if ((use & GLOWHIP_PACK_INVERSE) && n_kind[4] > 0)
             GH_TRY(launch_repack_sh2_gemm(at<RepackJob>(packed, slot_off) + (n_kind[0] + n_kind[1] + n_kind[2] + n_kind[3]), n_kind[4], packed, side));
     }
@@ -1079,6 +1096,49 @@ int glowhip_plan_set_family(glowhip_plan* plan, int family) {
 }
 
 int glowhip_plan_get_family(const glowhip_plan* plan) { return plan ? plan->family : GLOWHIP_EINVAL; }
+
+int glowhip_plan_bind_invconv_lu(glowhip_plan* plan, int layer, const glowhip_invconv_lu* lu) {
+    GH_REQUIRE(plan && lu, "plan_bind_invconv_lu: null argument");
+    GH_REQUIRE(layer >= 0 && layer < (int)plan->layers.size(), "plan_bind_invconv_lu: layer %d out of range", layer);
+    const LayerPlan& L = plan->layers[layer];
+    const glowhip_layer_desc& d = L.d;
+    GH_REQUIRE(d.kind == GLOWHIP_LAYER_FLOWSTEP && d.permutation == GLOWHIP_PERM_INVCONV, "plan_bind_invconv_lu: layer %d is not an invconv FlowStep", layer);
+    GH_REQUIRE(lu->perm && lu->l && lu->u && lu->log_s && lu->sign_s && lu->w, "plan_bind_invconv_lu: null pointer");
+    GH_REQUIRE(lu->w == d.invconv_w, "plan_bind_invconv_lu: w must be the buffer the layer's invconv_w points at");
+    GH_REQUIRE(d.C <= INVCONV_LU_MAX_C, "plan_bind_invconv_lu: C=%d unsupported (limit %d)", d.C, INVCONV_LU_MAX_C);
+    for (const glowhip_plan::LuLayer& q : plan->lu_layers) GH_REQUIRE(q.layer != layer, "plan_bind_invconv_lu: layer %d is bound already", layer);
+    int pj = 0;      // the layer's step-prepare job: FlowSteps in layer order
+    for (int i = 0; i < layer; ++i) pj += plan->layers[i].d.kind == GLOWHIP_LAYER_FLOWSTEP ? 1 : 0;
+    plan->prep_jobs[pj].w = nullptr; plan->prep_jobs[pj].lu_form = 1;
+    plan->max_lds_c = plan->max_c = 0;      // what is left for the factorisations
+    for (const StepPrepJob& j : plan->prep_jobs) {
+        if (j.w && j.C <= 64) plan->max_lds_c = std::max(plan->max_lds_c, j.C);
+        if (j.w) plan->max_c = std::max(plan->max_c, j.C);
+    }
+    LuJob j{};
+    j.perm = lu->perm; j.l = lu->l; j.u = lu->u; j.log_s = lu->log_s; j.sign_s = lu->sign_s; j.w = lu->w;
+    j.an_logs = d.an_logs; j.C = d.C; j.HW = d.H * d.W;
+    j.winv_off = L.winv; j.logabsdet_off = L.logabsdet; j.konst_off = L.konst;
+    plan->lu_jobs.push_back(j);
+    plan->lu_layers.push_back(glowhip_plan::LuLayer{layer, glowhip_invconv_lu_grads{nullptr, nullptr, nullptr}});
+    plan->lu_max_c = std::max(plan->lu_max_c, d.C);
+    plan->lu_grad_jobs.reserve(plan->lu_jobs.size());
+    // the tables in `packed` and the one-launch pack's segment table were built for the plan as it was
+    plan->tables_in = nullptr; plan->slots_in = 0; plan->segs_in = false; plan->pack_segs.clear(); plan->pack_segs_slot = -1;
+    return GLOWHIP_OK;
+}
+
+int glowhip_plan_bind_invconv_lu_grads(glowhip_plan* plan, int layer, const glowhip_invconv_lu_grads* grads) {
+    GH_REQUIRE(plan, "plan_bind_invconv_lu_grads: null plan");
+    for (glowhip_plan::LuLayer& q : plan->lu_layers)
+        if (q.layer == layer) {
+            GH_REQUIRE(!grads || (grads->dl && grads->du && grads->dlog_s), "plan_bind_invconv_lu_grads: null gradient pointer");
+            q.g = grads ? *grads : glowhip_invconv_lu_grads{nullptr, nullptr, nullptr};
+            return GLOWHIP_OK;
+        }
+    set_error("plan_bind_invconv_lu_grads: layer %d is not an LU-form layer", layer);
+    return GLOWHIP_EINVAL;
+}
 
 int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps) {
     GH_REQUIRE(plan, "plan_bind_latents: null plan");

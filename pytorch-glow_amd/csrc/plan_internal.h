@@ -10,6 +10,7 @@
 #include "sh.h"
 #include "backward.h"
 #include "tophead.h"
+#include "invconv_lu.h"
 #include "debug_switches.h"
 
 namespace glowhip {
@@ -85,6 +86,12 @@ struct glowhip_plan {
     int family = GLOWHIP_FAMILY_AUTO;          // kernel family of the coupling networks (glowhip_plan_set_family): a property of the plan
     // top head (tophead.hip): learned / class-conditional prior + classifier, its per-call io and gradient bindings
     bool head_on = false; glowhip_head_desc head{}; glowhip_head_io head_io{}; glowhip_head_grads head_grads{};
+    // FlowSteps whose 1x1 convolution is kept as P L U factors (glowhip_plan_bind_invconv_lu; invconv_lu.hip): their pack jobs (host
+    // copy + offset of the device copy inside `packed`, room reserved for every invconv FlowStep), the widest of them, their
+    // gradient bindings (dl == null: none) and the host copy of the last sweep's gradient job table
+    struct LuLayer { int layer; glowhip_invconv_lu_grads g; };
+    std::vector<LuLayer> lu_layers; std::vector<glowhip::LuJob> lu_jobs; size_t lu_off = 0; int lu_max_c = 0;
+    std::vector<glowhip::LuGradJob> lu_grad_jobs;
     std::map<std::string, long> launch_counts; // run-time record of which kernel families this plan launched (glowhip_plan_launch_counts)
 };
 

@@ -58,6 +58,7 @@ struct TrainWs {
     GradJob* jobs;                // device copy of the finalize job table (<= 9 per layer)
     LogsJob* ljobs;               // ... and of the log-scale job table (<= 2 per layer)
     size_t dacc_doubles;
+    float* ludw; LuGradJob* lujobs;   // LU-form layers: the data-term dW of each (C*C floats, in lu_layers order), their gradient job table
 };
 
 static size_t max_weight_floats(const glowhip_plan* p) {
@@ -159,12 +160,16 @@ static size_t train_ws_layout(const glowhip_plan* p, int N, void* base, TrainWs*
     const size_t o_col = take(off, colf * 4), o_part = take(off, 3 * partf * 4);      // three regions: a FlowStep's three GEMMs, reduced together
     const size_t o_jobs = take(off, p->layers.size() * 9 * sizeof(GradJob));
     const size_t o_ljobs = take(off, p->layers.size() * 2 * sizeof(LogsJob));
+    size_t ludw_floats = 0;
+    for (const LuJob& lj : p->lu_jobs) ludw_floats += (size_t)lj.C * lj.C;
+    const size_t o_ludw = take(off, ludw_floats * 4), o_lujobs = take(off, p->lu_jobs.size() * sizeof(LuGradJob));
     if (w && base) {
         w->col = at<float>(base, o_col); w->partial = at<float>(base, o_part); w->partial_floats = partf; w->jobs = at<GradJob>(base, o_jobs); w->ljobs = at<LogsJob>(base, o_ljobs);
         w->acc = at<unsigned long long>(base, o_acc); w->gld = at<float>(base, o_gld); w->gsum = at<double>(base, o_gsum);
         w->gA = at<float>(base, o_gA); w->gB = at<float>(base, o_gB); w->gh1 = at<float>(base, o_h1);
         w->gh2 = at<float>(base, o_h2); w->gpre = at<float>(base, o_gpre); w->wT = at<float>(base, o_wT);
         w->dacc = at<double>(base, o_dacc); w->dacc_doubles = nd; w->gsh = at<float>(base, o_gsh);
+        w->ludw = at<float>(base, o_ludw); w->lujobs = at<LuGradJob>(base, o_lujobs);
     }
     return align_up(off, 256);
 }
@@ -350,6 +355,25 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                    long stride = 0) {
         if (out) jobs.push_back(GradJob{acc, out, n, add_mul, winv, C, copies, stride});
     };
+    // the mixer's weight gradient.  Dense layer: dW + G HW W^-T (the log-det term).  LU-form layer: the data term alone into the
+    // layer's scratch -- no W^-1 term: its log-det term goes to dlog_s directly, in the gradient kernel launched behind the finalize
+    p->lu_grad_jobs.clear();
+    auto fin_w = [&](int li, const LayerPlan& L, const glowhip_layer_grads& G, const double* aW, int HW, int mcopies, long mstride) {
+        const glowhip_layer_desc& d = L.d;
+        size_t so = 0;
+        for (size_t q = 0; q < p->lu_layers.size(); ++q) {
+            const LuJob& lj = p->lu_jobs[q];
+            if (p->lu_layers[q].layer == li) {
+                const glowhip_invconv_lu_grads& g = p->lu_layers[q].g;
+                if (!g.dl) return;
+                fin(aW, w.ludw + so, d.C * d.C, 0.0, nullptr, 0, mcopies, mstride);
+                p->lu_grad_jobs.push_back(LuGradJob{lj.perm, lj.l, lj.u, lj.log_s, lj.sign_s, w.ludw + so, g.dl, g.du, g.dlog_s, d.C, w.gsum, (double)HW});
+                return;
+            }
+            so += (size_t)lj.C * lj.C;
+        }
+        fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+    };
     // log-scale gradients of the layers whose input-gradient chain ran as one k_cnet launch: d logs = 3 (<W, dW> + b db) READS the
     // weight gradients, which live in the per-level buckets a data-parallel run all-reduces (in place, on a side stream) as soon as
     // the level's mark has passed.  So the pending jobs are launched BEFORE a mark is recorded (computed after the sweep
@@ -486,7 +510,7 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                 mb.add_part = pend.scratch; mb.add_scale = 1.0f / sh_grad_scale; mb.add_C = Ch; mb.add_MS = pend.MS;
                 mb.add_tiles = pend.tiles; mb.add_R = pend.R; mb.add_NI = pend.NI; mb.add_lpxt = pend.lpxt; mb.add_H = d.H; mb.add_W = d.W;
                 GH_TRY(launch_chanmix_bwd(mb, s, &rj));
-                if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+                if (d.permutation == GLOWHIP_PERM_INVCONV) fin_w(li, L, G, aW, HW, mcopies, mstride);
                 fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
                 fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
                 fin(a0b, G.f0_an_bias, hid, 0.0);
@@ -569,7 +593,7 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             if (wide) g = gnext;
             // (f) fp64 accumulators -> fp32 gradients (+ the log-det terms that do not depend on the data): queued,
             // converted by ONE launch after the sweep
-            if (d.permutation == GLOWHIP_PERM_INVCONV) fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+            if (d.permutation == GLOWHIP_PERM_INVCONV) fin_w(li, L, G, aW, HW, mcopies, mstride);
             fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
             fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
             fin(a0b, G.f0_an_bias, hid, 0.0); fin(a0l, G.f0_an_logs, hid, 0.0);
@@ -610,6 +634,14 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             return GLOWHIP_ELAUNCH;
         }
         GH_TRY(launch_grad_finalize_batched(w.jobs, (int)jobs.size(), w.gsum, s));
+    }
+    if (!p->lu_grad_jobs.empty()) {      // dl, du, dlog_s of every LU-form layer from the dW just written: one launch per sweep
+        if (hipMemcpyAsync(w.lujobs, p->lu_grad_jobs.data(), p->lu_grad_jobs.size() * sizeof(LuGradJob), hipMemcpyHostToDevice, s) != hipSuccess) {
+            set_error("backward: hipMemcpyAsync of the LU gradient job table failed");
+            return GLOWHIP_ELAUNCH;
+        }
+        count_launch(p, "k_invconv_lu_backward");
+        GH_TRY(launch_invconv_lu_backward(w.lujobs, nullptr, (int)p->lu_grad_jobs.size(), p->lu_max_c, s));
     }
     GH_TRY(flush_logs());
     return GLOWHIP_OK;

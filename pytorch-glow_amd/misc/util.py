@@ -211,6 +211,24 @@ def load_model(result_subdir, step_or_model_path, graph, optimizer=None, criteri
 
 
 # ----------------------------------------------------------------------------- inference helpers (util.py:487-588)
+def lu_state_dict_from_dense(state_dict):
+    """A copy of ``state_dict`` with every ``...invconv.weight`` entry replaced by the five entries of `Invertible1x1ConvLU`
+    (``p``, ``sign_s``, ``l``, ``u``, ``log_s``: the fp64 partial-pivoting factors of that matrix): a dense or reference-written
+    snapshot then loads, ``strict=True``, into a model built with ``lu_decomposition=True``."""
+    from collections import OrderedDict
+    from ..network.module import plu_factors
+    out = OrderedDict()
+    for key, value in state_dict.items():
+        if key.endswith("invconv.weight") and getattr(value, "dim", lambda: 0)() == 2:
+            prefix = key[:-len("weight")]
+            fac = plu_factors(value)
+            for name in ("l", "u", "log_s", "p", "sign_s"):
+                out[prefix + name] = fac[name].to(value.device)
+        else:
+            out[key] = value
+    return out
+
+
 def save_deltaz(deltaz, save_dir):
     check_path(save_dir)
     np.save(os.path.join(save_dir, 'deltaz.npy'), deltaz)

@@ -8,7 +8,7 @@ from .inferer import Inferer
 from .latents import Latents
 from .trainer import Trainer
 
-_LAYERS = ("ActNorm", "LinearZeros", "Conv2d", "Conv2dZeros", "CouplingNet", "f", "Invertible1x1Conv",
+_LAYERS = ("ActNorm", "LinearZeros", "Conv2d", "Conv2dZeros", "CouplingNet", "f", "Invertible1x1Conv", "Invertible1x1ConvLU",
            "Permutation2d", "GaussianDiag", "Split2d", "Squeeze2d")
 _MODELS = ("FlowStep", "FlowModel", "Glow")
 

@@ -77,7 +77,9 @@ class FlowStep(nn.Module):
         self.actnorm_scale = actnorm_scale
         self.actnorm = module.ActNorm(num_channels=in_channels, scale=actnorm_scale)
         if permutation == 'invconv':
-            self.invconv = module.Invertible1x1Conv(num_channels=in_channels, lu_decomposition=lu_decomposition)
+            # (lu_decomposition: W kept as P L U factors -- its own class; the dense class keeps the reference's contract and raises)
+            self.invconv = (module.Invertible1x1ConvLU(num_channels=in_channels) if lu_decomposition
+                            else module.Invertible1x1Conv(num_channels=in_channels))
         elif permutation == 'reverse':
             self.reverse = module.Permutation2d(num_channels=in_channels, shuffle=False)
         else:

@@ -226,7 +226,8 @@ class Invertible1x1Conv(nn.Module):
         self.num_channels = num_channels
         self.lu_decomposition = lu_decomposition
         if self.lu_decomposition:
-            raise NotImplementedError()
+            raise NotImplementedError("the LU-parameterised 1x1 convolution is its own class: Invertible1x1ConvLU "
+                                      "(FlowStep(..., lu_decomposition=True) builds it)")
         w_init = np.linalg.qr(np.random.randn(num_channels, num_channels))[0].astype('float32')
         self.register_parameter('weight', nn.Parameter(torch.Tensor(w_init)))
 
@@ -246,6 +247,107 @@ class Invertible1x1Conv(nn.Module):
         m = winv if reverse else self.weight
         check(lib().glowhip_invconv(ptr(x), ptr(z), ptr(m), ptr(lad), n, c, h * w, int(bool(reverse)), ptr(ld_in),
                                     ptr(ld_out), s))
+        return z, ld_out
+
+
+def plu_factors(weight):
+    """W = P L U of a dense (C, C) matrix on the host in fp64 (partial pivoting, torch.linalg.lu), as the fp32 tensors
+    `Invertible1x1ConvLU` keeps: p (the permutation matrix), l / u (strictly lower / upper parts, zero elsewhere),
+    log_s = log|diag U| and sign_s = sign(diag U)."""
+    if isinstance(weight, torch.Tensor):
+        w64 = weight.detach().to(device="cpu", dtype=torch.float64)
+    else:
+        w64 = torch.from_numpy(np.array(weight, dtype=np.float64))
+    assert w64.dim() == 2 and w64.shape[0] == w64.shape[1], f"expected a square matrix, got {tuple(w64.shape)}"
+    P, L, U = torch.linalg.lu(w64)
+    d = torch.diagonal(U)
+    if not bool(torch.isfinite(d).all()) or bool((d == 0).any()):
+        raise ValueError("plu_factors: the matrix is singular (a zero pivot has no log_s / sign_s)")
+    return dict(p=P.float().contiguous(), l=torch.tril(L, -1).float().contiguous(), u=torch.triu(U, 1).float().contiguous(),
+                log_s=d.abs().log().float(), sign_s=torch.sign(d).float())
+
+
+def plu_assemble(p, l, u, log_s, sign_s):
+    """p (tril(l, -1) + I) (triu(u, 1) + diag(sign_s exp(log_s))) in fp64 with torch (differentiable; any device torch computes
+    on).  The HIP path never calls this: it is the host-side view of the parameterisation."""
+    c = l.shape[0]
+    eye = torch.eye(c, dtype=torch.float64, device=l.device)
+    lo = torch.tril(l.double(), -1) + eye
+    up = torch.triu(u.double(), 1) + torch.diag(sign_s.double() * torch.exp(log_s.double()))
+    return p.double() @ lo @ up
+
+
+class Invertible1x1ConvLU(nn.Module):
+    """Invertible 1x1 convolution kept as W = p (tril(l, -1) + I) (triu(u, 1) + diag(sign_s exp(log_s))) -- the parameterisation
+    of the Glow paper, which the reference names and does not implement (``lu_decomposition``, network/module.py:336-337).
+    Parameters: ``l``, ``u`` (C, C), ``log_s`` (C); buffers: ``p`` (C, C) permutation matrix, ``sign_s`` (C).  Entries of ``l`` on
+    or above and of ``u`` on or below the diagonal are never read and get exact-zero gradients.  log|det W| = sum(log_s): no
+    factorisation at run time; W^-1 is two triangular solves per column (csrc/invconv_lu.hip)."""
+
+    def __init__(self, num_channels, weight=None):
+        super().__init__()
+        self.num_channels = num_channels
+        self.lu_decomposition = True
+        if weight is None:      # the dense class' draw, with its consumption of numpy's global generator
+            weight = np.linalg.qr(np.random.randn(num_channels, num_channels))[0]
+        fac = plu_factors(weight)
+        assert fac["l"].shape == (num_channels, num_channels)
+        self.register_buffer('p', fac["p"])
+        self.register_buffer('sign_s', fac["sign_s"])
+        for name in ("l", "u", "log_s"):
+            self.register_parameter(name, nn.Parameter(fac[name]))
+
+    @classmethod
+    def from_weight(cls, weight):
+        """The module whose assembled matrix is the given dense (C, C) weight (up to the fp32 rounding of the factors)."""
+        return cls(int(weight.shape[0]), weight=weight)
+
+    def perm_table(self):
+        """Row table of ``p`` as a persistent int32 device tensor (row i of p has its one in column perm[i]): what the kernels
+        read.  Refreshed IN PLACE when ``p`` was written (load_state_dict, broadcast), so plans keep its address.  The refresh happens
+        here, on the host side of a pack (`FlowPlan.pack`, `FlowPlan.actnorm_init`): a captured graph that packs on replay re-reads
+        l, u and log_s but keeps the table of capture time until the next eager pack -- rewrite ``p`` outside captured replays."""
+        key = (self.p._version, self.p.data_ptr())
+        t = self.__dict__.get("_perm")
+        if t is None or t.device != self.p.device:
+            t = torch.empty(self.num_channels, dtype=torch.int32, device=self.p.device)
+            self.__dict__["_perm"], self.__dict__["_perm_key"] = t, None
+        if self.__dict__.get("_perm_key") != key:
+            t.copy_(self.p.argmax(dim=1))
+            self.__dict__["_perm_key"] = key
+        return t
+
+    def _prepare(self, want_inverse):
+        c, dev = self.num_channels, self.l.device
+        require_device_tensor(self.l.data, "Invertible1x1ConvLU.l")
+        w = torch.empty((c, c), dtype=torch.float32, device=dev)
+        winv = torch.empty((c, c), dtype=torch.float32, device=dev) if want_inverse else None
+        lad = torch.empty(1, dtype=torch.float32, device=dev)
+        check(lib().glowhip_invconv_lu_prepare(ptr(self.perm_table()), ptr(self.l), ptr(self.u), ptr(self.log_s), ptr(self.sign_s), c,
+                                               ptr(w), ptr(winv), ptr(lad), stream_ptr(dev)))
+        return w, winv, lad
+
+    @property
+    def weight(self):
+        """The assembled dense W (read-only view of the parameterisation, no autograd graph).  On the GPU it is what
+        k_invconv_lu_assemble computes -- bit for bit the matrix a plan's pack hands to the mixers; on the host, torch in fp64
+        rounded to fp32."""
+        with torch.no_grad():
+            if self.l.is_cuda:
+                return self._prepare(False)[0]
+            return plu_assemble(self.p, self.l, self.u, self.log_s, self.sign_s).float()
+
+    def forward(self, x, logdet=None, reverse=False):
+        x = require_device_tensor(x, "Invertible1x1ConvLU input")
+        n, c, h, w = x.shape
+        assert c == self.num_channels
+        dev = x.device
+        wmat, winv, lad = self._prepare(bool(reverse))
+        ld_in = _logdet_arg(logdet, n, dev)
+        ld_out = torch.empty(n, dtype=torch.float32, device=dev) if ld_in is not None else None
+        z = torch.empty_like(x)
+        check(lib().glowhip_invconv(ptr(x), ptr(z), ptr(winv if reverse else wmat), ptr(lad), n, c, h * w, int(bool(reverse)),
+                                    ptr(ld_in), ptr(ld_out), stream_ptr(dev)))
         return z, ld_out
 
 

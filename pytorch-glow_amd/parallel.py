@@ -41,6 +41,10 @@ def broadcast_parameters(module: torch.nn.Module, src: int = 0, world: Optional[
     if world <= 1:
         return
     params = [p for p in module.parameters()]
+    # the LU-form 1x1 convolutions' permutation and signs are buffers drawn per rank, and part of W: they travel with the
+    # parameters (a model without such modules sends exactly the flat tensor it always did)
+    params += [b for m in module.modules() if getattr(m, "lu_decomposition", False) is True and hasattr(m, "sign_s")
+               for b in (m.p, m.sign_s)]
     if not params:
         return
     with torch.no_grad():
