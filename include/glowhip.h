@@ -280,6 +280,22 @@ int glowhip_glow_backward(glowhip_plan* plan, const void* packed, const float* x
                           const float* prior_logs, long prior_stride, const glowhip_layer_grads* grads,
                           float* grad_x, int N, void* workspace, size_t workspace_bytes, glowhip_stream_t stream);
 
+/* Differentiable decode.  Vector-Jacobian product of glowhip_plan_decode at the latents whose decode is x (reference decode:
+ * network/model.py:119-154 FlowStep.reverse_flow, 278-294 FlowModel.decode; network/module.py:470-483 Conv2dZeros, 511-536
+ * Split2d): grad_z (shape of the plan's output) and grad_eps[k] (shape of the k-th Split2d's z2, DECODE order, as
+ * glowhip_plan_decode reads eps; contiguous) receive J^T grad_x.  A NULL grad_z or grad_eps[k] skips that output; n_eps must be the
+ * plan's Split2d count (GLOWHIP_EINVAL otherwise).  The call re-encodes x with the taping forward (no noise, no dequantisation
+ * draw, no prior or head work) into `tape` -- scratch of glowhip_plan_tape_bytes(plan, N) bytes, overwritten -- and sweeps it; a
+ * FlowStep's coupling network sees the same y1 in both directions, so that tape is the decode's to rounding.  packed must hold the
+ * GLOWHIP_PACK_TRAINING and GLOWHIP_PACK_INVERSE data.  Each sample's grad_x is normalised by a power of two taken from its own
+ * max-abs (on the device) and the factor undone on the outputs: the result is linear in grad_x to the bit over the whole fp32
+ * range, and an all-zero grad_x[n] gives exact zeros.  PARAMETER gradients do not flow through the decode.  No allocation, no
+ * host sync. */
+size_t glowhip_plan_decode_vjp_workspace_bytes(const glowhip_plan* plan, int N);
+int glowhip_plan_decode_vjp(glowhip_plan* plan, const void* packed, const float* x, const float* grad_x, float* grad_z,
+                            float* const* grad_eps, int n_eps, int N, void* tape, size_t tape_bytes, void* workspace,
+                            size_t workspace_bytes, glowhip_stream_t stream);
+
 /* Gradient-ready marks: lets the caller overlap the gradient all-reduce of one process per GPU (the replacement of
  * nn.DataParallel's reduce-to-GPU-0, network/trainer.py:117-123) with the rest of the backward sweep.  The sweep runs from the
  * last layer to the first; glowhip_glow_backward records events[i] (hipEvent_t handles owned by the caller) on its stream as

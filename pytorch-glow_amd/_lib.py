@@ -180,6 +180,8 @@ SIGNATURES = {
                                            c_size_t, _P]),
     "glowhip_glow_backward": (c_int, [_P, _P, _P, _P, c_size_t, _P, _P, _P, _P, c_long, POINTER(LayerGrads), _P, c_int,
                                       _P, c_size_t, _P]),
+    "glowhip_plan_decode_vjp_workspace_bytes": (c_size_t, [_P, c_int]),
+    "glowhip_plan_decode_vjp": (c_int, [_P, _P, _P, _P, _P, POINTER(c_void_p), c_int, c_int, _P, c_size_t, _P, c_size_t, _P]),
     "glowhip_plan_backward_marks": (c_int, [_P, POINTER(c_int32), POINTER(c_void_p), c_int]),
     "glowhip_optim_step": (c_int, [_P, c_int, c_int, c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_step_dev": (c_int, [_P, c_int, c_int, _P, ctypes.c_double, ctypes.c_double, c_float, c_float, c_float, c_float, _P, _P, c_int, _P]),

@@ -347,6 +347,35 @@ class FlowPlan:
                                         n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         return x, ld_out
 
+    def decode_vjp(self, x, grad_x, want_z=True, want_eps=None):
+        """Vector-Jacobian product of `decode` (glowhip_plan_decode_vjp) at the latents whose decode is ``x``: returns
+        ``(g_z, [g_eps])`` = J^T ``grad_x``, the eps gradients in decode order.  ``want_z`` / ``want_eps`` (one flag per Split2d)
+        skip outputs nobody asked for (None in their place).  One taping re-encode of ``x`` plus the sweep; the tape and the
+        workspace are cached per plan and live only for the call.  Gradients of the PARAMETERS do not flow through the decode."""
+        n = x.shape[0]
+        assert tuple(x.shape[1:]) == self.in_chw and grad_x.shape == x.shape, (x.shape, grad_x.shape, self.in_chw)
+        want_eps = [True] * self.n_split if want_eps is None else list(want_eps)
+        assert len(want_eps) == self.n_split
+        self.ensure_packed(use=self.PACK_TRAINING | self.PACK_INVERSE)
+        gz = torch.empty((n,) + self.out_chw, dtype=torch.float32, device=self.device) if want_z else None
+        geps = [torch.empty((n,) + s, dtype=torch.float32, device=self.device) if w else None for s, w in zip(self.split_chw, want_eps)]
+        if n == 0:
+            return gz, geps
+        tape = self._cached_bytes("_vjp_tape", int(lib().glowhip_plan_tape_bytes(self._h, n)))
+        ws = self._cached_bytes("_vjp_ws", int(lib().glowhip_plan_decode_vjp_workspace_bytes(self._h, n)))
+        arr = (ctypes.c_void_p * max(len(geps), 1))(*[_p(e) for e in geps])
+        check(lib().glowhip_plan_decode_vjp(self._h, ptr(self.packed), ptr(x), ptr(grad_x), ptr(gz), arr, len(geps), n, ptr(tape),
+                                            tape.numel(), ptr(ws), ws.numel(), stream_ptr(self.device)))
+        return gz, geps
+
+    def _cached_bytes(self, name, need):
+        buf = getattr(self, name, None)
+        if buf is None or buf.numel() < need:
+            setattr(self, name, None)
+            buf = torch.empty(max(need, 256), dtype=torch.uint8, device=self.device)
+            setattr(self, name, buf)
+        return buf
+
     def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None, head=None, *,
                      eps_out=None):
         """``eps_out``: as in `encode`."""

@@ -64,6 +64,46 @@ inline int chanmix_bwd_wide_copies(long pixels) {
     return (int)(blocks < 1 ? 1 : blocks > CHANMIX_BWD_WIDE_COPIES ? CHANMIX_BWD_WIDE_COPIES : blocks);
 }
 
+// ---- decode_bwd.hip: vector-Jacobian products of the decode direction (glowhip_plan_decode_vjp); no parameter gradients
+// words[n] = 2^-e, words[N + n] = 2^e, e = floor(log2 max|g[n]|) (0 for an all-zero or non-finite sample)
+int launch_grad_norm(const float* g, long per, float* words, int N, hipStream_t s);
+int launch_scale_rows(const float* x, float* y, long per, const float* word, int N, hipStream_t s);      // y[n] = x[n] * word[n]
+struct ChanMixInvBwdArgs {
+    const float* gx; float* gu; long g_bs;   // gradient of the step's input x in, of the mixer's input u out (may alias where C <= CHANMIX_BWD_NARROW_C)
+    const float* inv_scale;                  // exp(-3 logs)
+    const float* matrix;                     // W^-1 (C,C) or null
+    const int32_t* gather;                   // FORWARD permutation table or null
+    int N, C, HW;
+    // add_part != null: the first add_C channels of gx are gx + add_scale * (the partial sums the PREVIOUS step's backward k_cnet
+    // launch left: geometry add_*, as in ChanMixBwdArgs); refused above CHANMIX_BWD_NARROW_C
+    const float* add_part = nullptr; float add_scale = 0.f;
+    int add_C = 0, add_MS = 0, add_tiles = 0, add_R = 0, add_NI = 0, add_lpxt = 0, add_H = 0, add_W = 0;
+    int w_lds = 0;
+};
+int launch_chanmix_inv_bwd(const ChanMixInvBwdArgs& a, hipStream_t s);
+int launch_cpart_finish(const ChanMixInvBwdArgs& a, hipStream_t s);      // gather-only: gu[:add_C] = gx[:add_C] + add_scale * partial sums
+struct CouplingInvBwdArgs {
+    const float* hout;               // (N,Cout,HW) post-scale output of f.4
+    const float* z2out; long z_bs;   // second half of the step output (z2')
+    float* g2; long g_bs;            // gradient of y2 in, of z2' out (in place)
+    float* gpre;                     // (N,Cout,HW) gradient of (conv + bias) of f.4
+    const float* e4;                 // (Cout) exp(3 logs)
+    int N, Ch, Cout, HW, affine;
+};
+int launch_coupling_inv_bwd(const CouplingInvBwdArgs& a, hipStream_t s);
+struct SplitInvBwdArgs {
+    const float* hout;               // (N,2Ch,HW) prior conv output
+    const float* z2; long z_bs;      // the sampled half
+    const float* gz2; long g_bs;     // its gradient
+    float* geps; long eps_bs;        // caller's buffer of this split (null: skipped), its batch stride
+    const float* unscale;            // (N) factor that undoes the sweep's normalisation
+    float* gpre;                     // (N,2Ch,HW)
+    const float* e4;
+    int N, Ch, HW;
+};
+int launch_split_inv_bwd(const SplitInvBwdArgs& a, hipStream_t s);
+int launch_relu_bwd(float* g, const float* h, const float* e, int N, int Cm, int HW, hipStream_t s);      // k_act_bwd without accumulators
+
 int launch_prior_bwd(const float* z, const float* mean, const float* logs, long ml_bs, const float* gld,
                      const float* gz_in, float* gz, int N, long per, hipStream_t s);
 int launch_weight_flipT(const float* w, float* wT, int Cout, int Cin, int ksize, hipStream_t s);

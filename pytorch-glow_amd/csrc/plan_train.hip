@@ -113,12 +113,16 @@ static bool train_sh_enabled(const glowhip_plan* p) { return !debug_switches().e
 static bool tape_cnet(const glowhip_plan* p, const LayerPlan& L, int N, size_t scratch_floats);
 // ... and its input-gradient chain as one backward k_cnet launch?  Needs the taping forward (the sign bits) and all of the
 // coupling network's weight gradients requested (the log-scale gradients are derived from them).
-static bool bwd_cnet(const glowhip_plan* p, const LayerPlan& L, int li, const glowhip_layer_grads& G, int N, size_t scratch_floats) {
+// (the shape / tape conditions alone: the chain launch itself needs no weight gradient -- the decode VJP takes it without any)
+static bool bwd_cnet_chain(const glowhip_plan* p, const LayerPlan& L, int li, int N, size_t scratch_floats) {
     const glowhip_layer_desc& d = L.d;
-    return !debug_switches().train_per_layer_bwd && L.cnet_bwd && tape_cnet(p, L, N, scratch_floats) && G.f0_w && G.f2_w && G.f4_w &&
+    return !debug_switches().train_per_layer_bwd && L.cnet_bwd && tape_cnet(p, L, N, scratch_floats) &&
            li < (int)p->tape_has_masks.size() && p->tape_has_masks[li] &&      // (the forward that filled this tape stored the sign bits)
            cnet_tape_supported(L.Cout, d.H, d.W, d.hidden, d.C / 2, N) &&
            cnet_scratch_floats(N, d.H, d.W, d.C / 2) <= scratch_floats;
+}
+static bool bwd_cnet(const glowhip_plan* p, const LayerPlan& L, int li, const glowhip_layer_grads& G, int N, size_t scratch_floats) {
+    return G.f0_w && G.f2_w && G.f4_w && bwd_cnet_chain(p, L, li, N, scratch_floats);
 }
 static bool tape_cnet(const glowhip_plan* p, const LayerPlan& L, int N, size_t scratch_floats) {
     const glowhip_layer_desc& d = L.d;
@@ -647,6 +651,168 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
     return GLOWHIP_OK;
 }
 
+// ---------------------------------------------------------------- decode VJP (glowhip_plan_decode_vjp)
+// workspace: acc u64 | norm words (2 N) | gA | gB | gh1 | gh2 | gpre | gsh | wT -- no accumulators of any kind
+struct VjpWs {
+    unsigned long long* acc; float* words;
+    float* gA; float* gB; float* gh1; float* gh2; float* gpre; float* gsh; float* wT;
+};
+static size_t vjp_ws_layout(const glowhip_plan* p, int N, void* base, VjpWs* w) {
+    size_t off = 0;
+    const size_t o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA)), o_words = take(off, (size_t)N * 2 * 4);
+    const size_t o_gA = take(off, (size_t)N * p->max_chw * 4), o_gB = take(off, (size_t)N * p->max_chw * 4);
+    const size_t o_h1 = take(off, (size_t)N * p->max_hidden * 4), o_h2 = take(off, (size_t)N * p->max_hidden * 4);
+    const size_t o_gpre = take(off, (size_t)N * p->max_chw * 4);
+    const size_t o_gsh = take(off, (size_t)N * p->max_hidden * 4);
+    const size_t o_wT = take(off, max_weight_floats(p) * 4);
+    if (w && base) {
+        w->acc = at<unsigned long long>(base, o_acc); w->words = at<float>(base, o_words);
+        w->gA = at<float>(base, o_gA); w->gB = at<float>(base, o_gB); w->gh1 = at<float>(base, o_h1); w->gh2 = at<float>(base, o_h2);
+        w->gpre = at<float>(base, o_gpre); w->gsh = at<float>(base, o_gsh); w->wT = at<float>(base, o_wT);
+    }
+    return align_up(off, 256);
+}
+
+// The sweep: ENCODE order, layer 0 first -- the reverse of the decode.  g: the gradient with respect to the current layer's
+// encode-side INPUT, contiguous (N, C, H, W) in gA / gB and normalised per sample (words); every layer turns it into the gradient
+// with respect to its encode-side output.  FlowStep: mixer^-1 VJP, coupling-tail^-1 VJP, then g_y1 += f'(y1)^T g_pre -- the training
+// sweep's input-gradient chain, one backward k_cnet launch where the tape has the sign bits (its partial sums are gathered by the
+// NEXT layer's first kernel), per layer elsewhere.
+static int decode_vjp_sweep(glowhip_plan* p, const void* packed, const float* x_in, const char* tape, const std::vector<TapeLayer>& tl,
+                            float* grad_z, float* const* grad_eps, int N, VjpWs& w, hipStream_t s) {
+    const int nl = (int)p->layers.size();
+    float* g = w.gA;
+    bool pending = false;      // g's first pend_C channels still lack the partial sums in pend
+    CnetPending pend{};
+    int pend_C = 0, pend_H = 0, pend_W = 0;
+    auto add_args = [&](ChanMixInvBwdArgs& m) {
+        m.add_part = pend.scratch; m.add_scale = 1.0f; m.add_C = pend_C; m.add_MS = pend.MS; m.add_tiles = pend.tiles; m.add_R = pend.R;
+        m.add_NI = pend.NI; m.add_lpxt = pend.lpxt; m.add_H = pend_H; m.add_W = pend_W;
+    };
+    auto finish_pending = [&](long g_bs) {
+        if (!pending) return GLOWHIP_OK;
+        ChanMixInvBwdArgs m{};
+        m.gx = g; m.gu = g; m.g_bs = g_bs; m.N = N; m.C = 2 * pend_C; m.HW = pend_H * pend_W;
+        add_args(m);
+        pending = false;
+        count_launch(p, "k_cpart_finish");
+        return launch_cpart_finish(m, s);
+    };
+    for (int li = 0; li < nl; ++li) {
+        p->cur_layer = li;
+        const LayerPlan& L = p->layers[li];
+        const glowhip_layer_desc& d = L.d;
+        const float* xin = li > 0 ? at<float>(tape, tl[li - 1].out) : x_in;   // this layer's encode-side input
+        float* gnext = (g == w.gA) ? w.gB : w.gA;
+        const int HW = d.H * d.W, Ch = d.C / 2, hid = d.hidden;
+        const long chw = (long)d.C * HW;
+        if (d.kind == GLOWHIP_LAYER_SQUEEZE) {
+            GH_TRY(finish_pending(chw));
+            GH_TRY(launch_squeeze(g, nullptr, gnext, N, d.C, d.H, d.W, 2, 0, s));
+            g = gnext;
+        } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
+            const float* out = at<float>(tape, tl[li].out);
+            const float* h1 = at<float>(tape, tl[li].h1);
+            const float* h2 = at<float>(tape, tl[li].h2);
+            const float* hout = at<float>(tape, tl[li].hout);
+            const int affine = d.coupling == GLOWHIP_COUPLING_AFFINE;
+            // (a) mixer^-1: g (= g_x) -> g_u = (g_y1 without the coupling network's term, g_y2), into the other buffer
+            ChanMixInvBwdArgs mb{};
+            mb.gx = g; mb.gu = gnext; mb.g_bs = chw; mb.inv_scale = at<float>(packed, L.an_inv_scale);
+            mb.matrix = d.permutation == GLOWHIP_PERM_INVCONV ? at<float>(packed, L.winv) : nullptr;
+            mb.gather = d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx : nullptr;
+            mb.N = N; mb.C = d.C; mb.HW = HW;
+            if (pending) {
+                if (chanmix_bwd_wide(d.C) || pend_C != Ch || pend_H != d.H || pend_W != d.W) GH_TRY(finish_pending(chw));
+                else { add_args(mb); pending = false; }
+            }
+            count_launch(p, chanmix_bwd_wide(d.C) ? "k_chanmix_inv_bwd_wide" : "k_chanmix_inv_bwd");
+            GH_TRY(launch_chanmix_inv_bwd(mb, s));
+            g = gnext;
+            // (b) coupling tail^-1: g's second half g_y2 -> g_z2' in place; gpre = gradient of f.4's (conv + bias)
+            CouplingInvBwdArgs cb{hout, out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, w.gpre, at<float>(packed, L.f4_scale),
+                                  N, Ch, L.Cout, HW, affine};
+            GH_TRY(launch_coupling_inv_bwd(cb, s));
+            // (c) g_y1 += f'(y1)^T g_pre
+            if (wgrad_fast(L) && bwd_cnet_chain(p, L, li, N, (size_t)N * p->max_hidden)) {
+                CnetArgs c{};
+                c.w0 = at<char>(packed, L.cb_w0); c.w2 = at<char>(packed, L.cb_w2); c.w4 = at<char>(packed, L.cb_w4);
+                c.N = N; c.Cin = L.Cout; c.H = d.H; c.W = d.W; c.hidden = hid; c.Cout = Ch;
+                c.scratch = w.gsh; c.mode = TAIL_ADD_FWD;
+                c.x = w.gpre; c.x_bs = (long)L.Cout * HW; c.z_in = w.gpre; c.z_in_bs = (long)L.Cout * HW;
+                c.tape_h1 = w.gh2; c.tape_h2 = w.gh1;      // (g_u2 / g_u0: stored by the instance, read by nobody here)
+                c.mask1 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m1));
+                c.mask2 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m2));
+                // the gradients are normalised per sample (max |dL/dx| in [1, 2)): no further pre-scale
+                c.in_scale = SH2_ACT_SCALE; c.out_scale = SH2_ACT_INV * SH_LO_SCALE; c.bwd = 1;
+                pend = CnetPending{};
+                count_launch(p, "k_cnet(bwd)");
+                {
+                    ScopedTimer t(p, GLOWHIP_K_CNET_BWD, 1, s);
+                    GH_TRY(launch_cnet_main(c, s, &pend));
+                }
+                if (pend.one_wave) count_launch(p, "k_cnet1w(bwd)");
+                pending = true; pend_C = Ch; pend_H = d.H; pend_W = d.W;
+                continue;
+            }
+            const bool half_tape = li < (int)p->tape_has_masks.size() && p->tape_has_masks[li];
+            if (half_tape) {
+                GH_TRY(launch_half_to_float(h2, w.gsh, N, hid, HW, s));
+                h2 = w.gsh;
+            }
+            if (L.dg4_first) {
+                const float* wf = at<float>(packed, L.f4T_wf);
+                GH_TRY(launch_conv_mfma_first(w.gpre, (long)L.Cout * HW, wf, wf + (size_t)9 * L.Cout * hid, w.gh2, N, L.Cout,
+                                              d.H, d.W, hid, s, 0));
+            } else {
+                GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh2, N, hid, d.H, d.W, L.Cout, 3, s));
+            }
+            GH_TRY(launch_relu_bwd(w.gh2, h2, at<float>(packed, L.f2_scale), N, hid, HW, s));
+            if (half_tape) {
+                GH_TRY(launch_half_to_float(h1, w.gsh, N, hid, HW, s));
+                h1 = w.gsh;
+            }
+            if (L.mfma_mid) {
+                GH_TRY(launch_conv_mfma_wide(w.gh2, (long)hid * HW, d.f2_w, nullptr, nullptr, w.gh1, N, hid, d.H, d.W, hid, 1, s, 0));
+            } else {
+                GH_TRY(dgrad_direct(w.gh2, d.f2_w, w.wT, w.gh1, N, hid, d.H, d.W, hid, 1, s));
+            }
+            GH_TRY(launch_relu_bwd(w.gh1, h1, at<float>(packed, L.f0_scale), N, hid, HW, s));
+            if (L.dg0_tail) {
+                TailConvArgs t{};
+                t.x = w.gh1; t.x_bs = (long)hid * HW; t.wp = at<float>(packed, L.f0T_wp); t.bias = nullptr; t.scale = nullptr;
+                t.N = N; t.Cin = hid; t.H = d.H; t.W = d.W; t.Cout = Ch; t.mode = TAIL_ADD_FWD;
+                t.z2_in = g; t.z2_in_bs = chw; t.z2_out = g; t.z2_out_bs = chw; t.acc = nullptr;
+                t.zeros = at<float>(packed, 64); t.hout = nullptr;
+                GH_TRY(launch_conv_mfma_tail(t, s));
+            } else {
+                GH_TRY(dgrad_direct(w.gh1, d.f0_w, w.wT, w.gpre, N, Ch, d.H, d.W, hid, 3, s));   // gpre reused: (N,Ch,HW)
+                hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, g, chw, w.gpre,
+                                   (long)Ch * HW, (long)Ch * HW);
+                GH_LAUNCH_CHECK("k_add_inplace");
+            }
+        } else {  // SPLIT2D: input gradient (g_z1, g_z2) (N,C,HW) -> g_z1 + conv(g_pre, flipT(w)) (N,Ch,HW); g_eps to the caller
+            GH_TRY(finish_pending(chw));
+            const float* hout = at<float>(tape, tl[li].hout);
+            const int k = p->n_split - 1 - L.split_idx;      // DECODE order, as glowhip_plan_decode reads eps
+            SplitInvBwdArgs sb{hout, xin + (long)Ch * HW, chw, g + (long)Ch * HW, chw, grad_eps ? grad_eps[k] : nullptr, (long)Ch * HW,
+                               w.words + N, w.gpre, at<float>(packed, L.f4_scale), N, Ch, HW};
+            GH_TRY(launch_split_inv_bwd(sb, s));
+            GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh1, N, Ch, d.H, d.W, L.Cout, 3, s));     // (N,Ch,HW)
+            GH_TRY(launch_copy_strided(g, chw, gnext, (long)Ch * HW, N, (long)Ch * HW, s));
+            hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, gnext, (long)Ch * HW, w.gh1,
+                               (long)Ch * HW, (long)Ch * HW);
+            GH_LAUNCH_CHECK("k_add_inplace");
+            g = gnext;
+        }
+    }
+    const int* o = p->out_shape;
+    const long per = (long)o[0] * o[1] * o[2];
+    GH_TRY(finish_pending(per));
+    if (grad_z) GH_TRY(launch_scale_rows(g, grad_z, per, w.words + N, N, s));
+    return GLOWHIP_OK;
+}
+
 }  // namespace glowhip
 
 // ================================================================================================ C ABI
@@ -716,6 +882,39 @@ int glowhip_glow_backward(glowhip_plan* plan, const void* packed, const float* x
     GH_REQUIRE(!plan->head_on || 2L * o[0] <= plan->max_chw, "glow_backward: top head scratch does not fit");
     GH_TRY(launch_top_bwd(plan, zt, prior_mean, prior_logs, prior_stride, w.gld, z_grad, w.gA, w.gB, N, s));
     return backward_sweep(plan, packed, x, (const char*)tape, tl, grads, grad_x, N, w, w.gA, s);
+}
+
+size_t glowhip_plan_decode_vjp_workspace_bytes(const glowhip_plan* plan, int N) {
+    return (plan && N >= 0) ? vjp_ws_layout(plan, N, nullptr, nullptr) : 0;
+}
+
+int glowhip_plan_decode_vjp(glowhip_plan* plan, const void* packed, const float* x, const float* grad_x, float* grad_z,
+                            float* const* grad_eps, int n_eps, int N, void* tape, size_t tape_bytes, void* workspace,
+                            size_t workspace_bytes, glowhip_stream_t stream) {
+    GH_REQUIRE(plan != nullptr, "plan_decode_vjp: null plan");
+    GH_REQUIRE(n_eps == plan->n_split, "plan_decode_vjp: %d eps gradients given, plan has %d Split2d layers", n_eps, plan->n_split);
+    GH_REQUIRE(n_eps == 0 || grad_eps, "plan_decode_vjp: null grad_eps table");
+    GH_REQUIRE(N >= 0 && N <= 65535, "plan_decode_vjp: batch size %d out of range", N);
+    if (N == 0) return GLOWHIP_OK;
+    GH_REQUIRE(packed && x && grad_x && tape && workspace, "plan_decode_vjp: null argument");
+    std::vector<TapeLayer> tl;
+    GH_REQUIRE(tape_bytes >= tape_layout(plan, N, &tl), "plan_decode_vjp: tape too small");
+    VjpWs w;
+    GH_REQUIRE(workspace_bytes >= vjp_ws_layout(plan, N, workspace, &w), "plan_decode_vjp: workspace too small");
+    for (const LayerPlan& L : plan->layers)
+        GH_REQUIRE(L.d.kind != GLOWHIP_LAYER_FLOWSTEP || L.d.C <= CHANMIX_BWD_MAX_C, "plan_decode_vjp: C=%d unsupported (the channel mixer's limit is %d)", L.d.C, CHANMIX_BWD_MAX_C);
+    hipStream_t s = (hipStream_t)stream;
+    // (the flags of a training forward whose backward is still to come are this plan's too: put back on every way out)
+    struct KeepMasks { glowhip_plan* p; std::vector<char> v; ~KeepMasks() { p->tape_has_masks.swap(v); } } keep{plan, plan->tape_has_masks};
+    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA));
+    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
+    // the tape of the decode = the tape of the training forward on the decoded image (a FlowStep's coupling network sees the same
+    // y1 in both directions): no noise, no dequantisation draw, no prior, no head
+    GH_TRY(forward_train(plan, packed, x, nullptr, nullptr, N, (char*)tape, tl, w.acc, w.gsh, s));
+    const long per = (long)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
+    GH_TRY(launch_grad_norm(grad_x, per, w.words, N, s));
+    GH_TRY(launch_scale_rows(grad_x, w.gA, per, w.words, N, s));
+    return decode_vjp_sweep(plan, packed, x, (const char*)tape, tl, grad_z, grad_eps, N, w, s);
 }
 
 }  // extern "C"

@@ -88,6 +88,26 @@ class Inferer:
         t[-1] = 1.0
         return self.decode_full(both[0].lerp(both[1], t))
 
+    def fit_latents(self, target, mask=None, steps=100, lr=0.05, init=None):
+        """Latents whose decode matches ``target`` (C,H,W or N,C,H,W) where ``mask`` (broadcastable to it; None = everywhere) is
+        set: in-painting / projection by gradient descent on the latent tensors.  Starts from ``encode_full(target)`` (or
+        ``init``), minimises the masked squared error of `Glow.decode_latents` with torch.optim.Adam, the gradient coming from the
+        differentiable decode.  Returns ``(Latents, [loss per step])``; the model's parameters get no gradient."""
+        target = self._batch(target).float()
+        m = torch.ones_like(target) if mask is None else torch.as_tensor(mask, dtype=torch.float32, device=self.device).expand_as(target)
+        lat = (self.encode_full(target) if init is None else init.to(self.device)).detach()
+        lat = Latents(lat.z.clone(), [e.clone() for e in lat.eps]).requires_grad_()
+        opt = torch.optim.Adam(lat.tensors(), lr=lr)
+        history = []
+        with torch.enable_grad():
+            for _ in range(steps):
+                opt.zero_grad(set_to_none=True)
+                loss = ((self.graph.decode_latents(lat, safe=False) - target) ** 2 * m).sum() / m.sum().clamp(min=1.0)
+                loss.backward()
+                opt.step()
+                history.append(loss.detach())
+        return lat.detach(), [float(v) for v in torch.stack(history).cpu()] if history else []
+
     def compute_attribute_delta(self, dataset, samples_per_batch=None, shuffle=True, num_workers=None, world=1, _exact=False):
         """deltaz[c] = mean latent of the images with attribute c - mean latent of those without (inferer.py:104-153).
         `dataset` yields dicts with 'x' (C,H,W) and 'y_onehot' (classes,).

@@ -39,6 +39,17 @@ class Latents:
     def to(self, *args, **kwargs):
         return self._map(lambda t: t.to(*args, **kwargs))
 
+    def requires_grad_(self, requires_grad=True):
+        """Mark z and every eps as leaves that `Glow.decode_latents` differentiates with respect to (detached first where they
+        are results of other operations); the nll is carried along unchanged."""
+        def leaf(t):
+            return (t if t.is_leaf else t.detach()).requires_grad_(requires_grad)
+        return Latents(leaf(self.z), [leaf(e) for e in self.eps], self.nll)
+
+    def detach(self):
+        """The same latents cut out of any autograd graph (shared storage)."""
+        return self._map(lambda t: t.detach())
+
     def lerp(self, other, t):
         """(1 - t) * self + t * other on every latent tensor.  ``t``: a number, or a (steps,) sequence / tensor -- then both
         sides must hold ONE latent and the result holds ``steps`` of them.  The endpoints are exact (t = 0: self, t = 1: other).

@@ -190,6 +190,13 @@ class FlowModel(nn.Module):
         if eps is None:
             eps = self.draw_eps(n, plan, eps_std, z.device)
         eps = [require_device_tensor(e, "eps") for e in eps]
+        if torch.is_grad_enabled() and (z.requires_grad or any(e.requires_grad for e in eps)):
+            return _GlowDecodeFn.apply(plan, bool(safe), z, *eps[:plan.n_split])
+        return self._decode_plain(plan, z, eps, safe)
+
+    @staticmethod
+    def _decode_plain(plan, z, eps, safe):
+        n = z.shape[0]
         x, _ = plan.decode(z, eps, None, want_logdet=False)
         if safe and bool(plan.status(n, x).any()):       # out of the fp16 pairs' range somewhere: the exact-fp32 kernels, same draws
             FlowModel._RANGE_FALLBACKS += 1
@@ -232,6 +239,40 @@ class FlowModel(nn.Module):
 
     def __deepcopy__(self, memo):
         return _deepcopy_without_plans(self, memo)
+
+
+class _GlowDecodeFn(torch.autograd.Function):
+    """`FlowModel.decode` as one autograd node with respect to the LATENTS: forward is the plain decode (``safe`` keeps its
+    meaning), backward is `FlowPlan.decode_vjp` on the returned image -- one taping re-encode of it plus the HIP reverse-flow
+    sweep -- on the kernel family that produced the image.  Nothing is kept between forward and backward but the image, so the
+    node can be differentiated any number of times.  Gradients of the model's PARAMETERS do not flow through the decode; a
+    parameter changed between forward and backward raises."""
+
+    @staticmethod
+    def forward(ctx, plan, safe, z, *eps):
+        before = FlowModel._RANGE_FALLBACKS
+        x = FlowModel._decode_plain(plan, z, list(eps), safe)
+        ctx.plan = plan
+        ctx.family = plan.FAMILY_EXACT_FP32 if FlowModel._RANGE_FALLBACKS != before else plan.family
+        ctx.version = plan._version_signature()
+        ctx.save_for_backward(x)
+        return x
+
+    @staticmethod
+    def backward(ctx, gx):
+        plan = ctx.plan
+        x, = ctx.saved_tensors
+        if plan._version_signature() != ctx.version:
+            raise _lib.GlowHipError("decode backward: a parameter changed between the decode and its backward -- the gradient "
+                                    "would belong to another model than the image")
+        need = ctx.needs_input_grad[2:]
+        prev = plan.family
+        plan.set_family(ctx.family)
+        try:
+            gz, geps = plan.decode_vjp(x, gx.contiguous().float(), want_z=need[0], want_eps=need[1:])
+        finally:
+            plan.set_family(prev)
+        return (None, None, gz) + tuple(geps)
 
 
 class _GlowTrainFn(torch.autograd.Function):
@@ -569,6 +610,9 @@ class Glow(nn.Module):
         ``z=None``: the top latent is sampled from the (class-conditional) prior, mean + exp(logs) * eps (network/model.py:466-468);
         ``eps_top`` (beyond the reference signature) injects that draw, already multiplied by its std.
         ``eps_std``: a number, or one per level in decode order (`level_eps_stds`: the top prior's first)."""
+        # Differentiable with respect to the latents (`_GlowDecodeFn`) when grad mode is on and z, an eps or eps_top requires grad;
+        # otherwise -- and always for the parameters -- the call runs without autograd, bit for bit as it always did.
+        want_grad = torch.is_grad_enabled() and any(torch.is_tensor(t) and t.requires_grad for t in [z, eps_top] + list(eps or []))
         with torch.no_grad():
             std_top = level_eps_stds(eps_std, self.flow.L)[0]
             if z is None:
@@ -578,9 +622,13 @@ class Glow(nn.Module):
                     mean = logs = torch.zeros((self.batch_h_top, c2 // 2, h, w), device=self.h_top.device)
                 if eps_top is None:
                     z = module.GaussianDiag.sample(mean, logs, std_top)
-                else:
+                elif not want_grad:
                     z = mean + torch.exp(logs) * require_device_tensor(eps_top, "eps_top")
-            return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
+            if not want_grad:
+                return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
+        if z is None:      # (plain torch: eps_top gets its gradient through autograd by itself)
+            z = mean + torch.exp(logs) * require_device_tensor(eps_top, "eps_top")
+        return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
 
     # ---- full-latent encode: the bijection with nothing dropped
     def encode_latents(self, x, y_onehot=None, noise=None, dequantize=True, safe=None):
@@ -599,7 +647,9 @@ class Glow(nn.Module):
         return Latents(z, eps_out, nll)
 
     def decode_latents(self, latents, safe=None):
-        """Images of `Latents`: the decode with every Split2d fed the latents' own eps instead of a fresh draw."""
+        """Images of `Latents`: the decode with every Split2d fed the latents' own eps instead of a fresh draw.  Differentiable
+        with respect to the latents: with grad mode on and ``latents.requires_grad_()``, a loss on the result back-propagates
+        to ``z.grad`` and every ``eps.grad`` through the HIP reverse-flow sweep.  Parameter gradients do NOT flow through it."""
         if safe is None:
             safe = bool(self.range_check) and not self.training
         return self.reverse_flow(latents.z, eps=latents.eps, safe=safe)
