@@ -159,9 +159,6 @@ int launch_grad_finalize_batched(const GradJob* jobs_dev, int n_jobs, const doub
 // (sum_p g_u[r][p] u[r][p] = sum_k W[r][k] sum_p g_u[r][p] x_k[p] = <W[r], dW[r]>): no pass over the activations at all.
 struct LogsJob { const float* w; const float* dw; const float* b; const double* db; float* out; int rows, K; };
 int launch_logs_from_dw_batched(const LogsJob* jobs_dev, int n_jobs, hipStream_t s);
-int launch_grad_finalize(const double* acc, float* out, int n, const double* gsum, double add_mul, hipStream_t s);
-int launch_grad_finalize_w(const double* acc, float* out, int C, const double* gsum, double hw, const float* winv,
-                           hipStream_t s);
 int launch_sum_gld(const float* gld, int N, double* gsum, hipStream_t s);
 int launch_gld_from_nll(const float* nll_grad, float* gld, int N, double inv, hipStream_t s);
 

@@ -14,7 +14,7 @@
 //   k_wgrad_direct   dW of a convolution, one workgroup per (out, in) channel pair (generic / cross-check)
 //   k_weight_flipT   w[o][i][tap] -> wT[i][o][8-tap]: the input gradient of a convolution is a convolution with wT
 // Parameter gradients that are reductions over all pixels are accumulated with fp64 atomics (order effects are
-// below fp32 resolution after the final rounding) and converted by k_grad_finalize.
+// below fp32 resolution after the final rounding) and converted by k_grad_finalize_batched.
 #include "kernels.h"
 #include "backward.h"
 #include "wgrad_reduce.h"
@@ -353,7 +353,7 @@ int launch_act_bwd(float* g, const float* h, const float* e, int N, int Cm, int 
 // ------------------------------------------------------------------------------------------------
 // ActNorm + invertible 1x1 conv / permutation backward.  Forward: v = (x + b)*e, y = W v (or y[o] = v[idx[o]]).
 //   g_v = W^T g_y (or scatter);  g_x = g_v * e;
-//   dW[o][i] = sum_px g_y[o] v[i]  (+ G*HW*W^-1[i][o] added by k_grad_finalize_w, G = sum_n gld[n])
+//   dW[o][i] = sum_px g_y[o] v[i]  (+ G*HW*W^-1[i][o] added by k_grad_finalize_batched, G = sum_n gld[n])
 //   g_b[c] = sum g_v[c]*e[c];  g_logs[c] = 3*sum g_v[c]*v[c]  (+ 3*HW*G in finalize)
 // 64 pixels per workgroup; x->v, g_y and g_v live in LDS columns [c][px]; the C*C outer-product sums are formed
 // pair-by-pair over the 64 pixels and added with one fp64 atomic per pair per workgroup.
@@ -797,26 +797,10 @@ int launch_wgrad_direct(const float* gy, const float* x, long x_bs, float* dw, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// fp64 accumulators -> fp32 gradient tensors.
-//   out[i] = acc[i] * mul + add_const               (plain)
-//   invconv: dW[o][i] = acc[o*C+i] + G*HW*Winv[i*C+o]
+// fp64 accumulators -> fp32 gradient tensors (k_grad_finalize_batched, one launch per sweep; GradJob in backward.h).
+//   out[i] = sum over copies of acc[i] + G * add_mul                          (plain), G = sum_n gld[n]
+//   invconv: dW[o][i] = sum over copies of acc[o*C+i] + G * HW * Winv[i*C+o]
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_grad_finalize(const double* __restrict__ acc, float* __restrict__ out, int n,
-                                                       const double* __restrict__ gsum, double add_mul) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    out[i] = (float)(acc[i] + (gsum ? gsum[0] * add_mul : 0.0));
-}
-
-__global__ void __launch_bounds__(256) k_grad_finalize_w(const double* __restrict__ acc, float* __restrict__ out, int C,
-                                                         const double* __restrict__ gsum, double hw,
-                                                         const float* __restrict__ winv) {
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= C * C) return;
-    const int o = e / C, i = e - o * C;
-    out[e] = (float)(acc[e] + gsum[0] * hw * (double)winv[i * C + o]);
-}
-
 // gsum[0] = sum_n gld[n]  (one small workgroup, fixed order)
 __global__ void __launch_bounds__(64) k_sum_gld(const float* __restrict__ gld, int N, double* __restrict__ gsum) {
     double a = 0.0;
@@ -847,21 +831,6 @@ int launch_grad_finalize_batched(const GradJob* jobs_dev, int n_jobs, const doub
     if (n_jobs == 0) return GLOWHIP_OK;
     hipLaunchKernelGGL(k_grad_finalize_batched, dim3(8, n_jobs), dim3(256), 0, s, jobs_dev, gsum);
     GH_LAUNCH_CHECK("k_grad_finalize_batched");
-    return GLOWHIP_OK;
-}
-
-int launch_grad_finalize(const double* acc, float* out, int n, const double* gsum, double add_mul, hipStream_t s) {
-    if (n == 0 || out == nullptr) return GLOWHIP_OK;
-    hipLaunchKernelGGL(k_grad_finalize, dim3(cdiv(n, 256)), dim3(256), 0, s, acc, out, n, gsum, add_mul);
-    GH_LAUNCH_CHECK("k_grad_finalize");
-    return GLOWHIP_OK;
-}
-
-int launch_grad_finalize_w(const double* acc, float* out, int C, const double* gsum, double hw, const float* winv,
-                           hipStream_t s) {
-    if (out == nullptr) return GLOWHIP_OK;
-    hipLaunchKernelGGL(k_grad_finalize_w, dim3(cdiv(C * C, 256)), dim3(256), 0, s, acc, out, C, gsum, hw, winv);
-    GH_LAUNCH_CHECK("k_grad_finalize_w");
     return GLOWHIP_OK;
 }
 

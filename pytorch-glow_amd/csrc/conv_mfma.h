@@ -8,7 +8,7 @@ namespace glowhip {
 // network/module.py:300-319).  Implicit GEMM  Y[o][pixel] = sum_k Wt[k][o] * im2col(X)[k][pixel].
 bool conv_mfma_wide_supported(int Cin, int H, int W, int Cout, int ksize);
 size_t conv_mfma_wide_packed_bytes(int Cin, int Cout, int ksize);
-int conv_mfma_wide_pack(const float* w, int Cin, int Cout, int ksize, float* wt, hipStream_t s);
+
 // post_bias / post_scale may be NULL (0 / 1) and relu = 0 for a plain GEMM (input-gradient use) -- 1x1 LDS-DMA path only
 // splitk_scratch (optional, splitk_floats floats, must not overlap x or y): lets a launch with few output tiles and a long
 // reduction split the reduction over workgroups (partial sums there, summed in a fixed order by a second small kernel)

@@ -378,22 +378,6 @@ size_t conv_mfma_wide_packed_bytes(int Cin, int Cout, int ksize) {
     return (size_t)wide_kpad(Cin, ksize) * Cout * sizeof(float);
 }
 
-// w (Cout, Cin, k, k) -> wt [Kpad][Cout], k = ci*k*k + tap, zero rows beyond K
-__global__ void __launch_bounds__(256) k_pack_wide(const float* __restrict__ w, int K, int Kpad, int Cout,
-                                                   float* __restrict__ wt) {
-    long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)Kpad * Cout) return;
-    const int k = (int)(i / Cout), o = (int)(i - (long)k * Cout);
-    wt[i] = (k < K) ? w[(long)o * K + k] : 0.f;
-}
-
-int conv_mfma_wide_pack(const float* w, int Cin, int Cout, int ksize, float* wt, hipStream_t s) {
-    const int K = Cin * ksize * ksize, Kpad = wide_kpad(Cin, ksize);
-    hipLaunchKernelGGL(k_pack_wide, dim3(cdiv((long)Kpad * Cout, 256)), dim3(256), 0, s, w, K, Kpad, Cout, wt);
-    GH_LAUNCH_CHECK("k_pack_wide");
-    return GLOWHIP_OK;
-}
-
 // y[n][o][p] = act((sum_s part[s][n][o][p] + bias[o]) * scale[o]), s ascending (deterministic)
 __global__ void __launch_bounds__(256) k_splitk_finish(const float* __restrict__ part, int S, long per, const float* __restrict__ bias,
                                                        const float* __restrict__ scale, int relu, float* __restrict__ Y, int M, int HW) {

@@ -46,29 +46,24 @@ static size_t fin_cnt_words(const glowhip_plan* p, int N) {
     return ((size_t)N * px + 63) / 64 + 64;
 }
 
-static size_t workspace_bytes(const glowhip_plan* p, int N) {
+// fin_cnt | acc | bufA | bufB | h1 | h2; returns the size (w / base null: that alone)
+static size_t ws_layout(const glowhip_plan* p, int N, void* base, Workspace* w) {
     size_t off = 0;
-    take(off, fin_cnt_words(p, N) * 4);
-    take(off, (size_t)N * 8 * (2 + ACC_EXTRA));
-    take(off, (size_t)N * p->max_chw * 4);
-    take(off, (size_t)N * p->max_chw * 4);
-    take(off, (size_t)N * p->max_hidden * 4);
-    take(off, (size_t)N * p->max_hidden * 4);
+    const size_t chw = (size_t)N * p->max_chw * 4, hid = (size_t)N * p->max_hidden * 4;
+    const size_t o_fin = take(off, fin_cnt_words(p, N) * 4), o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA));
+    const size_t o_A = take(off, chw), o_B = take(off, chw), o_h1 = take(off, hid), o_h2 = take(off, hid);
+    if (w && base)
+        *w = Workspace{at<unsigned>(base, o_fin), at<unsigned long long>(base, o_acc), at<float>(base, o_A), at<float>(base, o_B),
+                       at<float>(base, o_h1), at<float>(base, o_h2)};
     return align_up(off, 256);
 }
 
 static int carve(const glowhip_plan* p, int N, void* ws, size_t bytes, Workspace& w) {
-    if (bytes < workspace_bytes(p, N) || ws == nullptr) {
-        set_error("workspace too small: need %zu bytes, got %zu", workspace_bytes(p, N), bytes);
+    const size_t need = ws_layout(p, N, ws, &w);
+    if (bytes < need || ws == nullptr) {
+        set_error("workspace too small: need %zu bytes, got %zu", need, bytes);
         return GLOWHIP_EWORKSPACE;
     }
-    size_t off = 0;
-    w.fin_cnt = at<unsigned>(ws, take(off, fin_cnt_words(p, N) * 4));
-    w.acc = at<unsigned long long>(ws, take(off, (size_t)N * 8 * (2 + ACC_EXTRA)));
-    w.bufA = at<float>(ws, take(off, (size_t)N * p->max_chw * 4));
-    w.bufB = at<float>(ws, take(off, (size_t)N * p->max_chw * 4));
-    w.h1 = at<float>(ws, take(off, (size_t)N * p->max_hidden * 4));
-    w.h2 = at<float>(ws, take(off, (size_t)N * p->max_hidden * 4));
     return GLOWHIP_OK;
 }
 
@@ -94,21 +89,26 @@ static int dnet_run_end(const glowhip_plan* p, int li, int dir) {
     }
     return lj;
 }
+// A level's run on the deep-level kernels begins at step li: the level's descriptor (state S, scratch h1), the padded operands'
+// borders, PREP (encode: with step li's ActNorm)
+static int dnet_open(glowhip_plan* p, const void* packed, int li, const float* cur, float* S, int N, const Workspace& w, int reverse,
+                     DnetLevel* D, hipStream_t s) {
+    const LayerPlan& L0 = p->layers[li];
+    const glowhip_layer_desc& d = L0.d;
+    const long chw = (long)d.C * d.H * d.W;
+    *D = DnetLevel{N, d.C, d.H, d.W, d.hidden, L0.Cout, S, chw, w.h1};
+    GH_TRY(dnet_level_begin(*D, s));
+    p->cur_layer = li;
+    ScopedTimer t(p, GLOWHIP_K_OTHER, 0, s);
+    count_launch(p, "k_dn_prep");
+    return dnet_prep(*D, cur, chw, reverse ? nullptr : d.an_bias, reverse ? nullptr : at<float>(packed, L0.an_scale), reverse, s);
+}
 // One level's run of FlowSteps [li .. lj] (encode) on the deep-level kernels: PREP, then MIX -> F0 -> F2 -> F4 -> FIN per step; the
 // result is left in `S` (N, C, H, W).
 static int run_dnet_forward(glowhip_plan* p, const void* packed, int li, int lj, const float* cur, float* S, int N, const Workspace& w,
                             hipStream_t s) {
-    const LayerPlan& L0 = p->layers[li];
-    const glowhip_layer_desc& d = L0.d;
-    const long chw = (long)d.C * d.H * d.W;
-    DnetLevel D{N, d.C, d.H, d.W, d.hidden, L0.Cout, S, chw, w.h1};
-    GH_TRY(dnet_level_begin(D, s));
-    p->cur_layer = li;
-    {
-        ScopedTimer t(p, GLOWHIP_K_OTHER, 0, s);
-        count_launch(p, "k_dn_prep");
-        GH_TRY(dnet_prep(D, cur, chw, d.an_bias, at<float>(packed, L0.an_scale), 0, s));
-    }
+    DnetLevel D{};
+    GH_TRY(dnet_open(p, packed, li, cur, S, N, w, 0, &D, s));
     for (int k = li; k <= lj; ++k) {
         const LayerPlan& L = p->layers[k];
         p->cur_layer = k;
@@ -134,17 +134,8 @@ static int run_dnet_forward(glowhip_plan* p, const void* packed, int li, int lj,
 // ... and decode: steps li, li - 1, ..., lj (li >= lj): PREP, then F0 -> F2 -> F4 -> FIN -> MIX^-1 per step
 static int run_dnet_reverse(glowhip_plan* p, const void* packed, int li, int lj, const float* cur, float* S, int N, const Workspace& w,
                             hipStream_t s) {
-    const LayerPlan& L0 = p->layers[li];
-    const glowhip_layer_desc& d = L0.d;
-    const long chw = (long)d.C * d.H * d.W;
-    DnetLevel D{N, d.C, d.H, d.W, d.hidden, L0.Cout, S, chw, w.h1};
-    GH_TRY(dnet_level_begin(D, s));
-    p->cur_layer = li;
-    {
-        ScopedTimer t(p, GLOWHIP_K_OTHER, 0, s);
-        count_launch(p, "k_dn_prep");
-        GH_TRY(dnet_prep(D, cur, chw, nullptr, nullptr, 1, s));
-    }
+    DnetLevel D{};
+    GH_TRY(dnet_open(p, packed, li, cur, S, N, w, 1, &D, s));
     for (int k = li; k >= lj; --k) {
         const LayerPlan& L = p->layers[k];
         p->cur_layer = k;
@@ -169,17 +160,6 @@ static int run_dnet_reverse(glowhip_plan* p, const void* packed, int li, int lj,
 // ---- the one-kernel coupling network (cnet_sh.hip).  A FlowStep is k_cnet (partial sums of h = f(z1)) + a finishing step
 // (coupling, log-det, channel mixer); the finishing step of step k runs either as its own kernel or inside step k+1's k_cnet
 // while that builds its window ("pending").
-static CnetArgs cnet_base(const LayerPlan& L, const void* packed, int N, int reverse, float* scratch, const Workspace& w) {
-    const glowhip_layer_desc& d = L.d;
-    CnetArgs c{};
-    c.w0 = at<char>(packed, L.cn_w0); c.w2 = at<char>(packed, L.cn_w2); c.w4 = at<char>(packed, L.cn_w4);
-    c.N = N; c.Cin = d.C / 2; c.H = d.H; c.W = d.W; c.hidden = d.hidden; c.Cout = L.Cout;
-    c.scratch = scratch;
-    c.bias = d.f4_bias; c.scale = at<float>(packed, L.f4_scale);
-    c.mode = tail_mode(d, reverse);
-    c.acc = w.acc;
-    return c;
-}
 // which instance of k_cnet ran (run-time evidence for the tests): "variant:k_cnet<hidden,row split,pixel tile>"
 static void count_cnet_variant(glowhip_plan* p, const CnetArgs& c, const CnetPending& pend) {
     char name[64];
@@ -320,6 +300,16 @@ static float* other_buf(const Workspace& w, const float* cur) { return cur == w.
 // kernel pairs) is not run at all: the mixer gathers the squeezed view itself, dequantisation noise and 8-bit scaling included
 // ("fuse uint8 -> fp32 scaling + noise + first squeeze into the first kernel").
 struct SqueezeFold { const void* src; int u8; float div; const float* noise; RngSpec rng; int W; long bs; };
+static void apply_fold(ChanMixArgs& m, SqueezeFold& fold) {      // a pending fold becomes this mixer's input
+    if (!fold.src) return;
+    m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; m.sq_bs = fold.bs;
+    fold = SqueezeFold{};
+}
+static int run_chanmix(glowhip_plan* p, const ChanMixArgs& m, hipStream_t s) {
+    ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
+    count_launch(p, "k_chanmix");
+    return launch_chanmix(m, s);
+}
 // (testing: the mixer-fusion switch glowhip_debug_force_tail_tile(0x8000) also brings the squeeze kernels back -- the two must
 // agree bit for bit)
 
@@ -384,7 +374,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 // ---- k_cnet path.  `cur` holds the input of this step's mixer, or -- `premixed` -- its output, or -- `pending` --
                 // the state the PREVIOUS step's k_cnet read, whose finishing (coupling + this step's mixer) this launch does itself
                 float* scratch = (scr_i ^= 1) ? w.h1 : w.h2;
-                CnetArgs c = cnet_base(L, packed, N, 0, scratch, w);
+                CnetArgs c = cnet_base(L, packed, N, 0, scratch, w.acc);
                 if (pending) {
                     float* nxt = other_buf(w, cur);
                     c.pre_on = 1; c.pre = pend; c.pre_mix = mixer_fwd(L, packed); c.pre_z_new = nxt; c.pre_z_new_bs = chw;
@@ -392,10 +382,8 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 } else {
                     if (!premixed) {
                         ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
-                        if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; m.sq_bs = fold.bs; fold = SqueezeFold{}; }
-                        ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
-                        count_launch(p, "k_chanmix");
-                        GH_TRY(launch_chanmix(m, s));
+                        apply_fold(m, fold);
+                        GH_TRY(run_chanmix(p, m, s));
                         cur = dst;
                     }
                     c.x = cur; c.x_bs = chw; c.z_in = cur; c.z_in_bs = chw;
@@ -426,10 +414,8 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                     dst = const_cast<float*>(cur);   // the step runs in place on the already mixed buffer
                 } else {
                     ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
-                    if (fold.src) { m.sq_src = fold.src; m.sq_u8 = fold.u8; m.sq_div = fold.div; m.sq_noise = fold.noise; m.sq_rng = fold.rng; m.sq_W = fold.W; m.sq_bs = fold.bs; fold = SqueezeFold{}; }
-                    ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
-                    count_launch(p, "k_chanmix");
-                    GH_TRY(launch_chanmix(m, s));
+                    apply_fold(m, fold);
+                    GH_TRY(run_chanmix(p, m, s));
                 }
                 float* z2 = dst + (long)Ch * HW;
                 GH_TRY(join_legacy(p, s));
@@ -489,7 +475,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                 // coupling^-1, permutation^-1 and ActNorm^-1 by the finishing step -- run by the next-executed step's k_cnet where
                 // the two chain, by the finishing kernel otherwise
                 float* scratch = (scr_i ^= 1) ? w.h1 : w.h2;
-                CnetArgs c = cnet_base(L, packed, N, 1, scratch, w);
+                CnetArgs c = cnet_base(L, packed, N, 1, scratch, w.acc);
                 if (pending) {
                     float* nxt = other_buf(w, cur);
                     c.pre_on = 1; c.pre = pend; c.pre_mix = mixer_rev(p->layers[li + 1], packed); c.pre_z_new = nxt; c.pre_z_new_bs = chw;
@@ -520,9 +506,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                     }
                     float* out = (li == 0) ? x_out : other_buf(w, mid);
                     ChanMixArgs m = chanmix_rev_args(L, packed, N, mid, mid + (long)Ch * HW, chw, out);
-                    ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
-                    count_launch(p, "k_chanmix");
-                    GH_TRY(launch_chanmix(m, s));
+                    GH_TRY(run_chanmix(p, m, s));
                     cur = out;
                 }
                 continue;
@@ -533,9 +517,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
             if (cur == w.bufA || cur == w.bufB) z2 = const_cast<float*>(cur) + (long)Ch * HW;
             GH_TRY(run_coupling(p, L, packed, cur, chw, cur + (long)Ch * HW, chw, z2, chw, N, 1, w, s));
             ChanMixArgs m = chanmix_rev_args(L, packed, N, cur, z2, chw, dst);
-            ScopedTimer tm(p, GLOWHIP_K_CHANMIX, 0, s);
-            count_launch(p, "k_chanmix");
-            GH_TRY(launch_chanmix(m, s));
+            GH_TRY(run_chanmix(p, m, s));
         } else {  // SPLIT2D reverse: z1 = cur (N, C/2, HW) -> cat(z1, mean + exp(logs)*eps)
             GH_REQUIRE(ke < n_eps && eps && eps[ke], "decode: missing eps draw for Split2d #%d", ke);
             GH_TRY(run_split(p, L, packed, cur, (long)Ch * HW, nullptr, 0, eps[ke], dst + (long)Ch * HW, chw, N, 1, w, s));
@@ -837,7 +819,7 @@ int glowhip_plan_timing_read(glowhip_plan* plan, glowhip_timing_record* out, int
 size_t glowhip_plan_packed_bytes(const glowhip_plan* plan) { return plan ? plan->packed_bytes : 0; }
 
 size_t glowhip_plan_workspace_bytes(const glowhip_plan* plan, int N) {
-    return (plan && N >= 0) ? workspace_bytes(plan, N) : 0;
+    return (plan && N >= 0) ? ws_layout(plan, N, nullptr, nullptr) : 0;
 }
 
 int glowhip_plan_output_shape(const glowhip_plan* plan, int reverse, int32_t out[3]) {

@@ -187,5 +187,18 @@ static inline ChanMixArgs chanmix_rev_args(const LayerPlan& L, const void* packe
                                            float* out) {
     return chanmix_args(L, mixer_rev(L, packed), N, in_a, in_b, in_bs, out);
 }
+// k_cnet of step L in the coupling network's own direction (cnet_sh.hip): weight images, shape, f.4's epilogue, the tail; the
+// caller sets the tensors
+static inline CnetArgs cnet_base(const LayerPlan& L, const void* packed, int N, int reverse, float* scratch, unsigned long long* acc) {
+    const glowhip_layer_desc& d = L.d;
+    CnetArgs c{};
+    c.w0 = at<char>(packed, L.cn_w0); c.w2 = at<char>(packed, L.cn_w2); c.w4 = at<char>(packed, L.cn_w4);
+    c.N = N; c.Cin = d.C / 2; c.H = d.H; c.W = d.W; c.hidden = d.hidden; c.Cout = L.Cout;
+    c.scratch = scratch;
+    c.bias = d.f4_bias; c.scale = at<float>(packed, L.f4_scale);
+    c.mode = tail_mode(d, reverse);
+    c.acc = acc;
+    return c;
+}
 
 }  // namespace glowhip

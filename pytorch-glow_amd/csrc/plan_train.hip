@@ -9,8 +9,11 @@
 //
 // Backward of one FlowStep (reference forward: network/model.py:82-117), all gradients "g_": see backward.hip for the
 // element-wise formulas.  Convolution input gradients are convolutions with flipped/transposed weights and reuse the
-// forward kernels; weight gradients use k_wgrad_direct for now (correctness first -- the MFMA wgrad is the next
-// step of this row).
+// forward kernels -- as ONE backward k_cnet launch on the transposed weight images where the tape holds the ReLU sign bits
+// (bwd_cnet), layer by layer elsewhere.  Weight gradients are split-K MFMA GEMMs (wgrad_mfma.hip) where wgrad_fast holds: three
+// per FlowStep, sharing launches where the shape allows (WgradRoute), their reductions riding in the mixer backward; the direct
+// kernel k_wgrad_direct takes the remaining shapes.  The decode VJP (decode_vjp_sweep) walks the same input-gradient chain in
+// encode order and has no parameter gradients.
 #include "plan_internal.h"
 #include "backward.h"
 
@@ -47,17 +50,24 @@ static size_t tape_layout(const glowhip_plan* p, int N, std::vector<TapeLayer>* 
     }
     return align_up(off, 256);
 }
+// a FlowStep's tape slots as pointers
+struct StepTape { float* out; float* h1; float* h2; float* hout; unsigned short* m1; unsigned short* m2; };
+static StepTape step_tape(const char* tape, const TapeLayer& t) {
+    return StepTape{at<float>(tape, t.out), at<float>(tape, t.h1), at<float>(tape, t.h2), at<float>(tape, t.hout),
+                    at<unsigned short>(tape, t.m1), at<unsigned short>(tape, t.m2)};
+}
 
-// backward workspace: acc u64 (N) | gld (N) | gsum | gA | gB | gh1 | gh2 | gpre | wT | fp64 accumulators
-struct TrainWs {
-    unsigned long long* acc; float* gld; double* gsum;
-    float* gA; float* gB; float* gh1; float* gh2; float* gpre; float* wT; double* dacc;
-    float* gsh;                   // partial-sum scratch of the taping / backward k_cnet launches
+// the buffers of a gradient sweep (training backward and decode VJP): the status / log-det accumulators, the travelling gradient
+// (gA / gB), the hidden gradients, f.4's pre-scale gradient, the partial-sum scratch of the taping / backward k_cnet launches, a
+// flipped weight
+struct GradBufs { unsigned long long* acc; float* gA; float* gB; float* gh1; float* gh2; float* gpre; float* gsh; float* wT; };
+// backward workspace: acc u64 (N) | gld (N) | gsum | gA | gB | gh1 | gh2 | gpre | gsh | wT | fp64 accumulators | ...
+struct TrainWs : GradBufs {
+    float* gld; double* gsum; double* dacc;
     float* col; float* partial;   // shift-expanded small operand / split-K partial tiles of the MFMA weight gradients
     size_t partial_floats;        // floats of ONE of the three split-K partial regions behind `partial`
     GradJob* jobs;                // device copy of the finalize job table (<= 9 per layer)
     LogsJob* ljobs;               // ... and of the log-scale job table (<= 2 per layer)
-    size_t dacc_doubles;
     float* ludw; LuGradJob* lujobs;   // LU-form layers: the data-term dW of each (C*C floats, in lu_layers order), their gradient job table
 };
 
@@ -149,14 +159,21 @@ static void wgrad_scratch_floats(const glowhip_plan* p, int N, size_t* col, size
     }
 }
 
+// gA .. wT, in this order from `off` on; acc lies in front of the caller's own leading fields, at o_acc
+static void carve_grad_bufs(const glowhip_plan* p, int N, size_t& off, size_t o_acc, void* base, GradBufs* b) {
+    const size_t chw = (size_t)N * p->max_chw * 4, hid = (size_t)N * p->max_hidden * 4;
+    const size_t o_gA = take(off, chw), o_gB = take(off, chw), o_h1 = take(off, hid), o_h2 = take(off, hid);
+    const size_t o_gpre = take(off, chw), o_gsh = take(off, hid), o_wT = take(off, max_weight_floats(p) * 4);
+    if (!b || !base) return;
+    b->acc = at<unsigned long long>(base, o_acc); b->gA = at<float>(base, o_gA); b->gB = at<float>(base, o_gB);
+    b->gh1 = at<float>(base, o_h1); b->gh2 = at<float>(base, o_h2); b->gpre = at<float>(base, o_gpre);
+    b->gsh = at<float>(base, o_gsh); b->wT = at<float>(base, o_wT);
+}
+
 static size_t train_ws_layout(const glowhip_plan* p, int N, void* base, TrainWs* w) {
     size_t off = 0;
     const size_t o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA)), o_gld = take(off, (size_t)N * 4), o_gsum = take(off, 64);
-    const size_t o_gA = take(off, (size_t)N * p->max_chw * 4), o_gB = take(off, (size_t)N * p->max_chw * 4);
-    const size_t o_h1 = take(off, (size_t)N * p->max_hidden * 4), o_h2 = take(off, (size_t)N * p->max_hidden * 4);
-    const size_t o_gpre = take(off, (size_t)N * p->max_chw * 4);
-    const size_t o_gsh = take(off, (size_t)N * p->max_hidden * 4);
-    const size_t o_wT = take(off, max_weight_floats(p) * 4);
+    carve_grad_bufs(p, N, off, o_acc, base, w);
     const size_t nd = max_acc_doubles(p, N);
     const size_t o_dacc = take(off, nd * 8);
     size_t colf, partf;
@@ -169,10 +186,7 @@ static size_t train_ws_layout(const glowhip_plan* p, int N, void* base, TrainWs*
     const size_t o_ludw = take(off, ludw_floats * 4), o_lujobs = take(off, p->lu_jobs.size() * sizeof(LuGradJob));
     if (w && base) {
         w->col = at<float>(base, o_col); w->partial = at<float>(base, o_part); w->partial_floats = partf; w->jobs = at<GradJob>(base, o_jobs); w->ljobs = at<LogsJob>(base, o_ljobs);
-        w->acc = at<unsigned long long>(base, o_acc); w->gld = at<float>(base, o_gld); w->gsum = at<double>(base, o_gsum);
-        w->gA = at<float>(base, o_gA); w->gB = at<float>(base, o_gB); w->gh1 = at<float>(base, o_h1);
-        w->gh2 = at<float>(base, o_h2); w->gpre = at<float>(base, o_gpre); w->wT = at<float>(base, o_wT);
-        w->dacc = at<double>(base, o_dacc); w->dacc_doubles = nd; w->gsh = at<float>(base, o_gsh);
+        w->gld = at<float>(base, o_gld); w->gsum = at<double>(base, o_gsum); w->dacc = at<double>(base, o_dacc);
         w->ludw = at<float>(base, o_ludw); w->lujobs = at<LuGradJob>(base, o_lujobs);
     }
     return align_up(off, 256);
@@ -199,9 +213,8 @@ static int forward_train(glowhip_plan* p, const void* packed, const float* x, co
             noise = nullptr;
         } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
             GH_REQUIRE(noise == nullptr, "forward_train: the dequantisation noise needs a leading Squeeze2d layer");
-            float* h1 = at<float>(tape, tl[li].h1);
-            float* h2 = at<float>(tape, tl[li].h2);
-            float* hout = at<float>(tape, tl[li].hout);
+            const StepTape T = step_tape(tape, tl[li]);
+            float* h1 = T.h1; float* h2 = T.h2; float* hout = T.hout;
             if (!premixed) {
                 ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
                 GH_TRY(launch_chanmix(m, s));
@@ -211,17 +224,11 @@ static int forward_train(glowhip_plan* p, const void* packed, const float* x, co
                 // the product path's two launches, taping: k_cnet stores h1 / h2, the finishing kernel hout, the step output
                 // (y1, z2') in place and -- when the next layer is a FlowStep of the same shape -- that step's mixer output into
                 // ITS tape slot
-                CnetArgs c{};
-                c.w0 = at<char>(packed, L.cn_w0); c.w2 = at<char>(packed, L.cn_w2); c.w4 = at<char>(packed, L.cn_w4);
-                c.N = N; c.Cin = Ch; c.H = d.H; c.W = d.W; c.hidden = hid; c.Cout = L.Cout;
-                c.scratch = sh_scratch;
-                c.bias = d.f4_bias; c.scale = at<float>(packed, L.f4_scale);
-                c.mode = tail_mode(d, 0);
-                c.acc = acc;
+                CnetArgs c = cnet_base(L, packed, N, 0, sh_scratch, acc);
                 c.x = dst; c.x_bs = chw; c.z_in = dst; c.z_in_bs = chw;
                 c.z_out = dst; c.z_out_bs = chw;
                 c.tape_h1 = h1; c.tape_h2 = h2; c.tape_hout = hout;
-                c.mask1 = at<unsigned short>(tape, tl[li].m1); c.mask2 = at<unsigned short>(tape, tl[li].m2);
+                c.mask1 = T.m1; c.mask2 = T.m2;
                 c.in_scale = SH2_ACT_SCALE; c.out_scale = SH2_ACT_INV;
                 if (li + 1 < nl) {
                     const LayerPlan& Ln = p->layers[li + 1];
@@ -328,6 +335,80 @@ __global__ void __launch_bounds__(256) k_add_inplace(float* __restrict__ dst, lo
     if (i < per) dst[n * dst_bs + i] += src[n * src_bs + i];
 }
 
+static int add_rows(float* dst, long dst_bs, const float* src, int N, long per, hipStream_t s) {      // dst[n][:per] += src[n][:per], src dense
+    hipLaunchKernelGGL(k_add_inplace, dim3(cdiv(per, 256), N), dim3(256), 0, s, dst, dst_bs, src, per, per);
+    GH_LAUNCH_CHECK("k_add_inplace");
+    return GLOWHIP_OK;
+}
+// the 3x3 input gradient added into dst's first Cin channels (batch stride dst_bs) through the dense (N, Cin, H, W) scratch `tmp`
+static int dgrad_direct_add(const float* gy, const float* w, float* wT, float* tmp, float* dst, long dst_bs, int N, int Cin, int H,
+                            int W, int Cout, hipStream_t s) {
+    GH_TRY(dgrad_direct(gy, w, wT, tmp, N, Cin, H, W, Cout, 3, s));
+    return add_rows(dst, dst_bs, tmp, N, (long)Cin * H * W, s);
+}
+
+// ---------------------------------------------------------------- a FlowStep's input-gradient chain, shared by the two sweeps
+// As ONE k_cnet launch (MODE 2, cnet_sh.hip) on the transposed weight images, the ReLU masks from the tape's sign bits:
+// g_pre -> g_u2 (gh2) -> g_u0 (gh1) -> the partial sums of d y1, described by *pend; their gathering rides in the caller's next
+// mixer kernel.  The gradients enter times grad_scale; g_u2 / g_u0 are stored times grad_scale * 2^11 (what the weight-gradient
+// GEMMs split with two instructions per value).
+static int launch_cnet_bwd(glowhip_plan* p, const LayerPlan& L, const void* packed, int N, const StepTape& T, const GradBufs& b,
+                           float grad_scale, CnetPending* pend, hipStream_t s) {
+    const glowhip_layer_desc& d = L.d;
+    const long gpre_bs = (long)L.Cout * d.H * d.W;
+    CnetArgs c{};
+    c.w0 = at<char>(packed, L.cb_w0); c.w2 = at<char>(packed, L.cb_w2); c.w4 = at<char>(packed, L.cb_w4);
+    c.N = N; c.Cin = L.Cout; c.H = d.H; c.W = d.W; c.hidden = d.hidden; c.Cout = d.C / 2;
+    c.scratch = b.gsh; c.mode = TAIL_ADD_FWD;
+    c.x = b.gpre; c.x_bs = gpre_bs; c.z_in = b.gpre; c.z_in_bs = gpre_bs;
+    c.tape_h1 = b.gh2; c.tape_h2 = b.gh1;
+    c.mask1 = T.m1; c.mask2 = T.m2;
+    c.in_scale = SH2_ACT_SCALE * grad_scale; c.out_scale = SH2_ACT_INV * SH_LO_SCALE; c.bwd = 1;
+    *pend = CnetPending{};
+    count_launch(p, "k_cnet(bwd)");
+    {
+        ScopedTimer t(p, GLOWHIP_K_CNET_BWD, 1, s);
+        GH_TRY(launch_cnet_main(c, s, pend));
+    }
+    if (pend->one_wave) count_launch(p, "k_cnet1w(bwd)");      // (run-time evidence for the tests: the backward instance of cnet1w_sh.hip took it)
+    return GLOWHIP_OK;
+}
+// Layer by layer: each helper holds its convolution's route.  The activation backward between them (and, in training, the weight
+// gradients) is the caller's.
+// The per-layer kernels read fp32: a tape written by the taping k_cnet holds h1 / h2 as fp16 -- converted into the partial-sum
+// scratch (unused on this path), h2 first, h1 once h2 has been consumed.
+static int tape_to_f32(const float*& h, bool half_tape, const LayerPlan& L, int N, const GradBufs& b, hipStream_t s) {
+    if (!half_tape) return GLOWHIP_OK;
+    GH_TRY(launch_half_to_float(h, b.gsh, N, L.d.hidden, L.d.H * L.d.W, s));
+    h = b.gsh;
+    return GLOWHIP_OK;
+}
+static int dgrad_f4(const LayerPlan& L, const void* packed, int N, const GradBufs& b, hipStream_t s) {      // gpre -> gh2 (raw)
+    const glowhip_layer_desc& d = L.d;
+    if (!L.dg4_first) return dgrad_direct(b.gpre, d.f4_w, b.wT, b.gh2, N, d.hidden, d.H, d.W, L.Cout, 3, s);
+    const float* wf = at<float>(packed, L.f4T_wf);
+    return launch_conv_mfma_first(b.gpre, (long)L.Cout * d.H * d.W, wf, wf + (size_t)9 * L.Cout * d.hidden, b.gh2, N, L.Cout, d.H, d.W,
+                                  d.hidden, s, 0);
+}
+static int dgrad_f2(const LayerPlan& L, int N, const GradBufs& b, hipStream_t s) {      // gh2 -> gh1 (raw)
+    const glowhip_layer_desc& d = L.d;
+    if (!L.mfma_mid) return dgrad_direct(b.gh2, d.f2_w, b.wT, b.gh1, N, d.hidden, d.H, d.W, d.hidden, 1, s);
+    // W2 in its reference layout [o][i] is already the K-major image of the transposed GEMM
+    return launch_conv_mfma_wide(b.gh2, (long)d.hidden * d.H * d.W, d.f2_w, nullptr, nullptr, b.gh1, N, d.hidden, d.H, d.W, d.hidden, 1, s, 0);
+}
+static int dgrad_f0_add(const LayerPlan& L, const void* packed, int N, const GradBufs& b, float* g, hipStream_t s) {      // g's y1 half += f.0^T gh1
+    const glowhip_layer_desc& d = L.d;
+    const int Ch = d.C / 2, HW = d.H * d.W;
+    const long chw = (long)d.C * HW;
+    if (!L.dg0_tail) return dgrad_direct_add(b.gh1, d.f0_w, b.wT, b.gpre, g, chw, N, Ch, d.H, d.W, d.hidden, s);   // gpre reused: (N,Ch,HW)
+    TailConvArgs t{};      // fused: the tail kernel's additive-coupling epilogue
+    t.x = b.gh1; t.x_bs = (long)d.hidden * HW; t.wp = at<float>(packed, L.f0T_wp); t.bias = nullptr; t.scale = nullptr;
+    t.N = N; t.Cin = d.hidden; t.H = d.H; t.W = d.W; t.Cout = Ch; t.mode = TAIL_ADD_FWD;
+    t.z2_in = g; t.z2_in_bs = chw; t.z2_out = g; t.z2_out_bs = chw; t.acc = nullptr;
+    t.zeros = at<float>(packed, 64); t.hout = nullptr;
+    return launch_conv_mfma_tail(t, s);
+}
+
 static int zero_f64(double* p, size_t n, hipStream_t s) {
     if (hipMemsetAsync(p, 0, n * sizeof(double), s) != hipSuccess) {
         set_error("backward: hipMemsetAsync failed");
@@ -337,6 +418,43 @@ static int zero_f64(double* p, size_t n, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------- backward sweep
+// a FlowStep's fp64 accumulators (layer_acc_doubles): mcopies x [W C*C][an_b C][an_l C] | [f0_b hid][f0_l hid][f2_b hid][f2_l hid] |
+// MIX_ACC_COPIES x [f4_b Cout][f4_l Cout]
+struct StepAcc { double* W; double* Ab; double* Al; double* b0; double* l0; double* b2; double* l2; double* b4; double* l4; int mcopies; long mstride; };
+static StepAcc step_acc(double* base, const LayerPlan& L, int N) {
+    const glowhip_layer_desc& d = L.d;
+    const int hid = d.hidden;
+    StepAcc a{};
+    a.mcopies = mix_acc_copies(d, N); a.mstride = (long)d.C * d.C + 2 * d.C;       // (one copy of the mixer accumulators)
+    a.W = base; a.Ab = a.W + (size_t)d.C * d.C; a.Al = a.Ab + d.C;
+    a.b0 = a.W + a.mcopies * a.mstride; a.l0 = a.b0 + hid; a.b2 = a.l0 + hid; a.l2 = a.b2 + hid; a.b4 = a.l2 + hid; a.l4 = a.b4 + L.Cout;
+    return a;
+}
+// the step's mixer backward, gy -> gx (the k_cnet branch adds add_*)
+static ChanMixBwdArgs chanmix_bwd_args(const LayerPlan& L, const void* packed, int N, const float* xin, const float* gy, float* gx,
+                                       const StepAcc& A) {
+    const glowhip_layer_desc& d = L.d;
+    const long chw = (long)d.C * d.H * d.W;
+    ChanMixBwdArgs mb{xin, chw, gy, gx, chw, d.an_bias, at<float>(packed, L.an_scale),
+                      d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
+                      d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr, A.W, A.Ab, A.Al, N, d.C, d.H * d.W};
+    mb.acc_copies = A.mcopies; mb.acc_stride = A.mstride;
+    return mb;
+}
+// How the three weight-gradient GEMMs of a step behind a backward k_cnet launch are launched.  trio: one launch.  pair: f.4's and
+// f.0's in one launch, f.2's alone.  taps: three launches, the 3x3 layers' shift-expanded operands gathered by the GEMM's loader
+// (WgradTaps: power-of-two widths).  expanded: three launches on operands written out by launch_shift_expand.
+enum class WgradRoute { trio, pair, taps, expanded };
+static WgradRoute wgrad_route(const LayerPlan& L, int N) {
+    const glowhip_layer_desc& d = L.d;
+    const int HW = d.H * d.W, m4 = round_up(L.Cout * 9, 128), n0 = round_up((d.C / 2) * 9, 64);
+    if (d.W < 4 || (d.W & (d.W - 1)) != 0) return WgradRoute::expanded;
+    if (!wgrad_pair_ok(HW, m4, d.hidden, n0)) return WgradRoute::taps;
+    // short pixel axes (<= 512 k-tiles of 32 pixels): f.2's GEMM joins the launch as well -- at 12 - 18 pixel slices instead of 32
+    // its workgroups' loops are two to three times as long and a third of the partial tiles is left
+    return (long)N * HW / 32 <= 512 ? WgradRoute::trio : WgradRoute::pair;
+}
+
 static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in, const char* tape,
                           const std::vector<TapeLayer>& tl, const glowhip_layer_grads* grads, float* grad_x, int N,
                           TrainWs& w, float* g_top, hipStream_t s) {
@@ -377,6 +495,20 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             so += (size_t)lj.C * lj.C;
         }
         fin(aW, G.invconv_w, d.C * d.C, (double)HW, at<float>(packed, L.winv), d.C, mcopies, mstride);
+    };
+    // a FlowStep's reduction-type gradients.  The log-scale gradients of f.0 / f.2 come from their accumulators, or -- logs_from_dw:
+    // the chain ran as one k_cnet launch, nothing filled them -- from dW and db (backward.h LogsJob)
+    auto fin_step = [&](int li, const LayerPlan& L, const glowhip_layer_grads& G, const StepAcc& A, bool logs_from_dw) {
+        const glowhip_layer_desc& d = L.d;
+        const int HW = d.H * d.W, hid = d.hidden;
+        if (logs_from_dw && G.f2_an_logs) p->logs_jobs.push_back(LogsJob{d.f2_w, G.f2_w, d.f2_an_bias, A.b2, G.f2_an_logs, hid, hid});
+        if (logs_from_dw && G.f0_an_logs) p->logs_jobs.push_back(LogsJob{d.f0_w, G.f0_w, d.f0_an_bias, A.b0, G.f0_an_logs, hid, (d.C / 2) * 9});
+        if (d.permutation == GLOWHIP_PERM_INVCONV) fin_w(li, L, G, A.W, HW, A.mcopies, A.mstride);
+        fin(A.Ab, G.an_bias, d.C, 0.0, nullptr, 0, A.mcopies, A.mstride);
+        fin(A.Al, G.an_logs, d.C, 3.0 * HW, nullptr, 0, A.mcopies, A.mstride);
+        fin(A.b0, G.f0_an_bias, hid, 0.0); if (!logs_from_dw) fin(A.l0, G.f0_an_logs, hid, 0.0);
+        fin(A.b2, G.f2_an_bias, hid, 0.0); if (!logs_from_dw) fin(A.l2, G.f2_an_logs, hid, 0.0);
+        fin(A.b4, G.f4_bias, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout); fin(A.l4, G.f4_logs, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout);
     };
     // log-scale gradients of the layers whose input-gradient chain ran as one k_cnet launch: d logs = 3 (<W, dW> + b db) READS the
     // weight gradients, which live in the per-level buckets a data-parallel run all-reduces (in place, on a side stream) as soon as
@@ -420,189 +552,123 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             GH_TRY(launch_squeeze(g, nullptr, dst, N, d.C * 4, d.H / 2, d.W / 2, 2, 1, s));
             g = dst;
         } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
-            const float* out = at<float>(tape, tl[li].out);
-            const float* h1 = at<float>(tape, tl[li].h1);
-            const float* h2 = at<float>(tape, tl[li].h2);
-            const float* hout = at<float>(tape, tl[li].hout);
+            const StepTape T = step_tape(tape, tl[li]);
+            const float* out = T.out; const float* h1 = T.h1; const float* h2 = T.h2;
             const int affine = d.coupling == GLOWHIP_COUPLING_AFFINE;
-            // accumulators: [W C*C][an_b C][an_l C][f0_b hid][f0_l hid][f2_b hid][f2_l hid][f4_b Cout][f4_l Cout]
-            const long mstride = (long)d.C * d.C + 2 * d.C;       // one copy of the mixer accumulators
-            double* aW = w.dacc + acc_base[li]; double* aAb = aW + (size_t)d.C * d.C; double* aAl = aAb + d.C;
-            const int mcopies = mix_acc_copies(d, N);
-            double* a0b = aW + mcopies * mstride; double* a0l = a0b + hid; double* a2b = a0l + hid; double* a2l = a2b + hid;
-            double* a4b = a2l + hid; double* a4l = a4b + L.Cout;
+            const StepAcc A = step_acc(w.dacc + acc_base[li], L, N);
             // (a) coupling tail: g (second half) becomes g_y2 in place; gpre = gradient of f.4's (conv + bias)
-            CouplingBwdArgs cb{hout, out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, g + (long)Ch * HW, w.gpre,
-                               at<float>(packed, L.f4_scale), w.gld, a4b, a4l, N, Ch, L.Cout, HW, affine};
+            CouplingBwdArgs cb{T.hout, out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, g + (long)Ch * HW, w.gpre,
+                               at<float>(packed, L.f4_scale), w.gld, A.b4, A.l4, N, Ch, L.Cout, HW, affine};
             cb.acc_copies = MIX_ACC_COPIES; cb.acc_stride = 2 * L.Cout;
             GH_TRY(launch_coupling_bwd(cb, s));
             // (b) f.4: weight gradient, then input gradient -> g_h2 (raw), then ReLU/ActNorm of f.2
             const bool fastw = wgrad_fast(L);
             if (fastw && bwd_cnet(p, L, li, G, N, (size_t)N * p->max_hidden)) {
-                // The input-gradient chain g_pre -> g_u2 -> g_u0 -> d y1 as ONE k_cnet launch (MODE 2, cnet_sh.hip) on the transposed
-                // weight images, the ReLU masks from the tape's sign bits; the bias gradients are row sums inside the weight-gradient
-                // GEMMs that read g_u2 / g_u0 anyway, the log-scale gradients follow from dW and db (backward.h LogsJob).
+                // The input-gradient chain as ONE k_cnet launch (launch_cnet_bwd); the bias gradients are row sums inside the
+                // weight-gradient GEMMs that read g_u2 / g_u0 anyway, the log-scale gradients follow from dW and db (backward.h LogsJob).
                 const int m4 = round_up(L.Cout * 9, 128), n0 = round_up(Ch * 9, 64);
-                // (the 3x3 layers' shift-expanded operands are gathered by the GEMM's loader: WgradTaps)
-                const bool vtaps = d.W >= 4 && (d.W & (d.W - 1)) == 0;
+                const WgradRoute route = wgrad_route(L, N);
+                // (the 3x3 layers' shift-expanded operands are gathered by the GEMM's loader: WgradTaps -- or, `expanded`, written out first)
                 const WgradTaps t4{0, L.Cout, d.H, d.W, -1}, t0{1, Ch, d.H, d.W, +1};
+                float* const part4 = w.partial; float* const part2 = w.partial + w.partial_floats; float* const part0 = w.partial + 2 * w.partial_floats;
                 WgradReduceJobs rj{};      // the three split-K reductions of this step run as one launch at its end
                 rj.n = 3;
-                // f.4's GEMM does not depend on the chain below, but it shares a launch with f.2's and f.0's, which do
-                // (launch_wgrad_trio); shapes that launch does not take run here, alone
-                const bool pair = vtaps && wgrad_pair_ok(HW, m4, hid, n0);
-                // short pixel axes (<= 512 k-tiles of 32 pixels): f.2's GEMM joins the launch as well -- at 12 - 18 pixel slices
-                // instead of 32 its workgroups' loops are two to three times as long and a third of the partial tiles is left
-                const bool trio = pair && (long)N * HW / 32 <= 512;
-                if (pair) {      // (launched below, behind the chain)
-                } else if (vtaps) {
-                    { ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s); GH_TRY(launch_wgrad_mfma(w.gpre, (long)L.Cout * HW, h2, (long)hid * HW, w.partial, G.f4_w, N, HW, m4, hid,
-                                             L.Cout * 9, hid, 1, s, sh_grad_scale, nullptr, &t4, &rj.job[0], 0, 1, 2)); }
-                } else {
-                    GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, m4, -1, s));
-                    { ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s); GH_TRY(launch_wgrad_mfma(w.col, (long)m4 * HW, h2, (long)hid * HW, w.partial, G.f4_w, N, HW, m4, hid,
-                                             L.Cout * 9, hid, 1, s, sh_grad_scale, nullptr, nullptr, &rj.job[0], 0, 1, 2)); }
-                }
-                CnetArgs c{};
-                c.w0 = at<char>(packed, L.cb_w0); c.w2 = at<char>(packed, L.cb_w2); c.w4 = at<char>(packed, L.cb_w4);
-                c.N = N; c.Cin = L.Cout; c.H = d.H; c.W = d.W; c.hidden = hid; c.Cout = Ch;
-                c.scratch = w.gsh; c.mode = TAIL_ADD_FWD;
-                c.x = w.gpre; c.x_bs = (long)L.Cout * HW; c.z_in = w.gpre; c.z_in_bs = (long)L.Cout * HW;
-                c.tape_h1 = w.gh2; c.tape_h2 = w.gh1;
-                c.mask1 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m1));
-                c.mask2 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m2));
-                c.in_scale = SH2_ACT_SCALE * sh_grad_scale; c.out_scale = SH2_ACT_INV * SH_LO_SCALE; c.bwd = 1;      // (g_u2 / g_u0 are stored times sh_grad_scale * 2^11: what the weight-gradient GEMMs split with two instructions per value)
+                auto wgrad_f4 = [&]() {      // dW4[o][i][tap] = sum_p g_pre[o][p - d(tap)] * h2[i][p]
+                    const bool ex = route == WgradRoute::expanded;
+                    if (ex) GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, m4, -1, s));
+                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
+                    return launch_wgrad_mfma(ex ? w.col : w.gpre, (long)(ex ? m4 : L.Cout) * HW, h2, (long)hid * HW, part4, G.f4_w, N, HW, m4, hid,
+                                             L.Cout * 9, hid, 1, s, sh_grad_scale, nullptr, ex ? nullptr : &t4, &rj.job[0], 0, 1, 2);
+                };
+                auto wgrad_f2 = [&]() {
+                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
+                    return launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, part2, G.f2_w, N, HW, hid, hid, hid, hid, 0, s,
+                                             sh_grad_scale, A.b2, nullptr, &rj.job[1], 0, 1, 7);
+                };
+                auto wgrad_f0 = [&]() {      // dW0[o][i][tap] = sum_p g_u0[o][p] * y1[i][p + d(tap)]
+                    const bool ex = route == WgradRoute::expanded;
+                    if (ex) GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, n0, +1, s));
+                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
+                    return launch_wgrad_mfma(w.gh1, (long)hid * HW, ex ? w.col : out, ex ? (long)n0 * HW : chw, part0, G.f0_w, N, HW, hid, n0,
+                                             hid, Ch * 9, 0, s, sh_grad_scale, A.b0, ex ? nullptr : &t0, &rj.job[2], 0, 0, 5);
+                };
+                // f.4's GEMM does not depend on the chain below, but where it shares a launch with f.0's (and f.2's), which do, it
+                // waits for it; alone it runs here
+                if (route == WgradRoute::taps || route == WgradRoute::expanded) GH_TRY(wgrad_f4());
                 CnetPending pend{};
-                count_launch(p, "k_cnet(bwd)");
-                {
-                    ScopedTimer t(p, GLOWHIP_K_CNET_BWD, 1, s);
-                    GH_TRY(launch_cnet_main(c, s, &pend));
-                }
-                if (pend.one_wave) count_launch(p, "k_cnet1w(bwd)");      // (run-time evidence for the tests: the backward instance of cnet1w_sh.hip took it)
+                GH_TRY(launch_cnet_bwd(p, L, packed, N, T, w, sh_grad_scale, &pend, s));
                 // (its finishing step -- g_y1 += the partial sums -- rides in k_chanmix_bwd below)
-                if (trio) {      // all three GEMMs side by side in one launch
+                switch (route) {
+                case WgradRoute::trio: {      // all three GEMMs side by side in one launch
                     count_launch(p, "k_wgrad(trio)");
                     ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    GH_TRY(launch_wgrad_trio(w.gh2, h1, w.partial + w.partial_floats, G.f2_w, a2b, w.gpre, (long)L.Cout * HW, h2, w.partial, G.f4_w, m4, L.Cout * 9,
-                                             w.gh1, out, chw, w.partial + 2 * w.partial_floats, G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, a0b, t4, t0,
+                    GH_TRY(launch_wgrad_trio(w.gh2, h1, part2, G.f2_w, A.b2, w.gpre, (long)L.Cout * HW, h2, part4, G.f4_w, m4, L.Cout * 9,
+                                             w.gh1, out, chw, part0, G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, A.b0, t4, t0,
                                              &rj.job[1], &rj.job[0], &rj.job[2], s));
-                } else {
-                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s); GH_TRY(launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, w.partial + w.partial_floats, G.f2_w, N, HW, hid, hid,
-                                         hid, hid, 0, s, sh_grad_scale, a2b, nullptr, &rj.job[1], 0, 1, 7));
+                    break;
                 }
-                if (trio) {
-                } else if (pair) {
+                case WgradRoute::pair: {      // f.2's alone, then f.4's and f.0's in one launch
+                    GH_TRY(wgrad_f2());
                     count_launch(p, "k_wgrad(pair)");
                     ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    GH_TRY(launch_wgrad_pair(w.gpre, (long)L.Cout * HW, h2, w.partial, G.f4_w, m4, L.Cout * 9, w.gh1, out, chw, w.partial + 2 * w.partial_floats,
-                                             G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, a0b, t4, t0, 2, 5, &rj.job[0], &rj.job[2], s));
-                } else if (vtaps) {
-                    { ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s); GH_TRY(launch_wgrad_mfma(w.gh1, (long)hid * HW, out, chw, w.partial + 2 * w.partial_floats, G.f0_w, N, HW, hid, n0,
-                                             hid, Ch * 9, 0, s, sh_grad_scale, a0b, &t0, &rj.job[2], 0, 0, 5)); }
-                } else {
-                    GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, n0, +1, s));
-                    { ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s); GH_TRY(launch_wgrad_mfma(w.gh1, (long)hid * HW, w.col, (long)n0 * HW, w.partial + 2 * w.partial_floats, G.f0_w, N, HW,
-                                             hid, n0, hid, Ch * 9, 0, s, sh_grad_scale, a0b, nullptr, &rj.job[2], 0, 0, 5)); }
+                    GH_TRY(launch_wgrad_pair(w.gpre, (long)L.Cout * HW, h2, part4, G.f4_w, m4, L.Cout * 9, w.gh1, out, chw, part0,
+                                             G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, A.b0, t4, t0, 2, 5, &rj.job[0], &rj.job[2], s));
+                    break;
+                }
+                case WgradRoute::taps:
+                case WgradRoute::expanded:
+                    GH_TRY(wgrad_f2());
+                    GH_TRY(wgrad_f0());
+                    break;
                 }
                 // (the three reductions ride in the mixer backward's launch below: k_chanmix_bwd_reduce)
-                if (G.f2_an_logs) p->logs_jobs.push_back(LogsJob{d.f2_w, G.f2_w, d.f2_an_bias, a2b, G.f2_an_logs, hid, hid});
-                if (G.f0_an_logs) p->logs_jobs.push_back(LogsJob{d.f0_w, G.f0_w, d.f0_an_bias, a0b, G.f0_an_logs, hid, Ch * 9});
-                ChanMixBwdArgs mb{xin, chw, g, g, chw, d.an_bias, at<float>(packed, L.an_scale),
-                                  d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
-                                  d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr, aW, aAb, aAl, N, d.C, HW};
-                mb.acc_copies = mcopies; mb.acc_stride = mstride;      // (C <= 96 here, tape_cnet: never the wide kernel)
+                ChanMixBwdArgs mb = chanmix_bwd_args(L, packed, N, xin, g, g, A);      // (C <= 96 here, tape_cnet: never the wide kernel)
                 mb.add_part = pend.scratch; mb.add_scale = 1.0f / sh_grad_scale; mb.add_C = Ch; mb.add_MS = pend.MS;
                 mb.add_tiles = pend.tiles; mb.add_R = pend.R; mb.add_NI = pend.NI; mb.add_lpxt = pend.lpxt; mb.add_H = d.H; mb.add_W = d.W;
                 GH_TRY(launch_chanmix_bwd(mb, s, &rj));
-                if (d.permutation == GLOWHIP_PERM_INVCONV) fin_w(li, L, G, aW, HW, mcopies, mstride);
-                fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
-                fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
-                fin(a0b, G.f0_an_bias, hid, 0.0);
-                fin(a2b, G.f2_an_bias, hid, 0.0);
-                fin(a4b, G.f4_bias, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout); fin(a4l, G.f4_logs, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout);
+                fin_step(li, L, G, A, true);
                 continue;
             }
-            // The per-layer kernels below read fp32: a tape written by the taping k_cnet holds h1 / h2 as fp16 -- converted into the
-            // partial-sum scratch (unused on this path), h2 first, h1 once h2 has been consumed.
             const bool half_tape = li < (int)p->tape_has_masks.size() && p->tape_has_masks[li];
-            if (half_tape) {
-                GH_TRY(launch_half_to_float(h2, w.gsh, N, hid, HW, s));
-                h2 = w.gsh;
-            }
+            const float wscale = train_sh_enabled(p) ? sh_grad_scale : 0.f;
+            GH_TRY(tape_to_f32(h2, half_tape, L, N, w, s));
             if (fastw) {   // dW4[o][i][tap] = sum_p g_pre[o][p - d(tap)] * h2[i][p]
                 const int m4 = round_up(L.Cout * 9, 128);
                 GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, m4, -1, s));
-                GH_TRY(launch_wgrad_mfma(w.col, (long)m4 * HW, h2, (long)hid * HW, w.partial, G.f4_w, N, HW, m4, hid,
-                                         L.Cout * 9, hid, 1, s, train_sh_enabled(p) ? sh_grad_scale : 0.f));
+                GH_TRY(launch_wgrad_mfma(w.col, (long)m4 * HW, h2, (long)hid * HW, w.partial, G.f4_w, N, HW, m4, hid, L.Cout * 9, hid, 1, s, wscale));
             } else {
                 GH_TRY(launch_wgrad_direct(w.gpre, h2, (long)hid * HW, G.f4_w, N, hid, d.H, d.W, L.Cout, 3, s));
             }
-            if (L.dg4_first) {
-                const float* wf = at<float>(packed, L.f4T_wf);
-                GH_TRY(launch_conv_mfma_first(w.gpre, (long)L.Cout * HW, wf, wf + (size_t)9 * L.Cout * hid, w.gh2, N, L.Cout,
-                                              d.H, d.W, hid, s, 0));
-            } else {
-                GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh2, N, hid, d.H, d.W, L.Cout, 3, s));
-            }
-            GH_TRY(launch_act_bwd(w.gh2, h2, at<float>(packed, L.f2_scale), N, hid, HW, a2b, a2l, s));
-            if (half_tape) {
-                GH_TRY(launch_half_to_float(h1, w.gsh, N, hid, HW, s));
-                h1 = w.gsh;
-            }
+            GH_TRY(dgrad_f4(L, packed, N, w, s));
+            GH_TRY(launch_act_bwd(w.gh2, h2, at<float>(packed, L.f2_scale), N, hid, HW, A.b2, A.l2, s));
+            GH_TRY(tape_to_f32(h1, half_tape, L, N, w, s));
             // (c) f.2 (1x1)
             if (fastw) {
-                GH_TRY(launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, w.partial, G.f2_w, N, HW, hid, hid, hid, hid,
-                                         0, s, train_sh_enabled(p) ? sh_grad_scale : 0.f));
+                GH_TRY(launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, w.partial, G.f2_w, N, HW, hid, hid, hid, hid, 0, s, wscale));
             } else {
                 GH_TRY(launch_wgrad_direct(w.gh2, h1, (long)hid * HW, G.f2_w, N, hid, d.H, d.W, hid, 1, s));
             }
-            if (L.mfma_mid) {   // W2 in its reference layout [o][i] is already the K-major image of the transposed GEMM
-                GH_TRY(launch_conv_mfma_wide(w.gh2, (long)hid * HW, d.f2_w, nullptr, nullptr, w.gh1, N, hid, d.H, d.W, hid, 1,
-                                             s, 0));
-            } else {
-                GH_TRY(dgrad_direct(w.gh2, d.f2_w, w.wT, w.gh1, N, hid, d.H, d.W, hid, 1, s));
-            }
-            GH_TRY(launch_act_bwd(w.gh1, h1, at<float>(packed, L.f0_scale), N, hid, HW, a0b, a0l, s));
+            GH_TRY(dgrad_f2(L, N, w, s));
+            GH_TRY(launch_act_bwd(w.gh1, h1, at<float>(packed, L.f0_scale), N, hid, HW, A.b0, A.l0, s));
             // (d) f.0: input is y1 = first half of the step output
             if (fastw) {   // dW0[o][i][tap] = sum_p g_u0[o][p] * y1[i][p + d(tap)]
                 const int n0 = round_up(Ch * 9, 64);
                 GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, n0, +1, s));
-                GH_TRY(launch_wgrad_mfma(w.gh1, (long)hid * HW, w.col, (long)n0 * HW, w.partial, G.f0_w, N, HW, hid, n0, hid,
-                                         Ch * 9, 0, s, train_sh_enabled(p) ? sh_grad_scale : 0.f));
+                GH_TRY(launch_wgrad_mfma(w.gh1, (long)hid * HW, w.col, (long)n0 * HW, w.partial, G.f0_w, N, HW, hid, n0, hid, Ch * 9, 0, s, wscale));
             } else {
                 GH_TRY(launch_wgrad_direct(w.gh1, out, chw, G.f0_w, N, Ch, d.H, d.W, hid, 3, s));
             }
-            if (L.dg0_tail) {   // g_y1 += conv(g_u0, flipT(W0)) fused: the tail kernel's additive-coupling epilogue
-                TailConvArgs t{};
-                t.x = w.gh1; t.x_bs = (long)hid * HW; t.wp = at<float>(packed, L.f0T_wp); t.bias = nullptr; t.scale = nullptr;
-                t.N = N; t.Cin = hid; t.H = d.H; t.W = d.W; t.Cout = Ch; t.mode = TAIL_ADD_FWD;
-                t.z2_in = g; t.z2_in_bs = chw; t.z2_out = g; t.z2_out_bs = chw; t.acc = nullptr;
-                t.zeros = at<float>(packed, 64); t.hout = nullptr;
-                GH_TRY(launch_conv_mfma_tail(t, s));
-            } else {
-                GH_TRY(dgrad_direct(w.gh1, d.f0_w, w.wT, w.gpre, N, Ch, d.H, d.W, hid, 3, s));   // gpre reused: (N,Ch,HW)
-                hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, g, chw, w.gpre,
-                                   (long)Ch * HW, (long)Ch * HW);
-                GH_LAUNCH_CHECK("k_add_inplace");
-            }
+            GH_TRY(dgrad_f0_add(L, packed, N, w, g, s));
             // (e) ActNorm + invconv / permutation: g (= g_y) -> g_x in place; wide levels (channel slices in separate workgroups, which
             // all read g_y) into the other gradient buffer
             const bool wide = chanmix_bwd_wide(d.C);
-            ChanMixBwdArgs mb{xin, chw, g, wide ? gnext : g, chw, d.an_bias, at<float>(packed, L.an_scale),
-                              d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr,
-                              d.permutation == GLOWHIP_PERM_GATHER ? d.perm_idx_inv : nullptr, aW, aAb, aAl, N, d.C, HW};
-            mb.acc_copies = mcopies; mb.acc_stride = mstride;
+            const ChanMixBwdArgs mb = chanmix_bwd_args(L, packed, N, xin, g, wide ? gnext : g, A);
             if (wide) count_launch(p, "k_chanmix_bwd_wide");
             GH_TRY(launch_chanmix_bwd(mb, s));
             if (wide) g = gnext;
             // (f) fp64 accumulators -> fp32 gradients (+ the log-det terms that do not depend on the data): queued,
             // converted by ONE launch after the sweep
-            if (d.permutation == GLOWHIP_PERM_INVCONV) fin_w(li, L, G, aW, HW, mcopies, mstride);
-            fin(aAb, G.an_bias, d.C, 0.0, nullptr, 0, mcopies, mstride);
-            fin(aAl, G.an_logs, d.C, 3.0 * HW, nullptr, 0, mcopies, mstride);
-            fin(a0b, G.f0_an_bias, hid, 0.0); fin(a0l, G.f0_an_logs, hid, 0.0);
-            fin(a2b, G.f2_an_bias, hid, 0.0); fin(a2l, G.f2_an_logs, hid, 0.0);
-            fin(a4b, G.f4_bias, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout); fin(a4l, G.f4_logs, L.Cout, 0.0, nullptr, 0, MIX_ACC_COPIES, 2 * L.Cout);
+            fin_step(li, L, G, A, false);
         } else {  // SPLIT2D: output z1 (N,Ch,HW); input x = (z1, z2)
             const float* hout = at<float>(tape, tl[li].hout);
             double* a4b = w.dacc + acc_base[li]; double* a4l = a4b + L.Cout;
@@ -623,10 +689,7 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                     GH_TRY(launch_wgrad_direct(w.gpre, xin, chw, G.f4_w, N, Ch, d.H, d.W, L.Cout, 3, s));
                 }
             }
-            GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh1, N, Ch, d.H, d.W, L.Cout, 3, s));     // (N,Ch,HW)
-            hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, gnext, chw, w.gh1,
-                               (long)Ch * HW, (long)Ch * HW);
-            GH_LAUNCH_CHECK("k_add_inplace");
+            GH_TRY(dgrad_direct_add(w.gpre, d.f4_w, w.wT, w.gh1, gnext, chw, N, Ch, d.H, d.W, L.Cout, s));
             fin(a4b, G.f4_bias, L.Cout, 0.0); fin(a4l, G.f4_logs, L.Cout, 0.0);
             g = gnext;
         }
@@ -653,23 +716,12 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
 
 // ---------------------------------------------------------------- decode VJP (glowhip_plan_decode_vjp)
 // workspace: acc u64 | norm words (2 N) | gA | gB | gh1 | gh2 | gpre | gsh | wT -- no accumulators of any kind
-struct VjpWs {
-    unsigned long long* acc; float* words;
-    float* gA; float* gB; float* gh1; float* gh2; float* gpre; float* gsh; float* wT;
-};
+struct VjpWs : GradBufs { float* words; };
 static size_t vjp_ws_layout(const glowhip_plan* p, int N, void* base, VjpWs* w) {
     size_t off = 0;
     const size_t o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA)), o_words = take(off, (size_t)N * 2 * 4);
-    const size_t o_gA = take(off, (size_t)N * p->max_chw * 4), o_gB = take(off, (size_t)N * p->max_chw * 4);
-    const size_t o_h1 = take(off, (size_t)N * p->max_hidden * 4), o_h2 = take(off, (size_t)N * p->max_hidden * 4);
-    const size_t o_gpre = take(off, (size_t)N * p->max_chw * 4);
-    const size_t o_gsh = take(off, (size_t)N * p->max_hidden * 4);
-    const size_t o_wT = take(off, max_weight_floats(p) * 4);
-    if (w && base) {
-        w->acc = at<unsigned long long>(base, o_acc); w->words = at<float>(base, o_words);
-        w->gA = at<float>(base, o_gA); w->gB = at<float>(base, o_gB); w->gh1 = at<float>(base, o_h1); w->gh2 = at<float>(base, o_h2);
-        w->gpre = at<float>(base, o_gpre); w->gsh = at<float>(base, o_gsh); w->wT = at<float>(base, o_wT);
-    }
+    carve_grad_bufs(p, N, off, o_acc, base, w);
+    if (w && base) w->words = at<float>(base, o_words);
     return align_up(off, 256);
 }
 
@@ -711,10 +763,8 @@ static int decode_vjp_sweep(glowhip_plan* p, const void* packed, const float* x_
             GH_TRY(launch_squeeze(g, nullptr, gnext, N, d.C, d.H, d.W, 2, 0, s));
             g = gnext;
         } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
-            const float* out = at<float>(tape, tl[li].out);
-            const float* h1 = at<float>(tape, tl[li].h1);
-            const float* h2 = at<float>(tape, tl[li].h2);
-            const float* hout = at<float>(tape, tl[li].hout);
+            const StepTape T = step_tape(tape, tl[li]);
+            const float* h1 = T.h1; const float* h2 = T.h2;
             const int affine = d.coupling == GLOWHIP_COUPLING_AFFINE;
             // (a) mixer^-1: g (= g_x) -> g_u = (g_y1 without the coupling network's term, g_y2), into the other buffer
             ChanMixInvBwdArgs mb{};
@@ -730,67 +780,25 @@ static int decode_vjp_sweep(glowhip_plan* p, const void* packed, const float* x_
             GH_TRY(launch_chanmix_inv_bwd(mb, s));
             g = gnext;
             // (b) coupling tail^-1: g's second half g_y2 -> g_z2' in place; gpre = gradient of f.4's (conv + bias)
-            CouplingInvBwdArgs cb{hout, out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, w.gpre, at<float>(packed, L.f4_scale),
+            CouplingInvBwdArgs cb{T.hout, T.out + (long)Ch * HW, chw, g + (long)Ch * HW, chw, w.gpre, at<float>(packed, L.f4_scale),
                                   N, Ch, L.Cout, HW, affine};
             GH_TRY(launch_coupling_inv_bwd(cb, s));
             // (c) g_y1 += f'(y1)^T g_pre
             if (wgrad_fast(L) && bwd_cnet_chain(p, L, li, N, (size_t)N * p->max_hidden)) {
-                CnetArgs c{};
-                c.w0 = at<char>(packed, L.cb_w0); c.w2 = at<char>(packed, L.cb_w2); c.w4 = at<char>(packed, L.cb_w4);
-                c.N = N; c.Cin = L.Cout; c.H = d.H; c.W = d.W; c.hidden = hid; c.Cout = Ch;
-                c.scratch = w.gsh; c.mode = TAIL_ADD_FWD;
-                c.x = w.gpre; c.x_bs = (long)L.Cout * HW; c.z_in = w.gpre; c.z_in_bs = (long)L.Cout * HW;
-                c.tape_h1 = w.gh2; c.tape_h2 = w.gh1;      // (g_u2 / g_u0: stored by the instance, read by nobody here)
-                c.mask1 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m1));
-                c.mask2 = const_cast<unsigned short*>(at<unsigned short>(tape, tl[li].m2));
-                // the gradients are normalised per sample (max |dL/dx| in [1, 2)): no further pre-scale
-                c.in_scale = SH2_ACT_SCALE; c.out_scale = SH2_ACT_INV * SH_LO_SCALE; c.bwd = 1;
-                pend = CnetPending{};
-                count_launch(p, "k_cnet(bwd)");
-                {
-                    ScopedTimer t(p, GLOWHIP_K_CNET_BWD, 1, s);
-                    GH_TRY(launch_cnet_main(c, s, &pend));
-                }
-                if (pend.one_wave) count_launch(p, "k_cnet1w(bwd)");
+                // the gradients are normalised per sample (max |dL/dx| in [1, 2)): no further pre-scale.  (g_u2 / g_u0: stored by the
+                // instance, read by nobody here)
+                GH_TRY(launch_cnet_bwd(p, L, packed, N, T, w, 1.0f, &pend, s));
                 pending = true; pend_C = Ch; pend_H = d.H; pend_W = d.W;
                 continue;
             }
             const bool half_tape = li < (int)p->tape_has_masks.size() && p->tape_has_masks[li];
-            if (half_tape) {
-                GH_TRY(launch_half_to_float(h2, w.gsh, N, hid, HW, s));
-                h2 = w.gsh;
-            }
-            if (L.dg4_first) {
-                const float* wf = at<float>(packed, L.f4T_wf);
-                GH_TRY(launch_conv_mfma_first(w.gpre, (long)L.Cout * HW, wf, wf + (size_t)9 * L.Cout * hid, w.gh2, N, L.Cout,
-                                              d.H, d.W, hid, s, 0));
-            } else {
-                GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh2, N, hid, d.H, d.W, L.Cout, 3, s));
-            }
+            GH_TRY(tape_to_f32(h2, half_tape, L, N, w, s));
+            GH_TRY(dgrad_f4(L, packed, N, w, s));
             GH_TRY(launch_relu_bwd(w.gh2, h2, at<float>(packed, L.f2_scale), N, hid, HW, s));
-            if (half_tape) {
-                GH_TRY(launch_half_to_float(h1, w.gsh, N, hid, HW, s));
-                h1 = w.gsh;
-            }
-            if (L.mfma_mid) {
-                GH_TRY(launch_conv_mfma_wide(w.gh2, (long)hid * HW, d.f2_w, nullptr, nullptr, w.gh1, N, hid, d.H, d.W, hid, 1, s, 0));
-            } else {
-                GH_TRY(dgrad_direct(w.gh2, d.f2_w, w.wT, w.gh1, N, hid, d.H, d.W, hid, 1, s));
-            }
+            GH_TRY(tape_to_f32(h1, half_tape, L, N, w, s));
+            GH_TRY(dgrad_f2(L, N, w, s));
             GH_TRY(launch_relu_bwd(w.gh1, h1, at<float>(packed, L.f0_scale), N, hid, HW, s));
-            if (L.dg0_tail) {
-                TailConvArgs t{};
-                t.x = w.gh1; t.x_bs = (long)hid * HW; t.wp = at<float>(packed, L.f0T_wp); t.bias = nullptr; t.scale = nullptr;
-                t.N = N; t.Cin = hid; t.H = d.H; t.W = d.W; t.Cout = Ch; t.mode = TAIL_ADD_FWD;
-                t.z2_in = g; t.z2_in_bs = chw; t.z2_out = g; t.z2_out_bs = chw; t.acc = nullptr;
-                t.zeros = at<float>(packed, 64); t.hout = nullptr;
-                GH_TRY(launch_conv_mfma_tail(t, s));
-            } else {
-                GH_TRY(dgrad_direct(w.gh1, d.f0_w, w.wT, w.gpre, N, Ch, d.H, d.W, hid, 3, s));   // gpre reused: (N,Ch,HW)
-                hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, g, chw, w.gpre,
-                                   (long)Ch * HW, (long)Ch * HW);
-                GH_LAUNCH_CHECK("k_add_inplace");
-            }
+            GH_TRY(dgrad_f0_add(L, packed, N, w, g, s));
         } else {  // SPLIT2D: input gradient (g_z1, g_z2) (N,C,HW) -> g_z1 + conv(g_pre, flipT(w)) (N,Ch,HW); g_eps to the caller
             GH_TRY(finish_pending(chw));
             const float* hout = at<float>(tape, tl[li].hout);
@@ -800,9 +808,7 @@ static int decode_vjp_sweep(glowhip_plan* p, const void* packed, const float* x_
             GH_TRY(launch_split_inv_bwd(sb, s));
             GH_TRY(dgrad_direct(w.gpre, d.f4_w, w.wT, w.gh1, N, Ch, d.H, d.W, L.Cout, 3, s));     // (N,Ch,HW)
             GH_TRY(launch_copy_strided(g, chw, gnext, (long)Ch * HW, N, (long)Ch * HW, s));
-            hipLaunchKernelGGL(k_add_inplace, dim3(cdiv((long)Ch * HW, 256), N), dim3(256), 0, s, gnext, (long)Ch * HW, w.gh1,
-                               (long)Ch * HW, (long)Ch * HW);
-            GH_LAUNCH_CHECK("k_add_inplace");
+            GH_TRY(add_rows(gnext, (long)Ch * HW, w.gh1, N, (long)Ch * HW, s));
             g = gnext;
         }
     }
