@@ -11,7 +11,7 @@ struct DebugSwitches {
     int tail_tile = 0;               // pixels per workgroup: 0 automatic (cost model), else 16 / 32 / 64 / 128
     int tail_msplit = -1;            // out-channel tiles over blockIdx.y: -1 automatic, 0 never, 1 always
     bool tail_no_dma = false;        // register-staged tail kernels only
-    // ---- executor (plan.hip, plan_train.hip)
+    // ---- executor and pack (plan.hip, plan_train.hip; the pack switches: plan_build.hip)
     bool exact_fp32 = false;         // the split-half path off: every coupling network on the exact-fp32 MFMA kernels, training included
     bool no_mixer_fusion = false;    // no mixer of the next step inside the finishing kernel, no squeeze folded into a mixer
     // FUSED FINISHING (k_cnet1w finishing the step itself, cnet1w_sh.hip FIN) is OFF unless asked for: built, bit-identical to the

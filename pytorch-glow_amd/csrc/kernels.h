@@ -100,7 +100,10 @@ struct RepackJob {
     int Cin, Cout, K, Kpad;      // wide: K = Cin*k*k
     int paired, MT; long total;  // tail
     const float* fold_bias; const float* fold_logs;  // first: ActNorm folded into the image (NULL: plain weights)
-    int use;                     // who reads this image: bit 0 = inference kernels (encode/decode/glow_forward), bit 1 = training
+    int use;                     // who reads this image, bits of a pack's use mask: GLOWHIP_PACK_INFERENCE (1: encode / decode /
+                                 // glow_forward), _TRAINING (2), _INVERSE (4: the deep levels' W^-1 images) and, plan_internal.h,
+                                 // PACK_EXACT_FP32 (8: the inference calls under the family switches), PACK_INIT_F0 (16: the init pass);
+                                 // PACK_NO_LU (32) is a bit of the mask only: no job carries it
     int transposed;              // source is the FORWARD weight (Cin,Cout,3,3) of which this is the input-gradient conv:
                                  // element (o, ci, tap) = w[ci][o][8 - tap]
     size_t w_off;                // w == nullptr: the source is packed + w_off (a transposed copy made by launch_flipT_batched, or W^-1)

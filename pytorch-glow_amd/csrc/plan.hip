@@ -4,10 +4,10 @@
 // replayed; all scratch comes from a caller-provided workspace, all parameter-derived data (exp(3 logs),
 // K-major MFMA weight images, W^-1, log|det W|) from a caller-provided `packed` buffer refreshed by
 // glowhip_plan_pack.
+// Here: the workspace carving, the inference executor (run_forward / run_reverse), the encode / decode / glow_forward / actnorm_init /
+// status entries, the describe / launch-count / timing / dequantisation calls and k_pack_scales (the init pass').  Plan construction and the pack: plan_build.hip.
 #include <math.h>
 #include <stdio.h>
-#include <string>
-#include <vector>
 
 #include "plan_internal.h"
 
@@ -535,258 +535,36 @@ static int check_plan_args(const glowhip_plan* plan, const void* packed, int N) 
     GH_REQUIRE(N >= 0 && N <= 65535, "batch size %d out of range", N);
     return GLOWHIP_OK;
 }
+// the workspace of a call on N samples, its log-det accumulators and finishing counters zeroed
+static int open_workspace(const glowhip_plan* p, int N, void* ws, size_t bytes, Workspace& w, hipStream_t s) {
+    GH_TRY(carve(p, N, ws, bytes, w));
+    return launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(p, N));
+}
+
+// Glow.normal_flow behind glowhip_glow_forward (x) and glowhip_glow_forward_u8 (x_u8 / divisor: 8-bit pixels, SURVEY.md 8f N4 --
+// the leading Squeeze2d reads the bytes itself, and the executor starts from bufA: the ping-pong parity of the workspace buffers
+// differs between the two)
+static int glow_forward(glowhip_plan* plan, const void* packed, const float* x, const uint8_t* x_u8, float divisor, const float* noise,
+                        const float* prior_mean, const float* prior_logs, long prior_stride, int n_bits, float* z, float* nll_out,
+                        float* objective_out, int N, void* workspace, size_t workspace_bytes, hipStream_t s) {
+    Workspace w;
+    GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
+    RngSpec rng{plan->rng_on && !noise, plan->rng_seed, plan->rng_calls, (float)(1.0 / pow(2.0, n_bits))};
+    if (rng.on) ++plan->rng_calls;
+    GH_TRY(run_forward(plan, packed, x_u8 ? w.bufA : x, noise, z, N, w, s, 0, rng.on ? &rng : nullptr, x_u8, divisor));
+    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
+    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // the sum of the log|det W| terms enters here
+    // objective = -ln(n_bins)*CHW + logdet + logp;  nll = -objective / (ln2 * CHW)   (network/model.py:425-450)
+    const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
+    const double offset = -log(pow(2.0, n_bits)) * chw;
+    const double scale = -1.0 / (log(2.0) * chw);
+    return launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, offset, scale, nll_out, objective_out, N, s, ACC_EXTRA);
+}
 
 }  // namespace glowhip
 
 // ================================================================================================ C ABI
 extern "C" {
-
-glowhip_plan* glowhip_plan_create(const glowhip_layer_desc* layers, int n_layers) {
-    if (!layers || n_layers <= 0) {
-        set_error("plan_create: empty layer list");
-        return nullptr;
-    }
-    glowhip_plan* p = new glowhip_plan();
-    size_t off = 0;
-    take(off, 256);  // offset 0: plan-wide data-independent log-det total (fp64); offset 64..127: zero block for LDS-DMA padding
-    int C = layers[0].C, H = layers[0].H, W = layers[0].W;
-    p->in_shape[0] = C; p->in_shape[1] = H; p->in_shape[2] = W;
-    for (int i = 0; i < n_layers; ++i) {
-        LayerPlan L;
-        L.d = layers[i];
-        const glowhip_layer_desc& d = L.d;
-        auto fail = [&](const char* why) {
-            set_error("plan_create: layer %d: %s (kind=%d C=%d H=%d W=%d)", i, why, d.kind, d.C, d.H, d.W);
-            delete p;
-            return (glowhip_plan*)nullptr;
-        };
-        if (d.C != C || d.H != H || d.W != W) return fail("input shape does not chain from the previous layer");
-        if (d.C <= 0 || d.H <= 0 || d.W <= 0) return fail("empty shape");
-        p->max_chw = std::max(p->max_chw, (long)C * H * W);
-        if (d.kind == GLOWHIP_LAYER_SQUEEZE) {
-            if (H % 2 || W % 2) return fail("squeeze needs even H and W");
-            C *= 4; H /= 2; W /= 2;
-        } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
-            if (C % 2) return fail("FlowStep needs an even channel count");  // network/model.py:169
-            if (d.hidden <= 0) return fail("hidden_channels must be positive");
-            if (!d.an_bias || !d.an_logs || !d.f0_w || !d.f0_an_bias || !d.f0_an_logs || !d.f2_w || !d.f2_an_bias ||
-                !d.f2_an_logs || !d.f4_w || !d.f4_bias || !d.f4_logs)
-                return fail("missing parameter pointer");
-            if (d.permutation == GLOWHIP_PERM_INVCONV) {
-                if (!d.invconv_w) return fail("missing invconv weight");
-            } else if (d.permutation == GLOWHIP_PERM_GATHER) {
-                if (!d.perm_idx || !d.perm_idx_inv) return fail("missing permutation tables");
-            } else return fail("unknown permutation");
-            if (d.coupling != GLOWHIP_COUPLING_ADDITIVE && d.coupling != GLOWHIP_COUPLING_AFFINE)
-                return fail("unknown coupling");
-            L.Cout = d.coupling == GLOWHIP_COUPLING_AFFINE ? C : C / 2;
-            L.an_scale = take(off, (size_t)C * 4);
-            L.an_inv_scale = take(off, (size_t)C * 4);
-            L.winv = take(off, (size_t)C * C * 4);
-            L.logabsdet = take(off, 4);
-            L.konst = take(off, 8);
-            L.lu_scratch = take(off, invconv_scratch_bytes(C));
-            L.f0_scale = take(off, (size_t)d.hidden * 4);
-            L.f2_scale = take(off, (size_t)d.hidden * 4);
-            L.f4_scale = take(off, (size_t)L.Cout * 4);
-            L.mfma_first = conv_mfma_wide_supported(C / 2, H, W, d.hidden, 3);
-            L.mfma_mid = conv_mfma_wide_supported(d.hidden, H, W, d.hidden, 1);
-            L.mfma_last = conv_mfma_tail_supported(d.hidden, H, W, L.Cout);
-            L.first_halo = conv_mfma_first_supported(C / 2, H, W, d.hidden);
-            if (L.first_halo) L.f0_wt = take(off, conv_mfma_first_packed_bytes(C / 2, d.hidden));
-            else if (L.mfma_first) L.f0_wt = take(off, conv_mfma_wide_packed_bytes(C / 2, d.hidden, 3));
-            if (L.mfma_mid) L.f2_wt = take(off, conv_mfma_wide_packed_bytes(d.hidden, d.hidden, 1));
-            if (L.first_halo && L.mfma_first) L.f0_init = take(off, conv_mfma_wide_packed_bytes(C / 2, d.hidden, 3));
-            else if (L.mfma_first) L.f0_init = L.f0_wt;      // already the plain K-major image
-            L.cnet = cnet_supported(C / 2, H, W, d.hidden, L.Cout);
-            if (L.cnet) {
-                L.cn_w0 = take(off, sh2_image_bytes(cnet_g0(C / 2) * 8, d.hidden));
-                L.cn_w2 = take(off, sh2_image_bytes(d.hidden, d.hidden));
-                L.cn_w4 = take(off, cnet_w4_bytes(d.hidden, L.Cout));
-                p->max_hidden = std::max(p->max_hidden, (long)cnet_scratch_floats_per_sample(H, W, L.Cout));
-                // the input-gradient chain on the same kernel: f.4^T is its first layer (Cin = Cout), f.0^T its last (Cout = C / 2)
-                L.cnet_bwd = d.hidden <= 512 && cnet_groups(C / 2) == 1 && cnet_supported(L.Cout, H, W, d.hidden, C / 2);
-                if (L.cnet_bwd) {
-                    L.cb_w0 = take(off, sh2_image_bytes(cnet_g0(L.Cout) * 8, d.hidden));
-                    L.cb_w2 = take(off, sh2_image_bytes(d.hidden, d.hidden));
-                    L.cb_w4 = take(off, cnet_w4_bytes(d.hidden, C / 2));
-                    L.wt4 = take(off, (size_t)L.Cout * d.hidden * 9 * 4);
-                    L.wt2 = take(off, (size_t)d.hidden * d.hidden * 4);
-                    L.wt0 = take(off, (size_t)d.hidden * (C / 2) * 9 * 4);
-                }
-            }
-            L.dnet = !L.cnet && d.permutation == GLOWHIP_PERM_INVCONV && dnet_supported(C, H, W, d.hidden, L.Cout);
-            if (L.dnet) {
-                L.dn_mix = take(off, sh2_image_bytes(C, C));
-                L.dn_mixinv = take(off, sh2_image_bytes(C, C));
-                L.dn_w0 = take(off, sh2_image_bytes(cnet_g0(C / 2) * 8, d.hidden));
-                L.dn_w2 = take(off, sh2_image_bytes(d.hidden, d.hidden));
-                L.dn_w4 = take(off, sh2_image_bytes(cnet_g0(d.hidden) * 8, L.Cout));
-                p->max_hidden = std::max(p->max_hidden, (long)((dnet_scratch_bytes_per_sample(C, H, W, d.hidden, L.Cout) + 3) / 4));
-            }
-            if (L.mfma_last) L.f4_wp = take(off, conv_mfma_tail_packed_bytes(d.hidden, L.Cout));
-            L.wide_last = !L.mfma_last && conv_mfma_wide_supported(d.hidden, H, W, L.Cout, 3);
-            if (L.wide_last) L.f4_wt = take(off, conv_mfma_wide_packed_bytes(d.hidden, L.Cout, 3));
-            L.dg4_first = conv_mfma_first_supported(L.Cout, H, W, d.hidden);
-            if (L.dg4_first) L.f4T_wf = take(off, conv_mfma_first_packed_bytes(L.Cout, d.hidden));
-            L.dg0_tail = conv_mfma_tail_supported(d.hidden, H, W, C / 2);
-            if (L.dg0_tail) L.f0T_wp = take(off, conv_mfma_tail_packed_bytes(d.hidden, C / 2));
-            p->max_hidden = std::max(p->max_hidden, (long)std::max(d.hidden, L.Cout) * H * W);
-        } else if (d.kind == GLOWHIP_LAYER_SPLIT2D) {
-            if (C % 2) return fail("Split2d needs an even channel count");
-            if (!d.f4_w || !d.f4_bias || !d.f4_logs) return fail("missing conv2d_zeros parameter pointer");
-            L.Cout = C;
-            L.f4_scale = take(off, (size_t)C * 4);
-            L.mfma_last = conv_mfma_tail_supported(C / 2, H, W, C);
-            if (L.mfma_last) L.f4_wp = take(off, conv_mfma_tail_packed_bytes(C / 2, C));
-            p->max_hidden = std::max(p->max_hidden, (long)C * H * W);
-            L.split_idx = p->n_split++;
-            C /= 2;
-        } else {
-            return fail("unknown layer kind");
-        }
-        p->max_chw = std::max(p->max_chw, (long)C * H * W);
-        p->layers.push_back(L);
-    }
-    p->out_shape[0] = C; p->out_shape[1] = H; p->out_shape[2] = W;
-    // job tables of the batched pack
-    for (const LayerPlan& L : p->layers) {
-        const glowhip_layer_desc& d = L.d;
-        if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
-            StepPrepJob j{};
-            j.w = d.permutation == GLOWHIP_PERM_INVCONV ? d.invconv_w : nullptr;
-            j.an_logs = d.an_logs; j.C = d.C; j.HW = d.H * d.W;
-            j.winv_off = L.winv; j.logabsdet_off = L.logabsdet; j.konst_off = L.konst; j.scratch_off = L.lu_scratch;
-            p->prep_jobs.push_back(j);
-            if (j.w && d.C <= 64) p->max_lds_c = std::max(p->max_lds_c, d.C);
-            if (j.w) p->max_c = std::max(p->max_c, d.C);
-            p->scale_jobs.push_back(ScaleJob{d.an_logs, L.an_scale, L.an_inv_scale, d.C, 1});
-            p->scale_jobs.push_back(ScaleJob{d.f0_an_logs, L.f0_scale, 0, d.hidden, 0});
-            p->scale_jobs.push_back(ScaleJob{d.f2_an_logs, L.f2_scale, 0, d.hidden, 0});
-            p->scale_jobs.push_back(ScaleJob{d.f4_logs, L.f4_scale, 0, L.Cout, 0});
-            // inference-use bit of the exact-fp32 images: layers that run k_cnet or the deep-level kernels read them only under the
-            // family switches (bit 8)
-            const int inf = (L.cnet || L.dnet) ? 8 : 1;
-            if (L.first_halo) {
-                RepackJob r{}; r.w = d.f0_w; r.out_off = L.f0_wt; r.kind = REPACK_FIRST; r.Cin = d.C / 2; r.Cout = d.hidden;
-                r.fold_bias = d.f0_an_bias; r.fold_logs = d.f0_an_logs; r.use = 2 | inf;
-                p->repack_jobs.push_back(r);
-            } else if (L.mfma_first) {
-                RepackJob r{}; r.w = d.f0_w; r.out_off = L.f0_wt; r.kind = REPACK_WIDE; r.Cin = d.C / 2; r.Cout = d.hidden;
-                r.K = r.Cin * 9; r.Kpad = wide_kpad(r.Cin, 3); r.use = 2 | inf; p->repack_jobs.push_back(r);
-            }
-            if (L.first_halo && L.f0_init) {   // use bit 16 (internal): read by the data-dependent init pass only
-                RepackJob r{}; r.w = d.f0_w; r.out_off = L.f0_init; r.kind = REPACK_WIDE; r.Cin = d.C / 2; r.Cout = d.hidden;
-                r.K = r.Cin * 9; r.Kpad = wide_kpad(r.Cin, 3); r.use = 16; p->repack_jobs.push_back(r);
-            }
-            if (L.mfma_mid) {
-                RepackJob r{}; r.w = d.f2_w; r.out_off = L.f2_wt; r.kind = REPACK_WIDE; r.Cin = d.hidden; r.Cout = d.hidden;
-                r.K = r.Cin; r.Kpad = wide_kpad(r.Cin, 1); r.use = 2 | inf; p->repack_jobs.push_back(r);
-            }
-            if (L.cnet) {
-                RepackJob r0{}; r0.w = d.f0_w; r0.out_off = L.cn_w0; r0.kind = REPACK_SH2_FIRST; r0.Cin = d.C / 2; r0.Cout = d.hidden;
-                r0.K = cnet_g0(d.C / 2); r0.fold_bias = d.f0_an_bias; r0.fold_logs = d.f0_an_logs; r0.use = 3;
-                p->repack_jobs.push_back(r0);
-                RepackJob r2{}; r2.kperm = 1; r2.w = d.f2_w; r2.out_off = L.cn_w2; r2.kind = REPACK_SH2_GEMM; r2.Cin = d.hidden; r2.Cout = d.hidden;
-                r2.K = d.hidden; r2.fold_bias = d.f2_an_bias; r2.fold_logs = d.f2_an_logs; r2.use = 3; p->repack_jobs.push_back(r2);
-                const int ng = cnet_groups(L.Cout), cg = L.Cout / ng;       // one image per group of f.4 output channels
-                for (int gi = 0; gi < ng; ++gi) {
-                    RepackJob r4{}; r4.w = d.f4_w + (size_t)gi * cg * d.hidden * 9; r4.out_off = L.cn_w4 + gi * sh2_image_bytes(d.hidden, cnet_mpad4(cg));
-                    r4.kind = REPACK_SH2_TAIL; r4.kperm = 1; r4.Cin = d.hidden; r4.Cout = cg;
-                    r4.Kpad = cnet_mpad4(cg); r4.use = 3; p->repack_jobs.push_back(r4);
-                }
-            }
-            if (L.dnet) {      // deep levels: the mixer as a GEMM image (W; W^-1 after the LU), f.0 / f.4 as (chunk, tap) images, f.2
-                RepackJob rm{}; rm.w = d.invconv_w; rm.out_off = L.dn_mix; rm.kind = REPACK_SH2_GEMM; rm.Cin = d.C; rm.Cout = d.C; rm.K = d.C; rm.use = 1;
-                p->repack_jobs.push_back(rm);
-                RepackJob ri{}; ri.w = nullptr; ri.w_off = L.winv; ri.out_off = L.dn_mixinv; ri.kind = REPACK_SH2_GEMM; ri.Cin = d.C; ri.Cout = d.C;
-                ri.K = d.C; ri.use = 4; ri.after_lu = 1; p->repack_jobs.push_back(ri);
-                RepackJob r0{}; r0.w = d.f0_w; r0.out_off = L.dn_w0; r0.kind = REPACK_SH2_FIRST; r0.Cin = d.C / 2; r0.Cout = d.hidden;
-                r0.K = cnet_g0(d.C / 2); r0.fold_bias = d.f0_an_bias; r0.fold_logs = d.f0_an_logs; r0.use = 1; p->repack_jobs.push_back(r0);
-                RepackJob r2{}; r2.w = d.f2_w; r2.out_off = L.dn_w2; r2.kind = REPACK_SH2_GEMM; r2.Cin = d.hidden; r2.Cout = d.hidden;
-                r2.K = d.hidden; r2.fold_bias = d.f2_an_bias; r2.fold_logs = d.f2_an_logs; r2.use = 1; p->repack_jobs.push_back(r2);
-                RepackJob r4{}; r4.w = d.f4_w; r4.out_off = L.dn_w4; r4.kind = REPACK_SH2_FIRST; r4.Cin = d.hidden; r4.Cout = L.Cout;
-                r4.K = cnet_g0(d.hidden); r4.use = 1; p->repack_jobs.push_back(r4);
-            }
-            if (L.cnet_bwd) {      // (training only) transposed copies, then the same three image kinds over them
-                const int Ch = d.C / 2;
-                p->flip_jobs.push_back(FlipJob{d.f4_w, L.wt4, L.Cout, d.hidden, 9});     // wt4[k][co][8 - tap] = W4[co][k][tap]
-                p->flip_jobs.push_back(FlipJob{d.f2_w, L.wt2, d.hidden, d.hidden, 1});   // wt2[i][o] = W2[o][i]
-                p->flip_jobs.push_back(FlipJob{d.f0_w, L.wt0, d.hidden, Ch, 9});         // wt0[ci][k][8 - tap] = W0[k][ci][tap]
-                const int th = (d.hidden + 31) / 32;
-                p->flip_tiles[0] = std::max(p->flip_tiles[0], th * ((L.Cout + 31) / 32));
-                p->flip_tiles[1] = std::max(p->flip_tiles[1], th * th);
-                p->flip_tiles[2] = std::max(p->flip_tiles[2], th * ((Ch + 31) / 32));
-                RepackJob r0{}; r0.w = nullptr; r0.w_off = L.wt4; r0.out_off = L.cb_w0; r0.kind = REPACK_SH2_FIRST; r0.Cin = L.Cout; r0.Cout = d.hidden;
-                r0.K = cnet_g0(L.Cout); r0.fold_bias = nullptr; r0.fold_logs = d.f2_an_logs; r0.use = 2;      // g_u2 = g_h2 (h2 > 0) exp(3 logs2)
-                p->repack_jobs.push_back(r0);
-                RepackJob r2{}; r2.kperm = 1; r2.w = nullptr; r2.w_off = L.wt2; r2.out_off = L.cb_w2; r2.kind = REPACK_SH2_GEMM; r2.Cin = d.hidden; r2.Cout = d.hidden;
-                r2.K = d.hidden; r2.fold_bias = nullptr; r2.fold_logs = d.f0_an_logs; r2.use = 2; p->repack_jobs.push_back(r2);
-                RepackJob r4{}; r4.kperm = 1; r4.w = nullptr; r4.w_off = L.wt0; r4.out_off = L.cb_w4; r4.kind = REPACK_SH2_TAIL; r4.Cin = d.hidden; r4.Cout = Ch;
-                r4.Kpad = cnet_mpad4(Ch); r4.use = 2; p->repack_jobs.push_back(r4);
-            }
-            if (L.mfma_last) {
-                RepackJob r{}; r.w = d.f4_w; r.out_off = L.f4_wp; r.kind = REPACK_TAIL; r.Cin = d.hidden; r.Cout = L.Cout;
-                r.paired = d.coupling == GLOWHIP_COUPLING_AFFINE; r.MT = tail_mt(L.Cout, r.paired);
-                r.use = 2 | inf;
-                r.total = (long)tail_chunks(r.Cin) * (TAIL_CK / 4) * 9 * r.MT * 64; p->repack_jobs.push_back(r);
-            }
-            if (L.wide_last) {
-                RepackJob r{}; r.w = d.f4_w; r.out_off = L.f4_wt; r.kind = REPACK_WIDE; r.Cin = d.hidden; r.Cout = L.Cout;
-                r.K = r.Cin * 9; r.Kpad = wide_kpad(r.Cin, 3); r.use = 2 | inf; p->repack_jobs.push_back(r);
-            }
-            if (L.dg4_first) {   // input gradient of f.4 = 3x3 conv Cout -> hidden with w[ci][o][8-tap]
-                RepackJob r{}; r.w = d.f4_w; r.out_off = L.f4T_wf; r.kind = REPACK_FIRST; r.Cin = L.Cout; r.Cout = d.hidden;
-                r.transposed = 1; r.use = 2; p->repack_jobs.push_back(r);
-            }
-            if (L.dg0_tail) {    // input gradient of f.0 = 3x3 conv hidden -> C/2
-                RepackJob r{}; r.w = d.f0_w; r.out_off = L.f0T_wp; r.kind = REPACK_TAIL; r.Cin = d.hidden; r.Cout = d.C / 2;
-                r.paired = 0; r.MT = tail_mt(r.Cout, 0); r.transposed = 1; r.use = 2;
-                r.total = (long)tail_chunks(r.Cin) * (TAIL_CK / 4) * 9 * r.MT * 64; p->repack_jobs.push_back(r);
-            }
-        } else if (d.kind == GLOWHIP_LAYER_SPLIT2D) {
-            p->scale_jobs.push_back(ScaleJob{d.f4_logs, L.f4_scale, 0, L.Cout, 0});
-            if (L.mfma_last) {
-                RepackJob r{}; r.w = d.f4_w; r.out_off = L.f4_wp; r.kind = REPACK_TAIL; r.Cin = d.C / 2; r.Cout = L.Cout;
-                r.paired = 1; r.MT = tail_mt(L.Cout, 1); r.use = 3;
-                r.total = (long)tail_chunks(r.Cin) * (TAIL_CK / 4) * 9 * r.MT * 64; p->repack_jobs.push_back(r);
-            }
-        }
-    }
-    p->prep_off = take(off, p->prep_jobs.size() * sizeof(StepPrepJob));
-    p->scale_off = take(off, p->scale_jobs.size() * sizeof(ScaleJob));
-    // one slot of selected repack jobs per combination of the use bits that select images (1, 2, 8, 16): a pack of one mask never
-    // rewrites the table a captured graph of another mask launches over
-    p->repack_off = take(off, REPACK_SLOTS * p->repack_jobs.size() * sizeof(RepackJob));
-    p->flip_off = take(off, p->flip_jobs.size() * sizeof(FlipJob));
-    {   // room for the LU-form job table (glowhip_plan_bind_invconv_lu comes after the caller sized `packed`): one per invconv FlowStep
-        size_t n_inv = 0;
-        for (const StepPrepJob& pj : p->prep_jobs) n_inv += pj.w ? 1 : 0;
-        p->lu_off = take(off, n_inv * sizeof(LuJob));
-    }
-    {   // the one-launch forward pack's table (k_pack_fused): an arrival counter, then at most one PackSeg per block of every job
-        size_t nseg = (p->prep_jobs.size() + 3) / 4 + 1;
-        for (const RepackJob& r : p->repack_jobs)
-            nseg += pack_fused_job_blocks(r.kind < REPACK_SH2_GEMM ? PACKSEG_LEGACY : PACKSEG_SH2_GEMM + (r.kind - REPACK_SH2_GEMM), &r, nullptr);
-        for (const ScaleJob& sj : p->scale_jobs) nseg += pack_fused_job_blocks(PACKSEG_SCALE, nullptr, &sj);
-        p->seg_cap = nseg;
-        p->seg_off = take(off, PACK_SEG_HEAD + nseg * sizeof(PackSeg));
-    }
-    p->packed_bytes = align_up(off, 256);
-    return p;
-}
-
-void glowhip_plan_destroy(glowhip_plan* plan) {
-    if (!plan) return;
-    if (plan->side) {      // (the side stream may still be writing into the caller's `packed` buffer)
-        (void)hipStreamSynchronize(plan->side);
-        (void)hipEventDestroy(plan->ev_fork); (void)hipEventDestroy(plan->ev_legacy); (void)hipEventDestroy(plan->ev_lu);
-        (void)hipStreamDestroy(plan->side);
-    }
-    for (hipEvent_t e : plan->ev_pool) (void)hipEventDestroy(e);
-    for (TimingSlot& t : plan->ev_used) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); }
-    delete plan;
-}
 
 int glowhip_plan_timing_enable(glowhip_plan* plan, int enable) {
     GH_REQUIRE(plan, "plan_timing_enable: null plan");
@@ -815,8 +593,6 @@ int glowhip_plan_timing_read(glowhip_plan* plan, glowhip_timing_record* out, int
     *n_out = n;
     return GLOWHIP_OK;
 }
-
-size_t glowhip_plan_packed_bytes(const glowhip_plan* plan) { return plan ? plan->packed_bytes : 0; }
 
 size_t glowhip_plan_workspace_bytes(const glowhip_plan* plan, int N) {
     return (plan && N >= 0) ? ws_layout(plan, N, nullptr, nullptr) : 0;
@@ -895,233 +671,6 @@ int glowhip_plan_describe_for(const glowhip_plan* plan, int N, char* buf, size_t
     return GLOWHIP_OK;
 }
 
-int glowhip_plan_pack(glowhip_plan* plan, void* packed, size_t packed_bytes, glowhip_stream_t stream) {
-    return glowhip_plan_pack_for(plan, packed, packed_bytes, GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING | GLOWHIP_PACK_INVERSE, stream);
-}
-
-int glowhip_plan_pack_for(glowhip_plan* plan, void* packed, size_t packed_bytes, int use, glowhip_stream_t stream) {
-    GH_REQUIRE(plan && packed, "plan_pack: null argument");
-    GH_REQUIRE(use & (GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING), "plan_pack: empty use mask");
-    // use bit 8 (internal): the exact-fp32 images of layers that normally run k_cnet / the deep-level kernels -- read by the inference
-    // calls only with the split-half path switched off through the debug hook
-    // (OR-ed in: the internal bits 16 = init pass' f.0 image and 32 = no LU of the caller's mask survive)
-    if (debug_switches().exact_fp32) use |= GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING | 8;
-    // a plan on the exact-fp32 family reads the fp32 MFMA images, which are the training path's
-    if (plan->family == GLOWHIP_FAMILY_EXACT_FP32) use |= GLOWHIP_PACK_TRAINING;
-    plan->repack_sel.clear();
-    int n_kind[5] = {0, 0, 0, 0, 0}, tail_blocks = 1, first_blocks = 2;
-    // (group 4: SH2 GEMM images of W^-1 -- launched after the LU factorisations, on their stream)
-    auto group = [](const RepackJob& r) { return r.after_lu ? 4 : (r.kind < REPACK_SH2_GEMM ? 0 : r.kind - REPACK_SH2_GEMM + 1); };
-    for (int gk = 0; gk < 5; ++gk)            // sorted by kind group: each image kernel is launched over its own jobs only
-        for (const RepackJob& r : plan->repack_jobs)
-            if ((r.use & use) && group(r) == gk) {
-                plan->repack_sel.push_back(r);
-                ++n_kind[gk];
-                if (gk == 3) tail_blocks = std::max(tail_blocks, (r.Cout + 7) / 8);
-                if (gk == 2 && r.Cin >= 64) first_blocks = std::max(first_blocks, std::min(16, (r.Cout + 31) / 32));
-            }
-    GH_REQUIRE(packed_bytes >= plan->packed_bytes, "plan_pack: packed buffer too small (%zu < %zu)", packed_bytes,
-               plan->packed_bytes);
-    hipStream_t s = (hipStream_t)stream;
-    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // (a previous pack's side-stream part writes the same buffer)
-    // The forward-only pack of a plan whose LU jobs are all one-wave jobs and that keeps everything on one stream is ONE launch
-    // (pack.hip k_pack_fused); every other pack -- inverse, training, wide plans, the init pass -- is the launch sequence below.
-    // (the debug switch picks the launches only: the table travels either way, so the two routes leave the same bytes in `packed`)
-    bool fusable = use == GLOWHIP_PACK_INFERENCE && plan->max_c <= 128 && n_kind[4] == 0 && !debug_switches().lu_workgroup;
-    for (const StepPrepJob& pj : plan->prep_jobs) fusable = fusable && step_prepare_small_takes(pj);
-    const bool fused = fusable && !debug_switches().pack_unfused;
-    // job tables -> device (plan-constant contents; re-sent because `packed` is caller memory), then the launches
-    if (!fused && hipMemsetAsync(packed, 0, 256, s) != hipSuccess) {
-        set_error("plan_pack: hipMemsetAsync failed");
-        return GLOWHIP_ELAUNCH;
-    }
-    auto upload = [&](size_t off, const void* src, size_t bytes) {
-        return bytes == 0 || hipMemcpyAsync((char*)packed + off, src, bytes, hipMemcpyHostToDevice, s) == hipSuccess;
-    };
-    // The job tables are plan constants: they travel once per buffer -- the selected repack jobs once per (buffer, image bits of the
-    // use mask), each mask into its OWN slot -- and stay in `packed`: a re-pack of the same buffer is then kernel launches only (no
-    // host-to-device copy per step, and the sequence can be captured in a hipGraph whose table no later pack of another mask --
-    // a training step, the exact-fp32 fall-back, the init pass -- overwrites).
-    const int slot = repack_slot(use);
-    const size_t slot_off = plan->repack_off + (size_t)slot * plan->repack_jobs.size() * sizeof(RepackJob);
-    if (plan->tables_in != packed) {
-        if (!upload(plan->prep_off, plan->prep_jobs.data(), plan->prep_jobs.size() * sizeof(StepPrepJob)) ||
-            !upload(plan->scale_off, plan->scale_jobs.data(), plan->scale_jobs.size() * sizeof(ScaleJob)) ||
-            !upload(plan->flip_off, plan->flip_jobs.data(), plan->flip_jobs.size() * sizeof(FlipJob)) ||
-            !upload(plan->lu_off, plan->lu_jobs.data(), plan->lu_jobs.size() * sizeof(LuJob))) {
-            set_error("plan_pack: hipMemcpyAsync of the job tables failed");
-            return GLOWHIP_ELAUNCH;
-        }
-        plan->tables_in = packed; plan->slots_in = 0; plan->segs_in = false;
-    }
-    if (!(plan->slots_in & (1u << slot))) {
-        // (hipMemcpyAsync from pageable memory stages the source before it returns; the per-slot host copy is kept anyway)
-        std::vector<RepackJob>& keep = plan->repack_slot_host[slot];
-        keep = plan->repack_sel;
-        if (!upload(slot_off, keep.data(), keep.size() * sizeof(RepackJob))) {
-            set_error("plan_pack: hipMemcpyAsync of the repack job table failed");
-            return GLOWHIP_ELAUNCH;
-        }
-        plan->slots_in |= 1u << slot;
-    }
-    // LU-form layers first, on the caller's stream and ahead of the fork: W = P L U_f into the layer's own buffer (the mixers and the
-    // deep levels' weight images read it) and the layer's log-det and constant slots, which the step-prepare kernels below then
-    // leave alone (StepPrepJob::lu_form) and their totals read
-    if (!plan->lu_jobs.empty()) {
-        plan->launch_counts["pack:invconv_lu"] += (long)plan->lu_jobs.size();
-        GH_TRY(launch_invconv_lu_assemble(at<LuJob>(packed, plan->lu_off), nullptr, (int)plan->lu_jobs.size(), plan->lu_max_c, packed, s));
-    }
-    if (fusable) {
-        // The table holds indices into the repack table of THIS slot (repack_sel of this use mask, sorted by kind group).  Today
-        // `fusable` admits one mask only, so it is a plan constant; it is keyed by the slot all the same: a pack of another slot
-        // rebuilds it and sends it again, and never launches over job indices of another selection.
-        if (plan->pack_segs.empty() || plan->pack_segs_slot != slot) {
-            std::vector<PackSeg>& t = plan->pack_segs;
-            t.clear(); plan->pack_segs_slot = slot; plan->segs_in = false;
-            for (int b = 0; b < ((int)plan->prep_jobs.size() + 3) / 4; ++b) t.push_back(PackSeg{PACKSEG_LU, 0, b, 1});
-            static const int order[4] = {1, 2, 3, 0};      // kind groups of repack_sel: SH2 GEMM, FIRST, TAIL, then the legacy kinds
-            for (int g : order) {
-                int first = 0;
-                for (int q = 0; q < g; ++q) first += n_kind[q];
-                const int kind = g == 0 ? PACKSEG_LEGACY : PACKSEG_SH2_GEMM + (g - 1);
-                for (int jn = first; jn < first + n_kind[g]; ++jn) {
-                    const int nb = pack_fused_job_blocks(kind, &plan->repack_sel[jn], nullptr);
-                    for (int b = 0; b < nb; ++b) t.push_back(PackSeg{kind, jn, b, nb});
-                }
-            }
-            for (int jn = 0; jn < (int)plan->scale_jobs.size(); ++jn) {
-                const int nb = pack_fused_job_blocks(PACKSEG_SCALE, nullptr, &plan->scale_jobs[jn]);
-                for (int b = 0; b < nb; ++b) t.push_back(PackSeg{PACKSEG_SCALE, jn, b, nb});
-            }
-            t.push_back(PackSeg{PACKSEG_ZERO, 0, 0, 1});
-        }
-        GH_REQUIRE(plan->pack_segs.size() <= plan->seg_cap, "plan_pack: segment table larger than its slot");
-        if (!plan->segs_in) {
-            static const char zero_head[PACK_SEG_HEAD] = {0};
-            if (!upload(plan->seg_off, zero_head, PACK_SEG_HEAD) ||
-                !upload(plan->seg_off + PACK_SEG_HEAD, plan->pack_segs.data(), plan->pack_segs.size() * sizeof(PackSeg))) {
-                set_error("plan_pack: hipMemcpyAsync of the segment table failed");
-                return GLOWHIP_ELAUNCH;
-            }
-            plan->segs_in = true;
-        }
-    }
-    if (fused) {
-        count_launch(plan, "pack:k_pack_fused");
-        return launch_pack_fused(at<PackSeg>(packed, plan->seg_off + PACK_SEG_HEAD), (int)plan->pack_segs.size(),
-                                 at<StepPrepJob>(packed, plan->prep_off), (int)plan->prep_jobs.size(), at<RepackJob>(packed, slot_off),
-                                 at<ScaleJob>(packed, plan->scale_off), at<unsigned>(packed, plan->seg_off), packed, s);
-    }
-    // Fork: the legacy-kind images and the LU factorisations go to the plan's side stream (created on first use; a host resource
-    // like the timing events) behind everything enqueued so far; whoever reads their results joins (join_legacy / join_lu).  What
-    // the first kernels of a forward need -- scale tables, the product kernels' images -- stays on `stream`.
-    // Only where it pays: plans with invertible 1x1 convolutions beyond 128 channels (blocked LU in global memory, 2.4 ms per pack
-    // at config E: +5 % on its forward).  At config B the side stream's workgroups only get in the way of the k_cnet launch that
-    // runs beside them (-0.5 %): everything stays on `stream` there.
-    hipStream_t side = s;
-    if (!debug_switches().pack_one_stream && plan->max_c > 128) {
-        if (!plan->side) {
-            if (hipStreamCreateWithFlags(&plan->side, hipStreamNonBlocking) != hipSuccess ||
-                hipEventCreateWithFlags(&plan->ev_fork, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&plan->ev_legacy, hipEventDisableTiming) != hipSuccess ||
-                hipEventCreateWithFlags(&plan->ev_lu, hipEventDisableTiming) != hipSuccess) {
-                set_error("plan_pack: could not create the side stream / events");
-                return GLOWHIP_ELAUNCH;
-            }
-        }
-        side = plan->side;
-        if (hipEventRecord(plan->ev_fork, s) != hipSuccess || hipStreamWaitEvent(side, plan->ev_fork, 0) != hipSuccess) {
-            set_error("plan_pack: fork onto the side stream failed");
-            return GLOWHIP_ELAUNCH;
-        }
-    }
-    if (use & GLOWHIP_PACK_TRAINING)      // transposed weight copies for the backward k_cnet images (read by the image kernels below)
-        GH_TRY(launch_flipT_batched(at<FlipJob>(packed, plan->flip_off), (int)plan->flip_jobs.size(), plan->flip_tiles, packed, s));
-    GH_TRY(launch_pack_batched(at<ScaleJob>(packed, plan->scale_off), (int)plan->scale_jobs.size(),
-                               at<RepackJob>(packed, slot_off), n_kind, tail_blocks, packed, s, side, first_blocks));
-    if (side != s) {
-        if (hipEventRecord(plan->ev_legacy, side) != hipSuccess) { set_error("plan_pack: hipEventRecord failed"); return GLOWHIP_ELAUNCH; }
-        plan->legacy_pending = true; plan->pending_captured = stream_capturing(s);
-    }
-    if (!(use & 32)) {      // (32, internal: weight images and scale tables only -- the init pass' first pack)
-        bool all_small = !debug_switches().lu_workgroup;
-        for (const StepPrepJob& pj : plan->prep_jobs) all_small = all_small && step_prepare_small_takes(pj);
-        const bool inv = (use & (GLOWHIP_PACK_INVERSE | GLOWHIP_PACK_TRAINING)) != 0;
-        count_launch(plan, (all_small && !inv) ? "pack:k_step_prepare_small" : "pack:k_step_prepare_batched");
-        if (!(all_small && !inv)) {      // which factorisation each matrix takes there (tallied first: at most five map updates per pack)
-            std::map<const char*, long> routes;
-            for (const StepPrepJob& pj : plan->prep_jobs)
-                if (pj.w) ++routes[step_prepare_route_name(pj.C, inv ? 1 : 0)];
-            for (const auto& kv : routes) plan->launch_counts[kv.first] += kv.second;
-        }
-        GH_TRY(launch_step_prepare_batched(at<StepPrepJob>(packed, plan->prep_off), (int)plan->prep_jobs.size(),
-                                           plan->max_lds_c, packed, side, inv, plan->max_c, all_small ? 1 : 0));
-        // W^-1 of the LU-form layers by substitution -- for decode only: the backward sweep does not read it (their GradJob has no
-        // W^-1 term), so a training pack without GLOWHIP_PACK_INVERSE skips it
-        if ((use & GLOWHIP_PACK_INVERSE) && !plan->lu_jobs.empty())
-            GH_TRY(launch_invconv_lu_inverse(at<LuJob>(packed, plan->lu_off), nullptr, (int)plan->lu_jobs.size(), plan->lu_max_c, packed, side));
-        if ((use & GLOWHIP_PACK_INVERSE) && n_kind[4] > 0)
-            GH_TRY(launch_repack_sh2_gemm(at<RepackJob>(packed, slot_off) + (n_kind[0] + n_kind[1] + n_kind[2] + n_kind[3]), n_kind[4], packed, side));
-    }
-    if (side != s) {
-        if (hipEventRecord(plan->ev_lu, side) != hipSuccess) { set_error("plan_pack: hipEventRecord failed"); return GLOWHIP_ELAUNCH; }
-        plan->lu_pending = true; plan->pending_captured = stream_capturing(s);
-    }
-    return GLOWHIP_OK;
-}
-
-int glowhip_plan_set_family(glowhip_plan* plan, int family) {
-    GH_REQUIRE(plan, "plan_set_family: null plan");
-    GH_REQUIRE(family == GLOWHIP_FAMILY_AUTO || family == GLOWHIP_FAMILY_EXACT_FP32, "plan_set_family: unknown family %d", family);
-    plan->family = family;
-    return GLOWHIP_OK;
-}
-
-int glowhip_plan_get_family(const glowhip_plan* plan) { return plan ? plan->family : GLOWHIP_EINVAL; }
-
-int glowhip_plan_bind_invconv_lu(glowhip_plan* plan, int layer, const glowhip_invconv_lu* lu) {
-    GH_REQUIRE(plan && lu, "plan_bind_invconv_lu: null argument");
-    GH_REQUIRE(layer >= 0 && layer < (int)plan->layers.size(), "plan_bind_invconv_lu: layer %d out of range", layer);
-    const LayerPlan& L = plan->layers[layer];
-    const glowhip_layer_desc& d = L.d;
-    GH_REQUIRE(d.kind == GLOWHIP_LAYER_FLOWSTEP && d.permutation == GLOWHIP_PERM_INVCONV, "plan_bind_invconv_lu: layer %d is not an invconv FlowStep", layer);
-    GH_REQUIRE(lu->perm && lu->l && lu->u && lu->log_s && lu->sign_s && lu->w, "plan_bind_invconv_lu: null pointer");
-    GH_REQUIRE(lu->w == d.invconv_w, "plan_bind_invconv_lu: w must be the buffer the layer's invconv_w points at");
-    GH_REQUIRE(d.C <= INVCONV_LU_MAX_C, "plan_bind_invconv_lu: C=%d unsupported (limit %d)", d.C, INVCONV_LU_MAX_C);
-    for (const glowhip_plan::LuLayer& q : plan->lu_layers) GH_REQUIRE(q.layer != layer, "plan_bind_invconv_lu: layer %d is bound already", layer);
-    int pj = 0;      // the layer's step-prepare job: FlowSteps in layer order
-    for (int i = 0; i < layer; ++i) pj += plan->layers[i].d.kind == GLOWHIP_LAYER_FLOWSTEP ? 1 : 0;
-    plan->prep_jobs[pj].w = nullptr; plan->prep_jobs[pj].lu_form = 1;
-    plan->max_lds_c = plan->max_c = 0;      // what is left for the factorisations
-    for (const StepPrepJob& j : plan->prep_jobs) {
-        if (j.w && j.C <= 64) plan->max_lds_c = std::max(plan->max_lds_c, j.C);
-        if (j.w) plan->max_c = std::max(plan->max_c, j.C);
-    }
-    LuJob j{};
-    j.perm = lu->perm; j.l = lu->l; j.u = lu->u; j.log_s = lu->log_s; j.sign_s = lu->sign_s; j.w = lu->w;
-    j.an_logs = d.an_logs; j.C = d.C; j.HW = d.H * d.W;
-    j.winv_off = L.winv; j.logabsdet_off = L.logabsdet; j.konst_off = L.konst;
-    plan->lu_jobs.push_back(j);
-    plan->lu_layers.push_back(glowhip_plan::LuLayer{layer, glowhip_invconv_lu_grads{nullptr, nullptr, nullptr}});
-    plan->lu_max_c = std::max(plan->lu_max_c, d.C);
-    plan->lu_grad_jobs.reserve(plan->lu_jobs.size());
-    // the tables in `packed` and the one-launch pack's segment table were built for the plan as it was
-    plan->tables_in = nullptr; plan->slots_in = 0; plan->segs_in = false; plan->pack_segs.clear(); plan->pack_segs_slot = -1;
-    return GLOWHIP_OK;
-}
-
-int glowhip_plan_bind_invconv_lu_grads(glowhip_plan* plan, int layer, const glowhip_invconv_lu_grads* grads) {
-    GH_REQUIRE(plan, "plan_bind_invconv_lu_grads: null plan");
-    for (glowhip_plan::LuLayer& q : plan->lu_layers)
-        if (q.layer == layer) {
-            GH_REQUIRE(!grads || (grads->dl && grads->du && grads->dlog_s), "plan_bind_invconv_lu_grads: null gradient pointer");
-            q.g = grads ? *grads : glowhip_invconv_lu_grads{nullptr, nullptr, nullptr};
-            return GLOWHIP_OK;
-        }
-    set_error("plan_bind_invconv_lu_grads: layer %d is not an LU-form layer", layer);
-    return GLOWHIP_EINVAL;
-}
-
 int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps) {
     GH_REQUIRE(plan, "plan_bind_latents: null plan");
     if (!eps_out && n_eps == 0) {
@@ -1145,21 +694,6 @@ int glowhip_plan_status(const glowhip_plan* plan, const void* workspace, size_t 
     return launch_status(w.acc, N, result, elems_per_sample, status_out, (hipStream_t)stream);
 }
 
-int glowhip_plan_pack_sync(glowhip_plan* plan) {
-    GH_REQUIRE(plan, "plan_pack_sync: null plan");
-    if (plan->side && (plan->legacy_pending || plan->lu_pending)) {
-        if (hipStreamSynchronize(plan->side) != hipSuccess) { set_error("plan_pack_sync: hipStreamSynchronize failed"); return GLOWHIP_ELAUNCH; }
-        plan->legacy_pending = plan->lu_pending = false;
-    }
-    return GLOWHIP_OK;
-}
-
-int glowhip_plan_forget_packed(glowhip_plan* plan) {
-    GH_REQUIRE(plan, "plan_forget_packed: null plan");
-    plan->tables_in = nullptr; plan->slots_in = 0; plan->segs_in = false;
-    return GLOWHIP_OK;
-}
-
 int glowhip_plan_encode(glowhip_plan* plan, const void* packed, const float* x, const float* noise,
                         const float* logdet_in, float* z, float* logdet_out, int N, void* workspace,
                         size_t workspace_bytes, glowhip_stream_t stream) {
@@ -1168,8 +702,7 @@ int glowhip_plan_encode(glowhip_plan* plan, const void* packed, const float* x, 
     if (N == 0) return GLOWHIP_OK;
     hipStream_t s = (hipStream_t)stream;
     Workspace w;
-    GH_TRY(carve(plan, N, workspace, workspace_bytes, w));
-    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(plan, N)));
+    GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
     GH_TRY(run_forward(plan, packed, x, noise, z, N, w, s));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
     if (logdet_out)
@@ -1187,8 +720,7 @@ int glowhip_plan_decode(glowhip_plan* plan, const void* packed, const float* z, 
     if (N == 0) return GLOWHIP_OK;
     hipStream_t s = (hipStream_t)stream;
     Workspace w;
-    GH_TRY(carve(plan, N, workspace, workspace_bytes, w));
-    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(plan, N)));
+    GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // decode reads W^-1 and the deep levels' images first
     GH_TRY(run_reverse(plan, packed, z, eps, n_eps, x, N, w, s));
     if (logdet_out)
@@ -1204,24 +736,10 @@ int glowhip_glow_forward(glowhip_plan* plan, const void* packed, const float* x,
     GH_REQUIRE(x && z && nll_out, "glow_forward: null tensor");
     GH_REQUIRE(n_bits > 0 && n_bits <= 30, "glow_forward: n_bits=%d", n_bits);
     if (N == 0) return GLOWHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    Workspace w;
-    GH_TRY(carve(plan, N, workspace, workspace_bytes, w));
-    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(plan, N)));
-    RngSpec rng{plan->rng_on && !noise, plan->rng_seed, plan->rng_calls, (float)(1.0 / pow(2.0, n_bits))};
-    if (rng.on) ++plan->rng_calls;
-    GH_TRY(run_forward(plan, packed, x, noise, z, N, w, s, 0, rng.on ? &rng : nullptr));
-    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
-    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // the sum of the log|det W| terms enters here
-    // objective = -ln(n_bins)*CHW + logdet + logp;  nll = -objective / (ln2 * CHW)   (network/model.py:425-450)
-    const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
-    const double offset = -log(pow(2.0, n_bits)) * chw;
-    const double scale = -1.0 / (log(2.0) * chw);
-    GH_TRY(launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, offset, scale, nll_out, objective_out, N, s, ACC_EXTRA));
-    return GLOWHIP_OK;
+    return glow_forward(plan, packed, x, nullptr, 1.f, noise, prior_mean, prior_logs, prior_stride, n_bits, z, nll_out, objective_out, N,
+                        workspace, workspace_bytes, (hipStream_t)stream);
 }
 
-// Glow.normal_flow from 8-bit pixels: the leading Squeeze2d reads the bytes itself
 int glowhip_glow_forward_u8(glowhip_plan* plan, const void* packed, const uint8_t* x_u8, float divisor, const float* noise,
                             const float* prior_mean, const float* prior_logs, long prior_stride, int n_bits, float* z,
                             float* nll_out, float* objective_out, int N, void* workspace, size_t workspace_bytes,
@@ -1233,21 +751,8 @@ int glowhip_glow_forward_u8(glowhip_plan* plan, const void* packed, const uint8_
     GH_REQUIRE(plan->layers.size() >= 2 && plan->layers[0].d.kind == GLOWHIP_LAYER_SQUEEZE,
                "glow_forward_u8: the plan must start with a Squeeze2d layer (and not end with it)");
     if (N == 0) return GLOWHIP_OK;
-    hipStream_t s = (hipStream_t)stream;
-    Workspace w;
-    GH_TRY(carve(plan, N, workspace, workspace_bytes, w));
-    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(plan, N)));
-    const glowhip_layer_desc& d0 = plan->layers[0].d;
-    plan->cur_layer = 0;
-    RngSpec rng{plan->rng_on && !noise, plan->rng_seed, plan->rng_calls, (float)(1.0 / pow(2.0, n_bits))};
-    if (rng.on) ++plan->rng_calls;
-    (void)d0;
-    GH_TRY(run_forward(plan, packed, w.bufA, noise, z, N, w, s, 0, rng.on ? &rng : nullptr, x_u8, divisor));
-    GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
-    const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
-    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
-    return launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, -log(pow(2.0, n_bits)) * chw, -1.0 / (log(2.0) * chw),
-                           nll_out, objective_out, N, s, ACC_EXTRA);
+    return glow_forward(plan, packed, nullptr, x_u8, divisor, noise, prior_mean, prior_logs, prior_stride, n_bits, z, nll_out,
+                        objective_out, N, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int glowhip_plan_actnorm_init(glowhip_plan* plan, void* packed, size_t packed_bytes, const float* x, const float* noise,
@@ -1257,11 +762,10 @@ int glowhip_plan_actnorm_init(glowhip_plan* plan, void* packed, size_t packed_by
     GH_REQUIRE(x && N > 0, "plan_actnorm_init: empty batch");
     hipStream_t s = (hipStream_t)stream;
     Workspace w;
-    GH_TRY(carve(plan, N, workspace, workspace_bytes, w));
-    GH_TRY(launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(plan, N)));
+    GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
     // plain (ActNorm-free) fp32 MFMA weight images of every convolution: the training family's + the init pass's own f.0 image
     // (no LU here: the invertible 1x1 convolutions are applied with W itself, and the pack at the end factorises them)
-    GH_TRY(glowhip_plan_pack_for(plan, packed, packed_bytes, GLOWHIP_PACK_TRAINING | 16 | 32, stream));
+    GH_TRY(glowhip_plan_pack_for(plan, packed, packed_bytes, GLOWHIP_PACK_TRAINING | PACK_INIT_F0 | PACK_NO_LU, stream));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
     // Layer by layer: set the ActNorm statistics from the activations that reach it, refresh the packed
     // data of that layer, then run the layer forward with the fresh parameters (first training-mode

@@ -1,5 +1,5 @@
-// plan_internal.h -- plan data structures shared by plan.hip (inference executor) and plan_train.hip
-// (training forward with a tape + backward executor).
+// plan_internal.h -- plan data structures shared by plan_build.hip (plan construction, parameter pack), plan.hip (inference
+// executor) and plan_train.hip (training forward with a tape + backward executor).
 #pragma once
 #include <map>
 #include <string>
@@ -40,6 +40,16 @@ struct LayerPlan {
                               // the ActNorm being initialised folded in); 0 = none (the direct kernel runs)
 };
 
+// The use mask of a pack (glowhip_plan_pack_for, RepackJob::use): GLOWHIP_PACK_INFERENCE / _TRAINING / _INVERSE of the header, and
+enum { PACK_EXACT_FP32 = 8,      // the exact-fp32 images of layers that normally run k_cnet / the deep-level kernels
+       PACK_INIT_F0 = 16,        // the init pass' plain f.0 image
+       PACK_NO_LU = 32 };        // no LU: weight images and scale tables only
+// the bits that select images (INVERSE: the W^-1 images of the deep levels); PACK_NO_LU does not change the repack table
+constexpr int PACK_IMAGE_BITS = GLOWHIP_PACK_INFERENCE | GLOWHIP_PACK_TRAINING | GLOWHIP_PACK_INVERSE | PACK_EXACT_FP32 | PACK_INIT_F0;
+constexpr int REPACK_SLOTS = PACK_IMAGE_BITS + 1;
+static inline int repack_slot(int use) { return use & PACK_IMAGE_BITS; }      // slot of a use mask's selected repack jobs
+constexpr size_t PACK_SEG_HEAD = 16;
+
 }  // namespace glowhip
 
 using namespace glowhip;
@@ -69,7 +79,7 @@ struct glowhip_plan {
     bool legacy_pending = false, lu_pending = false;
     const void* tables_in = nullptr;      // the `packed` buffer that already holds the job tables (glowhip_plan_forget_packed resets)
     unsigned slots_in = 0;                // ... and which of its repack-table slots (repack_slot) have been filled
-    std::vector<RepackJob> repack_slot_host[32];
+    std::vector<RepackJob> repack_slot_host[REPACK_SLOTS];
     bool pending_captured = false;        // ev_legacy / ev_lu were last recorded inside a stream capture (see join_legacy)
     int max_lds_c = 0, max_c = 0;
     size_t packed_bytes = 0;
@@ -111,13 +121,6 @@ struct ScopedTimer {
     }
     ~ScopedTimer() { if (on) { (void)hipEventRecord(slot.b, s); p->ev_used.push_back(slot); } }
 };
-
-
-constexpr size_t PACK_SEG_HEAD = 16;
-constexpr int REPACK_SLOTS = 32;
-// slot of a use mask's selected repack jobs: the five bits that select images (1 inference, 2 training, 4 inverse: the W^-1 images
-// of the deep levels, 8 round-1 images of cnet / dnet layers, 16 init pass' f.0 image); 32 (no LU) does not change the table
-static inline int repack_slot(int use) { return use & 31; }
 
 static inline bool stream_capturing(hipStream_t s) {
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;

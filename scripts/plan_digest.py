@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Behaviour table of a libglowhip build, for executor refactors: per (model, debug switch, operation) the plan's launch counts
 and a sha256 of every output tensor, from seeded weights and inputs.  Two builds that run the same kernels on the same arguments
-print the same table.
+print the same table.  Operations: encode, decode, init (the data-dependent ActNorm pass of a fresh model: z, nll and every ActNorm
+bias / logs), decode_vjp and train; the switches of PACK_ONLY change the pack alone and run the first three.
 
     python scripts/plan_digest.py LIB [LIB ...]
 
@@ -29,7 +30,9 @@ MODELS = {      # affine + invconv unless said otherwise
 }
 SWITCHES = {"none": [], "per_layer_bwd": ["TRAIN_PER_LAYER_BWD"], "per_layer_fwd": ["TRAIN_PER_LAYER_FWD"],
             "per_layer_both": ["TRAIN_PER_LAYER_FWD", "TRAIN_PER_LAYER_BWD"], "exact_fp32": ["EXACT_FP32"],
-            "no_cnet1w_bwd": ["NO_CNET1W_BWD"], "wgrad_narrow": ["WGRAD_NARROW"], "no_mixer_fusion": ["NO_MIXER_FUSION"]}
+            "no_cnet1w_bwd": ["NO_CNET1W_BWD"], "wgrad_narrow": ["WGRAD_NARROW"], "no_mixer_fusion": ["NO_MIXER_FUSION"],
+            "pack_unfused": ["PACK_UNFUSED"], "lu_workgroup": ["LU_WORKGROUP"], "pack_one_stream": ["PACK_ONE_STREAM"]}
+PACK_ONLY = ("pack_unfused", "lu_workgroup", "pack_one_stream")      # these change the pack alone: encode, decode and init rows
 
 
 def worker():
@@ -70,16 +73,19 @@ def worker():
         y = torch.nn.functional.one_hot(torch.arange(n) % 5, 5).float().to(dev) if m.get("ycond") else None
         for sw, bits in SWITCHES.items():
             with _lib.debug_flags(sum(int(_lib.DBG[b]) for b in bits)):
-                np.random.seed(2)      # (the fixed permutations are drawn at construction)
-                glow = G.Glow(hps(m, bool(m.get("lu"))))
-                glow.load_state_dict({k: v.clone() for k, v in sd.items()})
+                def model():
+                    np.random.seed(2)      # (the fixed permutations are drawn at construction)
+                    glow = G.Glow(hps(m, bool(m.get("lu"))))
+                    glow.load_state_dict({k: v.clone() for k, v in sd.items()})
+                    return glow.to(dev)
+
+                glow = model().eval()
                 glow.set_actnorm_inited()
-                glow = glow.to(dev).eval()
                 plan = glow.flow.plan_for(x)
                 z0 = torch.randn((n,) + tuple(plan.out_chw), generator=g).to(dev) * 0.7
                 eps = [(torch.randn((n,) + tuple(s), generator=g) * 0.7).to(dev) for s in plan.split_chw]
 
-                def row(op, outs):
+                def row(op, outs, plan=plan):
                     torch.cuda.synchronize()
                     counts = " ".join(f"{k}={v}" for k, v in sorted(plan.launch_counts(reset=True).items()))
                     print(f"{name} | {sw} | {op} | {counts} | " + " ".join(f"{k}:{sha(t)}" for k, t in outs), flush=True)
@@ -89,6 +95,12 @@ def worker():
                     z, nll, _ = glow.normal_flow(x, y, noise=noise)
                     row("encode", [("z", z), ("nll", nll)])
                     row("decode", [("x", glow.reverse_flow(z0, y, eps=eps))])
+                    fresh = model().train()      # data-dependent ActNorm init: the first training-mode forward of an un-initialised model
+                    z, nll, _ = fresh.normal_flow(x, y, noise=noise)
+                    row("init", [("z", z), ("nll", nll)] + [(k, p) for k, p in fresh.named_parameters() if k.endswith(("bias", "logs")) and "actnorm" in k],
+                        fresh.flow.plan_for(x))
+                if sw in PACK_ONLY:
+                    continue
                 with torch.enable_grad():
                     lat = Latents(z0.clone(), [e.clone() for e in eps]).requires_grad_()
                     grads = torch.autograd.grad(glow.decode_latents(lat, safe=False), lat.tensors(), gx)

@@ -173,7 +173,7 @@ def apply_bound_sh2(M, v):
     return rel * (aM @ av) + 2.0 ** -37 * aM.max(axis=1)[:, None] * av.sum(axis=0)[None, :] + 2.0 ** -29 * aM.sum(axis=1)[:, None]
 
 
-# ---- routes.  Names are the launch counters of glowhip_plan_launch_counts (csrc/plan.hip glowhip_plan_pack_for; csrc/lu.hip
+# ---- routes.  Names are the launch counters of glowhip_plan_launch_counts (csrc/plan_build.hip glowhip_plan_pack_for; csrc/lu.hip
 # step_prepare_route_name).  The GPU tests ASSERT these from the counters; the widths below are where each route is exercised.
 FUSED, SMALL, BATCHED = "pack:k_pack_fused", "pack:k_step_prepare_small", "pack:k_step_prepare_batched"
 R_LDS, R_BLOCKED, R_GLOBAL = "pack:lu:logdet_only(lds)", "pack:lu:logdet_blocked", "pack:lu:logdet_only(global)"

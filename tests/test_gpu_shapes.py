@@ -1,7 +1,7 @@
 """Non-square and non-power-of-two images (-m gpu): one training step, the same step on the per-layer kernels, inference and the
 data-dependent ActNorm initialisation of whole L = 2 models whose level maps are tall, wide, flat (H = 2), ragged (W % 4 != 0) or
 odd -- the shapes at which the backward sweep, the tape and the workspaces pick their kernels and sizes from H, W and H * W
-separately (csrc/plan_train.hip, csrc/backward.hip, csrc/plan.hip).  Every other gradient test of the suite runs on a square
+separately (csrc/plan_build.hip, csrc/plan.hip, csrc/plan_train.hip, csrc/backward.hip).  Every other gradient test of the suite runs on a square
 power-of-two image, where an index that takes W for H, a halo row from the wrong side or a buffer sized from max(H, W)^2 cannot show.
 
 The yardstick of every gradient is torch autograd through the oracle in fp64 (the reference network/model.py:82-117 and
