@@ -18,16 +18,22 @@ import latents_oracle as LO
 MIN_MARGIN = 1e-5
 
 
+def image_hw(image):
+    """(H, W) of ``image``: an int (square) or an (H, W) pair."""
+    return (image, image) if isinstance(image, int) else (int(image[0]), int(image[1]))
+
+
 def build_case(image, hidden, K, L, batch, seed, zeros_std, perm="invconv", coup="affine", tables=None, invconv_perturb=0.02):
     """(cfg, sd, z, eps, g_x): seeded weights + ActNorm init from the batch; the latents are the fp32 full-latent encode of that
-    batch (no noise); g_x ~ N(0, 1)."""
-    cfg = O.default_cfg(image_shape=(image, image, 3), hidden_channels=hidden, K=K, L=L, flow_permutation=perm, flow_coupling=coup,
+    batch (no noise); g_x ~ N(0, 1).  ``image``: the side of a square image, or (H, W)."""
+    H, W = image_hw(image)
+    cfg = O.default_cfg(image_shape=(H, W, 3), hidden_channels=hidden, K=K, L=L, flow_permutation=perm, flow_coupling=coup,
                         batch=batch)
     sd = O.seeded_state_dict(cfg, seed=seed, zeros_std=zeros_std, invconv_perturb=invconv_perturb if perm == "invconv" else 0.0)
     g = torch.Generator().manual_seed(seed + 1)
-    x = torch.floor(torch.rand(batch, 3, image, image, generator=g) * 256.0) / 256.0
-    noise = torch.rand(batch, 3, image, image, generator=g) / 256
-    gx = torch.randn(batch, 3, image, image, generator=g)
+    x = torch.floor(torch.rand(batch, 3, H, W, generator=g) * 256.0) / 256.0
+    noise = torch.rand(batch, 3, H, W, generator=g) / 256
+    gx = torch.randn(batch, 3, H, W, generator=g)
     with torch.no_grad():
         sd = O.glow_init_actnorm(x, noise, sd, cfg, perm_tables=tables)
         z, eps = encode_latents(x, sd, cfg, tables)
@@ -105,7 +111,8 @@ def perm_tables(image, hidden, K, L, batch, perm, coup, np_seed):
     """The tables a `Glow` of this config draws at construction under np.random.seed(np_seed) (no GPU involved)."""
     import pytorch_glow_amd as G
     from pytorch_glow_amd.misc import util
-    cfg = O.default_cfg(image_shape=(image, image, 3), hidden_channels=hidden, K=K, L=L, flow_permutation=perm, flow_coupling=coup, batch=batch)
+    H, W = image_hw(image)
+    cfg = O.default_cfg(image_shape=(H, W, 3), hidden_channels=hidden, K=K, L=L, flow_permutation=perm, flow_coupling=coup, batch=batch)
     np.random.seed(np_seed)
     proto = G.Glow(hps_for(cfg, batch))
     return {i: (torch.as_tensor(getattr(l, perm).indices), torch.as_tensor(getattr(l, perm).indices_inverse))

@@ -1,5 +1,6 @@
 """Host tests of the differentiable decode (no GPU): the two exports, the error paths of glowhip_plan_decode_vjp that need no device,
-the workspace query, `Latents.requires_grad_ / detach`, and the CPU oracle helpers the GPU tests rest on."""
+the workspace query, `Latents.requires_grad_ / detach`, the CPU oracle helpers the GPU tests rest on, and the seeded non-square /
+odd / ragged cases of tests/test_gpu_decode_grad_shapes.py (their table lives here, so that the seeds are checked without a GPU)."""
 import ctypes
 import os
 
@@ -102,3 +103,69 @@ def test_oracle_helpers_agree_with_the_oracle_and_with_finite_algebra():
     lhs = float((ref["gx"].double() * (xp - xm) / 2).sum())
     rhs = float((ref["gz"] * dz).sum() + (ref["geps"][0] * de).sum())
     assert abs(lhs - rhs) <= 1e-6 * max(abs(lhs), abs(rhs)), (lhs, rhs)
+
+
+# ------------------------------------------------------------------------------------------------ H x W cases
+# The cases of tests/test_gpu_decode_grad_shapes.py (L = 2 unless said otherwise), with the fp64 ReLU margin of each seed as a CPU scan
+# found it (alternate seeds in brackets) and the floor this file holds it to: MIN_MARGIN where the GPU test compares every entry,
+# the recorded margin rounded down for W and T, which go under the capped rule (no seed of 200 / 150 scanned reaches 1e-5 there).
+#   R   12x20  hidden 64   seed 20 (30, 54):     9.0e-5      O   20x12  hidden 32   seed 34 (29, 5):    1.8e-4
+#   N2  32x48  hidden 128  seed 180 (199, 110):  1.6e-5      D6  64x192 L 6         seed 59 (56, 101):  1.5e-5
+#   S   8x64   hidden 128  seed 23 (33, 15):     2.2e-5      F   8x256  hidden 128  seed 26 (82, 115):  2.9e-5
+#   W   16x128 hidden 128  seed 197 (134):       9.4e-6      T   64x16  hidden 512  seed 129 (115):     4.6e-6
+NP_SEED = 5      # numpy seed of the fixed-permutation tables (test_gpu_decode_grad.NP_SEED)
+SHAPE_CASES = {
+    "R": dict(image=(12, 20), hidden=64, K=2, L=2, batch=3, zeros_std=0.05, seed=20),
+    "O": dict(image=(20, 12), hidden=32, K=2, L=2, batch=3, zeros_std=0.05, seed=34, perm="shuffle", coup="additive", np_seed=NP_SEED),
+    "N2": dict(image=(32, 48), hidden=128, K=2, L=2, batch=2, zeros_std=0.05, seed=180),
+    "D6": dict(image=(64, 192), hidden=32, K=1, L=6, batch=2, zeros_std=0.02, seed=59, stable=True),
+    "S": dict(image=(8, 64), hidden=128, K=2, L=2, batch=3, zeros_std=0.05, seed=23),
+    "F": dict(image=(8, 256), hidden=128, K=1, L=2, batch=2, zeros_std=0.01, seed=26, perm="reverse", coup="additive", np_seed=NP_SEED),
+    "W": dict(image=(16, 128), hidden=128, K=2, L=2, batch=2, zeros_std=0.01, seed=197),
+    "T": dict(image=(64, 16), hidden=512, K=2, L=2, batch=3, zeros_std=0.01, seed=129),
+}
+SHAPE_MARGIN = {"R": 9.0e-5, "O": 1.8e-4, "N2": 1.6e-5, "D6": 1.5e-5, "S": 2.2e-5, "F": 2.9e-5, "W": 9.4e-6, "T": 4.6e-6}
+SHAPE_MARGIN_FLOOR = dict({c: D.MIN_MARGIN for c in SHAPE_CASES}, W=9e-6, T=4e-6)
+
+
+def test_int_and_pair_forms_of_image_give_the_same_reference_bit_for_bit():
+    kw = dict(hidden=32, K=2, L=2, batch=3, zeros_std=0.05, seed=1)      # test_gpu_decode_grad.TINY_AFF
+    a, b = D.reference(image=16, **kw), D.reference(image=(16, 16), **kw)
+    assert a is not b and tuple(a["cfg"]["image_shape"]) == tuple(b["cfg"]["image_shape"]) == (16, 16, 3)
+    assert set(a["sd"]) == set(b["sd"]) and all(torch.equal(a["sd"][k], b["sd"][k]) for k in a["sd"])
+    for k in ("z", "gx", "x", "gz"):
+        assert torch.equal(a[k], b[k]), k
+    for k in ("eps", "geps"):
+        assert len(a[k]) == len(b[k]) == 1 and torch.equal(a[k][0], b[k][0]), k
+    assert a["margin"] == b["margin"]
+    ta, tb = (D.perm_tables(im, 32, 2, 2, 3, "shuffle", "additive", NP_SEED) for im in (16, (16, 16)))
+    assert ta.keys() == tb.keys() and all(torch.equal(ta[i][j], tb[i][j]) for i in ta for j in (0, 1))
+
+
+@pytest.mark.parametrize("cid", list(SHAPE_CASES))
+def test_shape_case_seed_keeps_its_margin_and_the_fp32_oracle_stays_inside_the_bound(cid):
+    """The seed's fp64 margin is above the case's floor, every reference gradient is finite, and autograd through the same oracle in
+    fp32 has no entry beyond 2e-4 max|g| + 1e-7 of the fp64 one: what the GPU test asks of the kernels, the formats themselves can
+    deliver.  (The recorded margin is printed, not asserted: the latents are an fp32 encode, whose last bits -- and with them the
+    third digit of the margin -- depend on the host's convolution: W 9.4e-6 / 9.2e-6, T 4.6e-6 / 4.5e-6 on two machines.)"""
+    from oracle import glow_oracle as O
+    kw = SHAPE_CASES[cid]
+    ref = D.reference(**kw)
+    H, W = kw["image"]
+    assert tuple(ref["cfg"]["image_shape"]) == (H, W, 3) and tuple(ref["gx"].shape) == (kw["batch"], 3, H, W)
+    L = kw["L"]
+    assert tuple(ref["z"].shape[1:]) == (3 * 2 ** (L + 1), H >> L, W >> L)
+    assert [tuple(e.shape[1:]) for e in ref["eps"]] == [(3 * 2 ** l, H >> l, W >> l) for l in range(L - 1, 0, -1)]
+    print(f"{cid}: margin {ref['margin']:.3e} (recorded {SHAPE_MARGIN[cid]:.1e}, floor {SHAPE_MARGIN_FLOOR[cid]:.0e})")
+    assert ref["margin"] >= SHAPE_MARGIN_FLOOR[cid]
+    assert all(bool(torch.isfinite(t).all()) for t in [ref["x"], ref["gz"]] + ref["geps"])
+    prev = O.STABLE_LOGDET
+    O.STABLE_LOGDET = bool(kw.get("stable", False))
+    try:
+        _, gz32, geps32 = D.decode_grads(ref["z"], ref["eps"], ref["gx"], ref["sd"], ref["cfg"], ref["tables"], dtype=torch.float32)
+    finally:
+        O.STABLE_LOGDET = prev
+    for name, a, r in [("g_z", gz32, ref["gz"])] + [(f"g_eps[{k}]", a, r) for k, (a, r) in enumerate(zip(geps32, ref["geps"]))]:
+        frac, rel = D.beyond(a, r)
+        print(f"{cid} fp32 oracle {name}: {frac:.3%} beyond the bound, worst err / max|g| {rel:.2e}")
+        assert frac == 0.0, f"{cid} {name}: the fp32 oracle itself has {frac:.3%} of its entries beyond the bound ({rel:.2e})"
