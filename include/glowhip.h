@@ -237,6 +237,47 @@ int glowhip_dequant_noise(float* out, long n, unsigned long long seed, unsigned 
  * the ranks of a data-parallel job key it differently (pytorch-glow_amd/network/model.py: torch's seed, the rank folded in). */
 int glowhip_plan_set_dequant_stream(glowhip_plan* plan, unsigned long long seed, unsigned long long call);
 
+/* The sampler's random stream: the N(0, 1) draws of GaussianDiag.sample (network/module.py:470-483) made inside the kernels that
+ * consume them -- no noise tensor in HBM, and every draw has a name, (seed, call, stream, element).
+ *   generator  Philox4x32-10, key = seed (the round function and key schedule of the dequantisation noise above); counter of the
+ *              group of four elements 4j .. 4j+3 of stream s at call c:
+ *                c0 = j & 0xffffffff, c1 = j >> 32, c2 = c & 0xffffffff, c3 = ((s + 1) << 24) | ((c >> 32) & 0xffffff)
+ *   stream     s = 0: the top latent; s = 1 + k: the k-th Split2d in DECODE order (the order of glowhip_plan_decode's eps).  Plans
+ *              with more than 254 Split2d layers are refused; call < 2^56.  The top byte of c3 is never zero, the dequantisation
+ *              stream's always is: the two share no counter under one seed.
+ *   element    flat index in the contiguous (N, C, H, W) draw tensor
+ *   normals    words (w0, w1) give elements 0, 1 of the group, (w2, w3) elements 2, 3, by Box-Muller in fp32:
+ *                u1 = ((w >> 9) + 0.5) * 2^-23, u2 = (w' >> 8) * 2^-24, r = sqrtf(-2 logf(u1)),
+ *                even element = r cosf(2 pi u2), odd element = r sinf(2 pi u2);  |e| <= 5.77, never infinite
+ *   value      e * std, one rounded fp32 product (csrc/sampler_rng.h: one device function behind every site)
+ * glowhip_normal_noise writes n elements of a stream as a tensor: a decode with that tensor injected as eps[k] is bitwise equal
+ * to the in-kernel draw of stream 1 + k. */
+int glowhip_normal_noise(float* out, long n, unsigned long long seed, unsigned long long call, int stream_id, float std,
+                         glowhip_stream_t stream);
+/* Bind the stream to a plan, in the pattern of glowhip_plan_bind_latents (HOST bookkeeping; (NULL, NULL, 0, 0) unbinds).
+ * rng_dev: DEVICE word of two uint64 {seed, call}, read by the kernels through the pointer -- the arguments of a captured graph
+ * are frozen, the word is not.  std_split (HOST, n_split floats, copied): the std of every Split2d's draw in decode order; n_split
+ * must be the plan's Split2d count.  While bound, glowhip_plan_decode accepts eps == NULL, n_eps < the Split2d count or
+ * eps[k] == NULL, and the prior kernel of such a Split2d draws its eps itself -- all three Split2d routes, no extra launch; a
+ * non-NULL eps[k] is injected as before.  Unbound, a missing eps is the error it always was.  advance != 0: a call that drew
+ * ends with a one-thread launch doing call += 1 on the device word (no host upload between the replays of a graph). */
+int glowhip_plan_bind_sampler(glowhip_plan* plan, void* rng_dev, const float* std_split, int n_split, int advance);
+/* Glow.reverse_flow(z=None) (network/model.py:454-471) as one call: the top draw, the decode and the store.
+ *   z_top    NULL: one launch computes the top prior -- zeros, or the head attached with glowhip_plan_set_head (learn_top and / or
+ *            y_emb(y_onehot), y_onehot from glowhip_plan_bind_head), plus the optional dense base prior_mean / prior_logs
+ *            (N,Cz,Hz,Wz, batch stride prior_stride) -- and writes z = mean + exp(logs) * draw, draw = stream 0 times std_top; no
+ *            dense mean / logs exist in HBM.  Non-NULL: that latent is decoded as given.
+ *   eps      as for glowhip_plan_decode with the sampler bound: NULL entries are drawn in the Split2d kernels.
+ *   x, x_u8  outputs (one may be NULL): fp32 pixels, and / or 8-bit pixels u8 = (uint8) min(max(x * 255, 0), 255), truncating,
+ *            NaN -> 0 -- the reference's tensor_to_ndarray (misc/util.py:405-407) on every pixel in [0, 1], saturating where its cast
+ *            would wrap -- stored by the final un-squeeze itself; x_u8 needs a plan that starts with a Squeeze2d.
+ *   z_out    NULL, or receives the top latent that was decoded.
+ * A sampler must be bound unless z_top and every eps are given; with `advance` bound the call's last launch moves the device
+ * position by one.  No allocation, no host sync: the call can be captured into a hipGraph. */
+int glowhip_plan_sample(glowhip_plan* plan, const void* packed, const float* z_top, const float* prior_mean, const float* prior_logs,
+                        long prior_stride, float std_top, const float* const* eps, int n_eps, float* x, uint8_t* x_u8, float* z_out,
+                        int N, void* workspace, size_t workspace_bytes, glowhip_stream_t stream);
+
 /* Data-dependent ActNorm initialisation pass over a whole plan (first training-mode forward,
  * network/trainer.py:112-115 + network/module.py:45-46,66-67): runs encode on x and writes every
  * ActNorm's bias/logs THROUGH the parameter pointers of the layer descs (which must be writable).  Ends with

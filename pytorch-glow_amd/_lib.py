@@ -168,6 +168,9 @@ SIGNATURES = {
     "glowhip_plan_set_dequant_rng": (c_int, [_P, ctypes.c_ulonglong, c_int, POINTER(ctypes.c_ulonglong)]),
     "glowhip_plan_set_dequant_stream": (c_int, [_P, ctypes.c_ulonglong, ctypes.c_ulonglong]),
     "glowhip_dequant_noise": (c_int, [_P, c_long, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, _P]),
+    "glowhip_normal_noise": (c_int, [_P, c_long, ctypes.c_ulonglong, ctypes.c_ulonglong, c_int, c_float, _P]),
+    "glowhip_plan_bind_sampler": (c_int, [_P, _P, POINTER(c_float), c_int, c_int]),
+    "glowhip_plan_sample": (c_int, [_P, _P, _P, _P, _P, c_long, c_float, POINTER(c_void_p), c_int, _P, _P, _P, c_int, _P, c_size_t, _P]),
     "glowhip_plan_actnorm_init": (c_int, [_P, _P, c_size_t, _P, _P, c_float, c_int, _P, c_size_t, _P]),
     "glowhip_plan_output_shape": (c_int, [_P, c_int, POINTER(c_int32)]),
     "glowhip_plan_describe": (c_int, [_P, c_char_p, c_size_t]),

@@ -298,6 +298,75 @@ class FlowPlan:
         check(lib().glowhip_dequant_noise(ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), int(call), int(n_bits), stream_ptr(self.device)))
         return out
 
+    # ------------------------------------------------------------------ the sampler's stream (csrc/sampler_rng.h)
+    def normal_noise(self, shape, seed, call, stream, std=1.0) -> torch.Tensor:
+        """Stream ``stream`` (0 = the top latent, 1 + k = the k-th Split2d in decode order) at position ``(seed, call)`` as a
+        tensor, times ``std``: the draw the kernels make in place (glowhip_normal_noise)."""
+        out = torch.empty(tuple(shape), dtype=torch.float32, device=self.device)
+        check(lib().glowhip_normal_noise(ptr(out), out.numel(), int(seed) & _U64, int(call), int(stream), float(std),
+                                         stream_ptr(self.device)))
+        return out
+
+    def sampler_position(self, seed, call) -> torch.Tensor:
+        """A device word ``{seed, call}`` for `bind_sampler` (two uint64 kept in an int64 tensor)."""
+        return torch.tensor([_i64(int(seed) & _U64), _i64(int(call))], dtype=torch.int64, device=self.device)
+
+    @staticmethod
+    def read_position(pos: torch.Tensor):
+        """``(seed, call)`` held by a device word (synchronises)."""
+        seed, call = (int(v) & _U64 for v in pos.cpu().tolist())
+        return seed, call
+
+    def bind_sampler(self, pos: Optional[torch.Tensor], std_split: Sequence[float] = (), advance: bool = False) -> None:
+        """Bind the stream at the device word ``pos`` (glowhip_plan_bind_sampler; ``None`` unbinds): while bound, `decode` draws
+        the eps of every Split2d it is given ``None`` for inside that split's prior kernel, with ``std_split[k]`` (decode order).
+        ``advance``: a call that drew ends with ``call += 1`` on the device word."""
+        if pos is None:
+            check(lib().glowhip_plan_bind_sampler(self._h, None, None, 0, 0))
+            self._sampler_pos = None
+            return
+        if pos.device != self.device or pos.dtype != torch.int64 or pos.numel() != 2 or not pos.is_contiguous():
+            raise _lib.GlowHipError(f"bind_sampler: the position is two int64 words on {self.device} (sampler_position)")
+        stds = [float(v) for v in std_split]
+        if len(stds) != self.n_split:
+            raise _lib.GlowHipError(f"bind_sampler: {len(stds)} stds given, the plan has {self.n_split} Split2d layers")
+        arr = (ctypes.c_float * max(len(stds), 1))(*stds)
+        check(lib().glowhip_plan_bind_sampler(self._h, ptr(pos), arr, len(stds), int(bool(advance))))
+        self._sampler_pos = pos      # (the C plan holds its address)
+
+    def sample(self, n, std_top=1.0, z=None, eps=None, head=None, want_x=True, want_u8=False, out=None, prior=None):
+        """glowhip_plan_sample: the top draw (``z=None``; from the attached head's prior, labels through ``head``), the decode
+        and the store in one C call, with the sampler bound by `bind_sampler` supplying every draw not injected through ``z`` /
+        ``eps[k]``.  Returns ``(x, x_u8, z_used)`` -- fp32 pixels (``want_x``), 8-bit pixels (``want_u8``; stored by the final
+        un-squeeze) and the top latent that was decoded.  ``out``: the three buffers to write instead of fresh ones (None
+        entries for outputs not wanted).  ``prior``: a dense ``(mean, logs)`` base of shape (n,) + out_chw added to the head's.  No packing here: `ensure_packed(use=PACK_INFERENCE | PACK_INVERSE)` first."""
+        dev = self.device
+        if out is None:
+            x = torch.empty((n,) + self.in_chw, dtype=torch.float32, device=dev) if want_x else None
+            x8 = torch.empty((n,) + self.in_chw, dtype=torch.uint8, device=dev) if want_u8 else None
+            z_used = torch.empty((n,) + self.out_chw, dtype=torch.float32, device=dev)
+        else:
+            x, x8, z_used = out
+        if n == 0:
+            return x, x8, z_used
+        if z is not None:
+            assert tuple(z.shape) == (n,) + self.out_chw, (z.shape, self.out_chw)
+        eps = [None] * self.n_split if eps is None else list(eps)
+        assert len(eps) >= self.n_split
+        if getattr(self, "_sampler_pos", None) is None and (z is None or any(e is None for e in eps[:self.n_split])):
+            raise _lib.GlowHipError("sample: a draw is needed and no sampler is bound (bind_sampler)")
+        if z is None or head is not None:      # (a given top latent needs no prior: no labels, no head call)
+            self._bind_head(head)
+        ws = self._workspace(n)
+        arr = (ctypes.c_void_p * max(len(eps), 1))(*[_p(e) for e in eps])
+        pm, pl = (None, None) if prior is None else prior
+        for t in (pm, pl):
+            assert t is None or (t.is_contiguous() and t.dtype == torch.float32 and tuple(t.shape) == (n,) + self.out_chw)
+        per = self.out_chw[0] * self.out_chw[1] * self.out_chw[2]
+        check(lib().glowhip_plan_sample(self._h, ptr(self.packed), ptr(z), ptr(pm), ptr(pl), per, float(std_top), arr, len(eps), ptr(x),
+                                        ptr(x8), ptr(z_used), n, ptr(ws), ws.numel(), stream_ptr(dev)))
+        return x, x8, z_used
+
     def describe(self, n: int = 0) -> str:
         """Kernel selection per layer; with a batch size ``n`` the choices that depend on the grid size are resolved as a
         call with that batch resolves them (n = 0: what the shapes support)."""
@@ -332,17 +401,20 @@ class FlowPlan:
                 self._unbind_latents()
         return z, ld_out
 
-    def decode(self, z, eps: Sequence[torch.Tensor], logdet=None, want_logdet=False, repack=False):
+    def decode(self, z, eps: Sequence[Optional[torch.Tensor]], logdet=None, want_logdet=False, repack=False):
+        """``eps[k]`` may be ``None`` while a sampler is bound (`bind_sampler`): that Split2d draws its own."""
         n = z.shape[0]
         assert tuple(z.shape[1:]) == self.out_chw, (z.shape, self.out_chw)
         assert len(eps) >= self.n_split
+        if getattr(self, "_sampler_pos", None) is None and any(e is None for e in eps[:self.n_split]):
+            raise _lib.GlowHipError("decode: an eps entry is None and no sampler is bound (bind_sampler)")
         self.ensure_packed(repack, use=self.PACK_INFERENCE | self.PACK_INVERSE)
         x = torch.empty((n,) + self.in_chw, dtype=torch.float32, device=self.device)
         ld_out = torch.empty(n, dtype=torch.float32, device=self.device) if want_logdet else None
         if n == 0:
             return x, ld_out
         ws = self._workspace(n)
-        arr = (ctypes.c_void_p * max(len(eps), 1))(*[e.data_ptr() for e in eps])
+        arr = (ctypes.c_void_p * max(len(eps), 1))(*[_p(e) for e in eps])
         check(lib().glowhip_plan_decode(self._h, ptr(self.packed), ptr(z), arr, len(eps), ptr(logdet), ptr(x), ptr(ld_out),
                                         n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         return x, ld_out
@@ -570,6 +642,14 @@ class FlowPlan:
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+_U64 = 2 ** 64 - 1
+
+
+def _i64(v: int) -> int:
+    """The int64 with the bit pattern of the uint64 ``v``."""
+    return v - 2 ** 64 if v >= 2 ** 63 else v
 
 
 class HeadCall:

@@ -1,6 +1,7 @@
 // conv_mfma.h -- MFMA (fp32-input, exact fp32) convolution kernels of the coupling network.
 #pragma once
 #include "common.h"
+#include "sampler_rng.h"
 
 namespace glowhip {
 
@@ -32,7 +33,7 @@ enum TailMode {
     TAIL_ADD_FWD,        // z2 = z2 + h
     TAIL_ADD_REV,        // z2 = z2 - h
     TAIL_SPLIT_FWD,      // acc += logp(z2 | mean, logs); z2_out (optional) = (z2 - mean) * exp(-logs), the implied draw
-    TAIL_SPLIT_REV,      // z2_out = mean + exp(logs) * eps   (eps passed as z2_in)
+    TAIL_SPLIT_REV,      // z2_out = mean + exp(logs) * eps   (eps passed as z2_in, or drawn from TailConvArgs::rng)
 };
 struct TailConvArgs {
     const float* x; long x_bs;   // (N,Cin,H,W)
@@ -46,6 +47,7 @@ struct TailConvArgs {
     unsigned long long* acc;
     const float* zeros;          // >= 16 B of zeros in global memory (16-byte aligned), or null: no LDS-DMA kernels
     float* hout;                 // optional (training tape): (N,Cout,HW) <- (conv + bias) * scale
+    SamplerSpec rng;             // TAIL_SPLIT_REV with z2_in == null: eps is drawn in the epilogue (sampler_rng.h)
 };
 constexpr int TAIL_CK = 32;  // input channels per LDS chunk of the tail kernel
 // number of 16-row MFMA tiles on the out-channel axis

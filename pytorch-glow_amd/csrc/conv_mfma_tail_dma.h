@@ -67,8 +67,10 @@ __device__ __forceinline__ double tail_epilogue(const TailConvArgs& a, const f32
                         ld += (double)gauss_logp1_(A_, B_, z2);
                         // full-latent encode: the draw this z2 is under the prior, what TAIL_SPLIT_REV takes back as z2_in
                         if (a.z2_out) a.z2_out[zo] = (z2 - A_) * expf(-B_);
-                    } else {  // TAIL_SPLIT_REV
-                        a.z2_out[zo] = A_ + expf(B_) * a.z2_in[zi];
+                    } else {  // TAIL_SPLIT_REV: the injected draw, or the stream's element at the draw tensor's flat (n, c, p) index
+                        const float draw = a.z2_in ? a.z2_in[zi]
+                                                   : sampler_draw(a.rng, (unsigned long long)((n * (a.Cout / 2) + c) * HW + p));
+                        a.z2_out[zo] = A_ + expf(B_) * draw;
                     }
                 }
             } else {

@@ -371,14 +371,23 @@ static DnScratch dn_carve(const DnetLevel& L, void* base) {
     return d;
 }
 
+// zero two 16-byte aligned ranges (n16a, n16b: their sizes in 16-byte words)
+__global__ void __launch_bounds__(256) k_dn_zero(uint4* __restrict__ a, long n16a, uint4* __restrict__ b, long n16b) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16a + n16b; i += (long)gridDim.x * 256) {
+        if (i < n16a) a[i] = make_uint4(0u, 0u, 0u, 0u);
+        else b[i - n16a] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
 int dnet_level_begin(const DnetLevel& L, hipStream_t s) {
     // the padded tensors' borders are zero for the whole level: nothing ever writes them
     const DnScratch d = dn_carve(L, L.scratch);
-    if (hipMemsetAsync(d.ypad, 0, (size_t)4 * (L.C / 2) * d.SLN, s) != hipSuccess ||
-        hipMemsetAsync(d.h2pad, 0, (size_t)4 * L.hidden * d.SLN, s) != hipSuccess) {
-        set_error("dnet: hipMemsetAsync of the padded operands failed");
-        return GLOWHIP_ELAUNCH;
-    }
+    const size_t ya = (size_t)4 * (L.C / 2) * d.SLN, hb = (size_t)4 * L.hidden * d.SLN;
+    GH_REQUIRE(ya % 16 == 0 && hb % 16 == 0, "dnet: padded operands of C=%d, hidden=%d are not whole 16-byte words", L.C, L.hidden);
+    const long n16 = (long)(ya + hb) / 16;
+    hipLaunchKernelGGL(k_dn_zero, dim3((unsigned)std::min<long>((n16 + 255) / 256, 2048)), dim3(256), 0, s, (uint4*)d.ypad, (long)(ya / 16),
+                       (uint4*)d.h2pad, (long)(hb / 16));
+    GH_LAUNCH_CHECK("k_dn_zero");
     return GLOWHIP_OK;
 }
 

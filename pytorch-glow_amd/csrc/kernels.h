@@ -1,6 +1,7 @@
 // kernels.h -- internal launcher interface between the plan executor / C-ABI and the kernel files.
 #pragma once
 #include "common.h"
+#include "sampler_rng.h"
 
 namespace glowhip {
 
@@ -11,7 +12,13 @@ int launch_squeeze(const float* x, const float* noise, float* y, int N, int C, i
                    hipStream_t s, const RngSpec* rng = nullptr);
 int launch_squeeze_u8(const uint8_t* x, const float* noise, float* y, int N, int C, int H, int W, int f, float divisor,
                       hipStream_t s, const RngSpec* rng = nullptr);
+// factor-2 un-squeeze x (N,C,H,W) -> 8-bit pixels y8 (N,C/4,2H,2W) = (uint8) min(max(v * 255, 0), 255) (+ the fp32 pixels to y when given)
+int launch_unsqueeze2_u8(const float* x, uint8_t* y8, float* y, int N, int C, int H, int W, hipStream_t s);
 int launch_dequant_noise(float* out, long n, unsigned long long seed, unsigned long long call, float scale, hipStream_t s);
+// the sampler's stream (sampler_rng.h) as a tensor: out[i] = element i of (seed, call, stream) times std
+int launch_normal_noise(float* out, long n, unsigned long long seed, unsigned long long call, int stream, float std, hipStream_t s);
+// pos[1] += 1: the last launch of a call that drew from the stream with `advance` bound (pos = the device word {seed, call})
+int launch_sampler_advance(unsigned long long* pos, hipStream_t s);
 int launch_copy_strided(const float* x, long xbs, float* y, long ybs, int N, long per_sample, hipStream_t s);
 int launch_actnorm_init(const float* x, long xbs, int N, int C, int HW, float scale, float* bias, float* logs,
                         hipStream_t s, int batch_variance = 0);
@@ -55,10 +62,11 @@ int launch_coupling_tail(const CouplingTailArgs& a, hipStream_t s);
 struct SplitTailArgs {
     const float* h;        // (N, 2*Ch, HW): prior conv output, mean = even, logs = odd channels
     const float* z2; long z2_bs;   // forward: z2 to score
-    const float* eps;      // reverse: (N,Ch,HW) injected draw
+    const float* eps;      // reverse: (N,Ch,HW) injected draw, or null: drawn in the kernel from `rng`
     float* z2_out; long z2_out_bs; // reverse: sampled z2; forward (optional): the implied draw (z2 - mean) * exp(-logs)
     int N, Ch, HW, reverse;
     unsigned long long* acc;
+    SamplerSpec rng;       // reverse without eps: the stream of this split (sampler_rng.h)
 };
 int launch_split_tail(const SplitTailArgs& a, hipStream_t s);
 

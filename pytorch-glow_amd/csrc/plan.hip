@@ -266,9 +266,10 @@ static int run_coupling(glowhip_plan* P, const LayerPlan& L, const void* packed,
 
 // Split2d prior conv + tail (network/module.py:498-536).  d.C = channels of the un-split tensor.
 // Forward: z2_out (optional) receives the draw z2 implies under the prior, (z2 - mean) * exp(-logs) (glowhip_plan_bind_latents).
+// Reverse: eps == null draws it in the epilogue from `rng` (glowhip_plan_bind_sampler): same launches as with eps injected.
 static int run_split(glowhip_plan* P, const LayerPlan& L, const void* packed, const float* z1, long z1_bs, const float* z2, long z2_bs,
                      const float* eps, float* z2_out, long z2_out_bs, int N, int reverse, const Workspace& w,
-                     hipStream_t s) {
+                     hipStream_t s, const SamplerSpec& rng = SamplerSpec{}) {
     const glowhip_layer_desc& d = L.d;
     const int Ch = d.C / 2, HW = d.H * d.W;
     if (L.mfma_last) {
@@ -280,6 +281,7 @@ static int run_split(glowhip_plan* P, const LayerPlan& L, const void* packed, co
         t.z2_in = reverse ? eps : z2; t.z2_in_bs = reverse ? (long)Ch * HW : z2_bs;
         t.z2_out = z2_out; t.z2_out_bs = z2_out_bs; t.acc = w.acc;
         t.zeros = at<float>(packed, 64);
+        t.rng = rng;
         count_launch(P, conv_mfma_tail_takes_dma(t) ? "split_prior(k_conv_tail_dma)" : "split_prior(k_conv_tail)");
         GH_TRY(launch_conv_mfma_tail(t, s));
     } else {
@@ -287,7 +289,7 @@ static int run_split(glowhip_plan* P, const LayerPlan& L, const void* packed, co
                    N, Ch, d.H, d.W, L.Cout, 3};
         GH_TRY(launch_conv_direct(c, s));
         count_launch(P, "split_prior(k_split_tail)");
-        SplitTailArgs t{w.h1, z2, z2_bs, eps, z2_out, z2_out_bs, N, Ch, HW, reverse, w.acc};
+        SplitTailArgs t{w.h1, z2, z2_bs, eps, z2_out, z2_out_bs, N, Ch, HW, reverse, w.acc, rng};
         GH_TRY(launch_split_tail(t, s));
     }
     return GLOWHIP_OK;
@@ -442,8 +444,11 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
 }
 
 // ---------------------------------------------------------------- decode (network/model.py:278-294)
+// A Split2d without an injected eps (eps == null, k >= n_eps or eps[k] == null) draws stream 1 + k of the bound sampler
+// (sampler_rng.h) inside its prior kernel; *drawn (optional) receives how many did.  x_u8 (optional; layer 0 must be a
+// Squeeze2d): the final un-squeeze stores 8-bit pixels there -- and the fp32 ones to x_out only when that is given too.
 static int run_reverse(glowhip_plan* p, const void* packed, const float* z, const float* const* eps, int n_eps,
-                       float* x_out, int N, const Workspace& w, hipStream_t s) {
+                       float* x_out, int N, const Workspace& w, hipStream_t s, int* drawn = nullptr, uint8_t* x_u8 = nullptr) {
     const float* cur = z;
     const int nl = (int)p->layers.size();
     int ke = 0;
@@ -459,6 +464,10 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
         const long chw = (long)d.C * HW;
         const int Ch = d.C / 2;
         if (d.kind == GLOWHIP_LAYER_SQUEEZE) {
+            if (li == 0 && x_u8) {
+                count_launch(p, "unsqueeze(u8)");
+                GH_TRY(launch_unsqueeze2_u8(cur, x_u8, x_out, N, d.C * 4, d.H / 2, d.W / 2, s));
+            } else
             GH_TRY(launch_squeeze(cur, nullptr, dst, N, d.C * 4, d.H / 2, d.W / 2, 2, 1, s));
         } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
             float* z2 = dst + (long)Ch * HW;
@@ -519,14 +528,27 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
             ChanMixArgs m = chanmix_rev_args(L, packed, N, cur, z2, chw, dst);
             GH_TRY(run_chanmix(p, m, s));
         } else {  // SPLIT2D reverse: z1 = cur (N, C/2, HW) -> cat(z1, mean + exp(logs)*eps)
-            GH_REQUIRE(ke < n_eps && eps && eps[ke], "decode: missing eps draw for Split2d #%d", ke);
-            GH_TRY(run_split(p, L, packed, cur, (long)Ch * HW, nullptr, 0, eps[ke], dst + (long)Ch * HW, chw, N, 1, w, s));
+            const float* e = (eps && ke < n_eps) ? eps[ke] : nullptr;
+            GH_REQUIRE(e || p->sampler_pos, "decode: missing eps draw for Split2d #%d", ke);
+            SamplerSpec rng{};
+            if (!e) {
+                rng = SamplerSpec{p->sampler_pos, 1 + ke, p->sampler_std[ke]};
+                if (drawn) ++*drawn;
+            }
+            GH_TRY(run_split(p, L, packed, cur, (long)Ch * HW, nullptr, 0, e, dst + (long)Ch * HW, chw, N, 1, w, s, rng));
             GH_TRY(launch_copy_strided(cur, (long)Ch * HW, dst, chw, N, (long)Ch * HW, s));
             ++ke;
         }
         cur = dst;
     }
     return GLOWHIP_OK;
+}
+
+// the last launch of a call that drew from the bound sampler with `advance`: the next call draws at call + 1
+static int advance_sampler(glowhip_plan* plan, int drawn, hipStream_t s) {
+    if (!drawn || !plan->sampler_advance) return GLOWHIP_OK;
+    count_launch(plan, "k_sampler_advance");
+    return launch_sampler_advance(plan->sampler_pos, s);
 }
 
 static int check_plan_args(const glowhip_plan* plan, const void* packed, int N) {
@@ -671,6 +693,30 @@ int glowhip_plan_describe_for(const glowhip_plan* plan, int N, char* buf, size_t
     return GLOWHIP_OK;
 }
 
+int glowhip_normal_noise(float* out, long n, unsigned long long seed, unsigned long long call, int stream_id, float std,
+                         glowhip_stream_t stream) {
+    GH_REQUIRE(out && n >= 0, "normal_noise: bad argument");
+    GH_REQUIRE(stream_id >= 0 && stream_id <= 254, "normal_noise: stream %d out of range (0 = top latent, 1 + k = Split2d k; at most 254 splits)", stream_id);
+    GH_REQUIRE(call < (1ull << 56), "normal_noise: call numbers end at 2^56");
+    return launch_normal_noise(out, n, seed, call, stream_id, std, (hipStream_t)stream);
+}
+
+int glowhip_plan_bind_sampler(glowhip_plan* plan, void* rng_dev, const float* std_split, int n_split, int advance) {
+    GH_REQUIRE(plan, "plan_bind_sampler: null plan");
+    if (!rng_dev) {
+        plan->sampler_pos = nullptr; plan->sampler_std.clear(); plan->sampler_advance = false;
+        return GLOWHIP_OK;
+    }
+    GH_REQUIRE(n_split == plan->n_split, "plan_bind_sampler: %d stds given, plan has %d Split2d layers", n_split, plan->n_split);
+    GH_REQUIRE(n_split <= 254, "plan_bind_sampler: %d Split2d layers, the stream layout numbers at most 254", n_split);
+    GH_REQUIRE(n_split == 0 || std_split, "plan_bind_sampler: null std list");
+    GH_REQUIRE(((size_t)rng_dev & 7) == 0, "plan_bind_sampler: the position word must be 8-byte aligned");
+    plan->sampler_pos = (unsigned long long*)rng_dev;
+    plan->sampler_std.assign(std_split, std_split + n_split);
+    plan->sampler_advance = advance != 0;
+    return GLOWHIP_OK;
+}
+
 int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps) {
     GH_REQUIRE(plan, "plan_bind_latents: null plan");
     if (!eps_out && n_eps == 0) {
@@ -715,17 +761,46 @@ int glowhip_plan_decode(glowhip_plan* plan, const void* packed, const float* z, 
                         size_t workspace_bytes, glowhip_stream_t stream) {
     GH_TRY(check_plan_args(plan, packed, N));
     GH_REQUIRE(x && z, "plan_decode: null tensor");
-    GH_REQUIRE(n_eps >= plan->n_split, "plan_decode: %d eps draws given, plan has %d Split2d layers", n_eps,
-               plan->n_split);
+    GH_REQUIRE(plan->sampler_pos || n_eps >= plan->n_split, "plan_decode: %d eps draws given, plan has %d Split2d layers", n_eps,
+               plan->n_split);      // (with a sampler bound, the missing ones are drawn)
     if (N == 0) return GLOWHIP_OK;
     hipStream_t s = (hipStream_t)stream;
     Workspace w;
     GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // decode reads W^-1 and the deep levels' images first
-    GH_TRY(run_reverse(plan, packed, z, eps, n_eps, x, N, w, s));
+    int drawn = 0;
+    GH_TRY(run_reverse(plan, packed, z, eps, n_eps, x, N, w, s, &drawn));
     if (logdet_out)
         GH_TRY(launch_finalize(logdet_in, w.acc, at<double>(packed, 0), -1.0, 0.0, 1.0, logdet_out, nullptr, N, s, ACC_EXTRA));
-    return GLOWHIP_OK;
+    return advance_sampler(plan, drawn, s);
+}
+
+int glowhip_plan_sample(glowhip_plan* plan, const void* packed, const float* z_top, const float* prior_mean, const float* prior_logs,
+                        long prior_stride, float std_top, const float* const* eps, int n_eps, float* x, uint8_t* x_u8, float* z_out,
+                        int N, void* workspace, size_t workspace_bytes, glowhip_stream_t stream) {
+    GH_TRY(check_plan_args(plan, packed, N));
+    GH_REQUIRE(x || x_u8, "plan_sample: no output (x and x_u8 are both null)");
+    GH_REQUIRE(!x_u8 || (!plan->layers.empty() && plan->layers[0].d.kind == GLOWHIP_LAYER_SQUEEZE),
+               "plan_sample: 8-bit output needs a plan that starts with a Squeeze2d layer");
+    GH_REQUIRE(z_top || plan->sampler_pos, "plan_sample: no top latent given and no sampler bound (glowhip_plan_bind_sampler)");
+    if (N == 0) return GLOWHIP_OK;
+    hipStream_t s = (hipStream_t)stream;
+    Workspace w;
+    GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
+    GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));
+    int drawn = 0;
+    const long zchw = (long)plan->out_shape[0] * plan->out_shape[1] * plan->out_shape[2];
+    const float* z = z_top;
+    if (!z_top) {      // the top latent from the prior, into the caller's buffer or the workspace (where the decode's ping-pong begins)
+        float* zb = z_out ? z_out : w.bufA;
+        GH_TRY(launch_top_sample(plan, prior_mean, prior_logs, prior_stride, SamplerSpec{plan->sampler_pos, 0, std_top}, zb, N, s));
+        z = zb;
+        ++drawn;
+    } else if (z_out && z_out != z_top) {
+        GH_TRY(launch_copy_strided(z_top, zchw, z_out, zchw, N, zchw, s));
+    }
+    GH_TRY(run_reverse(plan, packed, z, eps, n_eps, x, N, w, s, &drawn, x_u8));
+    return advance_sampler(plan, drawn, s);
 }
 
 int glowhip_glow_forward(glowhip_plan* plan, const void* packed, const float* x, const float* noise,

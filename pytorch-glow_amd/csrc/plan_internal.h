@@ -92,6 +92,9 @@ struct glowhip_plan {
     std::vector<glowhip::LogsJob> logs_jobs;   // the same for the log-scale gradients derived from dW / db (backward.h)
     std::vector<glowhip::GradJob> grad_jobs;   // host copy of the last backward's finalize table (kept alive for the async copy)
     bool rng_on = false; unsigned long long rng_seed = 0, rng_calls = 0;   // in-kernel dequantisation noise (glowhip_plan_set_dequant_rng)
+    // glowhip_plan_bind_sampler: the device word {seed, call} (null = nothing bound), the std of every Split2d's draw in DECODE
+    // order, and whether a call that drew ends with call += 1 on the device
+    unsigned long long* sampler_pos = nullptr; std::vector<float> sampler_std; bool sampler_advance = false;
     std::vector<std::pair<int, hipEvent_t>> bwd_marks;   // (layer index, event): glowhip_plan_backward_marks
     int family = GLOWHIP_FAMILY_AUTO;          // kernel family of the coupling networks (glowhip_plan_set_family): a property of the plan
     // top head (tophead.hip): learned / class-conditional prior + classifier, its per-call io and gradient bindings

@@ -17,16 +17,10 @@ namespace glowhip {
 // the caller's seed, counter = (element index / 4, call number); element i takes word i % 4.  No noise tensor in HBM, no
 // separate RNG launch; the same stream is available as a tensor through glowhip_dequant_noise (parity tests).
 __device__ __forceinline__ float dequant_noise(unsigned long long seed, unsigned long long call, unsigned long long i, float scale) {
-    unsigned int c0 = (unsigned int)(i >> 2), c1 = (unsigned int)(i >> 34), c2 = (unsigned int)call, c3 = (unsigned int)(call >> 32);
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned int)p1; c3 = (unsigned int)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const unsigned int w = (i & 3) == 0 ? c0 : ((i & 3) == 1 ? c1 : ((i & 3) == 2 ? c2 : c3));
+    unsigned int v[4];
+    philox4x32_10((unsigned int)(i >> 2), (unsigned int)(i >> 34), (unsigned int)call, (unsigned int)(call >> 32), (unsigned int)seed,
+                  (unsigned int)(seed >> 32), v);      // (sampler_rng.h: the round function the sampler's stream shares)
+    const unsigned int w = (i & 3) == 0 ? v[0] : ((i & 3) == 1 ? v[1] : ((i & 3) == 2 ? v[2] : v[3]));
     return (float)(w >> 8) * (1.0f / 16777216.0f) * scale;          // 24 uniform bits in [0, 1), exact in fp32
 }
 
@@ -40,6 +34,45 @@ int launch_dequant_noise(float* out, long n, unsigned long long seed, unsigned l
     if (n == 0) return GLOWHIP_OK;
     hipLaunchKernelGGL(k_dequant_noise, dim3(cdiv(n, 256)), dim3(256), 0, s, out, n, seed, call, scale);
     GH_LAUNCH_CHECK("k_dequant_noise");
+    return GLOWHIP_OK;
+}
+
+// The sampler's stream as a tensor (sampler_rng.h; twin of k_dequant_noise): a thread owns one group of four elements -- one Philox
+// evaluation, one 16-byte store where the group is whole and `out` is 16-byte aligned.
+__global__ void __launch_bounds__(256) k_normal_noise(float* __restrict__ out, long n, unsigned long long seed, unsigned long long call,
+                                                      int stream, float std, int aligned) {
+    const long j = (long)blockIdx.x * 256 + threadIdx.x;
+    if (4 * j >= n) return;
+    unsigned int w[4];
+    sampler_words(seed, call, stream, (unsigned long long)j, w);
+    float e[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) e[q] = sampler_element(w, q, std);
+    if (aligned && 4 * j + 4 <= n) {
+        *reinterpret_cast<float4*>(out + 4 * j) = make_float4(e[0], e[1], e[2], e[3]);
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (4 * j + q < n) out[4 * j + q] = e[q];
+    }
+}
+
+int launch_normal_noise(float* out, long n, unsigned long long seed, unsigned long long call, int stream, float std, hipStream_t s) {
+    if (n == 0) return GLOWHIP_OK;
+    const long groups = (n + 3) / 4;
+    GH_REQUIRE((groups + 255) / 256 <= 0x7fffffffl, "normal_noise: %ld elements are more than one launch covers", n);
+    hipLaunchKernelGGL(k_normal_noise, dim3(cdiv(groups, 256)), dim3(256), 0, s, out, n, seed, call, stream, std, ((size_t)out & 15) == 0 ? 1 : 0);
+    GH_LAUNCH_CHECK("k_normal_noise");
+    return GLOWHIP_OK;
+}
+
+__global__ void __launch_bounds__(64) k_sampler_advance(unsigned long long* pos) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) pos[1] += 1ull;
+}
+
+int launch_sampler_advance(unsigned long long* pos, hipStream_t s) {
+    hipLaunchKernelGGL(k_sampler_advance, dim3(1), dim3(64), 0, s, pos);
+    GH_LAUNCH_CHECK("k_sampler_advance");
     return GLOWHIP_OK;
 }
 
@@ -104,16 +137,9 @@ __global__ void __launch_bounds__(256) k_squeeze_u8(const uint8_t* __restrict__ 
 // generic kernel evaluates all ten rounds per element and keeps one word of four).  32-bit index arithmetic, no LDS.  Same values,
 // bit for bit, as k_squeeze / k_squeeze_u8 (tests/test_gpu_parity.py, test_gpu_infer.py).
 __device__ __forceinline__ void dequant_noise4(unsigned long long seed, unsigned long long call, unsigned long long i4, float scale, float (&out)[4]) {
-    unsigned int c0 = (unsigned int)(i4 >> 2), c1 = (unsigned int)(i4 >> 34), c2 = (unsigned int)call, c3 = (unsigned int)(call >> 32);
-    unsigned int k0 = (unsigned int)seed, k1 = (unsigned int)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (unsigned int)p1; c3 = (unsigned int)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    const unsigned int w[4] = {c0, c1, c2, c3};
+    unsigned int w[4];
+    philox4x32_10((unsigned int)(i4 >> 2), (unsigned int)(i4 >> 34), (unsigned int)call, (unsigned int)(call >> 32), (unsigned int)seed,
+                  (unsigned int)(seed >> 32), w);
 #pragma unroll
     for (int q = 0; q < 4; ++q) out[q] = (float)(w[q] >> 8) * (1.0f / 16777216.0f) * scale;
 }
@@ -174,6 +200,65 @@ __global__ void __launch_bounds__(256) k_squeeze2_rev(const float* __restrict__ 
     float* o = y + (((long)n * Co + c) * 2 * H + 2 * h) * (2 * W) + 4 * k;
     *reinterpret_cast<float4*>(o) = make_float4(p[0].x, p[1].x, p[0].y, p[1].y);
     *reinterpret_cast<float4*>(o + 2 * W) = make_float4(p[2].x, p[3].x, p[2].y, p[3].y);
+}
+
+// The final un-squeeze of a sampler call with displayable bytes out: u8 = (uint8) min(max(x * 255, 0), 255), truncating, NaN -> 0
+// -- the reference's tensor_to_ndarray (misc/util.py:405-407) on every pixel in [0, 1], saturating where its cast would wrap.
+__device__ __forceinline__ unsigned int pixel_u8(float v) {
+    return (unsigned int)fminf(fmaxf(v * 255.0f, 0.f), 255.0f);      // (fmaxf(NaN, 0) = 0)
+}
+// k_squeeze2_rev's register transpose with 4-byte stores (a thread's four pixels of an output row are one uchar4); y (optional)
+// receives the fp32 pixels as k_squeeze2_rev writes them
+__global__ void __launch_bounds__(256) k_squeeze2_rev_u8(const float* __restrict__ x, uint8_t* __restrict__ y8, float* __restrict__ y,
+                                                         int C, int H, int W) {
+    const int W2 = W >> 1, Co = C >> 2;
+    const int per_img = Co * H * W2;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= per_img) return;
+    const int n = blockIdx.y;
+    const int k = t % W2, r = t / W2, h = r % H, c = r / H;
+    const float* in = x + ((long)n * C + 4 * c) * H * W + (long)h * W + 2 * k;
+    float2 p[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) p[q] = *reinterpret_cast<const float2*>(in + (long)q * H * W);
+    const long o = (((long)n * Co + c) * 2 * H + 2 * h) * (2 * W) + 4 * k;
+    *reinterpret_cast<uchar4*>(y8 + o) = make_uchar4(pixel_u8(p[0].x), pixel_u8(p[1].x), pixel_u8(p[0].y), pixel_u8(p[1].y));
+    *reinterpret_cast<uchar4*>(y8 + o + 2 * W) = make_uchar4(pixel_u8(p[2].x), pixel_u8(p[3].x), pixel_u8(p[2].y), pixel_u8(p[3].y));
+    if (y) {
+        *reinterpret_cast<float4*>(y + o) = make_float4(p[0].x, p[1].x, p[0].y, p[1].y);
+        *reinterpret_cast<float4*>(y + o + 2 * W) = make_float4(p[2].x, p[3].x, p[2].y, p[3].y);
+    }
+}
+// any width / alignment: one thread per output pixel (k_squeeze's reverse gather)
+__global__ void __launch_bounds__(256) k_unsqueeze2_u8(const float* __restrict__ x, uint8_t* __restrict__ y8, float* __restrict__ y,
+                                                       long total, int C, int H, int W) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= total) return;
+    const int Ho = H * 2, Wo = W * 2, Co = C / 4;
+    const int ww = (int)(idx % Wo);
+    long t = idx / Wo;
+    const int hh = (int)(t % Ho);
+    t /= Ho;
+    const int c = (int)(t % Co);
+    const long n = t / Co;
+    const int cs = c * 4 + (hh % 2) * 2 + (ww % 2);
+    const float v = x[((n * C + cs) * H + hh / 2) * (long)W + ww / 2];
+    y8[idx] = (uint8_t)pixel_u8(v);
+    if (y) y[idx] = v;
+}
+
+int launch_unsqueeze2_u8(const float* x, uint8_t* y8, float* y, int N, int C, int H, int W, hipStream_t s) {
+    GH_REQUIRE(C >= 4 && C % 4 == 0, "unsqueeze2d(u8): C must be a multiple of 4");
+    const long total = (long)N * C * H * W;
+    if (total == 0) return GLOWHIP_OK;
+    if (W % 2 == 0 && N <= 65535 && (long)C * H * W < (1l << 31) && ((size_t)x & 7) == 0 && ((size_t)y8 & 3) == 0 && ((size_t)y & 15) == 0) {
+        hipLaunchKernelGGL(k_squeeze2_rev_u8, dim3(cdiv((long)(C / 4) * H * (W / 2), 256), N), dim3(256), 0, s, x, y8, y, C, H, W);
+        GH_LAUNCH_CHECK("k_squeeze2_rev_u8");
+        return GLOWHIP_OK;
+    }
+    hipLaunchKernelGGL(k_unsqueeze2_u8, dim3(cdiv(total, 256)), dim3(256), 0, s, x, y8, y, total, C, H, W);
+    GH_LAUNCH_CHECK("k_unsqueeze2_u8");
+    return GLOWHIP_OK;
 }
 
 int launch_squeeze_u8(const uint8_t* x, const float* noise, float* y, int N, int C, int H, int W, int f, float divisor,
@@ -621,7 +706,8 @@ __global__ void __launch_bounds__(256) k_split_tail(SplitTailArgs a) {
             lp = (double)gauss_logp1(mean, logs, z2);
             if (a.z2_out) a.z2_out[n * a.z2_out_bs + e] = (z2 - mean) * expf(-logs);   // full-latent encode: the implied draw
         } else {
-            a.z2_out[n * a.z2_out_bs + e] = mean + expf(logs) * a.eps[n * per + e];
+            const float draw = a.eps ? a.eps[n * per + e] : sampler_draw(a.rng, (unsigned long long)(n * per + e));
+            a.z2_out[n * a.z2_out_bs + e] = mean + expf(logs) * draw;
         }
     }
     if (!a.reverse && a.acc) {

@@ -261,6 +261,25 @@ __global__ void __launch_bounds__(256) k_top_prior(glowhip_head_desc h, const fl
     }
 }
 
+// The sampler's top latent (reference network/model.py:466-468, GaussianDiag.sample network/module.py:470-483): the prior row of
+// k_top_prior in LDS (zeros without a head), then z = mean + exp(logs) * draw -- the draw is stream 0 of the sampler at the
+// element's flat index (sampler_rng.h), pm / pl the optional dense base as in k_top_head_fwd
+__global__ void __launch_bounds__(256) k_top_sample(glowhip_head_desc h, const float* __restrict__ y_onehot, int C, int HW,
+                                                    const float* __restrict__ pm, const float* __restrict__ pl, long p_bs,
+                                                    SamplerSpec rng, float* __restrict__ z) {
+    extern __shared__ float sm[];
+    const long n = blockIdx.x;
+    head_prior_row(h, y_onehot ? y_onehot + n * h.K : nullptr, 2 * C, sm, nullptr, nullptr);
+    __syncthreads();
+    const long per = (long)C * HW;
+    for (long e = threadIdx.x; e < per; e += 256) {
+        const int c = (int)(e / HW);
+        const float mean = pm ? sm[c] + pm[n * p_bs + e] : sm[c];
+        const float logs = pl ? sm[C + c] + pl[n * p_bs + e] : sm[C + c];
+        z[n * per + e] = mean + expf(logs) * sampler_draw(rng, (unsigned long long)(n * per + e));
+    }
+}
+
 int check_head_desc(const glowhip_head_desc* h, int C) {
     GH_REQUIRE(h->K >= 0 && h->K <= 4096, "top head: K=%d out of range", h->K);
     GH_REQUIRE(C > 0 && ((size_t)3 * C + h->K) * 4 <= 48 * 1024, "top head: C=%d, K=%d do not fit the head kernels' LDS", C, h->K);
@@ -296,6 +315,20 @@ int launch_top_logp(glowhip_plan* plan, const float* z, const float* prior_mean,
     hipLaunchKernelGGL(k_top_head_fwd, dim3(N), dim3(256), (size_t)(3 * C + h.K) * 4, s, a);
     GH_LAUNCH_CHECK("k_top_head_fwd");
     count_launch(plan, "k_top_head_fwd");
+    return GLOWHIP_OK;
+}
+
+int launch_top_sample(glowhip_plan* plan, const float* prior_mean, const float* prior_logs, long prior_stride, const SamplerSpec& rng,
+                      float* z, int N, hipStream_t s) {
+    const int* o = plan->out_shape;
+    const int C = o[0], HW = o[1] * o[2];
+    GH_REQUIRE((size_t)2 * C * 4 <= 48 * 1024, "top sample: C=%d does not fit the kernel's LDS", C);
+    const glowhip_head_desc h = plan->head_on ? plan->head : glowhip_head_desc{};
+    const float* yo = plan->head_on ? plan->head_io.y_onehot : nullptr;
+    GH_REQUIRE(!h.ye_w || yo, "top sample: a class-conditional prior needs y_onehot (glowhip_plan_bind_head)");
+    hipLaunchKernelGGL(k_top_sample, dim3(N), dim3(256), (size_t)2 * C * 4, s, h, yo, C, HW, prior_mean, prior_logs, prior_stride, rng, z);
+    GH_LAUNCH_CHECK("k_top_sample");
+    count_launch(plan, "k_top_sample");
     return GLOWHIP_OK;
 }
 

@@ -34,11 +34,44 @@ class Inferer:
         self.y_condition = self.hps.ablation.y_condition
         self.device = self.graph.h_top.device
 
-    def sample(self, z, y_onehot, eps_std=0.5):
+    def sample(self, z, y_onehot, eps_std=0.5, *, in_kernel=False, uint8=False, seed=None, call=None):
         """Images drawn from the model (z=None: the top latent is sampled too), inferer.py:41-62.  ``eps_std``: one temperature,
-        or one per level in decode order (the top prior's first, then every Split2d's from the deepest)."""
+        or one per level in decode order (the top prior's first, then every Split2d's from the deepest).
+        ``in_kernel=True`` (or a ``seed`` / ``call`` / ``uint8``; only with ``z=None``): the sampler route, `Glow.sample` --
+        every draw is made inside the kernel that consumes it and the batch is named by its ``(seed, call)``.  The images are
+        distributed the same; the bits differ from the default route, whose draws are torch's."""
         with torch.no_grad():
+            if in_kernel or uint8 or seed is not None or call is not None:
+                assert z is None, "the sampler route draws the top latent itself"
+                return self.graph.sample(y_onehot=y_onehot, eps_std=eps_std, uint8=uint8, seed=seed, call=call)
             return self.graph(z=z, y_onehot=y_onehot, eps_std=eps_std, reverse=True)
+
+    def resample_details(self, img, levels, eps_std=None, seed=None, call=None):
+        """Variations of an image that keep its layout: the image's full latents (`encode_full`) are decoded with the top latent
+        and the deepest Split2d draws as they are, while the finest ``levels`` Split2d layers draw afresh inside their kernels
+        (the sampler's stream at ``(seed, call)``, or the process's position).  ``levels=0`` is `reconstruct`.  ``eps_std``: the
+        std of the fresh draws (a number, or one per level as for `sample`)."""
+        from .model import sampler_position, sampler_stds
+        with torch.no_grad():
+            lat = self.encode_full(img)
+            flow = self.graph.flow
+            plan = flow.plan_for(flow.in_chw, self.device)
+            n_split = plan.n_split
+            assert 0 <= levels <= n_split, f"levels = {levels}: the model has {n_split} Split2d layers"
+            if levels == 0:
+                out = self.decode_full(lat)
+                return out[0] if img.dim() == 3 else out
+            eps = list(lat.eps[:n_split - levels]) + [None] * levels      # decode order: the finest splits come last
+            key, c = sampler_position(advance=seed is None and call is None)
+            key = key if seed is None else int(seed) & (2 ** 64 - 1)
+            c = c if call is None else int(call)
+            plan.ensure_packed(use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
+            plan.bind_sampler(plan.sampler_position(key, c), sampler_stds(eps_std, flow.L)[1], advance=False)
+            try:
+                out, _, _ = plan.sample(len(lat), z=lat.z, eps=eps)      # (z is given: the prior is not evaluated)
+            finally:
+                plan.bind_sampler(None)
+            return out[0] if img.dim() == 3 else out
 
     def encode(self, img):
         """Latent of ONE image (C,H,W tensor; a batch is accepted and its first latent returned), inferer.py:64-85."""

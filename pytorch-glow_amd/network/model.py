@@ -330,6 +330,126 @@ def dequant_position(advance=False):
     return (seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 64 - 1), call
 
 
+# The sampler's position (csrc/sampler_rng.h): ONE per process beside the dequantisation stream -- the key is torch's seed with the
+# rank folded in, the call number counts the implicit `Glow.sample` calls.  The kernels read the position from a device word (one
+# per device, created lazily): "holds" is what that word contains once everything enqueued has run, so it is uploaded only when a
+# call needs another position than the device reached by counting itself.
+_SAMPLER_STREAM = {"seed": None, "calls": 0, "words": {}}
+
+
+def reset_sampler_stream():
+    _SAMPLER_STREAM["seed"], _SAMPLER_STREAM["calls"] = None, 0
+
+
+def sampler_position(advance=False):
+    """(key, call) the next implicit `Glow.sample` draws with; advance=True consumes it."""
+    import torch.distributed as dist
+    seed = torch.initial_seed()
+    st = _SAMPLER_STREAM
+    if st["seed"] != seed:
+        st["seed"], st["calls"] = seed, 0
+    call = st["calls"]
+    if advance:
+        st["calls"] += 1
+    rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
+    return (seed + 0x9E3779B97F4A7C15 * rank) & (2 ** 64 - 1), call
+
+
+def _sampler_word(plan, key, call):
+    """The process's device word on the plan's device, holding (key, call): [tensor, (key, call) it holds]."""
+    words = _SAMPLER_STREAM["words"]
+    ent = words.get(str(plan.device))
+    if ent is None:
+        ent = words[str(plan.device)] = [plan.sampler_position(key, call), (key, call)]
+    elif ent[1] != (key, call):
+        ent[0].copy_(plan.sampler_position(key, call))
+        ent[1] = (key, call)
+    return ent
+
+
+def sampler_stds(eps_std, L):
+    """`level_eps_stds` as the numbers the sampler kernels multiply by: (std of the top draw, [std per Split2d, decode order]),
+    every entry following the reference's ``eps_std or 1.`` (network/module.py:419)."""
+    top, splits = level_eps_stds(eps_std, L)
+    return float(top or 1.), [float(v or 1.) for v in splits]
+
+
+class GraphedSampler:
+    """`Glow.sample` for one batch size, captured in a hipGraph: ONE graph launch per batch of images.
+
+    Static buffers: ``y_onehot`` (class-conditional models: write the labels in, or pass them to __call__), ``x`` (fp32 pixels)
+    or ``x_u8`` (8-bit pixels, ``uint8=True``), ``z`` (the top latent of the last replay).  The captured body is
+    `FlowPlan.sample` alone -- the top draw, the decode, the store and the one-thread launch that moves the device position --
+    a single linear chain of kernels: no pack (the plan is packed and synchronised before the capture), no side stream.  Every
+    replay draws at the position the previous one left: replay r after a capture at ``(seed, call)`` is
+    ``Glow.sample(seed=seed, call=call + r)`` bit for bit.  A changed parameter, a re-allocated one or a pack for the other
+    kernel family needs a new capture.  No range fall-back inside a graph."""
+
+    def __init__(self, glow, n, y_onehot=None, eps_std=None, uint8=False, seed=None, call=0):
+        assert not glow.training, "capture_sampler is the inference path: call glow.eval() first"
+        dev = glow.h_top.device
+        self.glow, self.uint8 = glow, bool(uint8)
+        self.plan = plan = glow.flow.plan_for(glow.flow.in_chw, dev)
+        self.n, y_onehot = glow._sampler_batch(n, y_onehot)
+        self.y_onehot = None if y_onehot is None else y_onehot.clone()
+        self.std_top, self.std_split = sampler_stds(eps_std, glow.flow.L)
+        if seed is None:
+            seed = sampler_position()[0]
+        self.seed, self._first, self._replays = int(seed) & (2 ** 64 - 1), int(call), 0
+        self.pos = plan.sampler_position(self.seed, self._first)
+        n = self.n
+        self.x = None if uint8 else torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
+        self.x_u8 = torch.empty((n,) + plan.in_chw, dtype=torch.uint8, device=dev) if uint8 else None
+        self.z = torch.empty((n,) + plan.out_chw, dtype=torch.float32, device=dev)
+        self._head = plan.head_call(n, self.y_onehot) if glow._attach_head(plan) else None
+        with torch.no_grad():
+            plan.ensure_packed(use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):          # warm-up on the capture stream: workspace, lazy inits
+                for _ in range(2):
+                    self._body()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            torch.cuda.synchronize(dev)
+            self.pos.copy_(plan.sampler_position(self.seed, self._first))      # (the warm-up moved it)
+            torch.cuda.synchronize(dev)
+            plan.pack_sync()            # nothing of an earlier pack is left for the captured call to join
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph, stream=side):
+                self._body()
+        self._version = plan._version_signature()
+        self._pack_epoch = getattr(plan, "_pack_epoch", 0)
+        self._family = plan.family
+
+    def _body(self):
+        plan = self.plan
+        plan.bind_sampler(self.pos, self.std_split, advance=True)
+        try:
+            plan.sample(self.n, self.std_top, head=self._head, out=(self.x, self.x_u8, self.z))
+        finally:
+            plan.bind_sampler(None)
+
+    @property
+    def last_position(self):
+        """``(seed, call)`` the last replay drew with (kept on the host by counting); None before the first."""
+        return None if self._replays == 0 else (self.seed, self._first + self._replays - 1)
+
+    def __call__(self, y_onehot=None):
+        """Replay; returns the static ``x`` (or ``x_u8``), valid until the next replay."""
+        plan = self.plan
+        if not plan.still_valid():
+            raise _lib.GlowHipError("capture_sampler: a parameter was re-allocated since the capture -- capture again")
+        if plan._version_signature() != self._version:
+            raise _lib.GlowHipError("capture_sampler: the parameters changed since the capture -- capture again")
+        if getattr(plan, "_pack_epoch", 0) != self._pack_epoch or plan.family != self._family:
+            raise _lib.GlowHipError("capture_sampler: the plan was packed for the other kernel family since the capture -- capture again")
+        if y_onehot is not None and y_onehot is not self.y_onehot:
+            self.y_onehot.copy_(y_onehot)
+        self.graph.replay()
+        self._replays += 1
+        return self.x_u8 if self.uint8 else self.x
+
+
 class GraphedForward:
     """`Glow.normal_flow` (eval, no grad; network/model.py:409-452) for one batch shape, captured in a hipGraph.
 
@@ -629,6 +749,81 @@ class Glow(nn.Module):
         if z is None:      # (plain torch: eps_top gets its gradient through autograd by itself)
             z = mean + torch.exp(logs) * require_device_tensor(eps_top, "eps_top")
         return self.flow.decode(z, eps_std=eps_std, eps=eps, safe=safe)
+
+    # ---- the sampler: draws made inside the kernels, every sample a (seed, call, index) triple
+    def _sampler_batch(self, n, y_onehot):
+        """(batch size, labels on the device) of a sampler call: the labels' batch under y_condition, else ``n`` or h_top's."""
+        if self.hps.ablation.y_condition:
+            assert y_onehot is not None, "y_condition: y_onehot is required"
+            y_onehot = require_device_tensor(y_onehot.float(), "y_onehot")
+            assert n is None or int(n) == y_onehot.shape[0], f"n = {n} but y_onehot holds {y_onehot.shape[0]} rows"
+            return y_onehot.shape[0], y_onehot
+        return (self.batch_h_top if n is None else int(n)), None
+
+    def sample(self, n=None, y_onehot=None, eps_std=None, uint8=False, return_latents=False, safe=None, seed=None, call=None):
+        """``n`` images drawn from the model -- `reverse_flow(z=None)` with every Gaussian draw made inside the kernel that
+        consumes it (csrc/sampler_rng.h: no noise tensor exists), the top prior computed where the top latent is written, and
+        optionally 8-bit pixels stored by the final un-squeeze (``uint8=True``: (N,C,H,W) uint8, the reference's
+        ``tensor_to_ndarray`` rule, saturating).  Sample i of the call is named by ``(seed, call, i)``: the same triple gives the
+        same bits again.  ``seed`` / ``call`` name the position for this one call; left out, the process's sampler position is
+        used (torch's seed with the rank folded in) and advances by one.  Same distribution as `reverse_flow`, other bits: the
+        generator is another one.
+        ``eps_std``: a number or one per level (`level_eps_stds`).  ``safe`` (None: `range_check` in eval mode): a flagged batch
+        is sampled again on the exact-fp32 kernels at the same position.  ``return_latents``: also the `Latents` whose
+        `decode_latents` is the returned image, rebuilt from the stream (`FlowPlan.normal_noise`) -- nothing extra is stored
+        during the decode."""
+        if safe is None:
+            safe = bool(self.range_check) and not self.training
+        with torch.no_grad():
+            dev = self.h_top.device
+            n, y_onehot = self._sampler_batch(n, y_onehot)
+            plan = self.flow.plan_for(self.flow.in_chw, dev)
+            std_top, std_split = sampler_stds(eps_std, self.flow.L)
+            head = plan.head_call(n, y_onehot) if self._attach_head(plan) else None
+            plan.ensure_packed(use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
+            implicit = seed is None and call is None
+            if implicit:
+                key, c = sampler_position(advance=True)
+                word = _sampler_word(plan, key, c)
+                pos = word[0]
+            else:
+                key = sampler_position()[0] if seed is None else int(seed) & (2 ** 64 - 1)
+                c = 0 if call is None else int(call)
+                pos = plan.sampler_position(key, c)
+            want_x = not uint8 or safe      # (the range status scans the fp32 pixels)
+
+            def run():
+                plan.bind_sampler(pos, std_split, advance=implicit)
+                try:
+                    return plan.sample(n, std_top, head=head, want_x=want_x, want_u8=uint8)
+                finally:
+                    plan.bind_sampler(None)
+            x, x8, z = run()
+            if implicit:
+                word[1] = (key, c + 1)
+            if safe and bool(plan.status(n, x).any()):      # out of the fp16 pairs' range: the exact-fp32 kernels, same position
+                FlowModel._RANGE_FALLBACKS += 1
+                if implicit:
+                    word = _sampler_word(plan, key, c)      # (back to where the flagged run drew)
+                prev = plan.family
+                plan.set_family(plan.FAMILY_EXACT_FP32)
+                try:
+                    plan.ensure_packed(use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
+                    x, x8, z = run()
+                finally:
+                    plan.set_family(prev)
+                if implicit:
+                    word[1] = (key, c + 1)
+            out = x8 if uint8 else x
+            if not return_latents:
+                return out
+            eps = [plan.normal_noise((n,) + s, key, c, 1 + k, std) for k, (s, std) in enumerate(zip(plan.split_chw, std_split))]
+            return out, Latents(z, eps)
+
+    def capture_sampler(self, n=None, y_onehot=None, eps_std=None, uint8=False, seed=None, call=0):
+        """`sample` for one batch size as ONE hipGraph launch (`GraphedSampler`), a class-conditional prior included: the first
+        replay draws at ``(seed, call)`` (seed None: the process's key), every later one at the next call number."""
+        return GraphedSampler(self, n, y_onehot, eps_std=eps_std, uint8=uint8, seed=seed, call=call)
 
     # ---- full-latent encode: the bijection with nothing dropped
     def encode_latents(self, x, y_onehot=None, noise=None, dequantize=True, safe=None):
