@@ -480,12 +480,10 @@ enum {
     GLOWHIP_DBG_PACK_UNFUSED        = 0x1000,     /* the forward-only pack as its per-kind launches, not the one k_pack_fused launch (same bytes: A/B) */
     GLOWHIP_DBG_NO_MIXER_FUSION     = 0x8000,     /* k_squeeze + k_chanmix + a plain finishing kernel as separate launches (bitwise equal) */
     GLOWHIP_DBG_NO_CNET1W           = 0x10000,    /* no k_cnet1w (one wave per SIMD, csrc/cnet1w_sh.hip): k_cnet takes its launches (A/B) */
-    GLOWHIP_DBG_CNET1W_ROW_SPLIT    = 0x20000,    /* k_cnet1w's row-split instance where it applies (C = 24 levels from 112 tiles of 128
-                                                     pixels; off by default: measured slower than k_cnet's 64-pixel tiles there) */
+    /* 0x20000: reserved, formerly GLOWHIP_DBG_CNET1W_ROW_SPLIT (removed; last present in commit ffbde06) */
     GLOWHIP_DBG_NO_CNET1W_BWD       = 0x40000,    /* no backward instance of k_cnet1w (level-1 input gradient back on k_cnet: A/B) */
     GLOWHIP_DBG_WGRAD_NARROW        = 0x80000,    /* f.2's weight-gradient GEMM on 128-column tiles at every level (no k_wgrad_gemm_ps512) */
-    GLOWHIP_DBG_FUSED_FINISH        = 0x100000,   /* a k_cnet1w launch finishes its FlowStep itself (arrival counters per tile; bit-identical,
-                                                     off by default: measured slower) */
+    /* 0x100000: reserved, formerly GLOWHIP_DBG_FUSED_FINISH (removed; last present in commit ffbde06) */
     GLOWHIP_DBG_LU_WORKGROUP        = 0x200000,   /* log|det W| of the 12 / 24 / 48-wide matrices on the workgroup-wide LU (same bits: A/B) */
     GLOWHIP_DBG_CNET_ROWS_SHIFT     = 22,         /* bits 22..24 = 1, 2 or 4: that many row splits of k_cnet (value << SHIFT) */
     GLOWHIP_DBG_CNET_128_ONLY       = 0x2000000,  /* k_cnet with 128-pixel tiles only */

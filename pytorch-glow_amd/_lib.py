@@ -102,10 +102,8 @@ class DBG(enum.IntFlag):
     PACK_UNFUSED = 0x1000
     NO_MIXER_FUSION = 0x8000
     NO_CNET1W = 0x10000
-    CNET1W_ROW_SPLIT = 0x20000
     NO_CNET1W_BWD = 0x40000
     WGRAD_NARROW = 0x80000
-    FUSED_FINISH = 0x100000
     LU_WORKGROUP = 0x200000
     CNET_128_ONLY = 0x2000000
     CNET_64 = 0x4000000

@@ -33,10 +33,8 @@ void glowhip_debug_force_tail_tile(int v) {
     d.exact_fp32 = bit(GLOWHIP_DBG_EXACT_FP32);
     d.no_mixer_fusion = bit(GLOWHIP_DBG_NO_MIXER_FUSION);
     d.no_cnet1w = bit(GLOWHIP_DBG_NO_CNET1W);
-    d.cnet1w_row_split = bit(GLOWHIP_DBG_CNET1W_ROW_SPLIT);
     d.no_cnet1w_bwd = bit(GLOWHIP_DBG_NO_CNET1W_BWD);
     d.wgrad_narrow = bit(GLOWHIP_DBG_WGRAD_NARROW);
-    d.fused_finish = bit(GLOWHIP_DBG_FUSED_FINISH);
     d.lu_workgroup = bit(GLOWHIP_DBG_LU_WORKGROUP);
     d.cnet_rows = (v >> GLOWHIP_DBG_CNET_ROWS_SHIFT) & 7;
     d.cnet_128_only = bit(GLOWHIP_DBG_CNET_128_ONLY);

@@ -18,20 +18,14 @@
 //     stays busy through what used to be separate phases.
 // Output: the partial sums `hpart` / `hup` / `hdn` of k_cnet at MS = 1 with 128-pixel tiles -- k_cfinish does not know the difference.
 // Instances (launch_cnet1w): product forward / inverse, the training step's taping forward (MODE 1) and its input-gradient launch
-// (MODE 2: the transposed network) for the C = 12 levels; no chained prologue, one group of f.4 output channels.
-// MS = 2: the h2 rows of a 128-pixel tile split over TWO workgroups (grid.y), each computing all of h1 again (f.0 is the small
-// layer) and half of f.2 / a K-half of f.4 -- for the levels whose 128-pixel tiles alone leave half the CUs idle (C = 24 at 16 x 16
-// pixels and batch 64: 128 tiles).  Weight bytes per MFMA stay those of a 128-pixel tile (a 64-pixel tile needs twice that, and at
-// one workgroup per CU the launch is then bound by the L2 -> LDS stream); the partial sums are k_cnet's MS = 2 layout.
-// (Measured 3 % slower than k_cnet's 64-pixel tiles where it applies -- each half repeats f.0, 29 % of its MFMAs -- and therefore
-// selected only behind the debug switch 0x20000: cnet_sh.hip cnet_select.)
+// (MODE 2: the transposed network) for the C = 12 levels; no chained prologue, no row split (the workgroup owns all h2 rows of its
+// tile), one group of f.4 output channels.
 #include "sh.h"
 #include <algorithm>
 #include <type_traits>
 
 #include "conv_mfma.h"
 #include "cnet_geo.h"
-#include "cnet_fin.h"
 
 GH_STAMPS_DEFINE(cnet1w)
 GH_WGTIMES_DEFINE(cnet1w)
@@ -48,13 +42,6 @@ __device__ __forceinline__ void c1_dma16o(const void* gsrc, void* ldst) {   // t
 template <int OFF>
 __device__ __forceinline__ void c1_bdma16o(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff, void* ldst) {      // the same through a buffer descriptor
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)ldst, 16, voff, soff, OFF, 0);
-}
-// a partial sum of f.4 to the scratch buffer: plain store, or -- fused finishing -- an agent-scope relaxed atomic store (sc1: written
-// through the XCD's L2, so that a workgroup on another XCD reads it with the matching load)
-template <bool COH>
-__device__ __forceinline__ void c1_publish(float* p, float v) {
-    if constexpr (COH) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
 }
 #define C1_MFMA(A_, B_, C_) __builtin_amdgcn_mfma_f32_32x32x16_f16(A_, B_, C_, 0, 0, 0)
 #define C1_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -89,13 +76,10 @@ __device__ __forceinline__ void c1_frag(const f32x4_t& v, h8& bh, h8& bl, int ha
     for (int t = 0; t < 4; ++t) { bh[4 * half + t] = hi[t]; bl[4 * half + t] = lo[t]; }
 }
 
-// f.0's MFMA j (k-step j / 3, product j % 3) of the chunk riding along: its slot among the chunk's 24 NQ f.2 slots.  Four quads per
-// k-step (MS = 1): k-step st in quad st, behind slots 3, 7, 11.  Two (MS = 2): one per slot from slot 0 on -- 27 of them (G0 = 18)
-// in the 24 slots of the chunk's first k-step, every ninth doubled up -- so that the epilogue has the second k-step's 24 slots.
-// (MS = 1 with more than five k-steps of f.0 -- the backward launch's first layer has C = 12 inputs, nine k-steps: every other slot.)
-__host__ __device__ constexpr int c1_f0slot(int nq, int nst0, int j) {
-    return nq == 4 ? (nst0 <= 5 ? 12 * (j / 3) + 3 + 4 * (j % 3) : 2 * j + 1) : j - (j + 1) / 9;
-}
+// f.0's MFMA j (k-step j / 3, product j % 3) of the chunk riding along: its slot among the chunk's 96 f.2 slots (four quads of 12 per
+// k-step): k-step st in quad st, behind slots 3, 7, 11.  (With more than five k-steps of f.0 -- the backward launch's first layer has
+// C = 12 inputs, nine k-steps: every other slot.)
+__host__ __device__ constexpr int c1_f0slot(int nst0, int j) { return nst0 <= 5 ? 12 * (j / 3) + 3 + 4 * (j % 3) : 2 * j + 1; }
 
 // TAPE (the training forward, plan_train.hip): h1 and h2 also go to memory as fp16 [pixel / 32][row][pixel % 32] and their signs as
 // 16-bit words -- the formats k_cnet MODE 1 writes and the backward k_cnet / the weight-gradient GEMMs read (cnet_sh.hip).  A lane
@@ -108,20 +92,17 @@ __host__ __device__ constexpr int c1_f0slot(int nq, int nst0, int j) {
 // words, one 16-bit word per lane and block, requested a block ahead -- and g_u2 / g_u0 go to memory as fp32 [pixel / 32][row][pixel % 32]
 // for the weight-gradient GEMMs: a lane's value of a row is 4 bytes of that row's 128-byte line, so a wave's store of one register
 // writes two full lines (no exchange between lanes), 16 stores per block.
-// FIN (product instance, MS = 1): the launch finishes the step itself (sh.h CnetArgs::fin_cnt; the tail of this kernel) -- no
-// finishing kernel, one kernel boundary per FlowStep instead of two.
-template <int HID, int G0, int NRT4, int MODE = 0, int MS = 1, bool FIN = false>
+template <int HID, int G0, int NRT4, int MODE = 0>
 __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
-    static_assert(!FIN || (MODE == 0 && MS == 1), "fused finishing: the product instance without row split");
     constexpr bool TAPE = MODE == 1, BWD = MODE == 2;
     constexpr int NT = 256, LPXT = 7;
     constexpr int NCH = HID / 32;             // 32-channel chunks of the hidden width = row tiles of h1
     constexpr int NKS = HID / 16;             // k-steps of f.2
-    constexpr int MR = HID / MS;              // h2 rows of this workgroup
+    constexpr int MR = HID;                   // h2 rows of this workgroup: all of them
     constexpr int NRT2 = MR / 32;             // ... as row tiles = accumulator blocks of the wave
     constexpr int NQ = NRT2 / 4;              // quads of row tiles = quads of 12 slots per k-step of f.2
     constexpr int NKS4 = MR / 16;             // k-steps of f.4 over this workgroup's h2 rows
-    constexpr int SLOT = MR * 64;             // ring slot: one k-step of the workgroup's rows of the f.2 image, both planes (32 / 16 KiB)
+    constexpr int SLOT = MR * 64;             // ring slot: one k-step of the f.2 image, both planes (32 KiB)
     constexpr int PPF = 2 * NQ;               // 1-KiB pieces per wave of such a fill
     constexpr int NST0 = G0 / 2;              // k-steps of f.0
     constexpr int NP0 = (G0 + 3) / 4;         // DMA pieces per wave of a chunk's f.0 rows (G0 KiB)
@@ -130,13 +111,12 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
     constexpr int NF4 = NKS4 / K4;            // fills of the f.4 image
     constexpr int PP4 = K4 * NRT4;            // 1-KiB pieces per plane of such a fill
     constexpr int PPW4 = (2 * PP4 + 3) / 4;   // ... per wave (both planes over four waves; a surplus piece repeats the last)
-    constexpr bool RUN4 = PP4 % 2 == 0;       // a wave's pieces of an f.4 fill are one run of one plane (else: placed piece by piece)
-    static_assert(PPW4 == PPF && NF4 >= 3 && NCH % 2 == 0 && NQ >= 2 && NKS4 % K4 == 0, "ring bookkeeping");
-    static_assert(MODE == 0 || MS == 1, "taping / backward: every workgroup would store its share of h1 (a run-time count of stores in the counted waits)");
+    static_assert(PPW4 == PPF && NF4 >= 3 && NCH % 2 == 0 && NQ == 4 && NKS4 % K4 == 0, "ring bookkeeping");
+    static_assert(PP4 % 2 == 0, "a wave's pieces of an f.4 fill are one run of one plane");
     constexpr int FL = NKS + NF4 - 1;         // last fill of the stream: fills 0 .. NKS - 1 = f.2 k-steps, NKS .. FL = f.4 fills
     constexpr int NF0 = 3 * NST0;             // MFMAs of f.0 per chunk
-    constexpr int EP0 = NQ == 4 ? 60 : 24;    // first of the 24 slots of f.0's epilogue among the chunk's 24 NQ
-    static_assert(c1_f0slot(NQ, NST0, NF0 - 1) < EP0 && EP0 + 24 <= 24 * NQ, "f.0 and its epilogue inside the chunk");
+    constexpr int EP0 = 60;                   // first of the 24 slots of f.0's epilogue among the chunk's 24 NQ
+    static_assert(c1_f0slot(NST0, NF0 - 1) < EP0 && EP0 + 24 <= 24 * NQ, "f.0 and its epilogue inside the chunk");
     // byte offsets of the LDS regions: tables | ring | f.0 double buffer | window.  (T, staged at the end, starts behind the tables.)
     constexpr int TABS = ((4 * HID + MP4) * 4 + 1023) / 1024 * 1024;
     constexpr int RINGB = TABS;
@@ -150,7 +130,6 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
     float* t_rs2 = t_b0 + HID;
     float* t_b2 = t_rs2 + HID;
     float* t_rs4 = t_b2 + HID;
-    const int ms_row0 = MS > 1 ? (int)blockIdx.y * MR : 0;       // first h2 row of this workgroup
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);       // = the wave's pixel tile
@@ -248,58 +227,43 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
     auto ring_begin = [&](int f, int slot_off, auto kind) {
         constexpr int KIND = decltype(kind)::value;
         const bool w2f = KIND == 0 || (KIND == 1 && f < NKS);
-        // f.2: the wave's PPF pieces are one run -- plane wid / 2, k group wid % 2 of the k-step, the workgroup's MR rows of it
-        // f.4: fill f - NKS = K4 k-steps of the workgroup's K range; RUN4: PPW4 pieces of one plane, else see ring_piece
+        // f.2: the wave's PPF pieces are one run -- plane wid / 2, k group wid % 2 of the k-step
+        // f.4: fill f - NKS = K4 k-steps; the wave's PPW4 pieces are one run of one plane
         const int p = wid >> 1;
-        const long o2 = (p * w2_plane + ((long)(2 * f + (wid & 1)) * HID + ms_row0) * 8) * 2;
-        const long o4 = ((RUN4 ? p * w4_plane + (wid & 1) * (PPW4 * 512) : 0) + ((long)(ms_row0 / 16) + (long)(f - NKS) * K4) * (2 * MP4 * 8)) * 2;
+        const long o2 = (p * w2_plane + (long)(2 * f + (wid & 1)) * HID * 8) * 2;
+        const long o4 = (p * w4_plane + (wid & 1) * (PPW4 * 512) + (long)(f - NKS) * K4 * (2 * MP4 * 8)) * 2;
 #ifndef C1_GLOBAL_DMA
         f_w2 = w2f ? 1 : 0;
         f_soff = (int)(w2f ? o2 : o4);
 #else
         f_src = w2f ? W2 + o2 / 2 : W4 + o4 / 2;
 #endif
-        f_dst = RINGB + slot_off + ((w2f || RUN4) ? wid * (PPF * 1024) : 0);
+        f_dst = RINGB + slot_off + wid * (PPF * 1024);
     };
     auto ring_piece = [&](int i, auto kind) {       // piece i (0 .. PPF - 1) of the fill in progress
         constexpr int KIND = decltype(kind)::value;
         char* dst = lds1 + f_dst;
-        if constexpr (!RUN4 && KIND != 0) {
-            // f.4 with an odd piece count per plane (MS = 2: 7 + 7 pieces of a k-step): piece wid + 4 i of the 2 PP4, plane and place
-            // worked out per piece (wave-uniform scalars; a few pieces per k-step of 21 MFMAs: their issue cost does not matter there)
-            const int j = min(wid + 4 * i, 2 * PP4 - 1);
-            const int pl = j >= PP4 ? 1 : 0, r = j - pl * PP4;
-            const int o4 = (int)((pl * w4_plane + r * 512) * 2), d4 = j * 1024;
 #ifndef C1_GLOBAL_DMA
-            const bool w2f = KIND == 1 && f_w2;
-            c1_bdma16o<0>(w2f ? rs_w2 : rs_w4, lane * 16, f_soff + (w2f ? i * 1024 : o4), dst + (w2f ? i * 1024 : d4));
-#else
-            static_assert(KIND == 2 || RUN4, "global-form DMA: debug builds of the full-height instances only");
-            c1_dma16(f_src + o4 / 2 + lane * 8, dst + d4);
-#endif
-        } else {
-#ifndef C1_GLOBAL_DMA
-            const __amdgpu_buffer_rsrc_t rs = KIND == 0 ? rs_w2 : (KIND == 2 ? rs_w4 : (f_w2 ? rs_w2 : rs_w4));
-            const int sb = i < 4 ? f_soff : f_soff + 4096;        // (the piece index is a constant after unrolling: the switch folds)
-            char* db = i < 4 ? dst : dst + 4096;
-            switch (i & 3) {
-            case 0: c1_bdma16o<0>(rs, lane * 16, sb, db); break;
-            case 1: c1_bdma16o<1024>(rs, lane * 16, sb, db); break;
-            case 2: c1_bdma16o<2048>(rs, lane * 16, sb, db); break;
-            default: c1_bdma16o<3072>(rs, lane * 16, sb, db); break;
-            }
-#else
-            const _Float16* src = f_src + lane * 8;
-            const _Float16* sb = i < 4 ? src : src + 2048;
-            char* db = i < 4 ? dst : dst + 4096;
-            switch (i & 3) {
-            case 0: c1_dma16o<0>(sb, db); break;
-            case 1: c1_dma16o<1024>(sb, db); break;
-            case 2: c1_dma16o<2048>(sb, db); break;
-            default: c1_dma16o<3072>(sb, db); break;
-            }
-#endif
+        const __amdgpu_buffer_rsrc_t rs = KIND == 0 ? rs_w2 : (KIND == 2 ? rs_w4 : (f_w2 ? rs_w2 : rs_w4));
+        const int sb = i < 4 ? f_soff : f_soff + 4096;        // (the piece index is a constant after unrolling: the switch folds)
+        char* db = i < 4 ? dst : dst + 4096;
+        switch (i & 3) {
+        case 0: c1_bdma16o<0>(rs, lane * 16, sb, db); break;
+        case 1: c1_bdma16o<1024>(rs, lane * 16, sb, db); break;
+        case 2: c1_bdma16o<2048>(rs, lane * 16, sb, db); break;
+        default: c1_bdma16o<3072>(rs, lane * 16, sb, db); break;
         }
+#else
+        const _Float16* src = f_src + lane * 8;
+        const _Float16* sb = i < 4 ? src : src + 2048;
+        char* db = i < 4 ? dst : dst + 4096;
+        switch (i & 3) {
+        case 0: c1_dma16o<0>(sb, db); break;
+        case 1: c1_dma16o<1024>(sb, db); break;
+        case 2: c1_dma16o<2048>(sb, db); break;
+        default: c1_dma16o<3072>(sb, db); break;
+        }
+#endif
     };
     using K_F2 = std::integral_constant<int, 0>;
     using K_ANY = std::integral_constant<int, 1>;
@@ -708,7 +672,7 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
 #ifndef C1_DBG_NO_P1
 #pragma unroll
                 for (int j = 0; j < NF0; ++j)
-                    if (c1_f0slot(NQ, NST0, j) == sl) f0_mfma(j);
+                    if (c1_f0slot(NST0, j) == sl) f0_mfma(j);
                 if (Q == 2 * NQ - 1 && k >= 8) {
                     const char* pa = lds1 + a0lane + (min(c + 2, NCH - 1) & 1) * (G0 * 1024);
                     if (k == 9) A0h = *reinterpret_cast<const h8*>(pa);
@@ -739,13 +703,12 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
 
     // ---- P3: T[m][px] += W4t[m][k] h2[k][px] with h2 = relu + split of the accumulator block k / 32, two k-steps per block.
     // (slot bookkeeping continues: the last TOP of the loop above made fill NKS = the first of the f.4 image readable in s_cur)
-    // MS = 1: T in VGPRs like f.0's block (asm MFMAs): h2 holds every AGPR until its last block has been consumed.  MS = 2: h2 is half
-    // as large and T (seven row tiles) takes the other AGPRs through the builtin.
-    constexpr bool T_ASM = NRT2 * 16 + NRT4 * 16 > 256;
+    // T in VGPRs like f.0's block (asm MFMAs): h2 holds every AGPR until its last block has been consumed.
+    static_assert(NRT2 * 16 == 256, "h2 fills the AGPRs");
     f32x16_t accT[NRT4];
     h8 Hh[2][2], Hl[2][2];      // [block & 1][k-step of the block]
-    const float* trs2 = t_rs2 + ms_row0;
-    const float* tbb2 = t_b2 + ms_row0;
+    const float* trs2 = t_rs2;
+    const float* tbb2 = t_b2;
     // BWD: the sign word of h2-position block b (mask1 of the forward: h1's), requested a block ahead of its epilogue
     [[maybe_unused]] unsigned mwB[NRT2];
     if constexpr (BWD) { mwB[0] = mask_get(mb2, 0); mwB[1] = mask_get(mb2, 1); }
@@ -757,12 +720,6 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
     };
 #pragma unroll
     for (int i = 0; i < NRT4; ++i) { ldA4one(s_cur, 0, i, 0, A4H[i]); ldA4one(s_cur, 0, i, 1, A4L[i]); }
-    if constexpr (!T_ASM) {
-#pragma unroll
-        for (int i = 0; i < NRT4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) accT[i][r] = 0.f;
-    }
 #pragma unroll
     for (int ks = 0; ks < NKS4; ++ks) {
         const int c = ks >> 1, s = ks & 1;
@@ -799,12 +756,8 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
             }
             if (K4 == 1 && F + 2 <= FL && k < 3 && !(k & 1) && PA + k / 2 < PPW4) ring_piece(PA + k / 2, K_F4{});
             const int i = k % NRT4, sw = k / NRT4;
-            if constexpr (T_ASM) {
-                if (ks == 0 && sw == 0) c1_mfma_v0(accT[i], A4H[i], Hh[0][0]);
-                else c1_mfma_v(accT[i], sw == 2 ? A4L[i] : A4H[i], sw == 1 ? Hl[c & 1][s] : Hh[c & 1][s]);
-            } else {
-                accT[i] = C1_MFMA(sw == 2 ? A4L[i] : A4H[i], sw == 1 ? Hl[c & 1][s] : Hh[c & 1][s], accT[i]);
-            }
+            if (ks == 0 && sw == 0) c1_mfma_v0(accT[i], A4H[i], Hh[0][0]);
+            else c1_mfma_v(accT[i], sw == 2 ? A4L[i] : A4H[i], sw == 1 ? Hl[c & 1][s] : Hh[c & 1][s]);
             if (ks + 1 < NKS4 && sw == 1) ldA4one(s_cur, (kk + 1) % K4, i, 0, A4H[i]);
             if (ks + 1 < NKS4 && sw == 2) ldA4one(s_cur, (kk + 1) % K4, i, 1, A4L[i]);
             // h2 of the next block: its epilogue's 24 ticks over this block's two k-steps, TPS per slot
@@ -819,10 +772,8 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
         }
     }
     GH_STAMP(4);
-    if constexpr (T_ASM) {
 #pragma unroll
-        for (int i = 0; i < NRT4; ++i) c1_settle(accT[i]);
-    }
+    for (int i = 0; i < NRT4; ++i) c1_settle(accT[i]);
     __syncthreads();           // every wave is done with the ring: it becomes the staging area of T
 
     // ---- P4: T -> LDS as fp32, PIXEL-major [pixel][RP rows] (row scale applied), then the 9-tap sums.  A lane's four consecutive
@@ -851,12 +802,9 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
     }
     __syncthreads();
     GH_STAMP(5);
-    // (MS = 2: each half leaves its own copy of the sums, k_cnet's layout -- the finishing kernel adds them in a fixed order)
-    const long msN = MS > 1 ? (long)blockIdx.y * a.N : 0;
-    const long mstile = MS > 1 ? (long)blockIdx.y * g.tiles : 0;
     float* hpart = a.scratch;
-    float* hup = a.scratch + (long)MS * a.N * a.Cout * HW;
-    float* hdn = hup + (long)MS * g.tiles * a.Cout * W;
+    float* hup = a.scratch + (long)a.N * a.Cout * HW;
+    float* hdn = hup + (long)g.tiles * a.Cout * W;
     const int ngrp = Cout / CGW;
     {
         // a thread keeps ITS pixel (tid & 127) and walks the groups of four channels tid >> 7, + 2, ...
@@ -875,7 +823,7 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
                 off[tap] = (q + (ok[tap] ? (dy - 1) * W + (dx - 1) : 0)) * RP + tap * Cout;
             }
         if (n < a.N) {
-            float* hp = hpart + ((msN + n) * a.Cout) * HW + (long)(y0 + r) * W + x;
+            float* hp = hpart + (n * a.Cout) * HW + (long)(y0 + r) * W + x;
             for (int cg = tid >> LPXT; cg < ngrp; cg += NT >> LPXT) {
                 const float* tp = T + CGW * cg;
                 tvec v[9];
@@ -889,7 +837,7 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
 #pragma unroll
                     for (int j = 0; j < CGW; ++j) sum[j] += ok[tap] ? v[tap][j] : 0.f;
 #pragma unroll
-                for (int j = 0; j < CGW; ++j) c1_publish<FIN>(hp + (long)(CGW * cg + j) * HW, sum[j]);
+                for (int j = 0; j < CGW; ++j) hp[(long)(CGW * cg + j) * HW] = sum[j];
             }
         }
     }
@@ -913,123 +861,52 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
 #pragma unroll
             for (int j = 0; j < CGW; ++j) {
                 const float sacc = (ok[0] ? v[0][j] : 0.f) + (ok[1] ? v[1][j] : 0.f) + (ok[2] ? v[2][j] : 0.f);
-                c1_publish<FIN>((dn ? hdn : hup) + ((mstile + tb) * a.Cout + CGW * cg + j) * W + x, sacc);
+                (dn ? hdn : hup)[((long)tb * a.Cout + CGW * cg + j) * W + x] = sacc;
             }
         }
     }
     GH_STAMP(6);
-    if constexpr (FIN) {
-        // ---- fused finishing.  The sums above went out as agent-scope atomic stores (written through the XCD's L2); once this
-        // wave's are acknowledged (vmcnt) and every wave is here, thread 0 bumps the arrival counter of its own tile and of the
-        // neighbouring tiles of the image -- they need this tile's halo rows -- and whoever completes a counter finishes THAT tile
-        // with the finishing kernel's own code, reading the other workgroups' sums around the L2 as they were written
-        // (scripts/ubench/fence_cost.hip MODE 3: no stale word in 12 800 exchanges, ~6 us for the chain on the last arriver; an
-        // agent-scope fence per workgroup instead cost 94 us per round).  Nobody waits: a workgroup finishes zero to three tiles and exits.
-        __shared__ long long fin_red[4];
-        __shared__ int fin_do[3];
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();                                  // (also: every thread is done reading T -- it becomes the finishing's staging area)
-        const bool halos = g.R < H;                       // (NI = 1: cnet1w_takes)
-        const int tpi = HW >> LPXT, j = tb & (tpi - 1);   // tiles per image (a power of two), this tile's place in its image
-        if (tid < 3) {
-            const int d = tid - 1, jj = j + d;
-            int mine = 0;
-            if (jj >= 0 && jj < tpi && (d == 0 || halos)) {
-                const unsigned need = halos ? 1u + (jj > 0) + (jj < tpi - 1) : 1u;
-                const unsigned old = __hip_atomic_fetch_add(a.fin_cnt + tb + d, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (old + 1 == need) {
-                    mine = 1;
-                    __hip_atomic_store(a.fin_cnt + tb + d, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (everyone who counts on it has: ready for the next launch)
-                }
-            }
-            fin_do[tid] = mine;
-        }
-        __syncthreads();
-        if (fin_do[0] | fin_do[1] | fin_do[2]) {
-            CfinArgs fa;
-            fa.p.scratch = a.scratch; fa.p.MS = 1; fa.p.tiles = g.tiles; fa.p.R = g.R; fa.p.NI = g.NI; fa.p.lpxt = LPXT;
-            fa.p.bias = a.bias; fa.p.scale = a.scale; fa.p.mode = a.mode; fa.p.Cout = a.Cout; fa.p.z = a.z_in; fa.p.z_bs = a.z_in_bs;
-            fa.p.one_wave = 1; fa.p.finished = 1;
-            fa.mix = a.mix; fa.z_out = a.z_out; fa.z_out_bs = a.z_out_bs; fa.acc = a.acc;
-            fa.N = a.N; fa.H = H; fa.W = W; fa.HW = HW; fa.wshift = g.wshift; fa.xcd_affine = 0; fa.tape_hout = nullptr;
-            const FinSrc fs = fin_src(fa.p, a.N, H, W, HW, g.wshift);
-            float* fsm = reinterpret_cast<float*>(lds1 + TABS);
-#pragma unroll 1
-            for (int d = 0; d < 3; ++d) {
-                if (!fin_do[d]) continue;
-#pragma unroll 1
-                for (int h = 0; h < 2; ++h) {             // a tile = two 64-pixel chunks of the finishing kernel
-                    const int chunk = 2 * (tb + d - 1) + h;
-                    cfinish_chunk<64, 1, true, true>(fa, fs, chunk, chunk & ACC_EXTRA, fsm, fin_red);
-                    __syncthreads();
-                }
-            }
-        }
-    }
     GH_WG_END();
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-static size_t cnet1w_lds_bytes(const CnetGeo& g, int hidden, int ms) {
+static size_t cnet1w_lds_bytes(const CnetGeo& g, int hidden) {
     const size_t tabs = (((size_t)4 * hidden + g.Mpad4) * sizeof(float) + 1023) / 1024 * 1024;
-    const size_t work = (size_t)3 * (hidden / ms) * 64 + (size_t)2 * g.G * 1024 + (size_t)2 * g.winplane * sizeof(_Float16);
+    const size_t work = (size_t)3 * hidden * 64 + (size_t)2 * g.G * 1024 + (size_t)2 * g.winplane * sizeof(_Float16);
     const size_t stage = (size_t)cnet_trow(9 * g.Cg) * 128 * sizeof(float);      // T, pixel-major
     return tabs + std::max(work, stage);
 }
 
-// instances: 1 = product, 2 = taping forward (both: C = 12 levels, the workgroup owns all 512 h2 rows), 3 = product with the h2 rows
-// split over two workgroups (C = 24 levels), 4 = the backward launch of the C = 12 levels (12 channels in, 6 out)
-static int cnet1w_instance(const CnetArgs& a, const CnetGeo& g, int ms) {      // 0: none
+// instances (no row split: the workgroup owns all 512 h2 rows): 1 = product, 2 = taping forward (both: C = 12 levels), 4 = the
+// backward launch of the C = 12 levels (12 channels in, 6 out)
+static int cnet1w_instance(const CnetArgs& a, const CnetGeo& g) {      // 0: none
     if (a.hidden != 512 || g.ng != 1 || g.pxt != 128) return 0;
-    if (a.bwd) return (ms == 1 && g.G == 18 && g.NRT4 == 2 && a.tape_h1) ? 4 : 0;
-    if (ms == 1 && g.G == 10 && g.NRT4 == 4) return a.tape_h1 ? 2 : 1;
-    if (ms == 2 && g.G == 18 && g.NRT4 == 7 && !a.tape_h1) return 3;
+    if (a.bwd) return (g.G == 18 && g.NRT4 == 2 && a.tape_h1) ? 4 : 0;
+    if (g.G == 10 && g.NRT4 == 4) return a.tape_h1 ? 2 : 1;
     return 0;
 }
 
-bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g, int ms) {
+bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g) {
     if (a.pre_on) return false;
     if ((a.tape_h1 || a.bwd) && (!a.tape_h1 || !a.tape_h2 || !a.mask1 || !a.mask2 || g.HW % 128 != 0)) return false;      // taping / backward: whole 32-pixel tiles of the batch per wave
     if (g.NI != 1) return false;                     // (tiles of whole small images stay on k_cnet: no level that large has them)
-    const int inst = cnet1w_instance(a, g, ms);
+    const int inst = cnet1w_instance(a, g);
     if (!inst) return false;
-    if (cnet1w_lds_bytes(g, a.hidden, ms) > 160 * 1024) return false;
+    if (cnet1w_lds_bytes(g, a.hidden) > 160 * 1024) return false;
     if (g.Cg % (inst == 4 ? 2 : 4) != 0) return false;      // the tap sums take four (backward: two) output channels per read
     return true;
 }
 
-// Does the launch finish the step itself (CnetArgs::fin_cnt)?  The product instance at MS = 1, whole tiles (no tail tile whose
-// arrival count would differ), a mixer of at most 48 channels staged beside the values (the staging area is T's), 64-pixel chunks
-// that stay inside one image row pair.
-bool cnet1w_finishes(const CnetArgs& a, const CnetGeo& g, int ms) {
-    if (!a.fin_cnt || !a.z_out || a.tape_h1 || a.bwd || a.pre_on || ms != 1 || cnet1w_instance(a, g, ms) != 1) return false;
-    const bool paired = a.mode == TAIL_AFFINE_FWD || a.mode == TAIL_AFFINE_REV;
-    const int C = 2 * (paired ? a.Cout / 2 : a.Cout);
-    if (a.mix.C != 0 && a.mix.C != C) return false;
-    if (g.NI != 1 || g.HW % 128 != 0 || (g.HW & (g.HW - 1)) != 0) return false;
-    const size_t stage = (size_t)cnet_trow(9 * g.Cg) * 128 * sizeof(float);
-    return ((size_t)C * 64 + (size_t)C * C) * sizeof(float) <= stage;
-}
-
-int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, int ms, hipStream_t s) {
-    const size_t lds = cnet1w_lds_bytes(g, a.hidden, ms);
-    switch (cnet1w_instance(a, g, ms)) {
+int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
+    const size_t lds = cnet1w_lds_bytes(g, a.hidden);
+    switch (cnet1w_instance(a, g)) {
     case 1:
-        if (cnet1w_finishes(a, g, ms)) {
-            (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 10, 4, 0, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            hipLaunchKernelGGL((k_cnet1w<512, 10, 4, 0, 1, true>), dim3(g.tiles), dim3(256), lds, s, a, g);
-            break;
-        }
         (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_cnet1w<512, 10, 4>), dim3(g.tiles), dim3(256), lds, s, a, g);
         break;
     case 2:
         (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 10, 4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_cnet1w<512, 10, 4, 1>), dim3(g.tiles), dim3(256), lds, s, a, g);
-        break;
-    case 3:
-        (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 18, 7, 0, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_cnet1w<512, 18, 7, 0, 2>), dim3(g.tiles, 2), dim3(256), lds, s, a, g);
         break;
     case 4:
         (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 18, 2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

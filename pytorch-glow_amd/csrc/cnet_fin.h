@@ -31,13 +31,10 @@ __device__ __forceinline__ FinSrc fin_src(const CnetPending& p, int N, int H, in
 // Partial sums of h = f(z1) for coupling channel c at pixel p of image n: (se, so) = the shift (and, affine, the scale logit) before
 // bias and exp(3 logs).  Every load is unconditional (clamped index, selected value), so a caller that gathers several elements
 // before using any has all of their loads in flight together.
-// COH: the partial sums come from other workgroups of the RUNNING launch (fused finishing): agent-scope relaxed atomic loads.
-template <bool COH>
-__device__ __forceinline__ float fin_ld(const float* p) {
-    if constexpr (COH) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <int MSV, bool HALO = true, bool COH = false>      // MSV > 0: f.MS known at compile time (loops unrolled: every load of the element in
+// (a function, not a plain dereference at the six call sites: written that way, the chained-prologue instances of k_cnet come out
+// with their gather loads scheduled differently from the code that was measured)
+__device__ __forceinline__ float fin_ld(const float* p) { return *p; }
+template <int MSV, bool HALO = true>      // MSV > 0: f.MS known at compile time (loops unrolled: every load of the element in
                                           // flight at once); HALO = false: the caller knows f.halos is false
 __device__ __forceinline__ void fin_gather_t(const FinSrc& f, long n, int c, int p, float& se, float& so) {
     const int ms = MSV > 0 ? MSV : f.MS;
@@ -47,8 +44,8 @@ __device__ __forceinline__ void fin_gather_t(const FinSrc& f, long n, int c, int
 #pragma unroll
     for (int m = 0; m < ms; ++m) {
         const long base = (((long)m * f.N + n) * f.Cout + ce) * f.HW + p;
-        se += fin_ld<COH>(f.hpart + base);
-        so += fin_ld<COH>(f.hpart + base + (f.paired ? f.HW : 0));
+        se += fin_ld(f.hpart + base);
+        so += fin_ld(f.hpart + base + (f.paired ? f.HW : 0));
     }
     if (HALO) {   // halo rows: no branch either (without halos the selects below drop a valid but unused slot of the scratch buffer)
         const int r = y & (f.R - 1);
@@ -62,8 +59,8 @@ __device__ __forceinline__ void fin_gather_t(const FinSrc& f, long n, int c, int
             const long hu = (((long)m * f.tiles + tu) * f.Cout + ce) * f.W + x;
             // loaded unconditionally, SELECTED (never multiplied by a 0/1 mask: an unused slot of the scratch buffer may hold
             // NaN or inf bit patterns, and 0 * NaN is NaN)
-            const float d0 = fin_ld<COH>(f.hdn + hd), u0 = fin_ld<COH>(f.hup + hu);
-            const float d1 = fin_ld<COH>(f.hdn + hd + (f.paired ? f.W : 0)), u1 = fin_ld<COH>(f.hup + hu + (f.paired ? f.W : 0));
+            const float d0 = fin_ld(f.hdn + hd), u0 = fin_ld(f.hup + hu);
+            const float d1 = fin_ld(f.hdn + hd + (f.paired ? f.W : 0)), u1 = fin_ld(f.hup + hu + (f.paired ? f.W : 0));
             se += (wd ? d0 : 0.f) + (wu ? u0 : 0.f);
             so += (wd ? d1 : 0.f) + (wu ? u1 : 0.f);
         }
@@ -141,12 +138,9 @@ __device__ __forceinline__ int cfin_chunk(int b, int nblk, int lr) {
 }
 
 // The finishing of ONE chunk of PXB consecutive pixels of one image x all channels by 256 threads -- the body of k_cfinish
-// (cnet_sh.hip), and of the fused finishing at the end of k_cnet1w (cnet1w_sh.hip: the workgroup that arrives LAST at a tile's counter
-// finishes the tile; COH = true there: the partial sums were written by other workgroups of the SAME launch, possibly on another XCD,
-// so they are read as agent-scope relaxed atomic loads -- around the XCD's L2 -- as they were written).  Same code, same operation
-// order: the two forms agree bit for bit.  `accrow`: which of the sample's 1 + ACC_EXTRA log-det accumulator rows takes the atomic.
-// fsm: (C * PXB + C * C) floats of LDS; red: 4 words.  Ends without a barrier: a caller that reuses fsm / red must place one.
-template <int PXB, int MSV, bool HALO, bool COH>
+// (cnet_sh.hip).  `accrow`: which of the sample's 1 + ACC_EXTRA log-det accumulator rows takes the atomic.
+// fsm: (C * PXB + C * C) floats of LDS; red: 4 words.
+template <int PXB, int MSV, bool HALO>
 __device__ __forceinline__ void cfinish_chunk(const CfinArgs& a, const FinSrc& f, int chunk, int accrow, float* fsm, long long* red) {
     const int tid = threadIdx.x;
     const int HW = a.HW;
@@ -186,7 +180,7 @@ __device__ __forceinline__ void cfinish_chunk(const CfinArgs& a, const FinSrc& f
             const int c = e / PXB, q = e - c * PXB;
             zin[u] = zi[(long)(Ch + c) * HW + p0 + q];
             z1v[u] = zi[(long)c * HW + p0 + q];
-            fin_gather_t<MSV, HALO, COH>(f, n, c, p0 + q, se[u], so[u]);
+            fin_gather_t<MSV, HALO>(f, n, c, p0 + q, se[u], so[u]);
             const int ce = f.paired ? 2 * c : c, co = ce + (f.paired ? 1 : 0);
             kb[u][0] = f.bias[ce]; kb[u][1] = f.scale[ce]; kb[u][2] = f.bias[co]; kb[u][3] = f.scale[co];
             km[u][0] = an ? a.mix.bias[c] : 0.f; km[u][1] = an ? a.mix.scale[c] : 1.f;

@@ -1078,7 +1078,7 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
 }
 
 // ------------------------------------------------------------------------------------------------ finishing kernel
-// (CfinArgs, cfinish_chunk: cnet_fin.h -- the same body runs at the end of k_cnet1w for the tiles a workgroup arrives last at)
+// (CfinArgs, cfinish_chunk: cnet_fin.h)
 template <int PXB, int MSV, bool HALO>
 __global__ void __launch_bounds__(256) k_cfinish(CfinArgs a) {
     extern __shared__ __attribute__((aligned(16))) float fsm[];   // [C][PXB] values, then [C*C] matrix
@@ -1086,7 +1086,7 @@ __global__ void __launch_bounds__(256) k_cfinish(CfinArgs a) {
     const FinSrc f = fin_src(a.p, a.N, a.H, a.W, a.HW, a.wshift);
     constexpr int LPXB = PXB == 256 ? 8 : (PXB == 64 ? 6 : 4);
     const int chunk = a.xcd_affine && f.lpxt >= LPXB ? cfin_chunk(blockIdx.x, gridDim.x, f.lpxt - LPXB) : (int)blockIdx.x;
-    cfinish_chunk<PXB, MSV, HALO, false>(a, f, chunk, (int)(blockIdx.x % (1 + ACC_EXTRA)), fsm, red);
+    cfinish_chunk<PXB, MSV, HALO>(a, f, chunk, (int)(blockIdx.x % (1 + ACC_EXTRA)), fsm, red);
 }
 
 // ------------------------------------------------------------------------------------------------ host side
@@ -1197,9 +1197,6 @@ static int launch_cnet_inst(const CnetArgs& a, const CnetGeo& g, hipStream_t s) 
 // 128-pixel tiles are taken from this many tiles on (they alone then give every CU a workgroup); it is also the first count at which
 // k_cnet1w takes a taping / backward launch
 constexpr int CN_TILES_128 = 224;
-// k_cnet1w's row-split instance (debug switch only): 128-pixel tiles from this many tiles on -- the C = 24 levels that otherwise run
-// one 64-pixel k_cnet workgroup per CU
-constexpr int CN1W_SPLIT_TILES = 112;
 // the h2 rows are split over more workgroups per tile while a launch has fewer workgroups than this
 constexpr int CN_MS_FILL_WGS = 160;
 
@@ -1219,22 +1216,15 @@ static bool cnet_select(const CnetArgs& a, CnetChoice* out) {
     bool use64 = !ok128 || (ok64 && g128.tiles < CN_TILES_128);
     if (sw.cnet_128_only) use64 = !ok128;      // testing: 128-pixel tiles wherever they exist
     if (sw.cnet_64) use64 = ok64;              // testing: 64-pixel tiles wherever they exist
-    // k_cnet1w (one wave per SIMD, cnet1w_sh.hip): which launches may go to it at all (the shape's say is cnet1w_takes), whether the
-    // 128-pixel tiles it needs may be preferred for it, and its row-split instance only behind its switch
+    // k_cnet1w (one wave per SIMD, cnet1w_sh.hip): which launches may go to it at all (the shape's say is cnet1w_takes), and whether
+    // the 128-pixel tiles it needs may be preferred for it
     const bool c1w_kind = !a.pre_on && !sw.no_cnet1w && !(a.bwd && sw.no_cnet1w_bwd);      // (no_cnet1w_bwd: no backward instance, A/B)
     const bool c1w_tile = c1w_kind && ok128 && !sw.cnet_64;
-    const bool c1w_split_on = sw.cnet1w_row_split && !sw.cnet_rows;
     // taping / backward launches: the 128-pixel instance is at the register limit and spills once the stores and the sign words
     // are in (184 B); 64-pixel tiles measured 2 % faster on the training step
     if (a.tape_h1 && ok64 && !sw.cnet_128_only) use64 = true;
     // ... except where the one-wave-per-SIMD kernel takes the taping forward (cnet1w_sh.hip: its registers hold the 128-pixel tile)
-    if (a.tape_h1 && c1w_tile && g128.tiles >= CN_TILES_128 && cnet1w_takes(a, g128, 1)) use64 = false;
-    // ... and, behind the debug switch 0x20000 only, that kernel's instance with the h2 rows split over two workgroups (128-pixel tiles
-    // from 112 tiles on: the C = 24 levels that otherwise run one 64-pixel k_cnet workgroup per CU).  Measured slower than k_cnet
-    // where it applies -- 47.0 against 45.5 us per launch at config B's level 2, 176 against 150 us at config E's (DESIGN.md 3.2:
-    // each half computes all of f.0 again, 29 % of its MFMAs) -- so it is not selected by default; the parity tests run it.
-    const bool c1w_split = c1w_tile && !a.bwd && c1w_split_on && g128.tiles >= CN1W_SPLIT_TILES && cnet1w_takes(a, g128, 2);
-    if (c1w_split) use64 = false;
+    if (a.tape_h1 && c1w_tile && g128.tiles >= CN_TILES_128 && cnet1w_takes(a, g128)) use64 = false;
     const CnetGeo& g = use64 ? g64 : g128;
     int ms = 1;
     const int ms_max = std::min(CN_MAXMS, a.hidden / (use64 ? 128 : 64));
@@ -1245,10 +1235,9 @@ static bool cnet_select(const CnetArgs& a, CnetChoice* out) {
     const int upw = g.NU4 * g.KS > 8 ? 2 : 1;
     if (upw == 2 && a.hidden == 512 && ms == 1 && !use64) ms = 2;
     while ((a.hidden / ms / 16) / g.KS < 1 && ms > 1) ms /= 2;
-    if (c1w_split) ms = 2;
     // one wave per SIMD wherever an instance exists for the launch: forward / inverse / taping forward / backward, 128-pixel tiles, no
-    // row split but the one of its row-split instance
-    const bool one_wave = c1w_kind && g.pxt == 128 && cnet1w_takes(a, g, ms) && (ms != 2 || c1w_split_on);
+    // row split
+    const bool one_wave = c1w_kind && g.pxt == 128 && ms == 1 && cnet1w_takes(a, g);
     *out = CnetChoice{g, ms, upw, one_wave};
     return true;
 }
@@ -1291,7 +1280,7 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
                "cnet: no taping / backward instance for this launch");
     int rc = GLOWHIP_EINVAL;
     if (c.one_wave) {
-        GH_TRY(launch_cnet1w(a, g, ms, s));
+        GH_TRY(launch_cnet1w(a, g, s));
         rc = GLOWHIP_OK;
     }
 #define GH_CNT(hid, m, px)                                                                                     \
@@ -1319,7 +1308,6 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
         out->z = a.pre_on ? a.pre_z_new : a.z_in;
         out->z_bs = a.pre_on ? a.pre_z_new_bs : a.z_in_bs;
         out->one_wave = c.one_wave ? 1 : 0;
-        out->finished = c.one_wave && cnet1w_finishes(a, g, ms) ? 1 : 0;      // (launch_cnet1w took the fused-finishing instance)
     }
     return GLOWHIP_OK;
 }
@@ -1357,7 +1345,6 @@ int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s) {
 int launch_cnet(const CnetArgs& a, hipStream_t s) {
     CnetPending p{};
     GH_TRY(launch_cnet_main(a, s, &p));
-    if (a.N == 0 || p.finished) return GLOWHIP_OK;      // (a launch that finished the step itself leaves nothing for k_cfinish)
     return launch_cnet_finish(a, p, s);
 }
 

@@ -14,12 +14,6 @@ struct DebugSwitches {
     // ---- executor and pack (plan.hip, plan_train.hip; the pack switches: plan_build.hip)
     bool exact_fp32 = false;         // the split-half path off: every coupling network on the exact-fp32 MFMA kernels, training included
     bool no_mixer_fusion = false;    // no mixer of the next step inside the finishing kernel, no squeeze folded into a mixer
-    // FUSED FINISHING (k_cnet1w finishing the step itself, cnet1w_sh.hip FIN) is OFF unless asked for: built, bit-identical to the
-    // finishing kernel (tests/test_gpu_fused.py), and measured SLOWER -- 7.68 against 6.80 ms per config-B forward, + 27 us per level-1
-    // launch: every workgroup arrives last at about one tile, so every CU pays the finishing's latency chain
-    // (store drain, counter round trip, a read-around-L2 round trip per 64-pixel chunk) twice per launch, one workgroup at a time,
-    // where the finishing kernel runs four workgroups per CU side by side.
-    bool fused_finish = false;
     bool lu_workgroup = false;       // log|det W| of the small matrices on the workgroup-wide LU (A/B and bitwise test of the one-wave form)
     bool pack_one_stream = false;    // glowhip_plan_pack without the side-stream fork
     bool pack_unfused = false;       // the forward-only pack as its per-kind launch sequence, not k_pack_fused (A/B, byte comparison)
@@ -32,7 +26,6 @@ struct DebugSwitches {
     bool cnet_chain = false;         // a step's finishing inside the next step's k_cnet (off by default: measured slower)
     bool cfinish_block_order = false;   // the finishing kernel takes its pixel chunks in block order, not the XCD-affine order
     bool no_cnet1w = false;          // no k_cnet1w (one wave per SIMD): k_cnet takes its launches
-    bool cnet1w_row_split = false;   // k_cnet1w's row-split instance where it applies (off by default: measured slower)
     bool no_cnet1w_bwd = false;      // no backward instance of k_cnet1w
     // ---- weight gradients (wgrad_mfma.hip)
     bool wgrad_narrow = false;       // f.2's weight-gradient GEMM on 128-column tiles everywhere

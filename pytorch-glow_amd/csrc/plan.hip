@@ -31,7 +31,6 @@ static int pack_scales(const float* logs, int n, float* scale, float* inv, hipSt
 
 // Workspace carving
 struct Workspace {
-    unsigned* fin_cnt;        // arrival counters of the fused finishing (sh.h CnetArgs::fin_cnt): one word per 64 pixels of the widest level
     unsigned long long* acc;
     float* bufA;
     float* bufB;
@@ -39,22 +38,15 @@ struct Workspace {
     float* h2;
 };
 
-static size_t fin_cnt_words(const glowhip_plan* p, int N) {
-    size_t px = 0;
-    for (const LayerPlan& L : p->layers)
-        if (L.d.kind == GLOWHIP_LAYER_FLOWSTEP) px = std::max(px, (size_t)L.d.H * L.d.W);
-    return ((size_t)N * px + 63) / 64 + 64;
-}
-
-// fin_cnt | acc | bufA | bufB | h1 | h2; returns the size (w / base null: that alone)
+// acc | bufA | bufB | h1 | h2; returns the size (w / base null: that alone)
 static size_t ws_layout(const glowhip_plan* p, int N, void* base, Workspace* w) {
     size_t off = 0;
     const size_t chw = (size_t)N * p->max_chw * 4, hid = (size_t)N * p->max_hidden * 4;
-    const size_t o_fin = take(off, fin_cnt_words(p, N) * 4), o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA));
+    const size_t o_acc = take(off, (size_t)N * 8 * (2 + ACC_EXTRA));
     const size_t o_A = take(off, chw), o_B = take(off, chw), o_h1 = take(off, hid), o_h2 = take(off, hid);
     if (w && base)
-        *w = Workspace{at<unsigned>(base, o_fin), at<unsigned long long>(base, o_acc), at<float>(base, o_A), at<float>(base, o_B),
-                       at<float>(base, o_h1), at<float>(base, o_h2)};
+        *w = Workspace{at<unsigned long long>(base, o_acc), at<float>(base, o_A), at<float>(base, o_B), at<float>(base, o_h1),
+                       at<float>(base, o_h2)};
     return align_up(off, 256);
 }
 
@@ -166,8 +158,7 @@ static void count_cnet_variant(glowhip_plan* p, const CnetArgs& c, const CnetPen
     snprintf(name, sizeof name, "variant:k_cnet%s<%d,%d,%d>", pend.one_wave ? "1w" : "", c.hidden, pend.MS, 1 << pend.lpxt);
     count_launch(p, name);
 }
-// One FlowStep's k_cnet launch (`pending`: it also finishes the previous step) and, with `finish`, this step's finishing: by the
-// launch itself where it took the offer (fused finishing, sh.h CnetArgs::fin_cnt), by the finishing kernel otherwise.
+// One FlowStep's k_cnet launch (`pending`: it also finishes the previous step) and, with `finish`, this step's finishing kernel.
 static int run_cnet_step(glowhip_plan* p, const CnetArgs& c, bool pending, bool finish, CnetPending* pend, hipStream_t s) {
     {
         ScopedTimer t(p, GLOWHIP_K_CNET, 1, s);
@@ -176,10 +167,6 @@ static int run_cnet_step(glowhip_plan* p, const CnetArgs& c, bool pending, bool 
         count_cnet_variant(p, c, *pend);
     }
     if (!finish) return GLOWHIP_OK;
-    if (pend->finished) {
-        count_launch(p, "k_cnet(finishes the step)");
-        return GLOWHIP_OK;
-    }
     ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
     count_launch(p, c.mix.C ? "k_cfinish+mixer" : "k_cfinish");
     return launch_cnet_finish(c, *pend, s);
@@ -403,8 +390,6 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                             premixed = true;
                         }
                     }
-                    // ... by the launch itself where it can (fused finishing, sh.h CnetArgs::fin_cnt; per-launch event timing keeps the two apart)
-                    if (debug_switches().fused_finish && !p->timing) c.fin_cnt = w.fin_cnt;
                 }
                 GH_TRY(run_cnet_step(p, c, pending, !chain, &pend, s));
                 pending = chain;
@@ -494,10 +479,9 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                 }
                 const bool chain = d.C <= 96 && li - 1 >= 0 && cnet_chain(p, L, p->layers[li - 1]) && p->layers[li - 1].d.C <= 96;
                 float* fout = nullptr;
-                if (!chain && d.C <= 96) {      // (as in run_forward: the finishing's arguments are there at launch time, the launch may do it)
+                if (!chain && d.C <= 96) {
                     fout = (li == 0) ? x_out : other_buf(w, cur);
                     c.z_out = fout; c.z_out_bs = chw; c.mix = mixer_rev(L, packed);
-                    if (debug_switches().fused_finish && !p->timing) c.fin_cnt = w.fin_cnt;
                 }
                 GH_TRY(run_cnet_step(p, c, pending, fout != nullptr, &pend, s));      // (its mixer is set: the finishing counts as "k_cfinish+mixer")
                 pending = chain;
@@ -557,10 +541,10 @@ static int check_plan_args(const glowhip_plan* plan, const void* packed, int N) 
     GH_REQUIRE(N >= 0 && N <= 65535, "batch size %d out of range", N);
     return GLOWHIP_OK;
 }
-// the workspace of a call on N samples, its log-det accumulators and finishing counters zeroed
+// the workspace of a call on N samples, its log-det accumulators zeroed
 static int open_workspace(const glowhip_plan* p, int N, void* ws, size_t bytes, Workspace& w, hipStream_t s) {
     GH_TRY(carve(p, N, ws, bytes, w));
-    return launch_zero_acc(w.acc, N, s, ACC_EXTRA, w.fin_cnt, fin_cnt_words(p, N));
+    return launch_zero_acc(w.acc, N, s, ACC_EXTRA);
 }
 
 // Glow.normal_flow behind glowhip_glow_forward (x) and glowhip_glow_forward_u8 (x_u8 / divisor: 8-bit pixels, SURVEY.md 8f N4 --

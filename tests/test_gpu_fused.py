@@ -29,8 +29,8 @@ def ncnet(counts):
 
 
 def nfinish(counts):
-    """FlowSteps finished: by a finishing launch, or (round 6) by their own k_cnet1w launch (fused finishing)."""
-    return counts.get("k_cfinish", 0) + counts.get("k_cfinish+mixer", 0) + counts.get("k_cnet(finishes the step)", 0)
+    """FlowSteps finished by a finishing launch."""
+    return counts.get("k_cfinish", 0) + counts.get("k_cfinish+mixer", 0)
 
 
 def _case(image, L, K, hidden, batch, seed=5, coup="affine", perm="invconv"):
@@ -103,22 +103,17 @@ def test_level1_runs_on_the_one_wave_per_simd_kernel_and_both_kernels_match_the_
         assert counts.get("variant:k_cnet<512,1,128>") == K and "variant:k_cnet1w<512,1,128>" not in counts, counts
 
 
-def test_row_split_instance_of_the_one_wave_kernel_matches_the_oracle():
-    """Round 5: k_cnet1w with the h2 rows of a 128-pixel tile split over TWO workgroups (each computes all of h1, half of f.2, a
-    K-half of f.4; partial sums in k_cnet's MS = 2 layout for the finishing kernel) -- built for the C = 24 levels whose 128-pixel
-    tiles alone fill half the CUs (config B's level 2 at batch 64: 128 tiles).  Measured 3 % slower there than k_cnet's 64-pixel
-    tiles, so it sits behind the debug switch 0x20000; this test is its parity evidence: forward and inverse at config-B geometry,
-    every element against the oracle (inside _case), the instance asserted from the run-time counters; without the switch the same
-    launches run on k_cnet<512,1,64>."""
+def test_c24_level_at_128_tiles_stays_on_k_cnet_with_64_pixel_tiles():
+    """Config-B geometry at batch 64: level 2 (C = 24 on 16x16 pixels) has 128 tiles of 128 pixels, too few to fill the chip, so its
+    launches run on k_cnet<512,1,64> (one 64-pixel workgroup per CU) and no row-split instance of k_cnet1w exists for them; level 1
+    stays on k_cnet1w<512,1,128>, level 3 on k_cnet<512,4,64>.  Forward and inverse, every element against the oracle (inside
+    _case), the instances asserted from the run-time counters."""
     K = 2
-    with _lib.debug_flags(_lib.DBG.CNET1W_ROW_SPLIT):
-        plan, fwd, rev = _case(64, 3, K, 512, 64, seed=14)
+    plan, fwd, rev = _case(64, 3, K, 512, 64, seed=14)
     for counts in (fwd, rev):
-        assert counts.get("variant:k_cnet1w<512,1,128>") == K and counts.get("variant:k_cnet1w<512,2,128>") == K, counts
-        assert counts.get("variant:k_cnet<512,4,64>") == K and ncnet(counts) == 3 * K and nfinish(counts) == 3 * K, counts
-    plan2, fwd2, rev2 = _case(64, 3, K, 512, 64, seed=14)
-    for counts in (fwd2, rev2):
         assert counts.get("variant:k_cnet<512,1,64>") == K and "variant:k_cnet1w<512,2,128>" not in counts, counts
+        assert counts.get("variant:k_cnet1w<512,1,128>") == K and counts.get("variant:k_cnet<512,4,64>") == K, counts
+        assert ncnet(counts) == 3 * K and nfinish(counts) == 3 * K, counts
 
 
 def test_one_wave_kernel_at_a_16_pixel_wide_level():
@@ -144,52 +139,6 @@ def test_one_wave_kernel_at_the_64_and_128_pixel_wide_levels_vs_oracle(image, ba
     for counts in (fwd, rev):
         assert counts.get("variant:k_cnet1w<512,1,128>") == K, counts
         assert ncnet(counts) == K and nfinish(counts) == K, counts
-
-
-@pytest.mark.parametrize("image,L,batch,K", [(64, 3, 64, 3), (64, 3, 32, 2), (128, 1, 7, 2), (256, 1, 2, 2), (32, 1, 112, 2)])
-def test_fused_finishing_equals_the_finishing_kernel_bitwise(image, L, batch, K):
-    """Round 6, a measured NEGATIVE kept behind the switch 0x100000: where a FlowStep runs on k_cnet1w the launch can
-    FINISH the step itself -- every workgroup publishes its partial sums of f.4 (agent-scope stores), bumps the arrival counters of
-    its tile and of the two neighbouring tiles of the image, and whoever completes a tile's counter runs the finishing kernel's own
-    code on that tile (coupling, log-det, the next step's mixer; cnet_fin.h cfinish_chunk) -- one launch per step instead of two.
-    It is slower (7.68 against 6.80 ms per config-B forward: every CU pays the finishing's latency chain twice per launch, one
-    workgroup at a time), so the default keeps the finishing kernel; this test is the parity evidence of the fused form: z, nll and
-    the decode are the same BITS either way, at every width the kernel runs at (32-, 64-, 128- and 16-pixel rows: four, two, one and
-    eight image rows per tile -- at 128 both halo rows of a tile come from other workgroups), and ten repetitions of the fused form
-    reproduce themselves (an arrival-counter race would show as a run-to-run difference).  Who finished: from the run-time counters.
-    Reference: network/model.py:105-117,131-139."""
-    cfg = O.default_cfg(image_shape=(image, image, 3), hidden_channels=512, K=K, L=L, batch=batch)
-    sd = O.seeded_state_dict(cfg, seed=19, invconv_perturb=0.02)
-    g = torch.Generator().manual_seed(19)
-    x = torch.rand(batch, 3, image, image, generator=g)
-    noise = torch.rand(batch, 3, image, image, generator=g) / 256
-    sd = O.glow_init_actnorm(x, noise, sd, cfg)
-    glow = make_glow(cfg, sd, batch)
-    plan = glow.flow.plan_for(dev(x))
-    eps = [dev(torch.randn(batch, *s, generator=g) * 0.7) for s in glow.flow.split_shapes((3, image, image))]
-
-    def run():
-        plan.launch_counts(reset=True)
-        z, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
-        fwd = plan.launch_counts(reset=True)
-        xr = glow.reverse_flow(z, None, eps=eps)
-        rev = plan.launch_counts(reset=True)
-        return z.clone(), nll.clone(), xr.clone(), fwd, rev
-
-    zu, nllu, xru, fwdu, revu = run()                  # the default: a finishing launch per step
-    for counts in (fwdu, revu):
-        assert "k_cnet(finishes the step)" not in counts and nfinish(counts) == L * K, counts
-    with _lib.debug_flags(_lib.DBG.FUSED_FINISH):
-        z, nll, xr, fwd, rev = run()
-        for counts in (fwd, rev):
-            assert counts.get("variant:k_cnet1w<512,1,128>") == K, counts
-            # every step of the level that runs on k_cnet1w is finished by its own launch (the mixer-less last step of a level too)
-            assert counts.get("k_cnet(finishes the step)") == K and nfinish(counts) == L * K, counts
-        for rep in range(10):
-            z2, nll2, xr2, _, _ = run()
-            assert torch.equal(z, z2) and torch.equal(nll, nll2) and torch.equal(xr, xr2), rep
-    assert torch.equal(z, zu) and torch.equal(nll, nllu) and torch.equal(xr, xru)
-    assert torch.isfinite(nll).all() and torch.isfinite(xr).all()
 
 
 def test_one_wave_per_matrix_logdet_equals_the_workgroup_lu_bitwise():
