@@ -96,7 +96,11 @@ int glowhip_conv2d(const float* x, long x_batch_stride, const float* w, const fl
 /* GaussianDiag.logp, network/module.py:453-467: out[n] = (in ? in[n] : 0) +
  * sum_{c,p} -0.5*(log(2pi) + 2*logs + (x-mean)^2/exp(2*logs)).  mean/logs may be NULL (= 0).
  * Element (n,c,p) of x/mean/logs at base[n*stride + c*HW + p].  scratch16N: 16*N bytes (per-sample fixed-point accumulator +
- * sticky non-finite flag: a NaN / inf term makes out[n] NaN, it is never dropped). */
+ * sticky non-finite flag: a NaN / inf term makes out[n] NaN, it is never dropped).
+ * Range: the kernel adds one partial sum v per 256 elements of a sample.  With P = ceil(C*HW / 256) <= 2^17 - 1 (checked: more is
+ * GLOWHIP_EINVAL) and every |v| < 2^43 nats, out[n] is in[n] + the exact sum of the partials, each rounded to 2^-32 nats, rounded to
+ * fp64 and stored as fp32 -- at any magnitude of the sum, beyond the 2^31 nats of the fixed-point word too.  A partial with |v| >= 2^43 makes
+ * out[n] -inf / +inf by its sign (NaN when both signs occur).  out[n] is never a finite value that is not that sum. */
 int glowhip_gaussian_logp(const float* x, long x_stride, const float* mean, const float* logs, long ml_stride,
                           int N, int C, int HW, const float* in, float* out, void* scratch16N,
                           glowhip_stream_t stream);
@@ -220,7 +224,12 @@ int glowhip_plan_get_family(const glowhip_plan* plan);
  * -inf term entered sample n's log-det sum (the sticky flags the nll reports as NaN / inf) | bit 3: an element of
  * result[n*elems_per_sample ..) (the call's output tensor: x of a decode, z of an encode; may be NULL) is not finite.
  * Non-zero means: out of the product kernels' range (or genuinely diverged) -- re-run on GLOWHIP_FAMILY_EXACT_FP32 to get
- * the reference's answer (Glow.reverse_flow network/model.py:454-471 has no nll that would show it).  No host sync. */
+ * the reference's answer (Glow.reverse_flow network/model.py:454-471 has no nll that would show it).  No host sync.
+ * Range of the log-det sum itself: a sample receives P workgroup partial sums from the Gaussian kernels (Split2d priors, top prior)
+ * and the terms of E affine-coupling elements; glowhip_plan_create refuses a layer list with 2^14 P + 104 E >= 2^31.  Under that
+ * inequality, partials of |v| < 2^43 nats are summed exactly (2^-32 nats each) whatever the size of the sum, and the status bits
+ * stay 0; a partial with |v| >= 2^43 sets bit 1 / bit 2 by its sign and the nll is +inf / -inf.  No input gives a finite nll that
+ * is not the sum of its terms. */
 int glowhip_plan_status(const glowhip_plan* plan, const void* workspace, size_t workspace_bytes, int N, const float* result,
                         long elems_per_sample, int32_t* status_out, glowhip_stream_t stream);
 

@@ -160,7 +160,11 @@ int glowhip_conv2d(const float* x, long x_batch_stride, const float* w, const fl
 
 int glowhip_gaussian_logp(const float* x, long x_stride, const float* mean, const float* logs, long ml_stride, int N,
                           int C, int HW, const float* in, float* out, void* scratch16N, glowhip_stream_t stream) {
+    if (N == 0) return GLOWHIP_OK;      // (an empty batch has no storage: its pointers may be null)
     GH_REQUIRE(x && out && scratch16N, "gaussian_logp: null argument");
+    // P = ceil(C HW / 256) workgroup partials per sample: 2^14 P < 2^31 (common.h RANGE)
+    GH_REQUIRE(FIX_COARSE_MIN * (double)cdiv((long)C * HW, 256) < 2147483648.0, "gaussian_logp: %ld elements per sample are more than the "
+               "accumulator's range guarantee covers", (long)C * HW);
     hipStream_t s = (hipStream_t)stream;
     unsigned long long* acc = (unsigned long long*)scratch16N;
     GH_TRY(launch_zero_acc(acc, N, s));

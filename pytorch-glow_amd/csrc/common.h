@@ -41,7 +41,8 @@ constexpr float LOGSCALE = 3.0f;  // network/module.py:10 logscale_factor
 // order-independent (bitwise reproducible), unlike float atomics.
 constexpr double FIX_SCALE = 4294967296.0;
 constexpr int ACC_EXTRA = 7;
-// acc: 2 N words -- acc[n] the accumulator of sample n, acc[N + n] its STICKY NON-FINITE FLAG -- and, in a plan's workspace,
+// acc: 2 N words -- acc[n] the accumulator of sample n, acc[N + n] its STICKY NON-FINITE FLAG (bits 0-2; the bits above them
+// count whole nats of large partials, see RANGE below) -- and, in a plan's workspace,
 // ACC_EXTRA more accumulator rows acc[(2 + k) N + n] that k_finalize adds to acc[n]: the finishing kernel of the product path
 // spreads its one-per-workgroup atomics over them (1 024 workgroups on the four cache lines of 64 samples' accumulators queue up).  A NaN / inf partial sum cannot
 // be represented in fixed point (the conversion would silently turn NaN into 0): it raises the flag instead, and k_finalize
@@ -49,16 +50,48 @@ constexpr int ACC_EXTRA = 7;
 // input surface as a non-finite nll exactly as in the reference, never as a finite wrong one.
 // flag bits: 1 = a NaN term, 2 = a +inf term, 4 = a -inf term (k_finalize: NaN wins, +inf and -inf together give NaN, as in the
 // reference's floating-point sum)
+//
+// RANGE.  Q31.32 holds |sum| < 2^31 nats, and a Gaussian term (x - mean)^2 / exp(2 logs) has no bound.  A workgroup partial v with
+// |v| >= FIX_COARSE_MIN is therefore split: its whole nats c = rint(v) go, shifted above the three flag bits, into the 61 spare bits of
+// the FLAG word (a signed count of nats; the carries of an add move upward only and the flags are set by atomicOr on bits 0-2, so
+// neither disturbs the other), and only the remainder v - c (exact in fp64, |v - c| <= 1/2) enters the fine accumulator.
+// rint(v 2^32) = c 2^32 + rint((v - c) 2^32): the two words together hold the very integer the fine word alone would have held, so
+// k_finalize (fix_total) returns the same bits as before whenever the sum fits Q31.32, and fine + coarse in fp64 when it does not.
+// A partial with |v| >= FIX_COARSE_MAX is not accumulated: it raises the +inf / -inf flag of its sign.
+// Guarantee, for a sample that receives P workgroup partials from the Gaussian kernels (k_gaussian_logp, k_split_tail, k_conv_tail,
+// k_conv_tail_dma, k_top_head_fwd) and the terms of E affine-coupling elements (|log sigmoid| < 104 each, converted per element):
+//     if  2^14 P + 104 E < 2^31                                      (acc_budget in plan_build.hip; glowhip_gaussian_logp)
+//     and every partial is finite with |v| < 2^43,
+//     then the result is the exact sum of the partials, each rounded once to 2^-32 nats, rounded once more to fp64:
+//     the fine word stays below 2^14 P + 104 E < 2^31 in magnitude and the coarse count below 2^43 P < 2^60, neither wraps.
+//     A partial that is NaN / inf or has |v| >= 2^43 makes the sample NaN / +inf / -inf with its flag bits set.
+// A finite wrong value needs a wrapped word, which the inequality excludes.
+constexpr double FIX_COARSE_MIN = 16384.0;              // 2^14 nats
+constexpr double FIX_COARSE_MAX = 8796093022208.0;      // 2^43 nats
+constexpr double FIX_COUPLING_TERM_MAX = 104.0;         // |logf(sigmoid)| of a positive fp32, denormals included
+constexpr unsigned long long FIX_FLAG_MASK = 7ull;
 __device__ __forceinline__ void fix_flag_nonfinite(unsigned long long* acc, long n, int N, double v) {
     atomicOr(acc + N + n, isnan(v) ? 1ull : (v > 0 ? 2ull : 4ull));
 }
 __device__ __forceinline__ void fix_atomic_add(unsigned long long* acc, long n, int N, double v) {
-    if (!isfinite(v)) { fix_flag_nonfinite(acc, n, N, v); return; }
+    if (!(fabs(v) < FIX_COARSE_MIN)) {      // rare: NaN / inf, or a partial the fine word must not take whole
+        if (!(fabs(v) < FIX_COARSE_MAX)) { fix_flag_nonfinite(acc, n, N, v); return; }
+        const double c = rint(v);
+        atomicAdd(acc + N + n, (unsigned long long)__double2ll_rn(c) << 3);
+        v -= c;
+    }
     long long q = __double2ll_rn(v * FIX_SCALE);
     atomicAdd(acc + n, (unsigned long long)q);
 }
 __device__ __forceinline__ double fix_to_double(unsigned long long a) {
     return (double)(long long)a * (1.0 / FIX_SCALE);
+}
+// fine word (all rows added) + the coarse count of the flag word, in nats
+__device__ __forceinline__ double fix_total(unsigned long long fine, unsigned long long flagword) {
+    const long long c = (long long)flagword >> 3, f = (long long)fine;
+    const long long hi = c + (f >> 32);
+    if (hi >= -2147483648ll && hi < 2147483648ll) return fix_to_double(fine + ((unsigned long long)c << 32));
+    return (double)c + fix_to_double(fine);
 }
 
 // ---- wave64 / workgroup reductions (fixed tree => deterministic) ------------------------------

@@ -137,6 +137,23 @@ static bool layout_layers(glowhip_plan* p, const glowhip_layer_desc* layers, int
     return true;
 }
 
+// The range guarantee of the per-sample log-det accumulators (common.h RANGE) needs  2^14 P + 104 E < 2^31  per sample.  Both counts
+// are fixed by the layer list.  P, workgroup partials of the Gaussian kernels: a Split2d's grid gives every workgroup its own
+// elements of the dropped half -- 256 of them in k_split_tail, at least one 16-pixel tile of one channel in the two MFMA tails -- and
+// the top prior is k_gaussian_logp's ceil(CHW / 256) workgroups (one, with a head attached).  E: the second half of every affine
+// FlowStep.  The same bound holds for the decode, whose only terms are the coupling's.
+static const char* acc_budget(const glowhip_plan* p) {
+    double P = 0.0, E = 0.0;
+    for (const LayerPlan& L : p->layers) {
+        const double half = (double)(L.d.C / 2) * L.d.H * L.d.W;
+        if (L.d.kind == GLOWHIP_LAYER_FLOWSTEP && L.d.coupling == GLOWHIP_COUPLING_AFFINE) E += half;
+        else if (L.d.kind == GLOWHIP_LAYER_SPLIT2D) P += ceil(half / (L.mfma_last ? 16.0 : 256.0));
+    }
+    P += ceil((double)p->out_shape[0] * p->out_shape[1] * p->out_shape[2] / 256.0);
+    return FIX_COARSE_MIN * P + FIX_COUPLING_TERM_MAX * E < 2147483648.0
+               ? nullptr : "the per-sample log-det accumulator cannot hold this many terms (common.h RANGE)";
+}
+
 // ---------------------------------------------------------------- create, step 2: the pack's job tables
 // The order of the pushes is kept: a pack's selection (select_jobs) is a stable filter of repack_jobs, and the one-launch pack's
 // segment table indexes into that.
@@ -354,6 +371,7 @@ glowhip_plan* glowhip_plan_create(const glowhip_layer_desc* layers, int n_layers
     size_t off = 0;
     take(off, 256);  // offset 0: plan-wide data-independent log-det total (fp64); offset 64..127: zero block for LDS-DMA padding
     if (!layout_layers(p, layers, n_layers, off)) { delete p; return nullptr; }
+    if (const char* why = acc_budget(p)) { set_error("plan_create: %s", why); delete p; return nullptr; }
     for (const LayerPlan& L : p->layers)
         if (L.d.kind == GLOWHIP_LAYER_FLOWSTEP) flowstep_jobs(p, L);
         else if (L.d.kind == GLOWHIP_LAYER_SPLIT2D) split_jobs(p, L);

@@ -772,9 +772,10 @@ __global__ void __launch_bounds__(256) k_finalize(const float* __restrict__ in,
     if (n >= N) return;
     unsigned long long a = acc ? acc[n] : 0ull;
     for (int k = 0; k < extra_rows; ++k) a += acc[(long)(2 + k) * N + n];      // (two's-complement sums: any grouping gives the same bits)
-    double v = (in ? (double)in[n] : 0.0) + offset + (konst ? sign * konst[0] : 0.0) + (acc ? fix_to_double(a) : 0.0);
-    if (acc && acc[N + n] != 0ull) {      // partial sums of this sample that were NaN / +inf / -inf (common.h)
-        const unsigned long long fl = acc[N + n];
+    const unsigned long long fw = acc ? acc[N + n] : 0ull;      // flags | whole nats of the large partials (common.h RANGE)
+    double v = (in ? (double)in[n] : 0.0) + offset + (konst ? sign * konst[0] : 0.0) + (acc ? fix_total(a, fw) : 0.0);
+    if (fw & FIX_FLAG_MASK) {      // partial sums of this sample that were NaN / +inf / -inf, or beyond the coarse range (common.h)
+        const unsigned long long fl = fw & FIX_FLAG_MASK;
         v = ((fl & 1ull) || (fl & 6ull) == 6ull) ? __builtin_nan("") : ((fl & 2ull) ? __builtin_inf() : -__builtin_inf());
     }
     if (out_unscaled) out_unscaled[n] = (float)v;
@@ -836,7 +837,7 @@ __global__ void __launch_bounds__(256) k_status(const unsigned long long* __rest
     }
     if (bad) any = 1;      // (benign race: every writer stores 1)
     __syncthreads();
-    if (threadIdx.x == 0) status[n] = (int32_t)(acc[N + n] & 7ull) | (any ? 8 : 0);
+    if (threadIdx.x == 0) status[n] = (int32_t)(acc[N + n] & FIX_FLAG_MASK) | (any ? 8 : 0);      // (the bits above the flags are a count, common.h RANGE)
 }
 
 int launch_status(const unsigned long long* acc, int N, const float* result, long elems, int32_t* status, hipStream_t s) {

@@ -220,8 +220,8 @@ def hip_forward(cid):
 @pytest.mark.parametrize("cid", ALL)
 def test_head_log_density_against_the_plain_prior_on_the_same_flow(cid):
     """nll_cond - nll_plain = -[logp(z | mean, logs) - logp(z | 0, 0)] / (ln 2 D): the flow is the same launches on the same bits
-    and cancels, so what is left is k_top_head_fwd against k_gaussian_logp (tested at every shape) and the fp64 densities
-    of the HIP path's own z.
+    and cancels, so what is left is k_top_head_fwd against k_gaussian_logp (held to fp64 on its own, shapes, arguments and range,
+    by tests/test_gpu_objective.py) and the fp64 densities of the HIP path's own z.
 
     Bound: both nll are fp32 outputs of a Q31.32 sum -- one rounding each plus the scaling, 4 u max|nll| -- and every top element's
     log-density is evaluated in fp32 from a handful of operations, each within a few u of the element's own size: 8 u = 2^-21
