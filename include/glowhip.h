@@ -377,6 +377,29 @@ int glowhip_optim_step(const glowhip_optim_chunk* chunks_dev, int n_chunks, int 
 int glowhip_optim_step_dev(const glowhip_optim_chunk* chunks_dev, int n_chunks, int kind, const double* hyper_dev, double beta1,
                            double beta2, float eps, float weight_decay, float clip_value, float max_norm, double* partial_dev,
                            float* grad_norm_out, int skip_if_nonfinite, glowhip_stream_t stream);
+/* The same two launches with a Polyak average (exponential moving average, EMA) of the weights updated by the update launch, at the
+ * moment the new parameter value p' is in a register.  THE definition of the arithmetic, per element, all in fp32 with three
+ * roundings (no fused multiply-add):
+ *     e' = e + (p' - e) * w
+ * w is the float the host passes -- the kernel knows no decay schedule (training._HipOptimizer.ema_weight: w = float(1 - decay_t)).
+ * ema_dev: n_chunks device pointers parallel to the chunk table, ema_dev[i] = the average of chunk i's n elements (the chunk struct
+ * keeps its 40-byte layout); a NULL entry = that chunk is not averaged.  The 16-byte path of a chunk needs its ema pointer 16-byte
+ * aligned like the other four, else the chunk runs element by element (same bits).  Parameters, state, gradients and the norm come
+ * out bit for bit as from glowhip_optim_step with the same arguments.  A step skipped by skip_if_nonfinite leaves e untouched too.
+ * No allocation, no host sync, capturable; still two launches. */
+int glowhip_optim_step_ema(const glowhip_optim_chunk* chunks_dev, float* const* ema_dev, int n_chunks, int kind, float lr, double beta1,
+                           double beta2, float eps, float weight_decay, int step, float clip_value, float max_norm, float ema_w,
+                           double* partial_dev, float* grad_norm_out, int skip_if_nonfinite, glowhip_stream_t stream);
+/* The device form: hyper_dev[4] = {lr, 1 - beta1^step, 1 - beta2^step, w (a float's value)} as doubles.  Same bits as
+ * glowhip_optim_step_ema. */
+int glowhip_optim_step_ema_dev(const glowhip_optim_chunk* chunks_dev, float* const* ema_dev, int n_chunks, int kind, const double* hyper_dev,
+                               double beta1, double beta2, float eps, float weight_decay, float clip_value, float max_norm,
+                               double* partial_dev, float* grad_norm_out, int skip_if_nonfinite, glowhip_stream_t stream);
+/* param[i] <-> ema_dev[i] for every chunk, ONE launch (16-byte accesses where both addresses allow; NULL entries are left alone):
+ * evaluate or sample under the averaged weights without moving an address -- plans, packed buffers and captured graphs stay valid
+ * (the caller bumps the parameters' version counters so that the plans re-derive their weight images).  Calling it twice restores
+ * both sides to the bit.  The gradient / m / v fields of the table are not read.  No allocation, no host sync, capturable. */
+int glowhip_optim_ema_swap(const glowhip_optim_chunk* chunks_dev, float* const* ema_dev, int n_chunks, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Top head: learned / class-conditional top prior + classifier (reference network/model.py:345-348, 362-379, 440-445,

@@ -210,6 +210,28 @@ def load_model(result_subdir, step_or_model_path, graph, optimizer=None, criteri
     return state
 
 
+def averaged_state_dict(state, graph):
+    """A snapshot dict (`save_model`) and its model -> a 'graph'-style state dict with every parameter replaced by its Polyak
+    average (the ``"ema"`` entries a HIP optimiser with ``ema_decay`` keeps in its state).  The optimiser's state is keyed by the
+    position of the parameter in ``graph.parameters()`` (what `build_optimizer` is handed); buffers and parameters the optimiser
+    holds no average for keep the snapshot's values.  Pure host code.  Raises when the snapshot carries no average."""
+    opt_state = (state.get('optimizer') or {}).get('state', {})
+    names = [name for name, _ in _bare(graph).named_parameters()]
+    found = {int(i): st['ema'] for i, st in opt_state.items() if isinstance(st, dict) and 'ema' in st}
+    if not found:
+        raise KeyError('the snapshot carries no averaged weights: its optimizer state has no "ema" entries '
+                       '(train with hps.optim.ema_decay > 0)')
+    if max(found) >= len(names):
+        raise KeyError('optimizer state index %d, but the graph has %d parameters' % (max(found), len(names)))
+    out = dict(state['graph'])
+    for i, ema in found.items():
+        live = out[names[i]]
+        if tuple(ema.shape) != tuple(live.shape):
+            raise ValueError('average of %s has shape %s, the parameter %s' % (names[i], tuple(ema.shape), tuple(live.shape)))
+        out[names[i]] = ema.detach().to(dtype=live.dtype, device=live.device).clone()
+    return out
+
+
 # ----------------------------------------------------------------------------- inference helpers (util.py:487-588)
 def lu_state_dict_from_dense(state_dict):
     """A copy of ``state_dict`` with every ``...invconv.weight`` entry replaced by the five entries of `Invertible1x1ConvLU`

@@ -50,6 +50,12 @@ class Builder:
             out['step'] = state['step']
         if hps.general.warm_start and state is None and not training:
             raise RuntimeError('No pre-trained model for inference')
+        # hps.general.use_ema (beyond the reference's schema, default false): inference runs on the Polyak-averaged weights the
+        # snapshot's optimizer state carries (hps.optim.ema_decay at training time), so `Inferer` samples from the average
+        if not training and hps.general.get('use_ema', False):
+            if state is None:
+                raise RuntimeError('hps.general.use_ema needs a snapshot to take the averaged weights from')
+            out['graph'].load_state_dict(util.averaged_state_dict(state, out['graph']))
 
         out['graph'] = out['graph'].to('cuda:{}'.format(devices[0]))
         print('[Builder] Use {} for model running and {} for data loading'.format(devices[0], data_device))

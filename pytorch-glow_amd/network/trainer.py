@@ -11,6 +11,7 @@ reconstruction / sampling calls every ``interval_valid`` / ``interval_sample`` s
 What changes: the step itself is `training.TrainLoop` -- HIP forward with tape, HIP backward, one flat RCCL all-reduce, fused
 clip + Adam -- and ``devices`` are RANKS (one process per GPU, `parallel`), not `DataParallel` replicas; ``tensorboardX`` and
 ``tqdm`` are optional (absent: scalars are kept in ``self.scalars`` and written to all_scalars.json at the end)."""
+import contextlib
 import json
 import os
 import time
@@ -133,11 +134,17 @@ class Trainer:
         self.interval_valid = self.hps.optim.interval_valid
         self.interval_sample = self.hps.optim.interval_sample
         self.num_sample = self.hps.optim.num_sample
+        # hps.optim.ema_eval (beyond the reference's schema): reconstructions and samples are drawn under the Polyak-averaged weights
+        # (hps.optim.ema_decay, training.averaged_weights: swapped in and out in place, the captured step stays valid)
+        self.ema_eval = bool(self.hps.optim.get("ema_eval", False))
         # the per-step arithmetic (trainer.py:88-150)
         # (a single-rank run replays its step as one hipGraph launch after the first eager steps -- training.GraphedTrainStep; the
         # environment variable GLOWHIP_TRAIN_GRAPH=0 keeps every step eager; a failed capture falls back to the eager step by itself)
         self.loop = training.TrainLoop(graph, hps, rank=rank, world=world, optimizer=optimizer,
                                        graph=world == 1 and os.environ.get("GLOWHIP_TRAIN_GRAPH", "1") != "0")
+        if self.ema_eval and not getattr(self.loop.optimizer, "ema_decay", 0.0):
+            raise ValueError("hps.optim.ema_eval is set but the optimiser keeps no averaged weights: set hps.optim.ema_decay > 0 "
+                             "(a HIP optimiser: not with GLOWHIP_TORCH_OPTIM=1) or unset hps.optim.ema_eval")
         self.loop.scheduler = scheduler or self.loop.scheduler
         self.loop.global_step = step
         self.last_loss = None
@@ -159,6 +166,13 @@ class Trainer:
 
     def _device(self):
         return next(self.graph.parameters()).device
+
+    def _eval_weights(self):
+        """The weights the interval_valid / interval_sample blocks run under: the average with hps.optim.ema_eval, else the live ones.
+        Rank-local (the blocks run on rank 0 alone): two launches on this rank's stream, ordered behind its last step; nothing here
+        resolves the deferred range check -- that can re-run a batch, a collective of every rank -- and a step the device skipped
+        left parameters and average alone."""
+        return training.averaged_weights(self.loop.optimizer) if self.ema_eval else contextlib.nullcontext()
 
     def train(self, max_steps=None):
         """The reference's loop.  ``max_steps`` (beyond its signature) stops early -- for tests and smoke runs."""
@@ -201,7 +215,7 @@ class Trainer:
                     util.save_model(result_subdir=self.result_subdir, step=self.step, graph=self.graph, optimizer=self.optimizer,
                                     seconds=time.time() - self.start_time, is_best=True)
                 if self.step % self.interval_valid == 0 and self.step > 0 and self.rank == 0:
-                    with torch.no_grad():
+                    with self._eval_weights(), torch.no_grad():
                         self.graph.eval()
                         z, _, _ = self.graph(x=x, y_onehot=y_onehot)
                         img = self.graph(z=z, y_onehot=y_onehot, reverse=True)
@@ -209,7 +223,7 @@ class Trainer:
                     for i in range(min(self.num_sample, img.shape[0])):
                         self.writer.add_image("reconstructed/{}".format(i), ops.cat_channel(img[i], x[i]), self.step)
                 if self.step % self.interval_sample == 0 and self.step > 0 and self.rank == 0:
-                    with torch.no_grad():
+                    with self._eval_weights(), torch.no_grad():
                         self.graph.eval()
                         img = self.graph(z=None, y_onehot=y_onehot, eps_std=0.5, reverse=True)
                         self.graph.train()

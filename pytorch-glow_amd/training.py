@@ -9,6 +9,7 @@ are ``torch.optim.Adam`` / ``Adamax`` exactly as in the reference (builder.py:10
 from functools import partial
 from typing import Iterable, Optional
 
+import contextlib
 import time
 
 import torch
@@ -29,17 +30,32 @@ class _HipOptimizer(torch.optim.Optimizer):
     reference snapshot (misc/util.py:309-322) loads.  The state tensors are views into two flat buffers.
 
     ``step()`` alone is torch's semantics; ``fused_step(max_grad_clip, max_grad_norm)`` also clips (in place, like
-    ``clip_grad_value_`` / ``clip_grad_norm_``) and returns the total gradient norm as a device tensor -- no host sync."""
+    ``clip_grad_value_`` / ``clip_grad_norm_``) and returns the total gradient norm as a device tensor -- no host sync.
+
+    ``ema_decay`` in (0, 1): a Polyak average of the weights (the Glow paper evaluates and samples from one), updated INSIDE the
+    update launch (glowhip_optim_step_ema: e' = e + (p' - e) * w, no extra launch or sweep), kept in a third flat buffer with the
+    views ``state[p]["ema"]`` -- so ``state_dict()`` / ``load_state_dict()`` carry it.  It starts as a copy of the parameters when the
+    state is first built (the first ``fused_step``: after the data-dependent ActNorm init).  ``ema_warmup``: decay_t =
+    min(ema_decay, (1 + t) / (10 + t)), t = the EMA updates applied so far (`ema_weight`).  ``swap_averaged()`` /
+    `averaged_weights` exchange parameters and average in place.  Off (0.0, the default): every launch, bit and state-dict key is
+    as without the option."""
 
     KIND = 0
     SECOND = "exp_avg_sq"
     CHUNK = 1 << 16
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, **unsupported):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, ema_decay=0.0, ema_warmup=False, **unsupported):
         for k, v in unsupported.items():
             if v not in (False, None, 0):
                 raise ValueError(f"{type(self).__name__}: option {k}={v!r} is not supported on the HIP optimiser")
+        ema_decay = float(ema_decay or 0.0)
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"{type(self).__name__}: ema_decay={ema_decay!r} must lie in [0, 1)")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
+        # (not in the param groups' defaults: an optimiser without EMA keeps the state-dict keys it had)
+        self.ema_decay, self.ema_warmup = ema_decay, bool(ema_warmup)
+        self._ema_t = 0              # EMA updates applied (the `t` of the warm-up rule)
+        self._swapped = None         # (tables, parameters) of a swap_averaged() that has not been swapped back
         self._flat = None
         self._steps = 0
 
@@ -54,6 +70,7 @@ class _HipOptimizer(torch.optim.Optimizer):
             raise _lib.GlowHipError("the HIP optimiser needs contiguous fp32 parameters on one HIP device")
         total = sum(p.numel() for p in ps)
         m, v = torch.zeros(total, device=dev), torch.zeros(total, device=dev)
+        e = torch.empty(total, device=dev) if self.ema_decay else None
         off = 0
         for p in ps:
             n = p.numel()
@@ -63,19 +80,134 @@ class _HipOptimizer(torch.optim.Optimizer):
                 if name in st:                      # state loaded before the first step (load_state_dict)
                     view.copy_(st[name])
                 st[name] = view
+            if e is not None:                       # (with EMA off a loaded "ema" stays where it is: kept, not used)
+                view = e[off:off + n].view_as(p)
+                view.copy_(st["ema"] if "ema" in st else p.detach())      # a state without one: the average starts at the parameters
+                st["ema"] = view
             st.setdefault("step", torch.tensor(float(self._steps)))
             off += n
-        self._flat = (m, v)
+        self._flat = (m, v) if e is None else (m, v, e)
         self._partial = None
         self._table_key = None       # the cached chunk table points into the previous state buffers
         self._keep = None
+        self._keep_ema = None
+        self._swap_table = None
 
     def load_state_dict(self, state_dict):
+        if self._swapped is not None:
+            raise _lib.GlowHipError("load_state_dict while the averaged weights are swapped in: swap back first")
         super().load_state_dict(state_dict)
         steps = [float(s["step"]) for s in self.state.values() if "step" in s]
         self._steps = int(max(steps)) if steps else 0
+        counts = [g.pop("ema_updates", None) for g in self.param_groups]
+        if self.ema_decay:           # a state with an average continues its count (its own, or the step count of a state that has none)
+            has = any("ema" in s for s in self.state.values())
+            self._ema_t = (int(counts[0]) if counts and counts[0] is not None else self._steps) if has else 0
         self._flat = None            # re-home the loaded tensors in the flat buffers at the next step
         self._ensure_state()
+
+    # ---- Polyak average of the weights
+    def ema_weight(self, t):
+        """The float w of e' = e + (p' - e) * w for the EMA update that follows `t` applied ones: 1 - decay_t in python doubles, then
+        through a float (what glowhip_optim_step_ema takes as its argument and the device form reads from hyper[3])."""
+        decay = min(self.ema_decay, (1.0 + t) / (10.0 + t)) if self.ema_warmup else self.ema_decay
+        return ctypes.c_float(1.0 - decay).value
+
+    @property
+    def ema_updates(self):
+        return self._ema_t
+
+    @property
+    def swapped(self):
+        """True between a swap_averaged() and the one that undoes it: the parameters ARE the average, the "ema" state the live weights."""
+        return self._swapped is not None
+
+    def _refuse_swapped(self, what):
+        if self._swapped is not None:
+            raise _lib.GlowHipError(f"{what} while the averaged weights are swapped in (swap_averaged / averaged_weights): "
+                                    "the step would train the average")
+
+    @torch.no_grad()
+    def swap_averaged(self):
+        """Exchange parameters and their average IN PLACE: one launch (glowhip_optim_ema_swap) plus one version bump of the
+        parameters, so the flow plans re-derive their weight images.  No address changes: plans, packed buffers and captured graphs
+        stay valid.  The second call swaps back, to the bit, through the very table that swapped in.  The kernel reads only the
+        parameter and average pointers, so the swap has a table of its own and leaves the step's chunk table (and a captured step
+        that holds it) alone.  It covers the parameters that have a gradient -- one without has no chunk in the step, is not averaged
+        and is left alone; when NO parameter has one (a state just loaded, ``zero_grad()``) it covers all of them: a parameter that
+        never trains equals its average, which started as its copy."""
+        if not self.ema_decay:
+            raise _lib.GlowHipError("swap_averaged: this optimiser keeps no average (ema_decay = 0)")
+        if self._swapped is None:
+            self._ensure_state()
+            plist = self._params_list()
+            if not plist:
+                return
+            touched = [p for p in plist if p.grad is not None] or list(plist)
+            key = (self._flat[2].data_ptr(),) + tuple(p.data_ptr() for p in touched)
+            held = getattr(self, "_swap_table", None)
+            if held is None or held[0] != key:
+                dev = plist[0].device
+                chunks, emas = [], []
+                for p in touched:
+                    n, p0, e0 = p.numel(), p.data_ptr(), self.state[p]["ema"].data_ptr()
+                    for o in range(0, n, self.CHUNK):
+                        chunks.append(_lib.OptimChunk(p0 + 4 * o, 0, 0, 0, min(self.CHUNK, n - o), 0))
+                        emas.append(e0 + 4 * o)
+                arr = (_lib.OptimChunk * len(chunks))(*chunks)
+                table = torch.frombuffer(bytearray(ctypes.string_at(arr, ctypes.sizeof(arr))), dtype=torch.uint8).to(dev, non_blocking=False)
+                ema_table = torch.tensor(emas, dtype=torch.int64).to(dev, non_blocking=False)
+                held = self._swap_table = (key, table, ema_table, len(chunks), touched)
+        else:
+            held = self._swapped
+        _, table, ema_table, n_chunks, touched = held
+        _lib.check(_lib.lib().glowhip_optim_ema_swap(_lib.ptr(table), _lib.ptr(ema_table), n_chunks, _lib.stream_ptr(touched[0].device)))
+        torch.autograd.graph.increment_version(touched)
+        self._swapped = held if self._swapped is None else None
+
+    def _params_list(self):
+        plist = getattr(self, "_plist", None)
+        if plist is None:
+            plist = self._plist = [p for g in self.param_groups for p in g["params"]]
+        return plist
+
+    def _chunk_table(self, grads_token):
+        """The device chunk table (and, with EMA, the pointer array parallel to it) for the current parameter / gradient addresses."""
+        plist = self._params_list()
+        # ``grads_token``: an object that stands for "the gradients are the plan's persistent buckets" (Glow.loss_and_grads): as long
+        # as the caller shows the same token, parameter, gradient and state addresses cannot have moved and the key below -- four
+        # attribute reads for each of ~1 060 parameters, 1.2 ms -- is not recomputed
+        fast = grads_token is not None and grads_token is getattr(self, "_table_token", None) and self._table_key is not None
+        # (dtype and contiguity are part of the key: a gradient that comes back at the same address as a different view must not ride
+        # on the checks the cached table was built under -- ADVICE r4)
+        key = self._table_key if fast else tuple((p.data_ptr(), p.grad.data_ptr(), p.grad.dtype, p.grad.is_contiguous()) if p.grad is not None else (0, 0, None, True) for p in plist)
+        if getattr(self, "_table_key", None) != key:
+            dev = plist[0].device
+            chunks, emas = [], []
+            for p in plist:
+                if p.grad is None:
+                    continue
+                gr = p.grad
+                if not gr.is_contiguous() or gr.dtype != torch.float32:
+                    raise _lib.GlowHipError("gradients must be contiguous fp32")
+                st = self.state[p]
+                n, base = p.numel(), (p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st[self.SECOND].data_ptr())
+                e0 = st["ema"].data_ptr() if self.ema_decay else 0
+                for o in range(0, n, self.CHUNK):
+                    chunks.append((base[0] + 4 * o, base[1] + 4 * o, base[2] + 4 * o, base[3] + 4 * o, min(self.CHUNK, n - o)))
+                    emas.append(e0 + 4 * o)
+            n_chunks = len(chunks)
+            table = ema_table = None
+            if n_chunks:
+                arr = (_lib.OptimChunk * n_chunks)(*[_lib.OptimChunk(*c, 0) for c in chunks])
+                host = torch.frombuffer(bytearray(ctypes.string_at(arr, ctypes.sizeof(arr))), dtype=torch.uint8)
+                table = host.to(dev, non_blocking=False)
+                if self.ema_decay:
+                    ema_table = torch.tensor(emas, dtype=torch.int64).to(dev, non_blocking=False)
+            # (the tables stay alive until the stream has consumed them: the next build replaces them)
+            self._table_key, self._n_chunks, self._keep, self._keep_ema = key, n_chunks, table, ema_table
+        self._table_token = grads_token
+        return self._keep, self._keep_ema, self._n_chunks
 
     @torch.no_grad()
     def fused_step(self, max_grad_clip=0.0, max_grad_norm=0.0, skip_nonfinite=False, grads_token=None, hyper_dev=None, norm_out=None):
@@ -83,7 +215,8 @@ class _HipOptimizer(torch.optim.Optimizer):
         the caller finds out from the returned norm when it next looks (``undo_step`` then takes the step count back).
         ``hyper_dev`` (3 doubles on the device, `hyper_values`) / ``norm_out`` (1 float on the device): the step as it sits in a
         captured graph (`GraphedTrainStep`) -- learning rate and bias corrections are read from device memory by the update kernel
-        (glowhip_optim_step_dev), the norm lands in the caller's static word."""
+        (glowhip_optim_step_dev), the norm lands in the caller's static word.  With ``ema_decay``: 4 doubles, `ema_weight` of the
+        EMA updates applied so far as the fourth (glowhip_optim_step_ema_dev)."""
         self._ensure_state()
         group0 = self.param_groups[0]
         dev = group0["params"][0].device
@@ -94,47 +227,32 @@ class _HipOptimizer(torch.optim.Optimizer):
         # addresses again, so the table is keyed by (parameter address, gradient address) of every parameter -- two data_ptr() calls
         # each -- and rebuilt (with the full checks) only when one of them moved; the state addresses change only with the state
         # buffers, which resets the key (a reloaded state or a re-allocated parameter must not reuse the table).
-        plist = getattr(self, "_plist", None)
-        if plist is None:
-            plist = self._plist = [p for g in self.param_groups for p in g["params"]]
-        # ``grads_token``: an object that stands for "the gradients are the plan's persistent buckets" (Glow.loss_and_grads): as long
-        # as the caller shows the same token, parameter, gradient and state addresses cannot have moved and the key below -- four
-        # attribute reads for each of ~1 060 parameters, 1.2 ms -- is not recomputed
-        fast = grads_token is not None and grads_token is getattr(self, "_table_token", None) and self._table_key is not None
-        # (dtype and contiguity are part of the key: a gradient that comes back at the same address as a different view must not ride
-        # on the checks the cached table was built under -- ADVICE r4)
-        key = self._table_key if fast else tuple((p.data_ptr(), p.grad.data_ptr(), p.grad.dtype, p.grad.is_contiguous()) if p.grad is not None else (0, 0, None, True) for p in plist)
+        self._refuse_swapped("fused_step")
+        plist = self._params_list()
+        table, ema_table, n_chunks = self._chunk_table(grads_token)
         self._steps += 1
         self._publish_step()
         norm = norm_out if norm_out is not None else torch.zeros(1, device=dev)
-        if getattr(self, "_table_key", None) == key:
-            table, n_chunks = self._keep, self._n_chunks
-        else:
-            chunks = []
-            for p in plist:
-                if p.grad is None:
-                    continue
-                gr = p.grad
-                if not gr.is_contiguous() or gr.dtype != torch.float32:
-                    raise _lib.GlowHipError("gradients must be contiguous fp32")
-                st = self.state[p]
-                n, base = p.numel(), (p.data_ptr(), gr.data_ptr(), st["exp_avg"].data_ptr(), st[self.SECOND].data_ptr())
-                for o in range(0, n, self.CHUNK):
-                    chunks.append((base[0] + 4 * o, base[1] + 4 * o, base[2] + 4 * o, base[3] + 4 * o, min(self.CHUNK, n - o)))
-            n_chunks = len(chunks)
-            if n_chunks:
-                arr = (_lib.OptimChunk * n_chunks)(*[_lib.OptimChunk(*c, 0) for c in chunks])
-                host = torch.frombuffer(bytearray(ctypes.string_at(arr, ctypes.sizeof(arr))), dtype=torch.uint8)
-                table = host.to(dev, non_blocking=False)
-            else:
-                table = None
-            self._table_key, self._n_chunks = key, n_chunks
-        self._table_token = grads_token
         if not n_chunks:
             return norm[0]
         if self._partial is None or self._partial.numel() < n_chunks:
             self._partial = torch.empty(n_chunks, dtype=torch.float64, device=dev)
-        if hyper_dev is not None:
+        if self.ema_decay:
+            w = self.ema_weight(self._ema_t)      # (the device form reads the caller's hyper_dev[3] instead: computed the same way)
+            self._ema_t += 1
+            if hyper_dev is not None:
+                if hyper_dev.numel() < 4:
+                    raise _lib.GlowHipError("fused_step: with EMA on, hyper_dev holds 4 doubles (hyper_values + ema_weight)")
+                _lib.check(_lib.lib().glowhip_optim_step_ema_dev(
+                    _lib.ptr(table), _lib.ptr(ema_table), n_chunks, self.KIND, _lib.ptr(hyper_dev), float(group0["betas"][0]),
+                    float(group0["betas"][1]), float(group0["eps"]), float(group0["weight_decay"]), float(max_grad_clip or 0.0),
+                    float(max_grad_norm or 0.0), _lib.ptr(self._partial), _lib.ptr(norm), int(bool(skip_nonfinite)), _lib.stream_ptr(dev)))
+            else:
+                _lib.check(_lib.lib().glowhip_optim_step_ema(
+                    _lib.ptr(table), _lib.ptr(ema_table), n_chunks, self.KIND, float(group0["lr"]), float(group0["betas"][0]),
+                    float(group0["betas"][1]), float(group0["eps"]), float(group0["weight_decay"]), self._steps, float(max_grad_clip or 0.0),
+                    float(max_grad_norm or 0.0), w, _lib.ptr(self._partial), _lib.ptr(norm), int(bool(skip_nonfinite)), _lib.stream_ptr(dev)))
+        elif hyper_dev is not None:
             _lib.check(_lib.lib().glowhip_optim_step_dev(
                 _lib.ptr(table), n_chunks, self.KIND, _lib.ptr(hyper_dev), float(group0["betas"][0]), float(group0["betas"][1]),
                 float(group0["eps"]), float(group0["weight_decay"]), float(max_grad_clip or 0.0), float(max_grad_norm or 0.0),
@@ -144,7 +262,6 @@ class _HipOptimizer(torch.optim.Optimizer):
                 _lib.ptr(table), n_chunks, self.KIND, float(group0["lr"]), float(group0["betas"][0]), float(group0["betas"][1]),
                 float(group0["eps"]), float(group0["weight_decay"]), self._steps, float(max_grad_clip or 0.0), float(max_grad_norm or 0.0),
                 _lib.ptr(self._partial), _lib.ptr(norm), int(bool(skip_nonfinite)), _lib.stream_ptr(dev)))
-        self._keep = table      # alive until the stream has consumed it (the next step replaces it)
         # the kernel wrote the parameters behind torch's back: bump their version counters, which is what tells the flow plans to
         # re-derive their packed weight images (one call for the whole list)
         torch.autograd.graph.increment_version([p for p in plist if p.grad is not None])
@@ -166,10 +283,16 @@ class _HipOptimizer(torch.optim.Optimizer):
     def state_dict(self):
         """torch's optimisers increment `step` IN PLACE per parameter after a load_state_dict: whoever receives this state must get
         one tensor object per parameter, not the shared one."""
+        if self._swapped is not None:
+            raise _lib.GlowHipError("state_dict while the averaged weights are swapped in: swap back first")
         for st in self.state.values():
             if "step" in st:
                 st["step"] = torch.tensor(float(self._steps))
-        return super().state_dict()
+        out = super().state_dict()
+        if self.ema_decay:           # the warm-up rule's count travels with the average
+            for g in out["param_groups"]:
+                g["ema_updates"] = self._ema_t
+        return out
 
     def hyper_values(self, lr, step):
         """{lr, 1 - beta1^step, 1 - beta2^step} as glowhip_optim_step computes them from its arguments (the learning rate passes
@@ -177,9 +300,16 @@ class _HipOptimizer(torch.optim.Optimizer):
         b1, b2 = self.param_groups[0]["betas"]
         return (ctypes.c_float(float(lr)).value, 1.0 - float(b1) ** step, 1.0 - float(b2) ** step)
 
+    def ema_state(self):
+        """The averages, one per parameter in parameter order (views into the flat buffer)."""
+        self._ensure_state()
+        return [self.state[p]["ema"] for p in self._params_list()]
+
     def undo_step(self):
         """Take back the count of a step the device skipped (fused_step(skip_nonfinite=True) with a non-finite norm)."""
         self._steps = max(self._steps - 1, 0)
+        if self.ema_decay:           # (the device left the average alone as well)
+            self._ema_t = max(self._ema_t - 1, 0)
         self._publish_step()
 
 
@@ -202,14 +332,33 @@ OPTIMIZERS = ({"adam": torch.optim.Adam, "adamax": torch.optim.Adamax} if _os.en
 
 
 def build_optimizer(hps, params: Iterable[torch.nn.Parameter]) -> torch.optim.Optimizer:
-    """``hps.optim.optimizer`` / ``optimizer_args`` -> optimiser (builder.py:108-113)."""
+    """``hps.optim.optimizer`` / ``optimizer_args`` -> optimiser (builder.py:108-113).  ``hps.optim.ema_decay`` / ``ema_warmup``
+    (beyond the reference's schema; absent or 0 = off) switch the HIP optimisers' Polyak average on."""
     name = hps.optim.optimizer.lower()
     if name not in OPTIMIZERS:
         raise KeyError(f"unknown optimizer {name!r}; the reference knows {sorted(OPTIMIZERS)}")
     args = dict(hps.optim.optimizer_args)
     if "betas" in args:
         args["betas"] = tuple(args["betas"])
+    ema_decay = float(hps.optim.get("ema_decay", 0.0) or 0.0)
+    if ema_decay:
+        if not issubclass(OPTIMIZERS[name], _HipOptimizer):
+            raise ValueError("hps.optim.ema_decay = %r: the Polyak average is part of the HIP optimisers' update launch; torch's own "
+                             "optimisers (GLOWHIP_TORCH_OPTIM=1) keep none -- unset one of the two" % ema_decay)
+        args.update(ema_decay=ema_decay, ema_warmup=bool(hps.optim.get("ema_warmup", False)))
     return OPTIMIZERS[name](list(params), **args)
+
+
+@contextlib.contextmanager
+def averaged_weights(optimizer):
+    """Run a block -- an evaluation, a sampling call -- under the Polyak-averaged weights of a HIP optimiser with ``ema_decay``:
+    swapped in on entry, swapped back on exit, also when the block raises.  Two launches in all; no address moves, so plans and a
+    captured training step stay valid.  Training steps inside the block raise."""
+    optimizer.swap_averaged()
+    try:
+        yield optimizer
+    finally:
+        optimizer.swap_averaged()
 
 
 def build_scheduler(hps):
@@ -231,7 +380,8 @@ class GraphedTrainStep:
     learned or class-conditional top prior and the classifier are inside: the top head is one launch each way (csrc/tophead.hip).
 
     Static buffers: ``x`` (the batch is copied in), the labels ``y_onehot`` / ``y`` of a class-conditional model beside it, the
-    noise, ``loss``, ``loss_classes``, ``norm``, and ``hyper`` = {lr, 1 - beta1^step, 1 - beta2^step}
+    noise, ``loss``, ``loss_classes``, ``norm``, and ``hyper`` = {lr, 1 - beta1^step, 1 - beta2^step} (with a Polyak average, the
+    optimiser's ``ema_decay``, the step's averaging weight as a fourth word: glowhip_optim_step_ema_dev)
     on the device: kernel arguments are frozen in a graph, so the update kernel reads the three values that change from step to step
     from memory (glowhip_optim_step_dev) and __call__ uploads them before each replay.  `glowhip_plan_pack` is inside the graph:
     every replay re-derives the weight images from the live parameters, as the forward after an update must.  Capture executes
@@ -254,12 +404,15 @@ class GraphedTrainStep:
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.loss_classes = torch.zeros((), dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.hyper = torch.zeros(3, dtype=torch.float64, device=dev)
+        # (with a Polyak average the averaging weight of the step rides as a fourth word: glowhip_optim_step_ema_dev)
+        self.ema = bool(getattr(optimizer, "ema_decay", 0.0))
+        words = 4 if self.ema else 3
+        self.hyper = torch.zeros(words, dtype=torch.float64, device=dev)
         # A pinned-source H2D copy reads the host words when the STREAM gets to it, not at enqueue time, and the host may run several
         # steps ahead of the device: one pinned slot per step in flight, each with the event recorded behind its copy, and a slot is
         # written again only once that event has passed (ADVICE r5 -- with a single slot, step N could read step N + 1's learning rate
         # and bias corrections)
-        self._hyper_host = [torch.zeros(3, dtype=torch.float64, pin_memory=True) for _ in range(self.HYPER_SLOTS)]
+        self._hyper_host = [torch.zeros(words, dtype=torch.float64, pin_memory=True) for _ in range(self.HYPER_SLOTS)]
         self._hyper_done = [None] * self.HYPER_SLOTS
         self._hyper_next = 0
         self._params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
@@ -267,7 +420,7 @@ class GraphedTrainStep:
         side.wait_stream(torch.cuda.current_stream(dev))
         torch.cuda.synchronize(dev)
         glow.flow.plan_for(x).pack_sync()
-        steps = optimizer._steps
+        steps, ema_t = optimizer._steps, optimizer._ema_t
         self.graph = torch.cuda.CUDAGraph()
         try:
             # (thread_local: a DataLoader's pinning thread may touch the device while this thread captures)
@@ -279,9 +432,10 @@ class GraphedTrainStep:
         finally:
             # the captured call counted a step on the host; nothing ran -- also when the capture failed half-way and TrainLoop carries
             # on eagerly: the bias corrections of every later step hang on this count
-            optimizer._steps = steps
+            optimizer._steps, optimizer._ema_t = steps, ema_t
             optimizer._publish_step()
         self.plan = glow.flow.plan_for(x)
+        self._had_ws = getattr(self.plan, "_ws", None) is not None
         self._buffers = self._buffer_signature()
 
     HYPER_SLOTS = 4
@@ -294,7 +448,9 @@ class GraphedTrainStep:
             while not ev.query():         # the copy that last read this slot has not run yet: sleep, do not spin (see _check_previous)
                 time.sleep(2e-4)
         host = self._hyper_host[i]
-        host[0], host[1], host[2] = values
+        host[0], host[1], host[2] = values[:3]
+        if self.ema:
+            host[3] = values[3]
         self.hyper.copy_(host, non_blocking=True)
         if ev is None:
             ev = self._hyper_done[i] = torch.cuda.Event()
@@ -307,8 +463,12 @@ class GraphedTrainStep:
         plan, opt = self.plan, self.optimizer
         ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else 0
         pg = getattr(plan, "_pgrad", None)
-        return (ptr(plan.packed), ptr(getattr(plan, "_ws", None)), ptr(getattr(plan, "_tws", None)),
+        # (the inference workspace only if it existed at capture: one allocated later -- the first evaluation forward between two
+        # training steps -- is a buffer no captured launch reaches, and must not cost a recapture)
+        return (ptr(plan.packed), ptr(getattr(plan, "_ws", None)) if self._had_ws else 0, ptr(getattr(plan, "_tws", None)),
                 tuple(ptr(f) for f in pg[0]) if pg else (), ptr(getattr(opt, "_partial", None)), ptr(getattr(opt, "_keep", None)),
+                # the Polyak average and the pointer array to it (0 without one); swap_averaged() moves neither
+                ptr(opt._flat[2]) if self.ema and opt._flat else 0, ptr(getattr(opt, "_keep_ema", None)),
                 # an eager pack of this plan for the OTHER kernel family since the capture (a re-run of an overflowed batch): it rebuilt
                 # the host-side job tables the captured pack's copy nodes read (measured: a replay after such a re-run faulted on a
                 # host address); packs of the same family keep them in place
@@ -335,6 +495,7 @@ class GraphedTrainStep:
 
     def __call__(self, x, lr, y_onehot=None, y=None):
         """Replay with this batch (and its labels) and learning rate; returns (loss, gradient norm) as fresh device scalars."""
+        self.optimizer._refuse_swapped("GraphedTrainStep")
         if not self.valid():
             raise _lib.GlowHipError("GraphedTrainStep: a parameter or a workspace was re-allocated since the capture -- capture again")
         if x is not self.x:
@@ -346,7 +507,11 @@ class GraphedTrainStep:
         opt = self.optimizer
         opt._steps += 1
         opt._publish_step()
-        self._upload_hyper(opt.hyper_values(lr, opt._steps))
+        values = opt.hyper_values(lr, opt._steps)
+        if self.ema:
+            values = values + (opt.ema_weight(opt._ema_t),)
+            opt._ema_t += 1
+        self._upload_hyper(values)
         self.graph.replay()
         torch.autograd.graph.increment_version(self._params)      # (the parameters changed behind torch's back, as after fused_step)
         out = torch.stack((self.loss, self.norm[0], self.loss_classes))      # (the static words are overwritten by the next replay)
@@ -394,7 +559,14 @@ class TrainLoop:
         self.lr = None
         self.criterion = hps.ablation.get("y_criterion", None) if hps.ablation.get("y_condition", False) else None
 
+    def _refuse_swapped(self, what):
+        """While the optimiser's averaged weights are swapped in nothing here may train -- not a step, not the re-run of a skipped
+        batch that `flush` or the deferred check would start (a collective on several ranks)."""
+        if getattr(self.optimizer, "swapped", False):
+            raise _lib.GlowHipError(f"TrainLoop.{what} while the averaged weights are swapped in (training.averaged_weights): swap back first")
+
     def step(self, x_local: torch.Tensor, y_onehot: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None):
+        self._refuse_swapped("step")
         labels = dict(y_onehot=y_onehot, y=y, criterion=self.criterion)
         if self.global_step == 0 and not self.glow.actnorm_inited():
             # data-dependent ActNorm init on rank 0's batch, broadcast to the others (trainer.py:112-115)
@@ -528,6 +700,7 @@ class TrainLoop:
 
     def flush(self):
         """Resolve the check of the last step (call before reading parameters for a snapshot, and at the end of training)."""
+        self._refuse_swapped("flush")
         self._rerun = None
         self._check_previous(drain=True)
         reruns, self._rerun = self._rerun, None
