@@ -402,6 +402,21 @@ int glowhip_optim_step_ema_dev(const glowhip_optim_chunk* chunks_dev, float* con
 int glowhip_optim_ema_swap(const glowhip_optim_chunk* chunks_dev, float* const* ema_dev, int n_chunks, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Restoration objective: the data term of an inverse problem under the flow prior (in-painting, denoising, super-resolution).
+ * x, grad_x: (N,C,H,W) contiguous; target, weight: (N,C,H/pool,W/pool); inv_wsum: (N).  P = the pool x pool average pool
+ * (pool = 1: the identity); weight == NULL means all ones, inv_wsum == NULL means 1 / (C (H/pool) (W/pool)).  Per sample n:
+ *     loss_out[n] = inv_wsum[n] * sum w (P x - t)^2                 (overwritten, never accumulated into; loss_out may be NULL)
+ *     grad_x      = 2 inv_wsum[n] * P^T (w (P x - t))               (every x under one measurement cell: the cell's value / pool^2)
+ * ONE launch, one workgroup per sample; x is read once and feeds both outputs.  pool == 1 moves 16 bytes per access where
+ * C H W % 4 == 0 and every address allows, element by element otherwise.  The loss is summed in fp64 in a fixed order inside the
+ * sample's workgroup: bitwise the same run to run, no atomics, no scratch buffer.  inv_wsum[n] == 0: exact zeros in grad_x[n] and
+ * loss 0, whatever x[n] holds.  A non-finite x[n] makes that sample's loss and gradient non-finite and no other's.  pool < 1,
+ * H % pool != 0, W % pool != 0 or a NULL x / target / grad_x: GLOWHIP_EINVAL with a message, no device call.  No allocation, no
+ * host sync, capturable.  grad_x is what glowhip_plan_decode_vjp takes: the two make the latent gradient of the objective. */
+int glowhip_restore_objective(const float* x, const float* target, const float* weight, const float* inv_wsum,
+                              int N, int C, int H, int W, int pool, float* grad_x, float* loss_out, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Top head: learned / class-conditional top prior + classifier (reference network/model.py:345-348, 362-379, 440-445,
  * 508-538; LinearZeros network/module.py:152-185: out = (x W^T + b) * exp(3 logs)).  All fp32, in both kernel families.
  *   prior    h[n, :, p] = base[:] + e[n, :];  e = y_emb(y_onehot) (width 2C);  base[c] = learn_top.bias[c] * exp(3 learn_top.logs[c])

@@ -189,6 +189,7 @@ SIGNATURES = {
     "glowhip_optim_step_ema": (c_int, [_P, _P, c_int, c_int, c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int, c_float, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_step_ema_dev": (c_int, [_P, _P, c_int, c_int, _P, ctypes.c_double, ctypes.c_double, c_float, c_float, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_ema_swap": (c_int, [_P, _P, c_int, _P]),
+    "glowhip_restore_objective": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_plan_set_head": (c_int, [_P, POINTER(HeadDesc)]),
     "glowhip_plan_head_state_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_bind_head": (c_int, [_P, POINTER(HeadIO)]),

@@ -401,15 +401,24 @@ class FlowPlan:
                 self._unbind_latents()
         return z, ld_out
 
-    def decode(self, z, eps: Sequence[Optional[torch.Tensor]], logdet=None, want_logdet=False, repack=False):
-        """``eps[k]`` may be ``None`` while a sampler is bound (`bind_sampler`): that Split2d draws its own."""
+    def _out_buffer(self, out, shape, what):
+        """A caller's persistent output buffer (``out=``), checked; None: a fresh one, as ever."""
+        if out is None:
+            return torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out.device != self.device or out.dtype != torch.float32 or not out.is_contiguous() or tuple(out.shape) != tuple(shape):
+            raise _lib.GlowHipError(f"{what}: out= needs a contiguous fp32 tensor of shape {tuple(shape)} on {self.device}")
+        return out
+
+    def decode(self, z, eps: Sequence[Optional[torch.Tensor]], logdet=None, want_logdet=False, repack=False, *, out=None):
+        """``eps[k]`` may be ``None`` while a sampler is bound (`bind_sampler`): that Split2d draws its own.
+        ``out``: the image buffer to write (a loop that decodes into one static image); None: a fresh tensor."""
         n = z.shape[0]
         assert tuple(z.shape[1:]) == self.out_chw, (z.shape, self.out_chw)
         assert len(eps) >= self.n_split
         if getattr(self, "_sampler_pos", None) is None and any(e is None for e in eps[:self.n_split]):
             raise _lib.GlowHipError("decode: an eps entry is None and no sampler is bound (bind_sampler)")
         self.ensure_packed(repack, use=self.PACK_INFERENCE | self.PACK_INVERSE)
-        x = torch.empty((n,) + self.in_chw, dtype=torch.float32, device=self.device)
+        x = self._out_buffer(out, (n,) + self.in_chw, "decode")
         ld_out = torch.empty(n, dtype=torch.float32, device=self.device) if want_logdet else None
         if n == 0:
             return x, ld_out
@@ -419,18 +428,22 @@ class FlowPlan:
                                         n, ptr(ws), ws.numel(), stream_ptr(self.device)))
         return x, ld_out
 
-    def decode_vjp(self, x, grad_x, want_z=True, want_eps=None):
+    def decode_vjp(self, x, grad_x, want_z=True, want_eps=None, *, out=None):
         """Vector-Jacobian product of `decode` (glowhip_plan_decode_vjp) at the latents whose decode is ``x``: returns
         ``(g_z, [g_eps])`` = J^T ``grad_x``, the eps gradients in decode order.  ``want_z`` / ``want_eps`` (one flag per Split2d)
         skip outputs nobody asked for (None in their place).  One taping re-encode of ``x`` plus the sweep; the tape and the
-        workspace are cached per plan and live only for the call.  Gradients of the PARAMETERS do not flow through the decode."""
+        workspace are cached per plan and live only for the call.  Gradients of the PARAMETERS do not flow through the decode.
+        ``out``: ``(g_z, [g_eps])`` buffers to write instead of fresh ones (persistent gradients of a loop; an entry for an output
+        not wanted is ignored)."""
         n = x.shape[0]
         assert tuple(x.shape[1:]) == self.in_chw and grad_x.shape == x.shape, (x.shape, grad_x.shape, self.in_chw)
         want_eps = [True] * self.n_split if want_eps is None else list(want_eps)
         assert len(want_eps) == self.n_split
         self.ensure_packed(use=self.PACK_TRAINING | self.PACK_INVERSE)
-        gz = torch.empty((n,) + self.out_chw, dtype=torch.float32, device=self.device) if want_z else None
-        geps = [torch.empty((n,) + s, dtype=torch.float32, device=self.device) if w else None for s, w in zip(self.split_chw, want_eps)]
+        out_z, out_eps = (None, [None] * self.n_split) if out is None else (out[0], list(out[1]))
+        assert len(out_eps) == self.n_split
+        gz = self._out_buffer(out_z, (n,) + self.out_chw, "decode_vjp g_z") if want_z else None
+        geps = [self._out_buffer(o, (n,) + s, "decode_vjp g_eps") if w else None for s, w, o in zip(self.split_chw, want_eps, out_eps)]
         if n == 0:
             return gz, geps
         tape = self._cached_bytes("_vjp_tape", int(lib().glowhip_plan_tape_bytes(self._h, n)))

@@ -6,6 +6,7 @@ from . import module as _module
 from .builder import Builder
 from .inferer import Inferer
 from .latents import Latents
+from .restore import LatentFit, RestoreInfo, restore_objective
 from .trainer import Trainer
 
 _LAYERS = ("ActNorm", "LinearZeros", "Conv2d", "Conv2dZeros", "CouplingNet", "f", "Invertible1x1Conv", "Invertible1x1ConvLU",
@@ -17,4 +18,4 @@ for _n in _LAYERS:
 for _n in _MODELS:
     globals()[_n] = getattr(_model, _n)
 
-__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Latents")
+__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Latents", "LatentFit", "RestoreInfo", "restore_objective")

@@ -141,6 +141,44 @@ class Inferer:
                 history.append(loss.detach())
         return lat.detach(), [float(v) for v in torch.stack(history).cpu()] if history else []
 
+    def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
+                graph=True, exact=False):
+        """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
+        image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
+        super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
+        pool) -- as a maximum-a-posteriori fit under the flow prior, on the device (`network.restore.LatentFit`):
+
+            minimise  sum_n  inv_wsum[n] * sum w (P decode(latents)_n - measurement_n)^2  +  prior_weight * 1/2 ||latents||^2
+
+        by ``steps`` Adam iterations at ``lr``.  Returns ``(Latents, RestoreInfo)``: the per-sample loss history (steps, N), the
+        gradient-norm history (steps,), ``finite``, ``captured``, ``fallback``.
+
+        The data term is normalised PER SAMPLE, ``inv_wsum[n] = 1 / max(sum w[n], 1)``: every image of a batch is its own
+        problem, its loss and its gradient independent of the others'.  Two couplings across the batch remain: the norm clip
+        (``max_grad_norm`` > 0 clips the total gradient norm of all samples) and the skip of an iteration whose total norm is not
+        finite (it is skipped for every sample).
+        ``prior_weight``: the weight of 1/2 ||latents||^2 -- the negative log-density of the latents when the top prior is standard
+        normal; it rides on the optimiser's weight decay and costs nothing.  A model with a learned or class-conditional top prior
+        (``learn_top`` / ``y_condition``) raises ValueError for ``prior_weight > 0``: its top latent is not standard normal.
+        ``init``: start `Latents`; None = ``encode_full`` of the measurement (``pool>1``: of its pixel-repeated upsampling).
+        ``graph``: iterations after the first run as ONE hipGraph launch each (a failed capture falls back to the eager loop;
+        the reason is in ``RestoreInfo.graph_error``).  ``exact``: the whole fit on the exact-fp32 kernel family.  With ``exact``
+        off and ``glow.range_check`` on, a fit whose norm history holds a non-finite value is run once more from the same start on
+        the exact family (``fallback=1``); non-finite there too: ``finite=False``.  Nothing raises; one host sync, at the end."""
+        from .restore import LatentFit, check_prior_weight
+        check_prior_weight(self.graph, prior_weight)
+        meas = self._batch(measurement).float().contiguous()
+        pool = int(pool)
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
+        if init is None:
+            start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
+            init = self.encode_full(start)
+        fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
+                        max_grad_norm=max_grad_norm, graph=graph)
+        info = fit.run(exact=exact)
+        return fit.latents(), info
+
     def compute_attribute_delta(self, dataset, samples_per_batch=None, shuffle=True, num_workers=None, world=1, _exact=False):
         """deltaz[c] = mean latent of the images with attribute c - mean latent of those without (inferer.py:104-153).
         `dataset` yields dicts with 'x' (C,H,W) and 'y_onehot' (classes,).

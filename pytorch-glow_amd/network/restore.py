@@ -1,0 +1,253 @@
+"""Inverse problems under the flow prior, on the device: in-painting, denoising, super-resolution, projection onto the model.
+
+A trained flow is a prior over images; a maximum-a-posteriori fit of its latents to a measurement minimises
+
+    sum_n  inv_wsum[n] * sum w (P decode(latents)_n - t_n)^2   +   prior_weight * 1/2 ||latents||^2
+
+with P the pool x pool average pool (pool = 1: a mask problem, pool > 1: super-resolution), t the measurement and w its weights.
+The pieces: `restore_objective` (glowhip_restore_objective, csrc/restore.hip: the data term's per-sample loss and its gradient with
+respect to the image, one launch), `FlowPlan.decode` / `decode_vjp` (the image and J^T of that gradient) and the fused Adam step
+(`training.HipAdam`), whose weight decay IS the prior term: the update kernel adds prior_weight * p to the gradient, the gradient of
+prior_weight * 1/2 ||p||^2.  `LatentFit` runs them as a device-resident loop -- no autograd, no host sync, the histories on the
+device -- and, with ``graph=True``, as one hipGraph launch per iteration."""
+from dataclasses import dataclass
+from typing import Optional
+
+import torch
+
+from .. import _lib
+from ..training import HipAdam, HyperRing
+from .latents import Latents
+
+
+def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None):
+    """``(loss (N,), grad_x)`` of the data term for images ``x`` (N,C,H,W): glowhip_restore_objective.  ``target`` / ``weight``
+    (N,C,H/pool,W/pool; weight None = ones), ``inv_wsum`` (N,; None = 1 / elements of one measurement).  Contiguous fp32 device
+    tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write."""
+    for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
+            raise _lib.GlowHipError(f"restore_objective: {name} must be a contiguous fp32 tensor on the device of x")
+    n, c, h, w = x.shape
+    pool = int(pool)
+    if pool >= 1 and h % pool == 0 and w % pool == 0:      # (anything else is the C call's to refuse)
+        mshape = (n, c, h // pool, w // pool)
+        if tuple(target.shape) != mshape or (weight is not None and tuple(weight.shape) != mshape):
+            raise _lib.GlowHipError(f"restore_objective: target / weight must have shape {mshape}")
+    if inv_wsum is not None and inv_wsum.numel() != n:
+        raise _lib.GlowHipError(f"restore_objective: inv_wsum holds {inv_wsum.numel()} values for a batch of {n}")
+    grad = torch.empty_like(x) if grad_out is None else grad_out
+    loss = torch.empty(n, dtype=torch.float32, device=x.device) if loss_out is None else loss_out
+    if tuple(grad.shape) != tuple(x.shape) or loss.numel() != n:
+        raise _lib.GlowHipError("restore_objective: grad_out must have the shape of x, loss_out one value per sample")
+    _lib.check(_lib.lib().glowhip_restore_objective(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), n, c, h, w,
+                                                    pool, _lib.ptr(grad), _lib.ptr(loss), _lib.stream_ptr(x.device)))
+    return loss, grad
+
+
+@dataclass
+class RestoreInfo:
+    """What a fit reports.  ``loss`` (steps, N): the per-sample data term BEFORE each iteration's update; ``grad_norm`` (steps,):
+    the total norm of the data term's latent gradient (all samples, before clipping; the prior term is not in it).  ``finite``: every
+    norm was finite -- when False, the iterations with a non-finite norm were skipped on the device.  ``captured``: the iterations
+    after the first ran as hipGraph replays.  ``fallback``: how many times the fit was run again on the exact-fp32 kernel family (0
+    or 1).  ``graph_error``: why a requested capture did not happen."""
+    loss: torch.Tensor
+    grad_norm: torch.Tensor
+    finite: bool
+    captured: bool
+    fallback: int = 0
+    graph_error: Optional[str] = None
+
+
+def check_prior_weight(glow, prior_weight):
+    """The prior term 1/2 ||latents||^2 is the latents' negative log-density only under a standard-normal top prior: a model whose
+    top prior is learned or class-conditional raises for ``prior_weight > 0`` (whitening its top latent is not implemented)."""
+    ab = glow.hps.ablation
+    unusual = [name for name in ("learn_top", "y_condition") if ab.get(name, False)]
+    if prior_weight and unusual:
+        raise ValueError(f"prior_weight = {prior_weight!r}: the prior term 1/2 ||latents||^2 assumes a standard-normal top prior, and this "
+                         f"model's is not ({' / '.join(unusual)}); whitening the top latent is not implemented")
+
+
+class LatentFit:
+    """The device-resident loop.  Owns the static buffers (image, target, weights, inv_wsum), the latent leaves -- ``z`` and every
+    ``eps`` of the start `Latents`, copied -- their persistent gradient buffers (bound once as the leaves' ``.grad``) and a
+    `training.HipAdam` over the leaves with ``weight_decay = prior_weight``.
+
+    One iteration: `FlowPlan.decode` into the static image; `restore_objective`; `FlowPlan.decode_vjp` into the gradient buffers;
+    ``fused_step(0, max_grad_norm, skip_nonfinite=True)``; the iteration's losses and norm into row ``row`` of the device histories
+    and ``row += 1`` (a device word: the host keeps no count the device could disagree with).  `step_eager` enqueues that from
+    Python; `capture` records it once as a hipGraph (after at least one eager iteration: lazy allocations, packed weights) and
+    `step_captured` replays it, the per-step {lr, 1 - beta1^t, 1 - beta2^t} travelling through a `training.HyperRing`.  Same kernels
+    and same bits either way.  `run` is the whole fit: ``steps`` iterations from the start, ONE host read at the end.
+
+    The data term is normalised per sample, so each image of a batch is its own problem; what still couples the batch is the norm
+    clip (``max_grad_norm``: one total norm) and the skip of an iteration whose norm is not finite (all samples or none).  A skipped
+    iteration still counts in the bias corrections (the host never looks): harmless, because a fit with a skipped iteration is
+    either run again on the exact-fp32 family or reported ``finite=False``."""
+
+    def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
+                 graph=True):
+        check_prior_weight(glow, prior_weight)
+        if init is None or steps < 1:
+            raise ValueError("LatentFit needs start latents (init) and steps >= 1")
+        self.glow, self.pool, self.steps = glow, int(pool), int(steps)
+        self.lr, self.max_grad_norm, self.want_graph = float(lr), float(max_grad_norm or 0.0), bool(graph)
+        meas = _lib.require_device_tensor(measurement, "measurement")
+        dev = self.device = meas.device
+        n, c, h, w = meas.shape
+        if self.pool < 1:
+            raise ValueError(f"pool = {pool}")
+        self.plan = plan = glow.flow.plan_for((c, h * self.pool, w * self.pool), dev)
+        if tuple(init.z.shape) != (n,) + plan.out_chw or len(init.eps) != plan.n_split:
+            raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
+        self.target = meas.clone()
+        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(meas).contiguous()
+        # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
+        self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=(1, 2, 3)).clamp(min=1.0)
+        self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
+        self.grad_x = torch.empty_like(self.image)
+        self.loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.loss_hist = torch.zeros((self.steps, n), dtype=torch.float32, device=dev)
+        self.norm_hist = torch.zeros(self.steps, dtype=torch.float32, device=dev)
+        self.row = torch.zeros(1, dtype=torch.int64, device=dev)
+        start = init.to(dev).detach()
+        self._start = [t.float().clone() for t in start.tensors()]
+        self.leaves = [t.clone().requires_grad_() for t in self._start]
+        self.grads = [torch.zeros_like(t) for t in self._start]
+        for p, g in zip(self.leaves, self.grads):
+            p.grad = g
+        self.optimizer = HipAdam(self.leaves, lr=self.lr, weight_decay=float(prior_weight or 0.0))
+        self._token = object()       # "the gradients are this loop's persistent buffers" (HipAdam._chunk_table)
+        self._ring = HyperRing(3, dev)
+        self._graph = None
+        self.graph_error = None
+
+    # ------------------------------------------------------------------ the iteration
+    def _body(self, hyper_dev=None):
+        plan = self.plan
+        plan.decode(self.leaves[0], self.leaves[1:], out=self.image)
+        restore_objective(self.image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=self.loss)
+        plan.decode_vjp(self.image, self.grad_x, out=(self.grads[0], self.grads[1:]))
+        self.optimizer.fused_step(0.0, self.max_grad_norm, skip_nonfinite=True, grads_token=self._token, hyper_dev=hyper_dev,
+                                  norm_out=self.norm)
+        self.loss_hist.index_copy_(0, self.row, self.loss.view(1, -1))
+        self.norm_hist.index_copy_(0, self.row, self.norm)
+        self.row.add_(1).remainder_(self.steps)      # (a loop driven past `steps` iterations wraps around instead of writing outside)
+
+    @torch.no_grad()
+    def step_eager(self):
+        """One iteration enqueued launch by launch."""
+        self._body()
+
+    def _signature(self):
+        """What a captured iteration reaches through the plan and the optimiser and an eager call in between could have moved or
+        rebuilt (`training.GraphedTrainStep._buffer_signature`)."""
+        plan, opt = self.plan, self.optimizer
+        ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else 0
+        return (plan._pointer_signature(), plan._version_signature(), plan.family, getattr(plan, "_pack_epoch", 0), ptr(plan.packed),
+                ptr(getattr(plan, "_ws", None)), ptr(getattr(plan, "_vjp_tape", None)), ptr(getattr(plan, "_vjp_ws", None)),
+                ptr(getattr(opt, "_partial", None)), ptr(getattr(opt, "_keep", None)))
+
+    @torch.no_grad()
+    def capture(self):
+        """Record one iteration as a hipGraph, by the rules `training.GraphedTrainStep` documents: an eager iteration behind it,
+        ``pack_sync()`` before, ``capture_error_mode="thread_local"``, the optimiser's step count restored after (the captured call
+        counted one on the host; nothing ran).  True on success; on failure the reason is kept in ``graph_error``, the loop stays
+        eager and nothing raises."""
+        opt, dev = self.optimizer, self.device
+        if opt._steps < 1:
+            raise _lib.GlowHipError("LatentFit.capture: run one eager iteration first (lazy allocations, packed weights)")
+        self._graph = None
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        torch.cuda.synchronize(dev)
+        self.plan.pack_sync()
+        steps = opt._steps
+        graph = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
+                self._body(hyper_dev=self._ring.words)
+        except Exception as e:       # capture is an optimisation of the host side only
+            opt._table_token = None
+            self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
+            return False
+        finally:
+            opt._steps = steps
+            opt._publish_step()
+        self._graph = (graph, self._signature())
+        return True
+
+    @property
+    def captured(self):
+        return self._graph is not None and self._graph[1] == self._signature()
+
+    @torch.no_grad()
+    def step_captured(self):
+        """One iteration as one graph launch (and the 24-byte upload of its learning rate and bias corrections)."""
+        if not self.captured:
+            raise _lib.GlowHipError("LatentFit.step_captured: no valid capture (capture() after an eager iteration; a parameter, a "
+                                    "workspace or the kernel family changed since)")
+        opt = self.optimizer
+        opt._steps += 1
+        opt._publish_step()
+        self._ring.upload(opt.hyper_values(self.lr, opt._steps))
+        self._graph[0].replay()
+        torch.autograd.graph.increment_version(self.leaves)      # (written behind torch's back, as after fused_step)
+
+    # ------------------------------------------------------------------ the fit
+    @torch.no_grad()
+    def reset(self):
+        """Back to the start latents with a fresh optimiser state and empty histories (addresses stay: a capture stays valid)."""
+        for p, s in zip(self.leaves, self._start):
+            p.copy_(s)
+        opt = self.optimizer
+        opt._ensure_state()
+        for buf in opt._flat or ():
+            buf.zero_()
+        opt._steps = 0
+        opt._publish_step()
+        self.row.zero_()
+        self.loss_hist.zero_()
+        self.norm_hist.zero_()
+
+    def latents(self):
+        """The current latents (copies)."""
+        return Latents(self.leaves[0].detach().clone(), [e.detach().clone() for e in self.leaves[1:]])
+
+    def _run_once(self):
+        self.reset()
+        replayed = False
+        for it in range(self.steps):
+            if self.want_graph and it >= 1 and self.graph_error is None and (self.captured or self.capture()):
+                self.step_captured()
+                replayed = True
+            else:
+                self.step_eager()
+        hist = torch.cat([self.loss_hist.reshape(-1), self.norm_hist]).cpu()      # the loop's one host read
+        n = self.loss_hist.shape[1]
+        return hist[:self.steps * n].view(self.steps, n), hist[self.steps * n:], replayed
+
+    def run(self, exact=False):
+        """The whole fit from the start latents: `RestoreInfo`; the result is in `latents()`.  ``exact``: on the exact-fp32 kernel
+        family (restored afterwards).  A non-finite norm anywhere in the history, with ``exact`` off and ``glow.range_check`` on,
+        runs the fit ONCE more from the same start on the exact family (the product kernels carry activations as fp16 pairs: a
+        latent the fp32 reference handles can be out of their range), as `Inferer.compute_attribute_delta` re-runs its pass; norms
+        that are non-finite there too are the problem's own, and the result says ``finite=False``.  Nothing raises."""
+        plan = self.plan
+        prev = plan.family
+        fallback = 0
+        try:
+            if exact:
+                plan.set_family(plan.FAMILY_EXACT_FP32)
+            loss, norm, replayed = self._run_once()
+            finite = bool(torch.isfinite(norm).all())
+            if not finite and not exact and getattr(self.glow, "range_check", True):
+                fallback = 1
+                plan.set_family(plan.FAMILY_EXACT_FP32)
+                loss, norm, replayed = self._run_once()
+                finite = bool(torch.isfinite(norm).all())
+        finally:
+            plan.set_family(prev)
+        return RestoreInfo(loss=loss, grad_norm=norm, finite=finite, captured=replayed, fallback=fallback, graph_error=self.graph_error)

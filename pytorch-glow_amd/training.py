@@ -372,6 +372,37 @@ def build_scheduler(hps):
     return partial(lr_scheduler.SCHEDULES[name], **args)
 
 
+class HyperRing:
+    """The device words a captured optimiser step reads its per-step values from -- {lr, 1 - beta1^step, 1 - beta2^step} and, with a
+    Polyak average, the averaging weight (glowhip_optim_step_dev / _ema_dev) -- and their way up from the host (`GraphedTrainStep`,
+    `network.restore.LatentFit`).  A pinned-source H2D copy reads the host words when the STREAM gets to it, not at enqueue time, and
+    the host may run several steps ahead of the device: one pinned slot per step in flight, each with the event recorded behind its
+    copy, and a slot is written again only once that event has passed (ADVICE r5 -- with a single slot, step N could read step
+    N + 1's learning rate and bias corrections)."""
+
+    def __init__(self, words, device, slots=4):
+        self.words = torch.zeros(words, dtype=torch.float64, device=device)
+        self._host = [torch.zeros(words, dtype=torch.float64, pin_memory=True) for _ in range(slots)]
+        self._done = [None] * slots
+        self._next = 0
+
+    def upload(self, values):
+        """Enqueue the copy of ``values`` (one per word) into `words` on the current stream."""
+        i = self._next
+        self._next = (i + 1) % len(self._host)
+        ev = self._done[i]
+        if ev is not None:
+            while not ev.query():         # the copy that last read this slot has not run yet: sleep, do not spin (see _check_previous)
+                time.sleep(2e-4)
+        host = self._host[i]
+        for k in range(host.numel()):
+            host[k] = values[k]
+        self.words.copy_(host, non_blocking=True)
+        if ev is None:
+            ev = self._done[i] = torch.cuda.Event()
+        ev.record()
+
+
 class GraphedTrainStep:
     """One training step of one rank -- dequantisation draw, HIP forward with tape, HIP reverse sweep, both clippings, the Adam /
     Adamax update (reference network/trainer.py:123-150) -- captured in ONE hipGraph: the step's ~1 300 launches cost the host one
@@ -407,14 +438,8 @@ class GraphedTrainStep:
         # (with a Polyak average the averaging weight of the step rides as a fourth word: glowhip_optim_step_ema_dev)
         self.ema = bool(getattr(optimizer, "ema_decay", 0.0))
         words = 4 if self.ema else 3
-        self.hyper = torch.zeros(words, dtype=torch.float64, device=dev)
-        # A pinned-source H2D copy reads the host words when the STREAM gets to it, not at enqueue time, and the host may run several
-        # steps ahead of the device: one pinned slot per step in flight, each with the event recorded behind its copy, and a slot is
-        # written again only once that event has passed (ADVICE r5 -- with a single slot, step N could read step N + 1's learning rate
-        # and bias corrections)
-        self._hyper_host = [torch.zeros(words, dtype=torch.float64, pin_memory=True) for _ in range(self.HYPER_SLOTS)]
-        self._hyper_done = [None] * self.HYPER_SLOTS
-        self._hyper_next = 0
+        self._ring = HyperRing(words, dev, self.HYPER_SLOTS)
+        self.hyper = self._ring.words
         self._params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -441,20 +466,7 @@ class GraphedTrainStep:
     HYPER_SLOTS = 4
 
     def _upload_hyper(self, values):
-        i = self._hyper_next
-        self._hyper_next = (i + 1) % self.HYPER_SLOTS
-        ev = self._hyper_done[i]
-        if ev is not None:
-            while not ev.query():         # the copy that last read this slot has not run yet: sleep, do not spin (see _check_previous)
-                time.sleep(2e-4)
-        host = self._hyper_host[i]
-        host[0], host[1], host[2] = values[:3]
-        if self.ema:
-            host[3] = values[3]
-        self.hyper.copy_(host, non_blocking=True)
-        if ev is None:
-            ev = self._hyper_done[i] = torch.cuda.Event()
-        ev.record()
+        self._ring.upload(values)
 
     def _buffer_signature(self):
         """Addresses of everything the captured launches reach through the plan and the optimiser and that an EAGER call in between
