@@ -402,6 +402,31 @@ int glowhip_optim_step_ema_dev(const glowhip_optim_chunk* chunks_dev, float* con
 int glowhip_optim_ema_swap(const glowhip_optim_chunk* chunks_dev, float* const* ema_dev, int n_chunks, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gradient accumulation: the training step (reference network/trainer.py:123-150: forward, loss.backward(), clippings,
+ * optimizer.step()) as k micro-batches whose gradients are combined before the ONE update.  No counterpart in the reference, which
+ * trains at the batch its memory allows.  A segment is one flat gradient buffer with its accumulator of the same length
+ * (FlowPlan's persistent buckets).  THE definition of the arithmetic, per element, fp32 with one rounding per operation (no fused
+ * multiply-add):
+ *     GLOWHIP_ACC_FIRST :  acc  = grad                    (no memset ever precedes a round of accumulation; grad is not written)
+ *     GLOWHIP_ACC_ADD   :  acc  = acc + grad              (grad is not written)
+ *     GLOWHIP_ACC_FINISH:  grad = (acc + grad) * scale    (acc is not written)
+ * scale is ignored by FIRST and ADD.  NaN and inf propagate by the IEEE rules, nothing is filtered: what a non-finite accumulated
+ * norm means is decided by skip_if_nonfinite of the update launch that follows.
+ * segs is a HOST array, copied into the kernel arguments: ONE launch for all segments, no device table, no upload, no allocation,
+ * no host sync; capturable when the addresses are persistent.  n_segs <= 16; a segment with n == 0 is legal and skipped;
+ * n_segs == 0 (or nothing but empty segments) returns GLOWHIP_OK without a launch.  16-byte accesses where a segment's grad and acc
+ * are both 16-byte aligned or reach a 16-byte boundary after the same 1-3 elements (peeled one by one), element by element where
+ * they share no such phase; the n % 4 tail one by one.  Element-wise, so every path gives the same bits.  No atomics, no LDS, no
+ * dependence on workgroup order.
+ * GLOWHIP_EINVAL with a message and no device call: n_segs < 0 or > 16, n < 0, a NULL (or not 4-byte aligned) grad or acc with
+ * n > 0, a mode outside the enum, a non-finite scale with FINISH, a segment of more than 2^36 elements.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct glowhip_grad_seg { float* grad; float* acc; int64_t n; } glowhip_grad_seg;
+enum { GLOWHIP_ACC_FIRST = 0, GLOWHIP_ACC_ADD = 1, GLOWHIP_ACC_FINISH = 2 };
+int glowhip_grad_accumulate(const glowhip_grad_seg* segs /* HOST, copied */, int n_segs, int mode, float scale,
+                            glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Restoration objective: the data term of an inverse problem under the flow prior (in-painting, denoising, super-resolution).
  * x, grad_x: (N,C,H,W) contiguous; target, weight: (N,C,H/pool,W/pool); inv_wsum: (N).  P = the pool x pool average pool
  * (pool = 1: the identity); weight == NULL means all ones, inv_wsum == NULL means 1 / (C (H/pool) (W/pool)).  Per sample n:

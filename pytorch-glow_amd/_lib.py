@@ -84,6 +84,15 @@ class OptimChunk(ctypes.Structure):
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int32), ("pad", c_int32)]
 
 
+class GradSeg(ctypes.Structure):
+    """Mirror of ``glowhip_grad_seg``."""
+    _fields_ = [("grad", c_void_p), ("acc", c_void_p), ("n", ctypes.c_int64)]
+
+
+ACC_FIRST, ACC_ADD, ACC_FINISH = 0, 1, 2      # glowhip.h GLOWHIP_ACC_*
+ACC_MAX_SEGS = 16
+
+
 class TimingRecord(ctypes.Structure):
     """Mirror of ``glowhip_timing_record``."""
     _fields_ = [("kind", c_int32), ("layer", c_int32), ("mfma", c_int32), ("ms", c_float)]
@@ -189,6 +198,7 @@ SIGNATURES = {
     "glowhip_optim_step_ema": (c_int, [_P, _P, c_int, c_int, c_float, ctypes.c_double, ctypes.c_double, c_float, c_float, c_int, c_float, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_step_ema_dev": (c_int, [_P, _P, c_int, c_int, _P, ctypes.c_double, ctypes.c_double, c_float, c_float, c_float, c_float, _P, _P, c_int, _P]),
     "glowhip_optim_ema_swap": (c_int, [_P, _P, c_int, _P]),
+    "glowhip_grad_accumulate": (c_int, [POINTER(GradSeg), c_int, c_int, c_float, _P]),
     "glowhip_restore_objective": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_plan_set_head": (c_int, [_P, POINTER(HeadDesc)]),
     "glowhip_plan_head_state_bytes": (c_size_t, [_P, c_int]),

@@ -618,6 +618,33 @@ class FlowPlan:
         self.last_grad_buckets = [(flats[b], events[k]) for k, b in enumerate(layout["mark_bucket"])] + [(flats[-1], done)]
         return grads, gx
 
+    # ------------------------------------------------------------------ gradient accumulation (csrc/accumulate.hip)
+    def grad_accumulators(self):
+        """The accumulators parallel to the persistent flat gradient buckets (same sizes; allocated at the first accumulation,
+        again when the buckets were): None before."""
+        held = getattr(self, "_gacc", None)
+        pg = getattr(self, "_pgrad", None)
+        return held[1] if held is not None and pg is not None and held[0] is pg[0] else None
+
+    def accumulate_grads(self, mode: int, scale: float = 1.0) -> None:
+        """One launch of glowhip_grad_accumulate over (persistent flat buckets, accumulators) on the current stream: `mode` =
+        _lib.ACC_FIRST (acc = g), ACC_ADD (acc += g) or ACC_FINISH (g = (acc + g) * scale).  The buckets are those of the last
+        ``glow_backward(persistent=True)``; the segment table is built once per set of buckets."""
+        pg = getattr(self, "_pgrad", None)
+        if pg is None:
+            raise _lib.GlowHipError("accumulate_grads: no persistent gradient buckets yet (glow_backward(persistent=True) first)")
+        flats = pg[0]
+        held = getattr(self, "_gacc", None)
+        if held is None or held[0] is not flats:
+            accs = [torch.empty_like(f) for f in flats]
+            tables = []
+            for i in range(0, len(flats), _lib.ACC_MAX_SEGS):      # (L + 1 buckets: one table for every model the reference trains)
+                part = list(zip(flats, accs))[i:i + _lib.ACC_MAX_SEGS]
+                tables.append((_lib.GradSeg * len(part))(*[_lib.GradSeg(f.data_ptr(), a.data_ptr(), f.numel()) for f, a in part]))
+            held = self._gacc = (flats, accs, tables)
+        for table in held[2]:
+            check(lib().glowhip_grad_accumulate(table, len(table), int(mode), float(scale), stream_ptr(self.device)))
+
     def _bucket_layout(self):
         lay = getattr(self, "_bucket_lay", None)
         if lay is not None:

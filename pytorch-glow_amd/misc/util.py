@@ -51,6 +51,24 @@ def load_profile(filepath):
     return None
 
 
+def accumulate_steps(hps, world=None):
+    """``hps.optim.accumulate_steps`` (beyond the reference's schema): the number of micro-batches every optimiser step's local
+    batch is run as (gradient accumulation).  Absent, None, 0 and 1 all mean off and give 1.  With ``world`` (the number of ranks)
+    the profile's global batch is checked too: ``num_batch_train`` must be a multiple of world * accumulate_steps."""
+    raw = hps.optim.get("accumulate_steps", None)
+    if raw is None or raw is False:
+        return 1
+    if isinstance(raw, bool) or not isinstance(raw, int) or raw < 0:
+        raise ValueError(f"hps.optim.accumulate_steps = {raw!r}: a non-negative integer (absent, 0 or 1 = off)")
+    k = max(int(raw), 1)
+    if world is not None:
+        batch = int(hps.optim.num_batch_train)
+        if batch % (int(world) * k) != 0:
+            raise ValueError(f"hps.optim.num_batch_train = {batch} is not a multiple of world * accumulate_steps = "
+                             f"{int(world)} * {k} = {int(world) * k}: every rank cuts its shard into equal micro-batches")
+    return k
+
+
 _CUDA_NAME = re.compile(r'cuda:(\d+)')
 
 

@@ -5,6 +5,8 @@ state_dict keys and shapes equal the reference's, so its snapshot
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 import torch.nn as nn
 
@@ -12,6 +14,7 @@ from .. import _lib
 from .._lib import require_device_tensor
 from .._plan import PlanCache
 from ..misc import util
+from ..parallel import micro_slices
 from . import module
 from .latents import Latents
 from .module import _deepcopy_without_plans, _logdet_arg
@@ -652,7 +655,7 @@ class Glow(nn.Module):
                                               eps_out=eps_out)      # (the latents of a flagged batch come from the re-run)
         return z, nll, (None if head is None else head.y_logits)
 
-    def loss_and_grads(self, x, noise=None, y_onehot=None, y=None, force_pack=False, criterion=None):
+    def loss_and_grads(self, x, noise=None, y_onehot=None, y=None, force_pack=False, criterion=None, accumulate=1):
         """mean(nll) of the batch (`generative_loss`) and its gradient for every trainable parameter, WITHOUT an autograd graph:
         the HIP forward with tape and the HIP reverse sweep are called directly, and the gradients land in the plan's persistent
         flat buckets, whose views are the parameters' ``.grad`` (assigned once).  This is `Trainer`'s step (network/trainer.py:123-133:
@@ -663,8 +666,19 @@ class Glow(nn.Module):
         Class-conditional model (network/trainer.py:100-131): ``y_onehot`` feeds the prior; with ``weight_y > 0`` and a
         ``criterion`` ('single_class': integer targets ``y``; 'multi_class': multi-hot ``y_onehot``) the head kernel computes the
         classification term and its gradient itself, and the returned loss is generative + weight_y * classification
-        (``self.last_losses`` holds the two terms)."""
+        (``self.last_losses`` holds the two terms).
+
+        ``accumulate`` = k > 1: gradient accumulation -- the batch is cut into k contiguous micro-batches (`parallel.micro_slices`;
+        views, labels and a given ``noise`` alike; ``noise=None`` draws one micro-batch-shaped ``uniform_`` per micro-step, in order),
+        each runs as a plain call on its slice (same plan, tape and workspace of batch n / k, same bits in the buckets), and one
+        launch per micro-step (csrc/accumulate.hip) carries the gradients: afterwards the ``.grad`` views hold
+        (g_0 + ... + g_{k-1}) * float32(1 / k), the effective batch's gradient, and the returned loss and ``last_losses`` are the
+        means over the micro-steps.  Needs n % k == 0 (ValueError) and an initialised ActNorm (the data-dependent init belongs
+        to the full batch: `training.TrainLoop.step`).  ``force_pack`` goes to the first micro-step only.  ``pop_grad_buckets()``
+        then returns every bucket with the ONE event recorded behind the last combine.  k = 1: the plain call, nothing added."""
         assert self.training, "loss_and_grads is the training step: call glow.train() first"
+        if accumulate is not None and int(accumulate) != 1:
+            return self._loss_and_grads_accumulated(x, noise, y_onehot, y, force_pack, criterion, int(accumulate))
         x = require_device_tensor(x, "Glow input", allow_uint8=True)
         if x.dtype == torch.uint8:
             x = x.float() / 255.0
@@ -700,6 +714,41 @@ class Glow(nn.Module):
                 p.grad = g
             plan._pgrad_bound = _GradBinding(grads)
         self._train_plan = plan        # (parallel.train_step: the optimiser's table stays valid while this plan's buckets are the gradients)
+        return loss
+
+    def _loss_and_grads_accumulated(self, x, noise, y_onehot, y, force_pack, criterion, k):
+        """`loss_and_grads(accumulate=k)`, k > 1."""
+        x = require_device_tensor(x, "Glow input", allow_uint8=True)
+        cuts = micro_slices(x.shape[0], k)
+        if x.dtype == torch.uint8:
+            x = x.float() / 255.0
+        if noise is not None:
+            noise = require_device_tensor(noise, "noise")
+            assert noise.shape == x.shape
+        if getattr(self.flow, "_actnorms_all_inited", None) != module.ActNorm.RESET_EPOCH[0] and _uninited_actnorms(self.flow):
+            raise _lib.GlowHipError("loss_and_grads(accumulate > 1): the ActNorm layers are not initialised -- the data-dependent init "
+                                    "takes the full batch, forward only (TrainLoop.step / parallel.data_dependent_init), not a micro-batch")
+        losses, terms = [], []
+        for i, (lo, hi) in enumerate(cuts):
+            losses.append(self.loss_and_grads(x[lo:hi], None if noise is None else noise[lo:hi],
+                                              None if y_onehot is None else y_onehot[lo:hi], None if y is None else y[lo:hi],
+                                              force_pack=force_pack and i == 0, criterion=criterion))
+            terms.append(self.last_losses)
+            plan = self._train_plan
+            if i == 0:
+                plan.accumulate_grads(_lib.ACC_FIRST)
+            elif i < k - 1:
+                plan.accumulate_grads(_lib.ACC_ADD)
+            else:
+                plan.accumulate_grads(_lib.ACC_FINISH, ctypes.c_float(1.0 / k).value)
+        done = torch.cuda.Event()
+        done.record()
+        # the per-level marks of the last sweep are not final gradients any more: every bucket is final behind the last combine
+        plan.last_grad_buckets = [(flat, done) for flat, _ in plan.last_grad_buckets]
+        with torch.no_grad():
+            loss = torch.stack(losses).mean()
+            self.last_losses = (torch.stack([t[0] for t in terms]).mean(),
+                                None if terms[0][1] is None else torch.stack([t[1] for t in terms]).mean())
         return loss
 
     def capture_forward(self, x, repack=True):

@@ -113,6 +113,8 @@ class Trainer:
         self.data_device = data_device
         self.batch_size = self.hps.optim.num_batch_train
         self.num_classes = self.hps.dataset.num_classes
+        # hps.optim.accumulate_steps (gradient accumulation: training.TrainLoop): the global batch must cut into world x steps equal parts
+        self.accumulate_steps = util.accumulate_steps(self.hps, world=world)
         # One process per GPU: every rank loads ONLY its shard of each global batch.  All ranks shuffle with the same seeded
         # generator (profile seed), so the global batch of a step is the same set of samples on every rank and rank r keeps
         # positions [r*B/G, (r+1)*B/G) of it -- no overlap, no omission, no G-fold loading.

@@ -29,6 +29,18 @@ def shard_bounds(n: int, world: int, rank: int) -> Tuple[int, int]:
     return rank * per, (rank + 1) * per
 
 
+def micro_slices(n: int, k: int):
+    """THE cut of a local batch of ``n`` samples into ``k`` micro-batches for gradient accumulation: k contiguous
+    (start, stop) pairs of n / k samples each, in order.  Model, captured step and tests share this one definition."""
+    n, k = int(n), int(k)
+    if k < 1:
+        raise ValueError(f"accumulate = {k}: the number of micro-batches must be at least 1")
+    if n < 1 or n % k != 0:
+        raise ValueError(f"a batch of {n} samples cannot be cut into {k} equal micro-batches ({n} % {k} != 0)")
+    b = n // k
+    return [(i * b, (i + 1) * b) for i in range(k)]
+
+
 def shard_batch(x: torch.Tensor, world: int, rank: int) -> torch.Tensor:
     lo, hi = shard_bounds(x.shape[0], world, rank)
     return x[lo:hi].contiguous()
@@ -193,7 +205,7 @@ def train_step(glow, optimizer, x_local: torch.Tensor, world: int = 1, max_grad_
                max_grad_norm: float = 0.0, skip_nonfinite: bool = False,
                before_update: Optional[Callable[[], None]] = None, direct: bool = True,
                y_onehot: Optional[torch.Tensor] = None, y: Optional[torch.Tensor] = None,
-               criterion: Optional[str] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               criterion: Optional[str] = None, accumulate: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """One data-parallel training step of the reference's loop (network/trainer.py:123-150) on this rank's shard:
     forward (HIP, with tape) -> loss = mean(nll) -> backward (HIP reverse sweep) -> gradient all-reduce (RCCL) ->
     clip_grad_value_ / clip_grad_norm_ -> optimizer.step().  Returns (global mean loss, gradient norm).
@@ -204,13 +216,23 @@ def train_step(glow, optimizer, x_local: torch.Tensor, world: int = 1, max_grad_
     the place where TrainLoop looks at the PREVIOUS step's norm (the device is still a whole forward + backward behind the host).
     The local loss is mean over the LOCAL shard; averaging the gradients over ranks makes it the global mean.
     Class-conditional model (trainer.py:100-131): ``y_onehot`` / ``y`` are this rank's shard of the labels, ``criterion`` is
-    'single_class' or 'multi_class'; loss = generative + weight_y * classification (the two terms: ``glow.last_losses``)."""
+    'single_class' or 'multi_class'; loss = generative + weight_y * classification (the two terms: ``glow.last_losses``).
+    ``accumulate`` = k > 1 (gradient accumulation, direct route and HIP optimisers only): the shard runs as k micro-batches of
+    n / k samples (`micro_slices`) whose gradients are combined on the device (csrc/accumulate.hip) -- the memory of batch n / k at
+    the mathematics of batch n.  The gradient exchange, ``before_update``, the optimiser step and the loss all-reduce still run
+    ONCE per call, after the last micro-step: the exchange's bytes per trained sample fall by k.  On several ranks that exchange is
+    not overlapped with the sweep -- the combine of the last micro-step must come first, so every bucket carries the one event
+    behind it.  (No multi-rank hardware run exists for any route: DESIGN.md section 0.)"""
     direct = direct and hasattr(glow, "loss_and_grads") and x_local.is_cuda
+    accumulate = int(accumulate or 1)
+    if accumulate > 1 and not (direct and hasattr(optimizer, "fused_step")):
+        raise ValueError(f"train_step(accumulate={accumulate}): gradient accumulation runs on the direct route only "
+                         "(direct=True: Glow.loss_and_grads on a device batch, with a HIP optimiser)")
     if direct:
         # HIP forward + reverse sweep called directly (Glow.loss_and_grads): same kernels and bits as the autograd route below,
         # gradients in the plan's persistent buckets (the parameters' .grad are views into them: nothing to zero, nothing to
         # re-assign) -- the per-step host work of autograd over ~1 060 parameter tensors is what eight ranks on one host cannot afford
-        loss = glow.loss_and_grads(x_local, y_onehot=y_onehot, y=y, criterion=criterion)
+        loss = glow.loss_and_grads(x_local, y_onehot=y_onehot, y=y, criterion=criterion, accumulate=accumulate)
     else:
         optimizer.zero_grad(set_to_none=True)
         with torch.enable_grad():

@@ -15,7 +15,8 @@ import time
 import torch
 
 from . import parallel
-from .misc import lr_scheduler
+from .misc import lr_scheduler, util
+from .parallel import micro_slices  # noqa: F401  (the one definition of the micro-batch cut: model, captured step and tests)
 
 import ctypes
 
@@ -417,14 +418,21 @@ class GraphedTrainStep:
     from memory (glowhip_optim_step_dev) and __call__ uploads them before each replay.  `glowhip_plan_pack` is inside the graph:
     every replay re-derives the weight images from the live parameters, as the forward after an update must.  Capture executes
     nothing, but it needs the lazy allocations of an eager step behind it: capture after at least one eager step of the same batch
-    shape (`TrainLoop(graph=True)` does).  Same kernels, same bits as the eager step (tests/test_gpu_grad.py)."""
+    shape (`TrainLoop(graph=True)` does).  Same kernels, same bits as the eager step (tests/test_gpu_grad.py).
+
+    ``accumulate`` = k > 1 (gradient accumulation): the graph holds all k micro-steps with their combine launches, the two optimiser
+    launches and the loss write -- still ONE graph launch, one hyper upload and one update per optimiser step.  The static ``x`` /
+    label buffers have the full local batch shape; the micro-steps read slices of them, and the noise is drawn per micro-batch, in
+    order, as the eager step draws it."""
 
     def __init__(self, glow, optimizer, x, max_grad_clip=0.0, max_grad_norm=0.0, skip_nonfinite=False, y_onehot=None, y=None,
-                 criterion=None):
+                 criterion=None, accumulate=1):
         if not (x.is_cuda and hasattr(optimizer, "fused_step") and hasattr(glow, "loss_and_grads")):
             raise _lib.GlowHipError("GraphedTrainStep: the HIP optimisers on a device batch")
         self.glow, self.optimizer = glow, optimizer
         self.criterion = criterion
+        self.accumulate = int(accumulate or 1)
+        self._cuts = micro_slices(x.shape[0], self.accumulate)
         self.y_onehot = None if y_onehot is None else y_onehot.float().clone()
         self.y = None if y is None else y.long().clone()
         self.clip, self.max_norm, self.skip = max_grad_clip, max_grad_norm, skip_nonfinite
@@ -479,6 +487,8 @@ class GraphedTrainStep:
         # training steps -- is a buffer no captured launch reaches, and must not cost a recapture)
         return (ptr(plan.packed), ptr(getattr(plan, "_ws", None)) if self._had_ws else 0, ptr(getattr(plan, "_tws", None)),
                 tuple(ptr(f) for f in pg[0]) if pg else (), ptr(getattr(opt, "_partial", None)), ptr(getattr(opt, "_keep", None)),
+                # the accumulators of a step with gradient accumulation (re-allocated with the buckets)
+                tuple(ptr(a) for a in plan.grad_accumulators() or ()) if self.accumulate > 1 else (),
                 # the Polyak average and the pointer array to it (0 without one); swap_averaged() moves neither
                 ptr(opt._flat[2]) if self.ema and opt._flat else 0, ptr(getattr(opt, "_keep_ema", None)),
                 # an eager pack of this plan for the OTHER kernel family since the capture (a re-run of an overflowed batch): it rebuilt
@@ -494,9 +504,10 @@ class GraphedTrainStep:
         return self.plan.still_valid() and self._buffer_signature() == self._buffers
 
     def _body(self):
-        self.noise.uniform_(0, 1. / 2 ** self.n_bits)
+        for lo, hi in self._cuts:            # (one draw per micro-batch, in order: the eager step's; k = 1 is the whole buffer)
+            self.noise[lo:hi].uniform_(0, 1. / 2 ** self.n_bits)
         loss = self.glow.loss_and_grads(self.x, noise=self.noise, y_onehot=self.y_onehot, y=self.y, criterion=self.criterion,
-                                        force_pack=True)
+                                        force_pack=True, accumulate=self.accumulate)
         if self.glow.last_losses[1] is not None:
             self.loss_classes.copy_(self.glow.last_losses[1])
         if hasattr(self.glow.flow, "pop_grad_buckets"):
@@ -570,6 +581,10 @@ class TrainLoop:
         self.global_step = 0
         self.lr = None
         self.criterion = hps.ablation.get("y_criterion", None) if hps.ablation.get("y_condition", False) else None
+        # hps.optim.accumulate_steps (beyond the reference's schema; absent, 0 or 1 = off): every step runs its local batch as that
+        # many micro-batches (gradient accumulation: parallel.train_step(accumulate=)) -- still one optimiser step, one global_step,
+        # one learning rate and one range check per step() call
+        self.accumulate = util.accumulate_steps(hps)
 
     def _refuse_swapped(self, what):
         """While the optimiser's averaged weights are swapped in nothing here may train -- not a step, not the re-run of a skipped
@@ -583,7 +598,10 @@ class TrainLoop:
         if self.global_step == 0 and not self.glow.actnorm_inited():
             # data-dependent ActNorm init on rank 0's batch, broadcast to the others (trainer.py:112-115)
             self.glow.train()
-            parallel.data_dependent_init(self.glow, x_local, rank=self.rank, world=self.world, y_onehot=y_onehot)
+            # (with gradient accumulation the init pass is forward only -- no tape of the FULL batch, the one buffer the option is
+            # there to avoid; the statistics are the full local batch's either way)
+            with torch.no_grad() if self.accumulate > 1 else contextlib.nullcontext():
+                parallel.data_dependent_init(self.glow, x_local, rank=self.rank, world=self.world, y_onehot=y_onehot)
         if not self.glow.training:      # (nn.Module.train() walks all ~6 400 sub-modules: 4.5 ms of host time when called every step)
             self.glow.train()
         self.lr = self.scheduler(global_step=self.global_step)
@@ -600,7 +618,7 @@ class TrainLoop:
             loss, grad_norm = parallel.train_step(self.glow, self.optimizer, x_local, world=self.world,
                                                   max_grad_clip=self.max_grad_clip, max_grad_norm=self.max_grad_norm,
                                                   skip_nonfinite=checked, before_update=self._check_previous if checked else None,
-                                                  **labels)
+                                                  **labels, **self._accumulate_kw())
         self.global_step += 1
         if checked:
             self._pending.append(self._stash(x_local, grad_norm, self.lr, y_onehot, y))
@@ -608,6 +626,10 @@ class TrainLoop:
             for pending in reruns or ():
                 self._run_again(pending)
         return loss, grad_norm
+
+    def _accumulate_kw(self):
+        """``accumulate=k`` for `parallel.train_step` when gradient accumulation is on; nothing at all when it is off."""
+        return dict(accumulate=self.accumulate) if self.accumulate > 1 else {}
 
     def _graph_for(self, x_local, checked, y_onehot=None, y=None):
         """The captured step for this batch, or None (eager): graph=True, one rank, a device batch, the HIP optimiser, past the
@@ -618,7 +640,8 @@ class TrainLoop:
             return None
         g = self._graphed
         if g is not None and (g.x.shape != x_local.shape or g.x.dtype != x_local.dtype or g.skip != checked
-                              or (g.y_onehot is None) != (y_onehot is None) or (g.y is None) != (y is None)):
+                              or (g.y_onehot is None) != (y_onehot is None) or (g.y is None) != (y is None)
+                              or g.accumulate != self.accumulate):
             # another batch shape: its lazy allocations (workspaces, tape, gradient tables) need an eager step behind them before a
             # capture, as the first one had -- this step runs eagerly, the next one captures
             self._graphed = None
@@ -634,7 +657,7 @@ class TrainLoop:
         if g is None:
             try:
                 g = self._graphed = GraphedTrainStep(self.glow, self.optimizer, x_local, self.max_grad_clip, self.max_grad_norm, checked,
-                                                     y_onehot=y_onehot, y=y, criterion=self.criterion)
+                                                     y_onehot=y_onehot, y=y, criterion=self.criterion, **self._accumulate_kw())
             except Exception as e:      # capture is an optimisation of the host side only
                 self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
                 return None
@@ -689,7 +712,9 @@ class TrainLoop:
         range check without a host sync on the step's own work; an overflow is a once-in-a-run event and the two updates commute to
         first order in the learning rate.  If step N + 1 is skipped on the device as well, its count is only taken back at N + 2, so
         this re-run's bias correction uses s + 2 instead of s + 1: a relative change of the step size of O(beta^s), nothing after
-        warm-up.  The float() conversions below are host syncs on this rare path only."""
+        warm-up.  The float() conversions below are host syncs on this rare path only.
+        With gradient accumulation the re-run is again all k micro-batches, on the same plan (a plan serves every batch size of its
+        image shape: the micro-batch's tape and workspace) switched to the exact-fp32 family for the whole call."""
         x_local, _, _, lr, y_onehot, y = pending
         plan = self.glow.flow.plan_for(x_local)
         prev = plan.family
@@ -699,7 +724,8 @@ class TrainLoop:
         try:
             loss, grad_norm = parallel.train_step(self.glow, self.optimizer, x_local, world=self.world,
                                                   max_grad_clip=self.max_grad_clip, max_grad_norm=self.max_grad_norm,
-                                                  skip_nonfinite=True, y_onehot=y_onehot, y=y, criterion=self.criterion)
+                                                  skip_nonfinite=True, y_onehot=y_onehot, y=y, criterion=self.criterion,
+                                                  **self._accumulate_kw())
         finally:
             plan.set_family(prev)
             for group in self.optimizer.param_groups:
