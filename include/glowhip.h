@@ -569,6 +569,49 @@ enum {
 };
 void glowhip_debug_force_tail_tile(int pixels_and_flags);
 
+/* Testing hook: ONE launch of the weight-gradient kernels (csrc/wgrad_mfma.hip, csrc/backward.hip) on operands the caller lays
+ * out, through the launchers the backward sweep itself calls -- tests/test_gpu_wgrad.py holds every instance to fp64 with it.
+ * Not part of the operator surface.  All pointers are device pointers; the layouts are those of the launchers (csrc/backward.h).
+ *   op GLOWHIP_WGRAD_MFMA:   gemm[0] through launch_wgrad_mfma with every argument below (taps[0].operand < 0: no gathered operand)
+ *   op GLOWHIP_WGRAD_PAIR:   gemm[0] = f.4 (A = g_pre, B = h2 fp16, Mpad = m4, Npad = hidden), gemm[1] = f.0 (A = g_u0, B = y1,
+ *                            Mpad = hidden, Npad = n0); taps[0] / taps[1] their gathered tensors; tiled4 / tiled0 = gemm[].tiled;
+ *                            then launch_wgrad_reduce_batched on the jobs the launcher returned
+ *   op GLOWHIP_WGRAD_TRIO:   the same with gemm[2] = f.2 (A = g_u2, B = h1 fp16, hidden x hidden)
+ *   op GLOWHIP_WGRAD_SHIFT_EXPAND:  gemm[0].A (batch stride a_bs) -> gemm[0].dw, taps[0] = (C, H, W, sign), rows_pad = gemm[0].Mpad
+ *   op GLOWHIP_WGRAD_DIRECT: gy = gemm[0].A, x = gemm[0].B (batch stride b_bs) -> gemm[0].dw; Cout = Mreal, Cin = Nreal,
+ *                            taps[0].H / W the map, ksize (1 or 3)
+ *   op GLOWHIP_WGRAD_HALF_TO_FLOAT: gemm[0].B (fp16, pixel-tile-major, Npad rows) -> gemm[0].dw (N, Npad, HW)
+ * A NULL gemm[i].partial in one of the three GEMM ops launches nothing: info->partial_floats[i] alone is filled, with what the
+ * sweep allocates for that GEMM (N, HW, Mpad, Npad).  Whatever the launchers refuse is refused here: GLOWHIP_EINVAL, no launch. */
+enum { GLOWHIP_WGRAD_MFMA = 0, GLOWHIP_WGRAD_PAIR = 1, GLOWHIP_WGRAD_TRIO = 2, GLOWHIP_WGRAD_SHIFT_EXPAND = 3,
+       GLOWHIP_WGRAD_DIRECT = 4, GLOWHIP_WGRAD_HALF_TO_FLOAT = 5 };
+/* glowhip_wgrad_info.instance: the kernel instance that ran */
+enum { GLOWHIP_WGI_F32_128 = 1, GLOWHIP_WGI_F32_64 = 2,                      /* k_wgrad_gemm<128 / 64> */
+       GLOWHIP_WGI_SH = 0x100,                                                /* k_wgrad_gemm_sh<...>: OR of the template flags below */
+       GLOWHIP_WGI_BN64 = 1, GLOWHIP_WGI_VA = 2, GLOWHIP_WGI_VB = 4, GLOWHIP_WGI_BV = 8, GLOWHIP_WGI_BH = 16,
+       GLOWHIP_WGI_PS128 = 0x200, GLOWHIP_WGI_PS64 = 0x201, GLOWHIP_WGI_PS512 = 0x202,   /* k_wgrad_gemm_ps<128 / 64>, k_wgrad_gemm_ps512 */
+       GLOWHIP_WGI_PAIR64 = 0x300, GLOWHIP_WGI_PAIR128 = 0x301,              /* k_wgrad_gemm_pair<64 / 128> */
+       GLOWHIP_WGI_TRIO64 = 0x400, GLOWHIP_WGI_TRIO128 = 0x401,              /* k_wgrad_gemm_trio<64 / 128> */
+       GLOWHIP_WGI_SHIFT_EXPAND = 0x500, GLOWHIP_WGI_DIRECT1 = 0x501, GLOWHIP_WGI_DIRECT3 = 0x503, GLOWHIP_WGI_HALF_TO_FLOAT = 0x600 };
+typedef struct glowhip_wgrad_gemm {
+    const void* A; const void* B; float* partial; float* dw; double* rowsum;   /* rowsum NULL: none */
+    int64_t a_bs, b_bs;                                                         /* batch strides in elements */
+    int32_t Mpad, Npad, Mreal, Nreal, mode, b_valid, b_half, tiled;
+} glowhip_wgrad_gemm;
+typedef struct glowhip_wgrad_taps { int32_t operand, C, H, W, sign; } glowhip_wgrad_taps;
+typedef struct glowhip_wgrad_probe {
+    int32_t op, N, HW, ksize;
+    float sh_scale; int32_t reserved;
+    glowhip_wgrad_gemm gemm[3];
+    glowhip_wgrad_taps taps[2];
+} glowhip_wgrad_probe;
+typedef struct glowhip_wgrad_info {
+    int32_t instance[3], splits[3], ktiles_per_split[3], blocks[3], live[3];   /* per GEMM, in the order of probe.gemm */
+    int32_t reserved;
+    int64_t partial_floats[3];
+} glowhip_wgrad_info;
+int glowhip_debug_wgrad(const glowhip_wgrad_probe* d, glowhip_wgrad_info* info, glowhip_stream_t stream);
+
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per
  * convolution).  Writes a NUL-terminated description into buf. */
 int glowhip_plan_describe(const glowhip_plan* plan, char* buf, size_t buf_bytes);

@@ -89,6 +89,37 @@ class GradSeg(ctypes.Structure):
     _fields_ = [("grad", c_void_p), ("acc", c_void_p), ("n", ctypes.c_int64)]
 
 
+class WgradGemm(ctypes.Structure):
+    """Mirror of ``glowhip_wgrad_gemm`` (the testing hook ``glowhip_debug_wgrad``)."""
+    _fields_ = [(n, c_void_p) for n in ("A", "B", "partial", "dw", "rowsum")] + [("a_bs", ctypes.c_int64), ("b_bs", ctypes.c_int64)] + \
+               [(n, c_int32) for n in ("Mpad", "Npad", "Mreal", "Nreal", "mode", "b_valid", "b_half", "tiled")]
+
+
+class WgradTaps(ctypes.Structure):
+    """Mirror of ``glowhip_wgrad_taps``."""
+    _fields_ = [(n, c_int32) for n in ("operand", "C", "H", "W", "sign")]
+
+
+class WgradProbe(ctypes.Structure):
+    """Mirror of ``glowhip_wgrad_probe``."""
+    _fields_ = [("op", c_int32), ("N", c_int32), ("HW", c_int32), ("ksize", c_int32), ("sh_scale", c_float), ("reserved", c_int32),
+                ("gemm", WgradGemm * 3), ("taps", WgradTaps * 2)]
+
+
+class WgradInfo(ctypes.Structure):
+    """Mirror of ``glowhip_wgrad_info``."""
+    _fields_ = [(n, c_int32 * 3) for n in ("instance", "splits", "ktiles_per_split", "blocks", "live")] + \
+               [("reserved", c_int32), ("partial_floats", ctypes.c_int64 * 3)]
+
+
+# glowhip.h GLOWHIP_WGRAD_* (op) and GLOWHIP_WGI_* (instance)
+WGRAD_MFMA, WGRAD_PAIR, WGRAD_TRIO, WGRAD_SHIFT_EXPAND, WGRAD_DIRECT, WGRAD_HALF_TO_FLOAT = range(6)
+WGI_F32_128, WGI_F32_64, WGI_SH = 1, 2, 0x100
+WGI_BN64, WGI_VA, WGI_VB, WGI_BV, WGI_BH = 1, 2, 4, 8, 16
+WGI_PS128, WGI_PS64, WGI_PS512 = 0x200, 0x201, 0x202
+WGI_PAIR64, WGI_PAIR128, WGI_TRIO64, WGI_TRIO128 = 0x300, 0x301, 0x400, 0x401
+WGI_SHIFT_EXPAND, WGI_DIRECT1, WGI_DIRECT3, WGI_HALF_TO_FLOAT = 0x500, 0x501, 0x503, 0x600
+
 ACC_FIRST, ACC_ADD, ACC_FINISH = 0, 1, 2      # glowhip.h GLOWHIP_ACC_*
 ACC_MAX_SEGS = 16
 
@@ -184,6 +215,7 @@ SIGNATURES = {
     "glowhip_plan_describe_for": (c_int, [_P, c_int, c_char_p, c_size_t]),
     "glowhip_plan_launch_counts": (c_int, [_P, c_char_p, c_size_t, c_int]),
     "glowhip_debug_force_tail_tile": (None, [c_int]),
+    "glowhip_debug_wgrad": (c_int, [POINTER(WgradProbe), POINTER(WgradInfo), _P]),
     "glowhip_plan_tape_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_train_workspace_bytes": (c_size_t, [_P, c_int]),
     "glowhip_glow_forward_train": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, _P, _P, _P, c_int, _P, c_size_t, _P,

@@ -939,7 +939,7 @@ bool wgrad_pair_ok(int HW, int m4, int hid, int n0) {
 int launch_wgrad_pair(const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
                       const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
                       int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0, int tiled4,
-                      int tiled0, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s) {
+                      int tiled0, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s, WgradLaunchInfo* info) {
     const bool ok = sh_scale > 0.f && N > 0 && wgrad_pair_ok(HW, m4, hid, n0) && t4.operand == 0 && t1_ok(t4, HW) && t0.operand == 1 && t1_ok(t0, HW) &&
                     tiled4 == 2 && tiled0 == 5;
     GH_REQUIRE(ok, "wgrad grouped launch: shapes outside wgrad_pair_ok / operands not as documented");
@@ -966,6 +966,11 @@ int launch_wgrad_pair(const float* gpre, long gpre_bs, const void* h2_half, floa
     if (bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_pair<64>, dim3(nb4 + nb0), dim3(256), 0, s, a4, a0, tiles4 * sp4);
     else hipLaunchKernelGGL(k_wgrad_gemm_pair<128>, dim3(nb4 + nb0), dim3(256), 0, s, a4, a0, tiles4 * sp4);
     GH_LAUNCH_CHECK("k_wgrad_gemm_pair");
+    if (info) {
+        const int inst = bn0 == 64 ? GLOWHIP_WGI_PAIR64 : GLOWHIP_WGI_PAIR128;
+        info[0] = WgradLaunchInfo{inst, sp4, per4, nb4, tiles4 * sp4};
+        info[1] = WgradLaunchInfo{inst, sp0, per0, nb0, nb0};
+    }
     *rj4 = WgradReduceJob{partial4, dw4, sp4, m4, hid, m4_real, hid, 1};
     *rj0 = WgradReduceJob{partial0, dw0, sp0, hid, n0, hid, n0_real, 0};
     return GLOWHIP_OK;
@@ -976,7 +981,7 @@ int launch_wgrad_trio(const float* gu2, const void* h1_half, float* partial2, fl
                       const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
                       const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
                       int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0,
-                      WgradReduceJob* rj2, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s) {
+                      WgradReduceJob* rj2, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s, WgradLaunchInfo* info) {
     const bool ok = sh_scale > 0.f && N > 0 && wgrad_pair_ok(HW, m4, hid, n0) && t4.operand == 0 && t1_ok(t4, HW) && t0.operand == 1 && t1_ok(t0, HW);
     GH_REQUIRE(ok, "wgrad grouped launch: shapes outside wgrad_pair_ok / operands not as documented");
     const int total = (int)((long)N * HW / 32);
@@ -1005,6 +1010,12 @@ int launch_wgrad_trio(const float* gu2, const void* h1_half, float* partial2, fl
     if (bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_trio<64>, dim3(nb2 + nb4 + nb0), dim3(256), 0, s, a2, a4, a0, live2, live4);
     else hipLaunchKernelGGL(k_wgrad_gemm_trio<128>, dim3(nb2 + nb4 + nb0), dim3(256), 0, s, a2, a4, a0, live2, live4);
     GH_LAUNCH_CHECK("k_wgrad_gemm_trio");
+    if (info) {
+        const int inst = bn0 == 64 ? GLOWHIP_WGI_TRIO64 : GLOWHIP_WGI_TRIO128;
+        info[0] = WgradLaunchInfo{inst, sp4, per4, nb4, live4};
+        info[1] = WgradLaunchInfo{inst, sp0, per0, nb0, nb0};
+        info[2] = WgradLaunchInfo{inst, sp2, per2, nb2, live2};
+    }
     *rj2 = WgradReduceJob{partial2, dw2, sp2, hid, hid, hid, hid, 0};
     *rj4 = WgradReduceJob{partial4, dw4, sp4, m4, hid, m4_real, hid, 1};
     *rj0 = WgradReduceJob{partial0, dw0, sp0, hid, n0, hid, n0_real, 0};
@@ -1013,7 +1024,7 @@ int launch_wgrad_trio(const float* gu2, const void* h1_half, float* partial2, fl
 
 int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, float* partial, float* dw, int N, int HW,
                       int Mpad, int Npad, int Mreal, int Nreal, int mode, hipStream_t s, float sh_scale, double* rowsum,
-                      const WgradTaps* taps, WgradReduceJob* defer, int b_valid, int b_half, int tiled) {
+                      const WgradTaps* taps, WgradReduceJob* defer, int b_valid, int b_half, int tiled, WgradLaunchInfo* info) {
     const bool ps = tiled & 4;          // bit 2: A holds g * sh_scale * 2^11 (the backward k_cnet's g_u2 / g_u0)
     const float a_pre = ps ? SH_LO_INV : sh_scale;
     GH_REQUIRE(!ps || !(taps && taps->operand == 0), "wgrad_mfma: a pre-scaled A is a plain one");
@@ -1039,16 +1050,21 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
     const int vC = taps ? taps->C : 0, vH = taps ? taps->H : 0, vW = taps ? taps->W : 1, vs = taps ? taps->sign : 0;
     const WgArgs wa{A, a_bs, B, b_bs, partial, HW, Mpad, Npad, total, per, sh_scale, a_pre, rowsum, vC, vH, vW, vs,
                     b_valid > 0 ? b_valid : Npad, tiled, tiles * splits};
-#define GH_WG(bn, va, vb) hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, vb>), dim3(tiles * splits), dim3(256), 0, s, wa)
-#define GH_WGH(bn, va) hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, false, false, true>), dim3(tiles * splits), dim3(256), 0, s, wa)
+    int inst = 0;      // GLOWHIP_WGI_* of the instance launched (reported through `info` only)
+#define GH_WGI(bn, va, vb, bv, bh) (GLOWHIP_WGI_SH | ((bn) == 64 ? GLOWHIP_WGI_BN64 : 0) | ((va) ? GLOWHIP_WGI_VA : 0) | ((vb) ? GLOWHIP_WGI_VB : 0) | \
+                                    ((bv) ? GLOWHIP_WGI_BV : 0) | ((bh) ? GLOWHIP_WGI_BH : 0))
+#define GH_WG(bn, va, vb) do { inst = GH_WGI(bn, va, vb, false, false); hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, vb>), dim3(tiles * splits), dim3(256), 0, s, wa); } while (0)
+#define GH_WGH(bn, va) do { inst = GH_WGI(bn, va, false, false, true); hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, false, false, true>), dim3(tiles * splits), dim3(256), 0, s, wa); } while (0)
     if (b_half && ps && wide) {        // ... with 256-column tiles and eight waves, one workgroup per CU
         GH_REQUIRE((tiled & 3) == 3, "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
         constexpr int lds256 = wgrad_sh_lds_bytes<256, true>();
         (void)hipFuncSetAttribute((const void*)k_wgrad_gemm_ps512, hipFuncAttributeMaxDynamicSharedMemorySize, lds256);
+        inst = GLOWHIP_WGI_PS512;
         hipLaunchKernelGGL(k_wgrad_gemm_ps512, dim3(tiles * splits), dim3(512), lds256, s, wa);
     } else
     if (b_half && ps) {                // f.2 behind the backward k_cnet: its own kernel
         GH_REQUIRE((tiled & 3) == 3, "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
+        inst = bn128 ? GLOWHIP_WGI_PS128 : GLOWHIP_WGI_PS64;
         if (bn128) hipLaunchKernelGGL(k_wgrad_gemm_ps<128>, dim3(tiles * splits), dim3(256), 0, s, wa);
         else hipLaunchKernelGGL(k_wgrad_gemm_ps<64>, dim3(tiles * splits), dim3(256), 0, s, wa);
     } else
@@ -1062,21 +1078,28 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
         else if (taps) GH_WG(128, false, true);
         else GH_WG(128, false, false);
     } else if (sh_scale > 0.f) {
-        if (taps && taps->operand == 0 && b_valid > 0)
+        if (taps && taps->operand == 0 && b_valid > 0) {
+            inst = GH_WGI(64, true, false, true, false);
             hipLaunchKernelGGL((k_wgrad_gemm_sh<64, true, false, true>), dim3(tiles * splits), dim3(256), 0, s, wa);
+        }
         else if (taps && taps->operand == 0) GH_WG(64, true, false);
         else if (taps) GH_WG(64, false, true);
         else GH_WG(64, false, false);
     }
 #undef GH_WG
 #undef GH_WGH
-    else if (bn128)
+#undef GH_WGI
+    else if (bn128) {
+        inst = GLOWHIP_WGI_F32_128;
         hipLaunchKernelGGL(k_wgrad_gemm<128>, dim3(tiles * splits), dim3(256), 0, s, A, a_bs, B, b_bs, partial, HW, Mpad, Npad,
                            total, per);
-    else
+    } else {
+        inst = GLOWHIP_WGI_F32_64;
         hipLaunchKernelGGL(k_wgrad_gemm<64>, dim3(tiles * splits), dim3(256), 0, s, A, a_bs, B, b_bs, partial, HW, Mpad, Npad,
                            total, per);
+    }
     GH_LAUNCH_CHECK("k_wgrad_gemm");
+    if (info) *info = WgradLaunchInfo{inst, splits, per, tiles * splits, tiles * splits};
     if (defer) {       // the caller reduces later (launch_wgrad_reduce_batched): `partial` must stay untouched until then
         *defer = WgradReduceJob{partial, dw, splits, Mpad, Npad, Mreal, Nreal, mode};
         return GLOWHIP_OK;
@@ -1088,3 +1111,82 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
 }
 
 }  // namespace glowhip
+
+using namespace glowhip;
+
+// Testing hook (include/glowhip.h): one launch of the launchers above / of backward.hip on the caller's operands.  No second
+// path: it decodes the probe, calls the launcher the sweep calls, and copies what the launcher reported.
+extern "C" int glowhip_debug_wgrad(const glowhip_wgrad_probe* d, glowhip_wgrad_info* info, glowhip_stream_t stream) {
+    GH_REQUIRE(d && info, "debug_wgrad: null probe / info");
+    hipStream_t s = (hipStream_t)stream;
+    *info = glowhip_wgrad_info{};
+    const int ngemm = d->op == GLOWHIP_WGRAD_MFMA ? 1 : d->op == GLOWHIP_WGRAD_PAIR ? 2 : d->op == GLOWHIP_WGRAD_TRIO ? 3 : 0;
+    GH_REQUIRE(d->N >= 0 && d->HW > 0, "debug_wgrad: bad batch / map size");
+    const glowhip_wgrad_gemm* g = d->gemm;
+    auto taps = [&](int i) { return WgradTaps{d->taps[i].operand, d->taps[i].C, d->taps[i].H, d->taps[i].W, d->taps[i].sign}; };
+    auto report = [&](int i, const WgradLaunchInfo& li) {
+        info->instance[i] = li.instance; info->splits[i] = li.splits; info->ktiles_per_split[i] = li.ktiles_per_split;
+        info->blocks[i] = li.blocks; info->live[i] = li.live;
+    };
+    if (ngemm) {
+        bool query = false;
+        for (int i = 0; i < ngemm; ++i) {
+            GH_REQUIRE(g[i].Mpad > 0 && g[i].Npad > 0 && wgrad_mfma_supported(d->HW, g[i].Mpad, g[i].Npad), "debug_wgrad: unsupported shape");
+            info->partial_floats[i] = (int64_t)wgrad_mfma_partial_floats(g[i].Mpad, g[i].Npad, d->N, d->HW);
+            query = query || !g[i].partial;
+        }
+        if (query) return GLOWHIP_OK;
+        for (int i = 0; i < ngemm; ++i) GH_REQUIRE(g[i].A && g[i].B && g[i].dw, "debug_wgrad: null operand / output");
+    }
+    switch (d->op) {
+    case GLOWHIP_WGRAD_MFMA: {
+        const WgradTaps t = taps(0);
+        WgradLaunchInfo li{};
+        GH_TRY(launch_wgrad_mfma((const float*)g[0].A, (long)g[0].a_bs, (const float*)g[0].B, (long)g[0].b_bs, g[0].partial, g[0].dw, d->N, d->HW,
+                                 g[0].Mpad, g[0].Npad, g[0].Mreal, g[0].Nreal, g[0].mode, s, d->sh_scale, g[0].rowsum, t.operand >= 0 ? &t : nullptr,
+                                 nullptr, g[0].b_valid, g[0].b_half, g[0].tiled, &li));
+        report(0, li);
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_WGRAD_PAIR:
+    case GLOWHIP_WGRAD_TRIO: {
+        const bool trio = d->op == GLOWHIP_WGRAD_TRIO;
+        const int hid = g[0].Npad;
+        GH_REQUIRE(g[1].Mpad == hid && (!trio || (g[2].Mpad == hid && g[2].Npad == hid)), "debug_wgrad: the grouped GEMMs share one hidden width");
+        GH_REQUIRE(!trio || (g[0].tiled == 2 && g[1].tiled == 5 && g[2].tiled == 7), "debug_wgrad: the three-GEMM launch has fixed operand layouts");
+        const WgradTaps t4 = taps(0), t0 = taps(1);
+        WgradLaunchInfo li[3] = {};
+        WgradReduceJobs rj{};
+        if (trio) {
+            rj.n = 3;
+            GH_TRY(launch_wgrad_trio((const float*)g[2].A, g[2].B, g[2].partial, g[2].dw, g[2].rowsum, (const float*)g[0].A, (long)g[0].a_bs, g[0].B,
+                                     g[0].partial, g[0].dw, g[0].Mpad, g[0].Mreal, (const float*)g[1].A, (const float*)g[1].B, (long)g[1].b_bs,
+                                     g[1].partial, g[1].dw, g[1].Npad, g[1].Nreal, d->N, d->HW, hid, d->sh_scale, g[1].rowsum, t4, t0,
+                                     &rj.job[2], &rj.job[0], &rj.job[1], s, li));
+        } else {
+            rj.n = 2;
+            GH_TRY(launch_wgrad_pair((const float*)g[0].A, (long)g[0].a_bs, g[0].B, g[0].partial, g[0].dw, g[0].Mpad, g[0].Mreal,
+                                     (const float*)g[1].A, (const float*)g[1].B, (long)g[1].b_bs, g[1].partial, g[1].dw, g[1].Npad, g[1].Nreal,
+                                     d->N, d->HW, hid, d->sh_scale, g[1].rowsum, t4, t0, g[0].tiled, g[1].tiled, &rj.job[0], &rj.job[1], s, li));
+        }
+        for (int i = 0; i < rj.n; ++i) report(i, li[i]);
+        return launch_wgrad_reduce_batched(rj, s);
+    }
+    case GLOWHIP_WGRAD_SHIFT_EXPAND:
+        GH_REQUIRE(g[0].A && g[0].dw && d->taps[0].C > 0 && d->taps[0].H * d->taps[0].W == d->HW && g[0].Mpad >= 9 * d->taps[0].C &&
+                   (d->taps[0].sign == 1 || d->taps[0].sign == -1), "debug_wgrad: shift_expand arguments");
+        info->instance[0] = GLOWHIP_WGI_SHIFT_EXPAND;
+        return launch_shift_expand((const float*)g[0].A, (long)g[0].a_bs, g[0].dw, d->N, d->taps[0].C, d->taps[0].H, d->taps[0].W, g[0].Mpad,
+                                   d->taps[0].sign, s);
+    case GLOWHIP_WGRAD_DIRECT:
+        GH_REQUIRE(g[0].A && g[0].B && g[0].dw && g[0].Mreal > 0 && g[0].Nreal > 0 && d->taps[0].H * d->taps[0].W == d->HW, "debug_wgrad: wgrad_direct arguments");
+        info->instance[0] = d->ksize == 1 ? GLOWHIP_WGI_DIRECT1 : GLOWHIP_WGI_DIRECT3;
+        return launch_wgrad_direct((const float*)g[0].A, (const float*)g[0].B, (long)g[0].b_bs, g[0].dw, d->N, g[0].Nreal, d->taps[0].H, d->taps[0].W,
+                                   g[0].Mreal, d->ksize, s);
+    case GLOWHIP_WGRAD_HALF_TO_FLOAT:
+        GH_REQUIRE(g[0].B && g[0].dw && g[0].Npad > 0, "debug_wgrad: half_to_float arguments");
+        info->instance[0] = GLOWHIP_WGI_HALF_TO_FLOAT;
+        return launch_half_to_float(g[0].B, g[0].dw, d->N, g[0].Npad, d->HW, s);
+    }
+    GH_REQUIRE(false, "debug_wgrad: unknown op %d", d->op);
+}
