@@ -191,6 +191,69 @@ int glowhip_plan_decode(glowhip_plan* plan, const void* packed, const float* z, 
  * (NULL, 0) unbinds; the training forward ignores it.  n_eps must equal the plan's Split2d count (GLOWHIP_EINVAL otherwise). */
 int glowhip_plan_bind_latents(glowhip_plan* plan, float* const* eps_out, int n_eps);
 
+/* ------------------------------------------------------------------------------------------------
+ * Held-out evaluation (csrc/evaluate.hip): where the bits of Glow.normal_flow's objective (network/model.py:409-452) go, and the
+ * bits per dimension of a data set.  No counterpart in the reference, which reports nll per training batch (network/trainer.py:123-133).
+ * ---------------------------------------------------------------------------------------------- */
+/* Per-level terms of the objective.  A LEVEL is a maximal run of layers that ends with a Split2d (network/module.py:511-536); the
+ * last level ends with the top prior (network/model.py:440-445) or the head: glowhip_plan_level_count = Split2d count + 1 (HOST
+ * bookkeeping, no device needed).  glowhip_plan_bind_level_terms is a per-call binding in the pattern of glowhip_plan_bind_latents
+ * (pointers copied; HOST bookkeeping): honoured at enqueue time by glowhip_glow_forward / glowhip_glow_forward_u8 until
+ * (NULL, NULL, 0) unbinds; the training forward, glowhip_plan_encode and glowhip_plan_decode ignore it.  While bound, the forward
+ * enqueues one snapshot launch behind the launches of every Split2d and one behind the top prior's -- each copies the (2 + 7) N
+ * words of the per-sample log-det accumulators into scratch (glowhip_plan_level_scratch_bytes(plan, N) bytes, the caller's;
+ * glowhip_plan_workspace_bytes does not change) -- and, behind the launch that writes nll / objective, ONE launch that writes
+ *     terms[l * N + n] = sum over the FlowSteps of level l of (3 sum(actnorm.logs) + log|det W|) H W      (network/module.py:76-82, 356-357)
+ *                        + fix(snapshot_l - snapshot_{l-1})                                               in nats, one fp32 rounding
+ * = level l's log-determinants (network/model.py:82-117) + the log-density its Split2d, or the top prior, scores.  The difference
+ * is taken on the integer words (the whole-nats count of the flag word included), before any conversion: the parts add up to the
+ * total exactly as integers, so  objective[n] = -ln(2^n_bits) C H W + sum_l terms[l][n]  up to the one rounding of each number.
+ * A sample whose non-finite flags are set at the snapshot that closes level l has terms[l ..][n] = NaN: a part is never finite and
+ * wrong.  z, nll and objective are bit for bit those of the unbound call; n_levels + 1 launches are added.  At most 16 levels and
+ * 896 FlowSteps (GLOWHIP_EINVAL at bind time); scratch smaller than the batch needs: GLOWHIP_EWORKSPACE from the forward. */
+int glowhip_plan_level_count(const glowhip_plan* plan);
+size_t glowhip_plan_level_scratch_bytes(const glowhip_plan* plan, int N);
+int glowhip_plan_bind_level_terms(glowhip_plan* plan, float* terms /* [n_levels][N] */, void* scratch, size_t scratch_bytes);
+
+/* The fold: one launch per evaluated batch, plan-independent.  objective [K][N]: the objective_out rows of K forwards of the same N
+ * images under K independent dequantisation draws (network/model.py:421; glowhip_plan_set_dequant_stream names them); terms
+ * [K][n_levels][N] (may be NULL): their level terms; dims = C H W of an image.  Per image, in fp64 with a max-subtracted log-sum-exp:
+ *     L          = logsumexp_k objective_k - ln K          (the importance-weighted bound log p(x) >= L; K = 1: today's nll)
+ *     bpd        = fp32(-L / (ln2 dims))                   -> per_image[offset + n]; this rounded value is what the state sums
+ *     bpd_single = -mean_k objective_k / (ln2 dims)        (>= bpd for every image, by Jensen)
+ *     level_bits[l] = -mean_k terms[k][l] / (ln2 dims)     (n_bits + sum_l level_bits[l] = bpd_single: the levels decompose the
+ *                                                           draw-averaged figure; the importance-weighted bound does not decompose)
+ * FLAGGED: an image with a non-finite objective_k, or whose |bpd|, |bpd_single| or a |level_bits[l]| is not below 2048 bits/dim
+ * (beyond the range the sums are guaranteed for).  It is counted in `flagged`, left out of count, every sum, min, max and the
+ * histogram, and its per-image output is NaN.
+ * only_if_nan (N floats of this batch, may be NULL; may alias per_image + offset): image n is folded only if only_if_nan[n] is NaN --
+ * the re-run of what a first pass flagged: every image the call folds is taken OUT of `flagged` first, so each image stays counted
+ * exactly once; the others are not touched, per_image included.
+ * STATE, all integers: every sum is the 128-bit two's-complement sum {lo, hi} of rint(v 2^32) over the counted images, v = bpd,
+ * bpd^2 (of the fp32 bpd, exact in fp64), bpd_single, level_bits[l]; min_key / max_key = min / max of rint(bpd 2^32) + 2^63 (reset:
+ * all ones / 0); hist[i] counts  lo <= bpd < hi  with  i = min(floor((bpd - lo) * (bins / (hi - lo))), bins - 1)  evaluated in fp64 --
+ * a value on an edge that this expression meets exactly belongs to the upper bin -- `under` bpd < lo, `over` bpd >= hi.  Integer
+ * sums, counts, min and max: the state after a data set is the same bits for any split into batches and any order of the folds.
+ * RANGE: |rint(v 2^32)| < 2^43 and rint(v^2 2^32) < 2^54 per image, a workgroup's 256 fit an int64, and the 128-bit sums hold more
+ * images than `count` can number: the image count is bounded by the counter alone, count + flagged < 2^64.
+ * glowhip_eval_reset zeroes the state and sets n_levels (<= 16), bins (<= 256; 0 = no histogram) and [lo, hi).  No allocation, no
+ * host sync, capturable. */
+#define GLOWHIP_EVAL_MAX_LEVELS 16
+#define GLOWHIP_EVAL_MAX_BINS 256
+typedef struct glowhip_eval_state {
+    uint64_t count, flagged;
+    uint64_t min_key, max_key;
+    uint64_t sum_bpd[2], sum_bpd2[2], sum_single[2];
+    uint64_t sum_level[GLOWHIP_EVAL_MAX_LEVELS][2];
+    double lo, hi;
+    int32_t bins, n_levels;
+    uint64_t under, over;
+    uint64_t hist[GLOWHIP_EVAL_MAX_BINS];
+} glowhip_eval_state;
+int glowhip_eval_reset(glowhip_eval_state* state /* DEVICE */, int n_levels, int bins, double lo, double hi, glowhip_stream_t stream);
+int glowhip_eval_fold(glowhip_eval_state* state /* DEVICE */, const float* objective, const float* terms, int K, int N, int n_levels,
+                      double dims, const float* only_if_nan, float* per_image, long offset, glowhip_stream_t stream);
+
 /* Glow.normal_flow (network/model.py:409-452) in one call: z = x + noise; objective = -ln(2^n_bits)*CHW
  * + encode logdet + logp(z | prior_mean, prior_logs);  nll = -objective / (ln2*CHW).
  * prior_mean/prior_logs: (N,Cz,Hz,Wz) with batch stride prior_stride, NULL = zeros.

@@ -120,6 +120,18 @@ WGI_PS128, WGI_PS64, WGI_PS512 = 0x200, 0x201, 0x202
 WGI_PAIR64, WGI_PAIR128, WGI_TRIO64, WGI_TRIO128 = 0x300, 0x301, 0x400, 0x401
 WGI_SHIFT_EXPAND, WGI_DIRECT1, WGI_DIRECT3, WGI_HALF_TO_FLOAT = 0x500, 0x501, 0x503, 0x600
 
+EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256       # glowhip.h GLOWHIP_EVAL_MAX_*
+
+
+class EvalState(ctypes.Structure):
+    """Mirror of ``glowhip_eval_state`` (device-resident; read back through a uint8 tensor of ``sizeof``)."""
+    _fields_ = [("count", ctypes.c_uint64), ("flagged", ctypes.c_uint64), ("min_key", ctypes.c_uint64), ("max_key", ctypes.c_uint64),
+                ("sum_bpd", ctypes.c_uint64 * 2), ("sum_bpd2", ctypes.c_uint64 * 2), ("sum_single", ctypes.c_uint64 * 2),
+                ("sum_level", (ctypes.c_uint64 * 2) * EVAL_MAX_LEVELS), ("lo", ctypes.c_double), ("hi", ctypes.c_double),
+                ("bins", c_int32), ("n_levels", c_int32), ("under", ctypes.c_uint64), ("over", ctypes.c_uint64),
+                ("hist", ctypes.c_uint64 * EVAL_MAX_BINS)]
+
+
 ACC_FIRST, ACC_ADD, ACC_FINISH = 0, 1, 2      # glowhip.h GLOWHIP_ACC_*
 ACC_MAX_SEGS = 16
 
@@ -237,6 +249,11 @@ SIGNATURES = {
     "glowhip_plan_bind_head": (c_int, [_P, POINTER(HeadIO)]),
     "glowhip_plan_bind_head_grads": (c_int, [_P, POINTER(HeadGrads)]),
     "glowhip_plan_bind_latents": (c_int, [_P, POINTER(c_void_p), c_int]),
+    "glowhip_plan_level_count": (c_int, [_P]),
+    "glowhip_plan_level_scratch_bytes": (c_size_t, [_P, c_int]),
+    "glowhip_plan_bind_level_terms": (c_int, [_P, _P, _P, c_size_t]),
+    "glowhip_eval_reset": (c_int, [_P, c_int, c_int, ctypes.c_double, ctypes.c_double, _P]),
+    "glowhip_eval_fold": (c_int, [_P, _P, _P, c_int, c_int, c_int, ctypes.c_double, _P, _P, c_long, _P]),
     "glowhip_top_prior": (c_int, [POINTER(HeadDesc), _P, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_plan_timing_enable": (c_int, [_P, c_int]),
     "glowhip_plan_timing_read": (c_int, [_P, POINTER(TimingRecord), c_int, POINTER(c_int)]),

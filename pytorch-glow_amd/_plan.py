@@ -199,6 +199,25 @@ class FlowPlan:
     def _unbind_latents(self) -> None:
         check(lib().glowhip_plan_bind_latents(self._h, None, 0))
 
+    # ------------------------------------------------------------------ per-level terms (glowhip_plan_bind_level_terms)
+    @property
+    def n_levels(self) -> int:
+        """Levels of the objective's split: Split2d count + 1 (glowhip_plan_level_count)."""
+        return int(lib().glowhip_plan_level_count(self._h))
+
+    def level_terms_buffer(self, n: int) -> torch.Tensor:
+        """A fresh (n_levels, n) buffer for ``level_terms=`` of `glow_forward`."""
+        return torch.empty((self.n_levels, n), dtype=torch.float32, device=self.device)
+
+    def _bind_level_terms(self, terms, n: int) -> None:
+        if terms.device != self.device or terms.dtype != torch.float32 or not terms.is_contiguous() or tuple(terms.shape) != (self.n_levels, n):
+            raise _lib.GlowHipError(f"level_terms: needs a contiguous fp32 tensor of shape {(self.n_levels, n)} on {self.device}")
+        scratch = self._cached_bytes("_level_scratch", int(lib().glowhip_plan_level_scratch_bytes(self._h, n)))
+        check(lib().glowhip_plan_bind_level_terms(self._h, ptr(terms), ptr(scratch), scratch.numel()))
+
+    def _unbind_level_terms(self) -> None:
+        check(lib().glowhip_plan_bind_level_terms(self._h, None, None, 0))
+
     # ------------------------------------------------------------------ execution
     def _workspace(self, n: int) -> torch.Tensor:
         need = int(lib().glowhip_plan_workspace_bytes(self._h, n))
@@ -462,8 +481,9 @@ class FlowPlan:
         return buf
 
     def glow_forward(self, x, noise, prior_mean, prior_logs, prior_stride, n_bits, repack=False, out=None, head=None, *,
-                     eps_out=None):
-        """``eps_out``: as in `encode`."""
+                     eps_out=None, level_terms=None):
+        """``eps_out``: as in `encode`.  ``level_terms``: a (n_levels, n) buffer (`level_terms_buffer`) that receives the per-level
+        terms of the objective, in nats (glowhip_plan_bind_level_terms); bound for this call only."""
         n = x.shape[0]
         self.ensure_packed(repack)
         if n:
@@ -479,6 +499,8 @@ class FlowPlan:
         ws = self._workspace(n)
         if eps_out is not None:
             self._bind_latents(eps_out, n)
+        if level_terms is not None:
+            self._bind_level_terms(level_terms, n)
         try:
             if x.dtype == torch.uint8:   # 8-bit pixels straight from the data loader: converted inside the leading squeeze
                 check(lib().glowhip_glow_forward_u8(self._h, ptr(self.packed), ptr(x), 255.0, ptr(noise), ptr(prior_mean),
@@ -491,6 +513,8 @@ class FlowPlan:
         finally:
             if eps_out is not None:
                 self._unbind_latents()
+            if level_terms is not None:
+                self._unbind_level_terms()
         return z, nll, obj
 
     # ------------------------------------------------------------------ training step

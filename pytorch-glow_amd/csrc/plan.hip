@@ -302,9 +302,16 @@ static int run_chanmix(glowhip_plan* p, const ChanMixArgs& m, hipStream_t s) {
 // (testing: the mixer-fusion switch glowhip_debug_force_tail_tile(0x8000) also brings the squeeze kernels back -- the two must
 // agree bit for bit)
 
+// the snapshot that closes a level (glowhip_plan_bind_level_terms; evaluate.hip): the accumulator words as every launch before it left them
+static int level_snapshot(glowhip_plan* p, unsigned long long* snaps, int level, int N, const Workspace& w, hipStream_t s) {
+    count_launch(p, "k_level_snapshot");
+    return launch_level_snapshot(w.acc, snaps + (size_t)level * (2 + ACC_EXTRA) * N, N, s);
+}
+
+// level_snaps (glow_forward alone, with level terms bound): one snapshot behind the launches of every Split2d
 static int run_forward(glowhip_plan* p, const void* packed, const float* x, const float* noise, float* z_out, int N,
                        const Workspace& w, hipStream_t s, int first_layer = 0, const RngSpec* rng = nullptr,
-                       const uint8_t* x_u8 = nullptr, float u8_div = 1.f) {
+                       const uint8_t* x_u8 = nullptr, float u8_div = 1.f, unsigned long long* level_snaps = nullptr) {
     const float* cur = x;
     SqueezeFold fold{};      // set by a skipped squeeze layer, consumed by the next layer's k_chanmix
     const int nl = (int)p->layers.size();
@@ -418,9 +425,11 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 if (li + 1 < nl && p->layers[li + 1].d.kind == GLOWHIP_LAYER_SQUEEZE && squeeze_folds(li + 1)) {
                     count_launch(p, "split2d:z1 in place");
                     cur_bs = chw;
+                    if (level_snaps) GH_TRY(level_snapshot(p, level_snaps, L.split_idx, N, w, s));
                     continue;
                 }
                 GH_TRY(launch_copy_strided(cur, chw, dst, (long)Ch * HW, N, (long)Ch * HW, s));
+                if (level_snaps) GH_TRY(level_snapshot(p, level_snaps, L.split_idx, N, w, s));
             }
         }
         cur = dst;
@@ -557,14 +566,37 @@ static int glow_forward(glowhip_plan* plan, const void* packed, const float* x, 
     GH_TRY(open_workspace(plan, N, workspace, workspace_bytes, w, s));
     RngSpec rng{plan->rng_on && !noise, plan->rng_seed, plan->rng_calls, (float)(1.0 / pow(2.0, n_bits))};
     if (rng.on) ++plan->rng_calls;
-    GH_TRY(run_forward(plan, packed, x_u8 ? w.bufA : x, noise, z, N, w, s, 0, rng.on ? &rng : nullptr, x_u8, divisor));
+    // per-level terms bound (glowhip_plan_bind_level_terms): a snapshot of the accumulators closes every level
+    unsigned long long* snaps = plan->level_terms ? plan->level_scratch : nullptr;
+    const int n_levels = plan->n_split + 1;
+    if (snaps) {
+        const size_t need = (size_t)n_levels * (2 + ACC_EXTRA) * (size_t)N * 8;
+        if (plan->level_scratch_bytes < need) {
+            set_error("glow_forward: level scratch too small: need %zu bytes for batch %d, got %zu", need, N, plan->level_scratch_bytes);
+            return GLOWHIP_EWORKSPACE;
+        }
+    }
+    GH_TRY(run_forward(plan, packed, x_u8 ? w.bufA : x, noise, z, N, w, s, 0, rng.on ? &rng : nullptr, x_u8, divisor, snaps));
     GH_TRY(launch_top_logp(plan, z, prior_mean, prior_logs, prior_stride, N, w.acc, s));      // (the head's one launch when one is attached)
+    if (snaps) GH_TRY(level_snapshot(plan, snaps, n_levels - 1, N, w, s));
     GH_TRY(join_legacy(plan, s)); GH_TRY(join_lu(plan, s));      // the sum of the log|det W| terms enters here
     // objective = -ln(n_bins)*CHW + logdet + logp;  nll = -objective / (ln2 * CHW)   (network/model.py:425-450)
     const double chw = (double)plan->in_shape[0] * plan->in_shape[1] * plan->in_shape[2];
     const double offset = -log(pow(2.0, n_bits)) * chw;
     const double scale = -1.0 / (log(2.0) * chw);
-    return launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, offset, scale, nll_out, objective_out, N, s, ACC_EXTRA);
+    GH_TRY(launch_finalize(nullptr, w.acc, at<double>(packed, 0), 1.0, offset, scale, nll_out, objective_out, N, s, ACC_EXTRA));
+    if (!snaps) return GLOWHIP_OK;
+    // ONE launch for every level's term: the data-independent konst words of its FlowSteps (final behind join_lu) + the integer
+    // difference of the snapshots that open and close it
+    LevelKonst kt{};
+    int level = 0; uint32_t ks = 0;
+    for (const LayerPlan& L : plan->layers) {
+        if (L.d.kind == GLOWHIP_LAYER_FLOWSTEP) kt.off8[ks++] = (uint32_t)(L.konst >> 3);
+        else if (L.d.kind == GLOWHIP_LAYER_SPLIT2D) kt.first[++level] = ks;
+    }
+    kt.first[n_levels] = ks;
+    count_launch(plan, "k_level_terms");
+    return launch_level_terms(snaps, packed, kt, n_levels, N, plan->level_terms, s);
 }
 
 }  // namespace glowhip

@@ -50,6 +50,15 @@ constexpr int REPACK_SLOTS = PACK_IMAGE_BITS + 1;
 static inline int repack_slot(int use) { return use & PACK_IMAGE_BITS; }      // slot of a use mask's selected repack jobs
 constexpr size_t PACK_SEG_HEAD = 16;
 
+// Per-level terms of the objective (evaluate.hip; glowhip_plan_bind_level_terms).  A level is a maximal run of layers that ends with a
+// Split2d, the last one ends with the top prior.  LevelKonst rides in the kernel arguments of the one k_level_terms launch: the konst
+// words (LayerPlan::konst, byte offset / 8) of the FlowSteps of level l are off8[first[l] .. first[l + 1]).
+constexpr int LEVEL_MAX = 16, LEVEL_MAX_STEPS = 896;
+struct LevelKonst { uint32_t first[LEVEL_MAX + 1]; uint32_t off8[LEVEL_MAX_STEPS]; };
+int launch_level_snapshot(const unsigned long long* acc, unsigned long long* dst, int N, hipStream_t s);
+int launch_level_terms(const unsigned long long* snap, const void* packed, const LevelKonst& kt, int n_levels, int N, float* terms,
+                       hipStream_t s);
+
 }  // namespace glowhip
 
 using namespace glowhip;
@@ -87,6 +96,8 @@ struct glowhip_plan {
     long max_chw = 0;      // max over layer inputs/outputs of C*H*W
     long max_hidden = 0;   // max over steps of max(hidden, Cout) * H*W
     int n_split = 0;
+    // glowhip_plan_bind_level_terms: terms [n_levels][N] and the caller's snapshot scratch (null = nothing bound)
+    float* level_terms = nullptr; unsigned long long* level_scratch = nullptr; size_t level_scratch_bytes = 0;
     std::vector<float*> eps_out;               // glowhip_plan_bind_latents: per Split2d in DECODE order, empty = nothing bound
     std::vector<char> tape_has_masks;          // per layer: the last glow_forward_train stored the ReLU sign bits (k_cnet MODE 1)
     std::vector<glowhip::LogsJob> logs_jobs;   // the same for the log-scale gradients derived from dW / db (backward.h)

@@ -69,6 +69,17 @@ def accumulate_steps(hps, world=None):
     return k
 
 
+def interval_eval(hps):
+    """``hps.optim.interval_eval`` (beyond the reference's schema): every that many steps `Trainer` evaluates its ``eval_loader``
+    (network.Evaluator: held-out bits per dimension).  Absent, None and 0 mean off and give 0."""
+    raw = hps.optim.get("interval_eval", None)
+    if raw is None or raw is False:
+        return 0
+    if isinstance(raw, bool) or not isinstance(raw, int) or raw < 0:
+        raise ValueError(f"hps.optim.interval_eval = {raw!r}: a non-negative integer (absent or 0 = off)")
+    return int(raw)
+
+
 _CUDA_NAME = re.compile(r'cuda:(\d+)')
 
 

@@ -4,6 +4,7 @@ around `training.TrainLoop`) and `Inferer` (the inverse-path application) -- the
 from . import model as _model
 from . import module as _module
 from .builder import Builder
+from .evaluate import EvalResult, Evaluator
 from .inferer import Inferer
 from .latents import Latents
 from .restore import LatentFit, RestoreInfo, restore_objective
@@ -18,4 +19,4 @@ for _n in _LAYERS:
 for _n in _MODELS:
     globals()[_n] = getattr(_model, _n)
 
-__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Latents", "LatentFit", "RestoreInfo", "restore_objective")
+__all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Evaluator", "EvalResult", "Latents", "LatentFit", "RestoreInfo", "restore_objective")

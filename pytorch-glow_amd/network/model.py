@@ -874,6 +874,13 @@ class Glow(nn.Module):
         replay draws at ``(seed, call)`` (seed None: the process's key), every later one at the next call number."""
         return GraphedSampler(self, n, y_onehot, eps_std=eps_std, uint8=uint8, seed=seed, call=call)
 
+    # ---- held-out evaluation (network/evaluate.py)
+    def evaluate(self, batches, **kw):
+        """Bits per dimension of a data set, importance-weighted over ``draws`` dequantisation draws, with the per-level breakdown:
+        ``Evaluator(self, **kw).run(batches)`` (draws=1, levels=True, seed=0, hist=None, safe=True) -> `EvalResult`."""
+        from .evaluate import Evaluator
+        return Evaluator(self, **kw).run(batches)
+
     # ---- full-latent encode: the bijection with nothing dropped
     def encode_latents(self, x, y_onehot=None, noise=None, dequantize=True, safe=None):
         """`Latents` of a batch (fp32 in [0, 1] or uint8 pixels): the top latent ``z``, the draw ``eps`` every Split2d's dropped

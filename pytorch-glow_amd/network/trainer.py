@@ -21,6 +21,7 @@ from torch.utils.data import DataLoader
 
 from .. import parallel, training
 from ..misc import ops, util
+from .evaluate import Evaluator
 from .model import Glow
 
 
@@ -91,6 +92,21 @@ class _ShardSampler(torch.utils.data.Sampler):
         return iter(shard.reshape(-1).tolist())
 
 
+class _EvalBatches:
+    """`Trainer.eval_loader` as the evaluator takes it: re-iterable (the range re-run walks it a second time), every batch with the
+    ``y_onehot`` the class-conditional prior needs, extracted as the training batches' labels are (`Trainer.labels_of`)."""
+
+    def __init__(self, trainer, loader):
+        self.trainer, self.loader = trainer, loader
+
+    def __iter__(self):
+        for batch in self.loader:
+            if isinstance(batch, dict) and self.trainer.y_condition:
+                _, y_onehot = self.trainer.labels_of(batch)
+                batch = {"x": batch["x"], "y_onehot": y_onehot.float()}
+            yield batch
+
+
 class Trainer:
     # reference network/trainer.py:14-17.  Deliberate deviation (INTEGRATION.md): the reference maps 'multi_class' to
     # single_class_loss as well, which raises inside torch for a multi-hot target; here it is Glow.multi_class_loss
@@ -100,7 +116,7 @@ class Trainer:
     }
 
     def __init__(self, hps, result_subdir, step, graph, optimizer, scheduler, devices, dataset, data_device,
-                 rank=0, world=1):
+                 rank=0, world=1, eval_loader=None):
         self.hps = hps
         self.result_subdir = result_subdir
         self.start_time = time.time()
@@ -139,6 +155,12 @@ class Trainer:
         # hps.optim.ema_eval (beyond the reference's schema): reconstructions and samples are drawn under the Polyak-averaged weights
         # (hps.optim.ema_decay, training.averaged_weights: swapped in and out in place, the captured step stays valid)
         self.ema_eval = bool(self.hps.optim.get("ema_eval", False))
+        # hps.optim.interval_eval + ``eval_loader`` (both beyond the reference): every interval_eval steps rank 0 evaluates the
+        # held-out batches of eval_loader (network.Evaluator) under the weights of `_eval_weights` and logs eval/bits_per_dim,
+        # eval/bits_per_dim_single and eval/level_bits/{l}.  The attribute may be set after construction; None = nothing to evaluate.
+        self.interval_eval = util.interval_eval(self.hps)
+        self.eval_loader = eval_loader
+        self.last_eval = None
         # the per-step arithmetic (trainer.py:88-150)
         # (a single-rank run replays its step as one hipGraph launch after the first eager steps -- training.GraphedTrainStep; the
         # environment variable GLOWHIP_TRAIN_GRAPH=0 keeps every step eager; a failed capture falls back to the eager step by itself)
@@ -231,6 +253,14 @@ class Trainer:
                         self.graph.train()
                     for i in range(min(self.num_sample, img.shape[0])):
                         self.writer.add_image("sample/{}".format(i), img[i], self.step)
+                if self.interval_eval and self.eval_loader is not None and self.step % self.interval_eval == 0 and self.step > 0 \
+                        and self.rank == 0:
+                    with self._eval_weights():
+                        self.last_eval = res = Evaluator(self.graph).run(_EvalBatches(self, self.eval_loader))      # (eval mode and no_grad inside; train mode restored)
+                    self.writer.add_scalar('eval/bits_per_dim', res.bits_per_dim, self.step)
+                    self.writer.add_scalar('eval/bits_per_dim_single', res.bits_per_dim_single, self.step)
+                    for l, bits in enumerate(res.level_bits):
+                        self.writer.add_scalar('eval/level_bits/{}'.format(l), bits, self.step)
                 self.step += 1
                 done += 1
                 if max_steps is not None and done >= max_steps:
