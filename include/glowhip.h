@@ -316,8 +316,10 @@ int glowhip_plan_set_dequant_stream(glowhip_plan* plan, unsigned long long seed,
  *                c0 = j & 0xffffffff, c1 = j >> 32, c2 = c & 0xffffffff, c3 = ((s + 1) << 24) | ((c >> 32) & 0xffffff)
  *   stream     s = 0: the top latent; s = 1 + k: the k-th Split2d in DECODE order (the order of glowhip_plan_decode's eps).  Plans
  *              with more than 254 Split2d layers are refused; call < 2^56.  The top byte of c3 is never zero, the dequantisation
- *              stream's always is: the two share no counter under one seed.
- *   element    flat index in the contiguous (N, C, H, W) draw tensor
+ *              stream's always is: the two share no counter under one seed.  Streams 128 + leaf (128 .. 247) and 254 belong
+ *              to the posterior chain ("Posterior sampling" below: the proposal's draws and the accept test's uniform, call =
+ *              the chain's iteration); 248 .. 253 are unassigned.
+ *   element   flat index in the contiguous (N, C, H, W) draw tensor
  *   normals    words (w0, w1) give elements 0, 1 of the group, (w2, w3) elements 2, 3, by Box-Muller in fp32:
  *                u1 = ((w >> 9) + 0.5) * 2^-23, u2 = (w' >> 8) * 2^-24, r = sqrtf(-2 logf(u1)),
  *                even element = r cosf(2 pi u2), odd element = r sinf(2 pi u2);  |e| <= 5.77, never infinite
@@ -503,6 +505,59 @@ int glowhip_grad_accumulate(const glowhip_grad_seg* segs /* HOST, copied */, int
  * host sync, capturable.  grad_x is what glowhip_plan_decode_vjp takes: the two make the latent gradient of the objective. */
 int glowhip_restore_objective(const float* x, const float* target, const float* weight, const float* inv_wsum,
                               int N, int C, int H, int W, int pool, float* grad_x, float* loss_out, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Posterior sampling: a Metropolis-adjusted Langevin (MALA) chain over the latents of an inverse problem, one independent chain
+ * per sample, and the Welford moments of its images (csrc/posterior.hip; numpy restatement tests/posterior_oracle.py).
+ * THE definition.  Per sample n, theta = all latent leaves of that sample (leaf 0 = z, leaf 1 + k = eps[k] in decode order):
+ *     U(theta) = L(theta) + 1/2 ||theta||^2,   L = sum w (P decode(theta) - t)^2 / (2 sigma^2)
+ *              = glowhip_restore_objective with inv_wsum[n] = 1 / (2 sigma^2);   grad U = g + theta,  g = decode_vjp(grad_x)
+ *   proposal   with the per-sample step h (fp32, one rounding per operation, no fused multiply-add):
+ *                d = g + theta;   theta' = (theta - h d) + sqrtf(2 h) xi
+ *              xi = the sampler's N(0, 1) draw (above) at (seed, call = iteration, stream = 128 + leaf, element = flat index in
+ *              the contiguous (N, ...) leaf);   a = sum xi^2
+ *   at theta'  L', g' by decode, objective, decode_vjp;   d' = g' + theta';   b = sum (theta - theta' + h d')^2;
+ *              p = sum theta^2;   p' = sum theta'^2       (a, b, p, p': fp64 sums of fp64 terms of the fp32 elements, fixed order)
+ *   test       log alpha = (L - L') + 1/2 (p - p') + 1/2 a - b / (4 h), in fp64.  Accept iff L', b and p' are finite and
+ *              log(u) < log alpha, u = ((w0 >> 8) + 0.5) 2^-24, w0 = word 0 of group n of stream 254 at the same (seed, call).
+ *   accept     theta <- theta', g <- g', L <- L', image <- proposal image: element copies, the bits are preserved.  A rejected
+ *              sample's state is not written.  A rejection because L', b or p' is not finite bumps the sample's counter: a
+ *              proposal outside the fp16 pairs' range is refused on the device, never accepted as a wrong value.
+ *   adaptation only while iteration < burn_in:  h <- clamp(h exp(gamma (min(1, e^{log alpha}) - 0.574)), step_min, step_max),
+ *              gamma = adapt_rate / sqrt(iteration + 1), a non-finite proposal counting as probability 0; frozen from burn_in on.
+ *   streams    128 + leaf (at most 120 leaves: 128 .. 247) and 254 are disjoint from the sampler's 0 .. n_split of any plan with
+ *              fewer than 127 Split2d layers, which is every plan whose leaves these entries accept.
+ *   moments    per chain and pixel, of the CURRENT image: fold number c = (t - burn_in) / thin + 1 at every iteration t >= burn_in
+ *              with (t - burn_in) % thin == 0:  delta = x - mean;  mean += delta / c;  M2 += delta (x - mean)   (c == 1 starts
+ *              them: mean = x, M2 = 0, whatever the buffers held).  The count is not stored: it is a function of t.
+ * Segments: a HOST array copied into the kernel arguments, in the style of glowhip_grad_seg.  A segment is one pair {current,
+ * proposal} of contiguous (N, per) tensors.  Segments 0 .. n_leaves - 1 are the leaves, n_leaves .. 2 n_leaves - 1 their gradients
+ * in the same order, the rest (the image) is only copied on acceptance.  n_segs <= 32; any 4-byte alignment; any per.
+ * Launches: glowhip_mala_propose (theta', a), glowhip_mala_energy (b, p, p'), glowhip_mala_select (the decision, re-derived by every
+ * workgroup of a sample from the same partial sums in the same order; the copies; then, by the workgroup that arrives last at
+ * `ticket` -- an integer counter the call zeroes itself with a memset in front of the launch -- L, h, counts (2,N: accepted, non-finite), row
+ * `iteration` of hist (3,steps,N: energy U after the decision, accept flag, log alpha; iteration >= steps writes no row), call += 1
+ * on pos {seed, call} and *iteration += 1).  scratch: glowhip_mala_scratch_bytes, shared by the three.  glowhip_mala_init fills
+ * step[n] = step_size and inv_wsum[n] = 1 / (2 noise_std^2) (inv_wsum may be NULL).  glowhip_posterior_moments folds n elements at
+ * t = *iteration + iter_offset (-1 behind a select).  No floating-point atomics, no dependence on workgroup order, bitwise the same
+ * run to run; no allocation, no host sync, capturable: nothing per iteration comes from the host.
+ * GLOWHIP_EINVAL with a message and no device call: n_leaves < 1 or > 120, n_segs outside 2 n_leaves .. 32, N < 1, a NULL or
+ * misaligned pointer of a segment with per > 0 or of any other argument, a gradient segment whose per differs from its leaf's, a
+ * scratch that is too small, a step size, noise_std or clamp that is not finite or <= 0, thin < 1, burn_in < 0, steps < 1.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct glowhip_mala_seg { float* cur; float* prop; int64_t per; } glowhip_mala_seg;
+size_t glowhip_mala_scratch_bytes(const glowhip_mala_seg* segs /* HOST */, int n_segs, int n_leaves, int N);   /* 0: see last_error */
+int glowhip_mala_init(float* step, float* inv_wsum, int N, float step_size, float noise_std, glowhip_stream_t stream);
+int glowhip_mala_propose(const glowhip_mala_seg* segs /* HOST, copied */, int n_segs, int n_leaves, int N, const float* step,
+                         const unsigned long long* pos, void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+int glowhip_mala_energy(const glowhip_mala_seg* segs /* HOST, copied */, int n_segs, int n_leaves, int N, const float* step,
+                        void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+int glowhip_mala_select(const glowhip_mala_seg* segs /* HOST, copied */, int n_segs, int n_leaves, int N, float* loss,
+                        const float* loss_prop, float* step, unsigned long long* pos, long long* iteration, int32_t* counts,
+                        float* hist, int steps, int burn_in, float adapt_rate, float step_min, float step_max, unsigned int* ticket,
+                        const void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+int glowhip_posterior_moments(const float* image, float* mean, float* m2, const long long* iteration, int iter_offset, int burn_in,
+                              int thin, long n, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Top head: learned / class-conditional top prior + classifier (reference network/model.py:345-348, 362-379, 440-445,

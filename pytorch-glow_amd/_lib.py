@@ -89,6 +89,11 @@ class GradSeg(ctypes.Structure):
     _fields_ = [("grad", c_void_p), ("acc", c_void_p), ("n", ctypes.c_int64)]
 
 
+class MalaSeg(ctypes.Structure):
+    """Mirror of ``glowhip_mala_seg``."""
+    _fields_ = [("cur", c_void_p), ("prop", c_void_p), ("per", ctypes.c_int64)]
+
+
 class WgradGemm(ctypes.Structure):
     """Mirror of ``glowhip_wgrad_gemm`` (the testing hook ``glowhip_debug_wgrad``)."""
     _fields_ = [(n, c_void_p) for n in ("A", "B", "partial", "dw", "rowsum")] + [("a_bs", ctypes.c_int64), ("b_bs", ctypes.c_int64)] + \
@@ -134,6 +139,7 @@ class EvalState(ctypes.Structure):
 
 ACC_FIRST, ACC_ADD, ACC_FINISH = 0, 1, 2      # glowhip.h GLOWHIP_ACC_*
 ACC_MAX_SEGS = 16
+MALA_MAX_SEGS, MALA_MAX_LEAVES = 32, 120      # csrc/posterior.hip
 
 
 class TimingRecord(ctypes.Structure):
@@ -244,6 +250,13 @@ SIGNATURES = {
     "glowhip_optim_ema_swap": (c_int, [_P, _P, c_int, _P]),
     "glowhip_grad_accumulate": (c_int, [POINTER(GradSeg), c_int, c_int, c_float, _P]),
     "glowhip_restore_objective": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
+    "glowhip_mala_scratch_bytes": (c_size_t, [POINTER(MalaSeg), c_int, c_int, c_int]),
+    "glowhip_mala_init": (c_int, [_P, _P, c_int, c_float, c_float, _P]),
+    "glowhip_mala_propose": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "glowhip_mala_energy": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "glowhip_mala_select": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_float, c_float,
+                                    c_float, _P, _P, c_size_t, _P]),
+    "glowhip_posterior_moments": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_long, _P]),
     "glowhip_plan_set_head": (c_int, [_P, POINTER(HeadDesc)]),
     "glowhip_plan_head_state_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_bind_head": (c_int, [_P, POINTER(HeadIO)]),

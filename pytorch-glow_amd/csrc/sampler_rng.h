@@ -7,6 +7,8 @@
 //             c0 = j & 0xffffffff, c1 = j >> 32, c2 = c & 0xffffffff, c3 = ((s + 1) << 24) | ((c >> 32) & 0xffffff)
 //   stream  s = 0: the top latent; s = 1 + k: the k-th Split2d in DECODE order (the order glowhip_plan_decode reads eps);
 //             at most 254 splits, so s + 1 fits the top byte of c3
+//             s = 128 + leaf (128 .. 247): the posterior chain's proposal draws, s = 254: its accept test (posterior.hip; call =
+//             the chain's iteration; the entries refuse more than 120 leaves, so the two ranges never meet a plan's 0 .. n_split)
 //   element index = flat index in the contiguous (N, C, H, W) draw tensor
 // The top byte of c3 is never zero here and always zero in the dequantisation stream (its c3 is call >> 32, calls < 2^56): the two
 // never share a counter under one seed.

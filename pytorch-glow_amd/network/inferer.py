@@ -179,6 +179,55 @@ class Inferer:
         info = fit.run(exact=exact)
         return fit.latents(), info
 
+    def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
+                  seed=None, init=None, graph=True, adapt_rate=0.5):
+        """Draws from the posterior of the latents given ``measurement`` -- what else is consistent with it, and how sure the model
+        is of each pixel -- by a Metropolis-adjusted Langevin chain on the device (`network.posterior.LatentMALA`):
+
+            p(latents | measurement)  ~  exp(-(sum w (P decode(latents) - measurement)^2 / (2 noise_std^2) + 1/2 ||latents||^2))
+
+        with ``measurement`` / ``weight`` / ``pool`` as for `restore` and ``noise_std`` the standard deviation of the measurement
+        noise.  A single measurement (C,H,W, or a batch of one) with ``chains=K`` runs K independent chains on it; a batch of
+        measurements runs one chain each.  ``steps`` iterations, the first ``burn_in`` (None: half) adapting each chain's step from
+        ``step_size`` towards an acceptance rate of 0.574 (``adapt_rate``) and the rest at a frozen step; every ``thin``-th image
+        from ``burn_in`` on enters the per-pixel moments.  Returns ``(Latents, PosteriorInfo)``: the final states, and ``mean`` /
+        ``std`` per chain, ``pooled_mean`` / ``pooled_std`` over the chains, ``count``, ``accept_rate``, ``step_size``,
+        ``nonfinite_rejections``, the ``energy`` history, ``finite``, ``captured``, ``graph_error``.
+
+        ``seed``: the chain is a function of it (two calls with one seed give the same bits); None takes the process's sampler
+        position and advances it, as `resample_details` does.  ``init``: start `Latents`; None = ``encode_full`` of the measurement
+        (``pool>1``: of its pixel-repeated upsampling).  A model with a learned or class-conditional top prior raises ValueError:
+        the prior term assumes a standard-normal top latent.  A proposal whose decode is not finite (outside the fp16 pairs' range
+        of the product kernels) is rejected on the device and counted; a start whose own decode is not finite gives
+        ``finite=False`` and runs no iteration.  Nothing else raises; one host sync at the start state, one read at the end."""
+        from .model import sampler_position
+        from .posterior import LatentMALA
+        from .restore import check_prior_weight
+        check_prior_weight(self.graph, 1.0)
+        meas = self._batch(measurement).float().contiguous()
+        pool, chains = int(pool), int(chains)
+        if chains < 1 or (chains > 1 and meas.shape[0] != 1):
+            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {meas.shape[0]} runs one chain each)")
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
+        if init is None:
+            start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
+            init = self.encode_full(start)
+        if chains > 1:
+            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
+            meas, weight = rep(meas), None if weight is None else rep(weight)
+            if len(init) == 1:
+                init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        if seed is None:
+            seed, call = sampler_position(advance=True)
+            call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)
+        else:
+            seed, call = int(seed) & (2 ** 64 - 1), 0
+        chain = LatentMALA(self.graph, meas, weight=weight, pool=pool, noise_std=noise_std, init=init, steps=steps, burn_in=burn_in,
+                           thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call)
+        info = chain.run()
+        return chain.latents(), info
+
     def compute_attribute_delta(self, dataset, samples_per_batch=None, shuffle=True, num_workers=None, world=1, _exact=False):
         """deltaz[c] = mean latent of the images with attribute c - mean latent of those without (inferer.py:104-153).
         `dataset` yields dicts with 'x' (C,H,W) and 'y_onehot' (classes,).
