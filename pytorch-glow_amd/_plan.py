@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _capture, _lib
 from ._lib import LayerDesc, check, lib, ptr, stream_ptr
 
 
@@ -126,6 +126,30 @@ class FlowPlan:
     def still_valid(self) -> bool:
         """False when a parameter was re-allocated (module moved / parameter replaced): rebuild the plan."""
         return self._pointer_signature() == self._ptr_sig
+
+    def capture_signature(self, versions=False, family=False, pack=True, buffers=(), grads=False, accumulators=False):
+        """This plan's part of a captured graph's signature (`_capture.Capture`).  Always the parameter addresses; ``versions``: the
+        parameters' version counters (a graph without a pack inside); ``family``: the kernel family; ``pack``: the count of packs
+        that changed family (`pack`); ``buffers``: names of this plan's lazily (re-)allocated buffers the captured launches reach
+        (None while absent); ``grads``: the persistent gradient buckets and the count of eager backwards with NON-persistent
+        gradients, which rewrite the gradient job tables with pointers to their own temporaries; ``accumulators``: the buffers of a
+        step with gradient accumulation."""
+        sig = {"parameters": self._pointer_signature()}
+        if versions:
+            sig["versions"] = self._version_signature()
+        if family:
+            sig["family"] = self.family
+        if pack:
+            sig["pack_epoch"] = getattr(self, "_pack_epoch", 0)
+        for name in buffers:
+            sig[name] = _capture.address(getattr(self, name, None))
+        if grads:
+            pg = getattr(self, "_pgrad", None)
+            sig["grad_buckets"] = tuple(f.data_ptr() for f in pg[0]) if pg else ()
+            sig["grad_table_epoch"] = getattr(self, "_grad_table_epoch", 0)
+        if accumulators:
+            sig["accumulators"] = tuple(a.data_ptr() for a in self.grad_accumulators() or ())
+        return sig
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -265,9 +289,9 @@ class FlowPlan:
         self._packed_use = use
         # (a pack for the OTHER kernel family rebuilds the plan's host-side job tables with other contents and sizes -- and the copy
         # nodes of a CAPTURED pack read them through the addresses of capture time: a replay of the training step's graph after a
-        # re-run on the exact-fp32 family faulted on a host address.  Whoever replays a graph with this plan's pack inside compares
-        # this count -- training.GraphedTrainStep, GraphedForward.  Packs of the same family, whatever their image set, keep their
-        # tables in place: tests/test_gpu_fused.py test_captured_forward_survives_packs_of_other_use_masks.)
+        # re-run on the exact-fp32 family faulted on a host address.  A graph with this plan's pack inside watches this count
+        # (`capture_signature`).  Packs of the same family, whatever their image set, keep their tables in place:
+        # tests/test_gpu_fused.py test_captured_forward_survives_packs_of_other_use_masks.)
         key = self.family
         if key != getattr(self, "_pack_key", None):
             self._pack_key = key

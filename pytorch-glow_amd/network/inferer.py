@@ -141,6 +141,25 @@ class Inferer:
                 history.append(loss.detach())
         return lat.detach(), [float(v) for v in torch.stack(history).cpu()] if history else []
 
+    def _problem(self, measurement, weight, pool, init, chains=1):
+        """``(measurement batch, weight broadcast to it, pool, start latents)`` of `restore` / `posterior`: ``init`` None = ``encode_full``
+        of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement."""
+        meas = self._batch(measurement).float().contiguous()
+        pool = int(pool)
+        if chains < 1 or (chains > 1 and meas.shape[0] != 1):
+            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {meas.shape[0]} runs one chain each)")
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
+        if init is None:
+            start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
+            init = self.encode_full(start)
+        if chains > 1:
+            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
+            meas, weight = rep(meas), None if weight is None else rep(weight)
+            if len(init) == 1:
+                init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        return meas, weight, pool, init
+
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
                 graph=True, exact=False):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
@@ -167,13 +186,7 @@ class Inferer:
         the exact family (``fallback=1``); non-finite there too: ``finite=False``.  Nothing raises; one host sync, at the end."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
-        meas = self._batch(measurement).float().contiguous()
-        pool = int(pool)
-        if weight is not None:
-            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
-        if init is None:
-            start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
-            init = self.encode_full(start)
+        meas, weight, pool, init = self._problem(measurement, weight, pool, init)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
                         max_grad_norm=max_grad_norm, graph=graph)
         info = fit.run(exact=exact)
@@ -204,20 +217,7 @@ class Inferer:
         from .posterior import LatentMALA
         from .restore import check_prior_weight
         check_prior_weight(self.graph, 1.0)
-        meas = self._batch(measurement).float().contiguous()
-        pool, chains = int(pool), int(chains)
-        if chains < 1 or (chains > 1 and meas.shape[0] != 1):
-            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {meas.shape[0]} runs one chain each)")
-        if weight is not None:
-            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
-        if init is None:
-            start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
-            init = self.encode_full(start)
-        if chains > 1:
-            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
-            meas, weight = rep(meas), None if weight is None else rep(weight)
-            if len(init) == 1:
-                init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        meas, weight, pool, init = self._problem(measurement, weight, pool, init, chains=int(chains))
         if seed is None:
             seed, call = sampler_position(advance=True)
             call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)

@@ -6,11 +6,13 @@ state_dict keys and shapes equal the reference's, so its snapshot
 from __future__ import annotations
 
 import ctypes
+from functools import partial
 
 import torch
 import torch.nn as nn
 
 from .. import _lib
+from .._capture import Capture
 from .._lib import require_device_tensor
 from .._plan import PlanCache
 from ..misc import util
@@ -385,8 +387,9 @@ class GraphedSampler:
     `FlowPlan.sample` alone -- the top draw, the decode, the store and the one-thread launch that moves the device position --
     a single linear chain of kernels: no pack (the plan is packed and synchronised before the capture), no side stream.  Every
     replay draws at the position the previous one left: replay r after a capture at ``(seed, call)`` is
-    ``Glow.sample(seed=seed, call=call + r)`` bit for bit.  A changed parameter, a re-allocated one or a pack for the other
-    kernel family needs a new capture.  No range fall-back inside a graph."""
+    ``Glow.sample(seed=seed, call=call + r)`` bit for bit.  A changed parameter, a re-allocated one, a pack for the other
+    kernel family or an eager call with a larger batch on this plan (it re-allocates the workspace) needs a new capture: the replay
+    raises.  No range fall-back inside a graph."""
 
     def __init__(self, glow, n, y_onehot=None, eps_std=None, uint8=False, seed=None, call=0):
         assert not glow.training, "capture_sampler is the inference path: call glow.eval() first"
@@ -407,22 +410,10 @@ class GraphedSampler:
         self._head = plan.head_call(n, self.y_onehot) if glow._attach_head(plan) else None
         with torch.no_grad():
             plan.ensure_packed(use=plan.PACK_INFERENCE | plan.PACK_INVERSE)
-            side = torch.cuda.Stream(device=dev)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):          # warm-up on the capture stream: workspace, lazy inits
-                for _ in range(2):
-                    self._body()
-            torch.cuda.current_stream(dev).wait_stream(side)
-            torch.cuda.synchronize(dev)
-            self.pos.copy_(plan.sampler_position(self.seed, self._first))      # (the warm-up moved it)
-            torch.cuda.synchronize(dev)
-            plan.pack_sync()            # nothing of an earlier pack is left for the captured call to join
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph, stream=side):
-                self._body()
-        self._version = plan._version_signature()
-        self._pack_epoch = getattr(plan, "_pack_epoch", 0)
-        self._family = plan.family
+        # (no pack inside: the parameters' versions, the family and the pack count are watched, and the workspace every batch size of
+        # this image shape shares -- an eager call with a larger batch re-allocates it)
+        self._capture = Capture(plan, self._body, partial(plan.capture_signature, versions=True, family=True, buffers=("_ws",)), warmup=2)
+        self.pos.copy_(plan.sampler_position(self.seed, self._first))      # (the warm-up moved it; the recording ran nothing)
 
     def _body(self):
         plan = self.plan
@@ -439,16 +430,10 @@ class GraphedSampler:
 
     def __call__(self, y_onehot=None):
         """Replay; returns the static ``x`` (or ``x_u8``), valid until the next replay."""
-        plan = self.plan
-        if not plan.still_valid():
-            raise _lib.GlowHipError("capture_sampler: a parameter was re-allocated since the capture -- capture again")
-        if plan._version_signature() != self._version:
-            raise _lib.GlowHipError("capture_sampler: the parameters changed since the capture -- capture again")
-        if getattr(plan, "_pack_epoch", 0) != self._pack_epoch or plan.family != self._family:
-            raise _lib.GlowHipError("capture_sampler: the plan was packed for the other kernel family since the capture -- capture again")
+        self._capture.check("capture_sampler")
         if y_onehot is not None and y_onehot is not self.y_onehot:
             self.y_onehot.copy_(y_onehot)
-        self.graph.replay()
+        self._capture.replay()
         self._replays += 1
         return self.x_u8 if self.uint8 else self.x
 
@@ -459,8 +444,9 @@ class GraphedForward:
     Static buffers: ``x`` (copy the batch in, or pass one to __call__), ``noise``, ``z``, ``nll``.  What a replay runs: the
     dequantisation draw U(0, 2^-n_bits) with torch's Philox generator (registered with the graph, so every replay advances the
     stream like an eager draw), optionally `glowhip_plan_pack`, then the plan's launch list.  Parameters are read through their
-    live addresses, so updates between replays are seen (with ``repack=True``); re-allocating a parameter or changing the
-    kernel family needs a new capture.  No range fall-back inside a graph: look at ``nll`` (non-finite = flagged)."""
+    live addresses, so updates between replays are seen (with ``repack=True``); re-allocating a parameter, changing the
+    kernel family or an eager call with a larger batch on this plan (it re-allocates the workspace) needs a new capture: the replay
+    raises.  No range fall-back inside a graph: look at ``nll`` (non-finite = flagged)."""
 
     def __init__(self, glow, x, repack=True):
         assert not glow.training, "capture_forward is the inference path: call glow.eval() first"
@@ -476,19 +462,10 @@ class GraphedForward:
         self.nll = torch.empty(n, dtype=torch.float32, device=x.device)
         self._obj = torch.empty(n, dtype=torch.float32, device=x.device)
         plan.set_dequant_rng(0, False)
-        side = torch.cuda.Stream(device=x.device)
-        side.wait_stream(torch.cuda.current_stream(x.device))
-        with torch.no_grad(), torch.cuda.stream(side):          # warm-up on the capture stream: workspace, job tables, lazy inits
-            for _ in range(2):
-                self._body()
-        torch.cuda.current_stream(x.device).wait_stream(side)
-        torch.cuda.synchronize(x.device)
-        plan.pack_sync()            # (repack=False: nothing of an earlier pack is left for the captured calls to join)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(self.graph, stream=side):
-            self._body()
-        self._version = plan._version_signature()
-        self._pack_epoch = getattr(plan, "_pack_epoch", 0)
+        # repack=True: the captured pack reads the live parameters, so their versions are NOT watched (updates between replays are
+        # the point) but the pack count is; repack=False: the versions instead.  Either way the shared inference workspace.
+        self._capture = Capture(plan, self._body, partial(plan.capture_signature, versions=not repack, pack=repack, buffers=("_ws",)),
+                                warmup=2)
 
     def _body(self):
         self.noise.uniform_(0, 1. / 2 ** self.n_bits)
@@ -498,16 +475,8 @@ class GraphedForward:
         """Replay; returns the static (z, nll) (valid until the next replay)."""
         if x is not None and x is not self.x:
             self.x.copy_(x)
-        if not self.plan.still_valid():
-            raise _lib.GlowHipError("capture_forward: a parameter was re-allocated since the capture -- capture again")
-        if not self.repack and self.plan._version_signature() != self._version:
-            raise _lib.GlowHipError("capture_forward(repack=False): the parameters changed since the capture")
-        if self.repack and getattr(self.plan, "_pack_epoch", 0) != self._pack_epoch:
-            # (an eager pack for the OTHER kernel family rebuilds the plan's host-side job tables; the captured pack's copy nodes read
-            # them through the addresses of capture time -- a replay after a re-run on the exact-fp32 family faulted on a host
-            # address when the training step's graph first met this, training.GraphedTrainStep)
-            raise _lib.GlowHipError("capture_forward: the plan was packed for the other kernel family since the capture -- capture again")
-        self.graph.replay()
+        self._capture.check("capture_forward")
+        self._capture.replay()
         return self.z, self.nll
 
 

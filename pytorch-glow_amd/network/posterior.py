@@ -19,7 +19,7 @@ import torch
 
 from .. import _lib
 from .latents import Latents
-from .restore import check_prior_weight, restore_objective
+from .restore import LatentLoop, check_prior_weight
 
 
 @dataclass
@@ -54,7 +54,7 @@ def kept_count(steps, burn_in, thin):
     return 0 if steps <= burn_in else (steps - burn_in - 1) // thin + 1
 
 
-class LatentMALA:
+class LatentMALA(LatentLoop):
     """The device-resident chain.  Owns the static buffers (target, weights, inv_wsum), two sets {current, proposal} of latent
     leaves, latent gradients and image, the per-sample loss and step, the device words (the stream position {seed, call} and the
     iteration), the histories and the image moments.
@@ -73,31 +73,18 @@ class LatentMALA:
         burn_in = int(steps) // 2 if burn_in is None else int(burn_in)
         if init is None or steps < 1 or burn_in < 0 or thin < 1:
             raise ValueError("LatentMALA needs start latents (init), steps >= 1, burn_in >= 0 and thin >= 1")
-        self.glow, self.pool, self.steps, self.burn_in, self.thin = glow, int(pool), int(steps), burn_in, int(thin)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph)
+        self.burn_in, self.thin = burn_in, int(thin)
         self.noise_std, self.step_size, self.adapt_rate = float(noise_std), float(step_size), float(adapt_rate)
         self.step_min, self.step_max = (float(v) for v in step_clamp)
-        self.seed, self.call, self.want_graph = int(seed) & (2 ** 64 - 1), int(call), bool(graph)
-        meas = _lib.require_device_tensor(measurement, "measurement")
-        dev = self.device = meas.device
-        n, c, h, w = meas.shape
-        if self.pool < 1:
-            raise ValueError(f"pool = {pool}")
-        self.plan = plan = glow.flow.plan_for((c, h * self.pool, w * self.pool), dev)
-        if tuple(init.z.shape) != (n,) + plan.out_chw or len(init.eps) != plan.n_split:
-            raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
-        self.n = n
-        self.target = meas.clone()
-        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(meas).contiguous()
+        self.seed, self.call = int(seed) & (2 ** 64 - 1), int(call)
+        n, dev, plan = self.n, self.device, self.plan
         f32 = dict(dtype=torch.float32, device=dev)
-        self.inv_wsum = torch.empty(n, **f32)
+        self.inv_wsum = torch.empty(n, **f32)      # 1 / (2 noise_std^2), written by glowhip_mala_init (`reset`)
         self.step = torch.empty(n, **f32)
-        self.image = torch.empty((n,) + plan.in_chw, **f32)
         self.image_prop = torch.empty_like(self.image)
-        self.grad_x = torch.empty_like(self.image)
         self.loss = torch.zeros(n, **f32)
         self.loss_prop = torch.zeros(n, **f32)
-        start = init.to(dev).detach()
-        self._start = [t.float().contiguous().clone() for t in start.tensors()]
         self.leaves = [t.clone() for t in self._start]
         self.leaves_prop = [torch.zeros_like(t) for t in self._start]
         self.grads = [torch.zeros_like(t) for t in self._start]
@@ -122,21 +109,12 @@ class LatentMALA:
         if need == 0:
             _lib.check(-1)
         self.scratch = torch.zeros(need // 8, dtype=torch.float64, device=dev)
-        self._graph = None
-        self.graph_error = None
-        self._iterations = 0
-        self._dirty = True
+        self._reset_at = None        # the iteration count the last reset left: nothing to do again while it stands
         self.reset()
         self.finite = bool(torch.isfinite(self.loss).all())      # the start state's own loss (one read, before any iteration)
 
     # ------------------------------------------------------------------ the iteration
-    def _evaluate(self, leaves, image, loss, grads):
-        plan = self.plan
-        plan.decode(leaves[0], leaves[1:], out=image)
-        restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss)
-        plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
-
-    def _body(self):
+    def _body(self, captured=False):
         lib, check, ptr = _lib.lib(), _lib.check, _lib.ptr
         stream = _lib.stream_ptr(self.device)
         table = (self._segs, self._n_segs, self._n_leaves, self.n)
@@ -151,64 +129,12 @@ class LatentMALA:
         check(lib.glowhip_posterior_moments(ptr(self.image), ptr(self.mean), ptr(self.m2), ptr(self.iteration), -1, self.burn_in,
                                             self.thin, self.image.numel(), stream))
 
-    @torch.no_grad()
-    def step_eager(self):
-        """One iteration enqueued launch by launch."""
-        self._body()
-        self._iterations += 1
-        self._dirty = True
-
-    def _signature(self):
-        """What a captured iteration reaches through the plan and an eager call in between could have moved or rebuilt
-        (`restore.LatentFit._signature`)."""
-        plan = self.plan
-        ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else 0
-        return (plan._pointer_signature(), plan._version_signature(), plan.family, getattr(plan, "_pack_epoch", 0), ptr(plan.packed),
-                ptr(getattr(plan, "_ws", None)), ptr(getattr(plan, "_vjp_tape", None)), ptr(getattr(plan, "_vjp_ws", None)))
-
-    @torch.no_grad()
-    def capture(self):
-        """Record one iteration as a hipGraph by `restore.LatentFit.capture`'s rules: an eager iteration behind it, ``pack_sync()``
-        before, ``capture_error_mode="thread_local"``.  True on success; on failure the reason is kept in ``graph_error``, the
-        chain stays eager and nothing raises.  Nothing runs during a capture: the device words do not move."""
-        if self._iterations < 1:
-            raise _lib.GlowHipError("LatentMALA.capture: run one eager iteration first (lazy allocations, packed weights)")
-        dev = self.device
-        self._graph = None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize(dev)
-        self.plan.pack_sync()
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                self._body()
-        except Exception as e:       # capture is an optimisation of the host side only
-            self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
-            return False
-        self._graph = (graph, self._signature())
-        return True
-
-    @property
-    def captured(self):
-        return self._graph is not None and self._graph[1] == self._signature()
-
-    @torch.no_grad()
-    def step_captured(self):
-        """One iteration as one graph launch -- and nothing else: no upload, no host word."""
-        if not self.captured:
-            raise _lib.GlowHipError("LatentMALA.step_captured: no valid capture (capture() after an eager iteration; a parameter, a "
-                                    "workspace or the kernel family changed since)")
-        self._graph[0].replay()
-        self._iterations += 1
-        self._dirty = True
-
     # ------------------------------------------------------------------ the chain
     @torch.no_grad()
     def reset(self):
         """Back to the start: the start latents and their image, loss and gradient (evaluated eagerly), the initial step, the
         stream position (seed, call), iteration 0, empty histories, counters and moments.  Addresses stay: a capture stays valid."""
-        if not self._dirty:
+        if self._reset_at == self._iterations:
             return
         for p, s in zip(self.leaves, self._start):
             p.copy_(s)
@@ -218,7 +144,7 @@ class LatentMALA:
         for t in (self.iteration, self.ticket, self.counts, self.hist, self.mean, self.m2, self.loss_prop):
             t.zero_()
         self._evaluate(self.leaves, self.image, self.loss, self.grads)
-        self._dirty = False
+        self._reset_at = self._iterations
 
     def latents(self):
         """The current states (copies)."""
@@ -228,14 +154,7 @@ class LatentMALA:
         """The whole chain from the start state: `PosteriorInfo`; the final states are in `latents()`.  Nothing raises; one host
         read, at the end.  A start whose own loss is not finite runs no iteration (``finite=False``)."""
         self.reset()
-        replayed = False
-        if self.finite:
-            for it in range(self.steps):
-                if self.want_graph and it >= 1 and self.graph_error is None and (self.captured or self.capture()):
-                    self.step_captured()
-                    replayed = True
-                else:
-                    self.step_eager()
+        replayed = self._iterate() if self.finite else False
         n, steps = self.n, self.steps
         parts = [self.hist.reshape(-1), self.step, self.counts.view(torch.float32).reshape(-1), self.mean.reshape(-1), self.m2.reshape(-1)]
         flat = torch.cat(parts).cpu()      # the chain's one host read

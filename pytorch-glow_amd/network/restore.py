@@ -10,12 +10,14 @@ respect to the image, one launch), `FlowPlan.decode` / `decode_vjp` (the image a
 (`training.HipAdam`), whose weight decay IS the prior term: the update kernel adds prior_weight * p to the gradient, the gradient of
 prior_weight * 1/2 ||p||^2.  `LatentFit` runs them as a device-resident loop -- no autograd, no host sync, the histories on the
 device -- and, with ``graph=True``, as one hipGraph launch per iteration."""
+import contextlib
 from dataclasses import dataclass
 from typing import Optional
 
 import torch
 
 from .. import _lib
+from .._capture import Capture
 from ..training import HipAdam, HyperRing
 from .latents import Latents
 
@@ -69,17 +71,114 @@ def check_prior_weight(glow, prior_weight):
                          f"model's is not ({' / '.join(unusual)}); whitening the top latent is not implemented")
 
 
-class LatentFit:
-    """The device-resident loop.  Owns the static buffers (image, target, weights, inv_wsum), the latent leaves -- ``z`` and every
-    ``eps`` of the start `Latents`, copied -- their persistent gradient buffers (bound once as the leaves' ``.grad``) and a
-    `training.HipAdam` over the leaves with ``weight_decay = prior_weight``.
+class LatentLoop:
+    """What the device-resident loops over the latents of a measurement share -- `LatentFit` here, `posterior.LatentMALA`: the
+    problem (``target``, ``weight``, ``pool``, the plan of the full-resolution image, the start leaves ``_start``, the static
+    ``image`` and its gradient ``grad_x``), one evaluation of it, and an iteration as either Python-enqueued launches
+    (`step_eager`) or one hipGraph launch (`capture` once, after at least one eager iteration -- lazy allocations, packed weights
+    -- then `step_captured`), by the package's one capture protocol (`_capture.Capture`).  Same kernels and same bits either way.
 
-    One iteration: `FlowPlan.decode` into the static image; `restore_objective`; `FlowPlan.decode_vjp` into the gradient buffers;
+    A subclass supplies ``inv_wsum`` (the per-sample factor of the data term), ``_body(captured)`` (the iteration), `reset`, and,
+    where a replay has a host side, ``_capturing()`` / ``_signature()`` / ``_replay_host()``."""
+
+    def __init__(self, glow, measurement, weight, pool, init, steps, graph):
+        self.glow, self.pool, self.steps, self.want_graph = glow, int(pool), int(steps), bool(graph)
+        meas = _lib.require_device_tensor(measurement, "measurement")
+        dev = self.device = meas.device
+        n, c, h, w = meas.shape
+        if self.pool < 1:
+            raise ValueError(f"pool = {pool}")
+        self.plan = plan = glow.flow.plan_for((c, h * self.pool, w * self.pool), dev)
+        if tuple(init.z.shape) != (n,) + plan.out_chw or len(init.eps) != plan.n_split:
+            raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
+        self.n = n
+        self.target = meas.clone()
+        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(meas).contiguous()
+        self._start = [t.float().contiguous().clone() for t in init.to(dev).detach().tensors()]
+        self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
+        self.grad_x = torch.empty_like(self.image)
+        self._capture = None
+        self.graph_error = None
+        self._iterations = 0         # run since construction (a reset does not take the lazy allocations back)
+
+    # ------------------------------------------------------------------ the iteration
+    def _evaluate(self, leaves, image, loss, grads):
+        """`FlowPlan.decode` of ``leaves`` into ``image``; `restore_objective` (per-sample loss into ``loss``, its image gradient
+        into ``grad_x``); `FlowPlan.decode_vjp` of that into ``grads``."""
+        plan = self.plan
+        plan.decode(leaves[0], leaves[1:], out=image)
+        restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss)
+        plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
+
+    def _capturing(self):            # the context of a recording (the fit: its optimiser's)
+        return contextlib.nullcontext()
+
+    def _replay_host(self):          # what a replay does on the host before the graph launch (the fit: the hyper upload)
+        pass
+
+    def _signature(self):
+        """What a captured iteration reaches through the plan and an eager call in between could have moved or rebuilt: no pack is
+        inside, so the parameters' versions and the family count, and the workspaces of the decode and of its VJP."""
+        return self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
+
+    @torch.no_grad()
+    def step_eager(self):
+        """One iteration enqueued launch by launch."""
+        self._body(captured=False)
+        self._iterations += 1
+
+    @torch.no_grad()
+    def capture(self):
+        """Record one iteration as a hipGraph.  True on success; on failure the reason is kept in ``graph_error``, the loop stays
+        eager and nothing raises.  Nothing runs during a capture: the device words do not move."""
+        if self._iterations < 1:
+            raise _lib.GlowHipError(f"{type(self).__name__}.capture: run one eager iteration first (lazy allocations, packed weights)")
+        self._capture = None
+        try:
+            with self._capturing():
+                self._capture = Capture(self.plan, lambda: self._body(captured=True), self._signature)
+        except Exception as e:       # capture is an optimisation of the host side only
+            self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
+            return False
+        return True
+
+    @property
+    def captured(self):
+        return self._capture is not None and not self._capture.moved()
+
+    @torch.no_grad()
+    def step_captured(self):
+        """One iteration as one graph launch (and whatever the subclass uploads for it)."""
+        if not self.captured:
+            raise _lib.GlowHipError(f"{type(self).__name__}.step_captured: no valid capture (capture() after an eager iteration; a "
+                                    "parameter, a workspace or the kernel family changed since)")
+        self._replay_host()
+        self._capture.replay()
+        self._iterations += 1
+
+    def _iterate(self):
+        """``steps`` iterations from where the loop stands: the first eagerly, the others as replays when a graph is wanted and can
+        be had (a stale one is recorded again, silently; a failed recording leaves the loop eager).  True when any was a replay."""
+        replayed = False
+        for it in range(self.steps):
+            if self.want_graph and it >= 1 and self.graph_error is None and (self.captured or self.capture()):
+                self.step_captured()
+                replayed = True
+            else:
+                self.step_eager()
+        return replayed
+
+
+class LatentFit(LatentLoop):
+    """The device-resident fit.  Owns, beyond `LatentLoop`'s buffers, ``inv_wsum`` = 1 / sum w per sample, the latent leaves --
+    ``z`` and every ``eps`` of the start `Latents`, copied -- their persistent gradient buffers (bound once as the leaves'
+    ``.grad``) and a `training.HipAdam` over the leaves with ``weight_decay = prior_weight``.
+
+    One iteration: decode into the static image, objective, decode VJP into the gradient buffers (`LatentLoop._evaluate`);
     ``fused_step(0, max_grad_norm, skip_nonfinite=True)``; the iteration's losses and norm into row ``row`` of the device histories
-    and ``row += 1`` (a device word: the host keeps no count the device could disagree with).  `step_eager` enqueues that from
-    Python; `capture` records it once as a hipGraph (after at least one eager iteration: lazy allocations, packed weights) and
-    `step_captured` replays it, the per-step {lr, 1 - beta1^t, 1 - beta2^t} travelling through a `training.HyperRing`.  Same kernels
-    and same bits either way.  `run` is the whole fit: ``steps`` iterations from the start, ONE host read at the end.
+    and ``row += 1`` (a device word: the host keeps no count the device could disagree with).  A replay's per-step
+    {lr, 1 - beta1^t, 1 - beta2^t} travel through a `training.HyperRing`.  `run` is the whole fit: ``steps`` iterations from the
+    start, ONE host read at the end.
 
     The data term is normalised per sample, so each image of a batch is its own problem; what still couples the batch is the norm
     clip (``max_grad_norm``: one total norm) and the skip of an iteration whose norm is not finite (all samples or none).  A skipped
@@ -91,29 +190,16 @@ class LatentFit:
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
-        self.glow, self.pool, self.steps = glow, int(pool), int(steps)
-        self.lr, self.max_grad_norm, self.want_graph = float(lr), float(max_grad_norm or 0.0), bool(graph)
-        meas = _lib.require_device_tensor(measurement, "measurement")
-        dev = self.device = meas.device
-        n, c, h, w = meas.shape
-        if self.pool < 1:
-            raise ValueError(f"pool = {pool}")
-        self.plan = plan = glow.flow.plan_for((c, h * self.pool, w * self.pool), dev)
-        if tuple(init.z.shape) != (n,) + plan.out_chw or len(init.eps) != plan.n_split:
-            raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
-        self.target = meas.clone()
-        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(meas).contiguous()
+        super().__init__(glow, measurement, weight, pool, init, steps, graph)
+        self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
+        n, dev = self.n, self.device
         # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
         self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=(1, 2, 3)).clamp(min=1.0)
-        self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
-        self.grad_x = torch.empty_like(self.image)
         self.loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_hist = torch.zeros((self.steps, n), dtype=torch.float32, device=dev)
         self.norm_hist = torch.zeros(self.steps, dtype=torch.float32, device=dev)
         self.row = torch.zeros(1, dtype=torch.int64, device=dev)
-        start = init.to(dev).detach()
-        self._start = [t.float().clone() for t in start.tensors()]
         self.leaves = [t.clone().requires_grad_() for t in self._start]
         self.grads = [torch.zeros_like(t) for t in self._start]
         for p, g in zip(self.leaves, self.grads):
@@ -121,79 +207,24 @@ class LatentFit:
         self.optimizer = HipAdam(self.leaves, lr=self.lr, weight_decay=float(prior_weight or 0.0))
         self._token = object()       # "the gradients are this loop's persistent buffers" (HipAdam._chunk_table)
         self._ring = HyperRing(3, dev)
-        self._graph = None
-        self.graph_error = None
 
     # ------------------------------------------------------------------ the iteration
-    def _body(self, hyper_dev=None):
-        plan = self.plan
-        plan.decode(self.leaves[0], self.leaves[1:], out=self.image)
-        restore_objective(self.image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=self.loss)
-        plan.decode_vjp(self.image, self.grad_x, out=(self.grads[0], self.grads[1:]))
-        self.optimizer.fused_step(0.0, self.max_grad_norm, skip_nonfinite=True, grads_token=self._token, hyper_dev=hyper_dev,
-                                  norm_out=self.norm)
+    def _body(self, captured):
+        self._evaluate(self.leaves, self.image, self.loss, self.grads)
+        self.optimizer.fused_step(0.0, self.max_grad_norm, skip_nonfinite=True, grads_token=self._token,
+                                  hyper_dev=self._ring.words if captured else None, norm_out=self.norm)
         self.loss_hist.index_copy_(0, self.row, self.loss.view(1, -1))
         self.norm_hist.index_copy_(0, self.row, self.norm)
         self.row.add_(1).remainder_(self.steps)      # (a loop driven past `steps` iterations wraps around instead of writing outside)
 
-    @torch.no_grad()
-    def step_eager(self):
-        """One iteration enqueued launch by launch."""
-        self._body()
+    def _capturing(self):
+        return self.optimizer.capturing()
 
     def _signature(self):
-        """What a captured iteration reaches through the plan and the optimiser and an eager call in between could have moved or
-        rebuilt (`training.GraphedTrainStep._buffer_signature`)."""
-        plan, opt = self.plan, self.optimizer
-        ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else 0
-        return (plan._pointer_signature(), plan._version_signature(), plan.family, getattr(plan, "_pack_epoch", 0), ptr(plan.packed),
-                ptr(getattr(plan, "_ws", None)), ptr(getattr(plan, "_vjp_tape", None)), ptr(getattr(plan, "_vjp_ws", None)),
-                ptr(getattr(opt, "_partial", None)), ptr(getattr(opt, "_keep", None)))
+        return {**super()._signature(), **self.optimizer.capture_signature()}
 
-    @torch.no_grad()
-    def capture(self):
-        """Record one iteration as a hipGraph, by the rules `training.GraphedTrainStep` documents: an eager iteration behind it,
-        ``pack_sync()`` before, ``capture_error_mode="thread_local"``, the optimiser's step count restored after (the captured call
-        counted one on the host; nothing ran).  True on success; on failure the reason is kept in ``graph_error``, the loop stays
-        eager and nothing raises."""
-        opt, dev = self.optimizer, self.device
-        if opt._steps < 1:
-            raise _lib.GlowHipError("LatentFit.capture: run one eager iteration first (lazy allocations, packed weights)")
-        self._graph = None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize(dev)
-        self.plan.pack_sync()
-        steps = opt._steps
-        graph = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(graph, stream=side, capture_error_mode="thread_local"):
-                self._body(hyper_dev=self._ring.words)
-        except Exception as e:       # capture is an optimisation of the host side only
-            opt._table_token = None
-            self.graph_error = f"{type(e).__name__}: {str(e)[:300]}"
-            return False
-        finally:
-            opt._steps = steps
-            opt._publish_step()
-        self._graph = (graph, self._signature())
-        return True
-
-    @property
-    def captured(self):
-        return self._graph is not None and self._graph[1] == self._signature()
-
-    @torch.no_grad()
-    def step_captured(self):
-        """One iteration as one graph launch (and the 24-byte upload of its learning rate and bias corrections)."""
-        if not self.captured:
-            raise _lib.GlowHipError("LatentFit.step_captured: no valid capture (capture() after an eager iteration; a parameter, a "
-                                    "workspace or the kernel family changed since)")
-        opt = self.optimizer
-        opt._steps += 1
-        opt._publish_step()
-        self._ring.upload(opt.hyper_values(self.lr, opt._steps))
-        self._graph[0].replay()
+    def _replay_host(self):          # the step count and the 24-byte upload of the iteration's learning rate and bias corrections
+        self.optimizer.replay_step(self._ring, self.lr)
         torch.autograd.graph.increment_version(self.leaves)      # (written behind torch's back, as after fused_step)
 
     # ------------------------------------------------------------------ the fit
@@ -202,12 +233,7 @@ class LatentFit:
         """Back to the start latents with a fresh optimiser state and empty histories (addresses stay: a capture stays valid)."""
         for p, s in zip(self.leaves, self._start):
             p.copy_(s)
-        opt = self.optimizer
-        opt._ensure_state()
-        for buf in opt._flat or ():
-            buf.zero_()
-        opt._steps = 0
-        opt._publish_step()
+        self.optimizer.reset_state()
         self.row.zero_()
         self.loss_hist.zero_()
         self.norm_hist.zero_()
@@ -218,13 +244,7 @@ class LatentFit:
 
     def _run_once(self):
         self.reset()
-        replayed = False
-        for it in range(self.steps):
-            if self.want_graph and it >= 1 and self.graph_error is None and (self.captured or self.capture()):
-                self.step_captured()
-                replayed = True
-            else:
-                self.step_eager()
+        replayed = self._iterate()
         hist = torch.cat([self.loss_hist.reshape(-1), self.norm_hist]).cpu()      # the loop's one host read
         n = self.loss_hist.shape[1]
         return hist[:self.steps * n].view(self.steps, n), hist[self.steps * n:], replayed
@@ -251,3 +271,5 @@ class LatentFit:
         finally:
             plan.set_family(prev)
         return RestoreInfo(loss=loss, grad_norm=norm, finite=finite, captured=replayed, fallback=fallback, graph_error=self.graph_error)
+
+

@@ -21,6 +21,7 @@ from .parallel import micro_slices  # noqa: F401  (the one definition of the mic
 import ctypes
 
 from . import _lib
+from ._capture import Capture, address
 
 
 class _HipOptimizer(torch.optim.Optimizer):
@@ -313,6 +314,51 @@ class _HipOptimizer(torch.optim.Optimizer):
             self._ema_t = max(self._ema_t - 1, 0)
         self._publish_step()
 
+    # ---- the optimiser's side of a captured step (`GraphedTrainStep`, `network.restore.LatentFit`)
+    @contextlib.contextmanager
+    def capturing(self):
+        """Around the recording of a ``fused_step(hyper_dev=...)`` into a hipGraph.  The recorded call counted a step (and an EMA
+        update) on the host; nothing ran -- so both counts are put back, also when the recording failed half-way and the caller
+        carries on eagerly: the bias corrections of every later step hang on them.  A recording that raised also drops the table
+        token: a table half-built under it must not be trusted by the eager steps that follow."""
+        steps, ema_t = self._steps, self._ema_t
+        try:
+            yield self
+        except BaseException:
+            self._table_token = None
+            raise
+        finally:
+            self._steps, self._ema_t = steps, ema_t
+            self._publish_step()
+
+    def replay_step(self, ring, lr):
+        """The host side of one replay of a captured step: count it, and enqueue the upload of what the update kernel reads from
+        device memory -- {lr, 1 - beta1^step, 1 - beta2^step} and, with a Polyak average, the averaging weight -- through the
+        `HyperRing` the step was captured with."""
+        self._steps += 1
+        self._publish_step()
+        values = self.hyper_values(lr, self._steps)
+        if self.ema_decay:
+            values = values + (self.ema_weight(self._ema_t),)
+            self._ema_t += 1
+        ring.upload(values)
+
+    def capture_signature(self):
+        """The optimiser's part of a captured step's signature (`_capture.Capture`): the chunk table and the norm scratch, which
+        follow the gradients, the Polyak average and the pointer array to it (None without one; swap_averaged() moves neither)."""
+        ema = self._flat[2] if self.ema_decay and self._flat else None
+        return {"optimizer scratch": address(getattr(self, "_partial", None)), "optimizer table": address(getattr(self, "_keep", None)),
+                "ema": address(ema), "ema table": address(getattr(self, "_keep_ema", None))}
+
+    @torch.no_grad()
+    def reset_state(self):
+        """Zero moments and step count, in place: the addresses stay, so a captured step stays valid (the average is left alone)."""
+        self._ensure_state()
+        for buf in (self._flat or ())[:2]:
+            buf.zero_()
+        self._steps = 0
+        self._publish_step()
+
 
 class HipAdam(_HipOptimizer):
     KIND, SECOND = 0, "exp_avg_sq"
@@ -444,64 +490,24 @@ class GraphedTrainStep:
         self.loss_classes = torch.zeros((), dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         # (with a Polyak average the averaging weight of the step rides as a fourth word: glowhip_optim_step_ema_dev)
-        self.ema = bool(getattr(optimizer, "ema_decay", 0.0))
-        words = 4 if self.ema else 3
-        self._ring = HyperRing(words, dev, self.HYPER_SLOTS)
+        self._ring = HyperRing(4 if optimizer.ema_decay else 3, dev)
         self.hyper = self._ring.words
         self._params = [p for g in optimizer.param_groups for p in g["params"] if p.grad is not None]
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        torch.cuda.synchronize(dev)
-        glow.flow.plan_for(x).pack_sync()
-        steps, ema_t = optimizer._steps, optimizer._ema_t
-        self.graph = torch.cuda.CUDAGraph()
-        try:
-            # (thread_local: a DataLoader's pinning thread may touch the device while this thread captures)
-            with torch.no_grad(), torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-                self._body()
-        except BaseException:
-            optimizer._table_token = None     # (a table half-built under a failed capture must not be trusted by the eager steps that follow)
-            raise
-        finally:
-            # the captured call counted a step on the host; nothing ran -- also when the capture failed half-way and TrainLoop carries
-            # on eagerly: the bias corrections of every later step hang on this count
-            optimizer._steps, optimizer._ema_t = steps, ema_t
-            optimizer._publish_step()
         self.plan = glow.flow.plan_for(x)
-        self._had_ws = getattr(self.plan, "_ws", None) is not None
-        self._buffers = self._buffer_signature()
+        with optimizer.capturing():
+            self._capture = Capture(self.plan, self._body, self._signature)
 
-    HYPER_SLOTS = 4
-
-    def _upload_hyper(self, values):
-        self._ring.upload(values)
-
-    def _buffer_signature(self):
-        """Addresses of everything the captured launches reach through the plan and the optimiser and that an EAGER call in between
-        may re-allocate (the workspaces grow with the batch size and differ by kernel family; the optimiser's table and scratch
-        follow the gradients): a replay over a moved buffer would write through a stale pointer."""
-        plan, opt = self.plan, self.optimizer
-        ptr = lambda t: t.data_ptr() if isinstance(t, torch.Tensor) else 0
-        pg = getattr(plan, "_pgrad", None)
-        # (the inference workspace only if it existed at capture: one allocated later -- the first evaluation forward between two
-        # training steps -- is a buffer no captured launch reaches, and must not cost a recapture)
-        return (ptr(plan.packed), ptr(getattr(plan, "_ws", None)) if self._had_ws else 0, ptr(getattr(plan, "_tws", None)),
-                tuple(ptr(f) for f in pg[0]) if pg else (), ptr(getattr(opt, "_partial", None)), ptr(getattr(opt, "_keep", None)),
-                # the accumulators of a step with gradient accumulation (re-allocated with the buckets)
-                tuple(ptr(a) for a in plan.grad_accumulators() or ()) if self.accumulate > 1 else (),
-                # the Polyak average and the pointer array to it (0 without one); swap_averaged() moves neither
-                ptr(opt._flat[2]) if self.ema and opt._flat else 0, ptr(getattr(opt, "_keep_ema", None)),
-                # an eager pack of this plan for the OTHER kernel family since the capture (a re-run of an overflowed batch): it rebuilt
-                # the host-side job tables the captured pack's copy nodes read (measured: a replay after such a re-run faulted on a
-                # host address); packs of the same family keep them in place
-                getattr(plan, "_pack_epoch", 0),
-                # an eager backward with NON-persistent gradients (normal_flow + loss.backward() on this plan) since the capture: it
-                # rewrote the gradient job tables with pointers to its own temporary buffers
-                getattr(plan, "_grad_table_epoch", 0))
+    def _signature(self):
+        """Everything the captured launches reach through the plan and the optimiser and that an EAGER call in between may
+        re-allocate or rebuild (the workspaces grow with the batch size and differ by kernel family; the optimiser's table and
+        scratch follow the gradients): a replay over a moved buffer would write through a stale pointer.  The parameters' versions
+        are not in it -- the pack is inside the graph."""
+        return {**self.plan.capture_signature(buffers=("packed", "_ws", "_tws"), grads=True, accumulators=self.accumulate > 1),
+                **self.optimizer.capture_signature()}
 
     def valid(self):
         """False once a parameter or one of the buffers above moved: capture again (after an eager step)."""
-        return self.plan.still_valid() and self._buffer_signature() == self._buffers
+        return not self._capture.moved()
 
     def _body(self):
         for lo, hi in self._cuts:            # (one draw per micro-batch, in order: the eager step's; k = 1 is the whole buffer)
@@ -519,23 +525,15 @@ class GraphedTrainStep:
     def __call__(self, x, lr, y_onehot=None, y=None):
         """Replay with this batch (and its labels) and learning rate; returns (loss, gradient norm) as fresh device scalars."""
         self.optimizer._refuse_swapped("GraphedTrainStep")
-        if not self.valid():
-            raise _lib.GlowHipError("GraphedTrainStep: a parameter or a workspace was re-allocated since the capture -- capture again")
+        self._capture.check("GraphedTrainStep")
         if x is not self.x:
             self.x.copy_(x, non_blocking=True)
         if self.y_onehot is not None and y_onehot is not self.y_onehot:
             self.y_onehot.copy_(y_onehot, non_blocking=True)
         if self.y is not None and y is not self.y:
             self.y.copy_(y, non_blocking=True)
-        opt = self.optimizer
-        opt._steps += 1
-        opt._publish_step()
-        values = opt.hyper_values(lr, opt._steps)
-        if self.ema:
-            values = values + (opt.ema_weight(opt._ema_t),)
-            opt._ema_t += 1
-        self._upload_hyper(values)
-        self.graph.replay()
+        self.optimizer.replay_step(self._ring, lr)
+        self._capture.replay()
         torch.autograd.graph.increment_version(self._params)      # (the parameters changed behind torch's back, as after fused_step)
         out = torch.stack((self.loss, self.norm[0], self.loss_classes))      # (the static words are overwritten by the next replay)
         if self.glow.last_losses[1] is not None:

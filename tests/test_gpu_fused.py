@@ -579,6 +579,34 @@ def test_captured_forward_refuses_a_replay_after_a_pack_for_the_other_kernel_fam
         assert torch.equal(z2, ze) and torch.equal(n2, ne) and torch.isfinite(n2).all()
 
 
+def test_captured_forward_refuses_a_replay_over_a_reallocated_workspace():
+    """A plan serves every batch size of its image shape from ONE inference workspace, re-allocated when a larger batch comes
+    (`FlowPlan._workspace`): the captured launches hold the old address.  A replay after such an eager forward is refused -- with
+    an error, the stale graph is never launched -- and a new capture replays the eager forward."""
+    cfg = O.default_cfg(image_shape=(16, 16, 3), hidden_channels=64, K=1, L=2, batch=2)
+    sd = O.seeded_state_dict(cfg, seed=4)
+    glow = make_glow(cfg, sd, 2).eval()
+    g = torch.Generator().manual_seed(6)
+    x, big = dev(torch.rand(2, 3, 16, 16, generator=g)), dev(torch.rand(64, 3, 16, 16, generator=g))
+    with torch.no_grad():
+        gf = glow.capture_forward(x, repack=True)
+        plan = gf.plan
+        z, n = (t.clone() for t in gf())
+        ze, ne, _ = glow.normal_flow(x, None, noise=gf.noise.clone())      # (an eager call of the SAME batch moves nothing)
+        assert torch.equal(z, ze) and torch.equal(n, ne)
+        gf()
+        before = (plan._ws.data_ptr(), plan._ws.numel())
+        assert bool(torch.isfinite(glow.normal_flow(big, None)[1]).all())
+        assert plan._ws.numel() > before[1] and (plan._ws.data_ptr(), plan._ws.numel()) != before, "the larger batch did not re-allocate"
+        with pytest.raises(G._lib.GlowHipError, match="capture again") as err:
+            gf()
+        assert "workspace" in str(err.value)
+        gf2 = glow.capture_forward(x, repack=True)
+        z2, n2 = gf2()
+        ze, ne, _ = glow.normal_flow(x, None, noise=gf2.noise.clone())
+        assert torch.equal(z2, ze) and torch.equal(n2, ne) and torch.isfinite(n2).all()
+
+
 def test_eager_calls_after_a_capture_with_side_stream_pack():
     """plans with C > 128 fork part of their pack onto a side stream and consumers join through events.  Events
     last recorded INSIDE a capture cannot be waited for from an eager stream (hipErrorCapturedEvent): after

@@ -214,6 +214,37 @@ def test_captured_eager_and_hand_composed_loops_agree_bitwise(cid, pool):
         assert same_bits(loss, other[1]) and same_bits(norm, other[2]), f"{name}: histories differ from the captured loop's"
 
 
+def test_a_reallocated_workspace_costs_the_fit_a_recapture_not_an_error():
+    """The 8x8 linear-Gaussian model of tests/posterior_oracle.py, two measurements.  A fit whose later iterations ran as replays;
+    then an eager decode of a larger batch on the same plan, which re-allocates the inference workspace the recorded launches
+    reach.  The next `run` records the iteration again, silently -- ``captured``, no ``graph_error`` -- and its histories and
+    latents are the eager fit's, bit for bit."""
+    import posterior_oracle as P
+    case = P.linear_case("affine")
+    glow = make_glow(dict(cfg=case["cfg"], sd=case["sd"]))
+    as_batch = lambda a, n: dev(torch.from_numpy(a).float()).expand(n, *a.shape).contiguous()
+    zeros = lambda n: [dev(torch.zeros((n,) + s)) for s in case["shapes"]]
+    init = Latents(zeros(2)[0], zeros(2)[1:])
+    args = dict(weight=as_batch(case["weight"], 2), init=init, steps=3, lr=0.05, prior_weight=1e-3)
+    fit = LatentFit(glow, as_batch(case["target"], 2), graph=True, **args)
+    first = fit.run()
+    assert first.captured and first.graph_error is None and fit.captured
+    plan = fit.plan
+    before = (plan._ws.data_ptr(), plan._ws.numel())
+    big = plan.decode(zeros(64)[0], zeros(64)[1:])[0]
+    assert bool(torch.isfinite(big).all())
+    assert plan._ws.numel() > before[1] and (plan._ws.data_ptr(), plan._ws.numel()) != before, "the larger batch did not re-allocate"
+    assert not fit.captured, "the recorded iteration still counts as valid over a freed workspace"
+    info = fit.run()
+    assert info.captured and info.graph_error is None and info.finite and fit.captured
+    eager = LatentFit(glow, as_batch(case["target"], 2), graph=False, **args)
+    ref = eager.run()
+    assert not ref.captured and float(ref.loss[0].min()) > 0.0
+    assert same_bits(info.loss, ref.loss) and same_bits(info.grad_norm, ref.grad_norm)
+    assert same_bits(first.loss, ref.loss) and same_bits(first.grad_norm, ref.grad_norm)
+    assert all(same_bits(a, b) for a, b in zip(fit.latents().tensors(), eager.latents().tensors()))
+
+
 # ------------------------------------------------------------------------------------------------ 5. the prior term
 def test_prior_term_is_the_optimiser_oracles_weight_decay_step():
     """An all-zero weight leaves the prior term alone: loss 0, gradient norm 0, and ONE step is tests/optim_oracle.py's Adam step

@@ -402,6 +402,26 @@ def test_captured_sampler_replays_the_eager_positions(variant, uint8):
         gs()
 
 
+def test_captured_sampler_refuses_a_replay_over_a_reallocated_workspace():
+    """A plan serves every batch size of its image shape from ONE inference workspace, re-allocated when a larger batch comes
+    (`FlowPlan._workspace`): the captured launches hold the old address.  A replay after such an eager call is refused -- with an
+    error, the stale graph is never launched -- and a new capture replays the eager sample of its position."""
+    glow, _, _ = _glow("plain", image=(16, 16), L=2, K=1)
+    gs = glow.capture_sampler(2, eps_std=0.8, seed=21, call=4)
+    plan = gs.plan
+    assert torch.equal(gs(), glow.sample(2, eps_std=0.8, seed=21, call=4, safe=False))      # (an eager call of the SAME batch moves nothing)
+    assert torch.equal(gs(), glow.sample(2, eps_std=0.8, seed=21, call=5, safe=False))
+    before = (plan._ws.data_ptr(), plan._ws.numel())
+    big = glow.sample(64, eps_std=0.8, seed=21, call=6, safe=False)
+    assert bool(torch.isfinite(big).all())
+    assert plan._ws.numel() > before[1] and (plan._ws.data_ptr(), plan._ws.numel()) != before, "the larger batch did not re-allocate"
+    with pytest.raises(_lib.GlowHipError, match="capture again") as err:
+        gs()
+    assert "workspace" in str(err.value) and gs.last_position == (21, 5)
+    gs2 = glow.capture_sampler(2, eps_std=0.8, seed=21, call=7)
+    assert torch.equal(gs2(), glow.sample(2, eps_std=0.8, seed=21, call=7, safe=False))
+
+
 # ------------------------------------------------------------------------------------------------ 7. range
 def test_out_of_range_sample_is_flagged_or_rerun_exactly():
     cfg = O.default_cfg(image_shape=(16, 16, 3), hidden_channels=64, K=1, L=2, batch=4)
