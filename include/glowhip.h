@@ -730,6 +730,59 @@ typedef struct glowhip_wgrad_info {
 } glowhip_wgrad_info;
 int glowhip_debug_wgrad(const glowhip_wgrad_probe* d, glowhip_wgrad_info* info, glowhip_stream_t stream);
 
+/* Testing hook: ONE launch of an HBM-bound gradient kernel of the training sweep (csrc/backward.hip) on operands the caller lays
+ * out, through the launchers the backward sweep itself calls (csrc/backward.h) -- tests/test_gpu_bwd_kernels.py holds every route
+ * to fp64 with it.  Not part of the operator surface.  All pointers are device pointers except the probe itself; strides are in
+ * elements; the accumulators are fp64 and zeroed by the caller, as the sweep zeroes them.  Operands per op (unused ones NULL / 0):
+ *   COUPLING     launch_coupling_bwd: src = {hout, z2out, g2, e4, gld}, bs = {z_bs, g_bs}, dst = {gy2 (may be g2), gpre},
+ *                acc = {acc_b, acc_l}; C = Ch, C2 = Cout, flag = affine, acc_copies / acc_stride
+ *   SPLIT        launch_split_bwd: src = {hout, z2, NULL, e4, gld}, bs = {z_bs, g_bs}, dst = {gz2, gpre}, acc = {acc_b, acc_l}; C = Ch
+ *   ACT          launch_act_bwd: src = {h, NULL, NULL, e}, dst = {g (in place)}, acc = {acc_b, acc_l}; C = Cm
+ *   CHANMIX      launch_chanmix_bwd: src = {x, gy, bias, scale, matrix or NULL, gather_inv or NULL, add_part or NULL}, bs = {x_bs, g_bs},
+ *                dst = {gx (may be gy)}, acc = {acc_w, acc_b, acc_l}, acc_copies / acc_stride, add_scale and add = {C, MS, tiles, R, NI,
+ *                lpxt, H, W}; n_jobs (0..3) split-K reductions ride along: job[i] = {a = partial, out = dw, n = {splits, Mpad, Npad,
+ *                Mreal, Nreal, mode}} (WgradReduceJob)
+ *   PRIOR        launch_prior_bwd: src = {z, mean or NULL, logs or NULL, NULL, gld, gz_in or NULL}, bs = {ml_bs}, dst = {gz}, per
+ *   FLIP         launch_weight_flipT: src = {w}, dst = {wT}; C = Cout, C2 = Cin, ksize
+ *   LOGS_FROM_DW launch_logs_from_dw_batched on n_jobs jobs {a = w, b = dw, c = b, d = db (fp64), out, n = {rows, K}} (LogsJob)
+ *   FINALIZE     launch_gld_from_nll (src[0] = nll_grad -> dst[0] = gld, N values, factor inv), launch_sum_gld (gld -> acc[0], one
+ *                double) and launch_grad_finalize_batched on n_jobs jobs {a = acc, b = winv or NULL, out (NULL: the job is skipped),
+ *                n = {n, C, copies}, stride, add_mul} (GradJob)
+ * The two job tables are copied to the device by the hook, which waits for the stream before it returns in those two ops.
+ * Whatever a launcher refuses is refused here: GLOWHIP_EINVAL, no launch. */
+enum { GLOWHIP_BWD_COUPLING = 0, GLOWHIP_BWD_SPLIT = 1, GLOWHIP_BWD_ACT = 2, GLOWHIP_BWD_CHANMIX = 3, GLOWHIP_BWD_PRIOR = 4,
+       GLOWHIP_BWD_FLIP = 5, GLOWHIP_BWD_LOGS_FROM_DW = 6, GLOWHIP_BWD_FINALIZE = 7 };
+/* glowhip_bwd_info.kernel: the kernel that ran */
+enum { GLOWHIP_BWI_COUPLING4 = 1, GLOWHIP_BWI_COUPLING1 = 2,       /* k_coupling_bwd4 (16-byte accesses) / k_coupling_bwd */
+       GLOWHIP_BWI_SPLIT = 3,
+       GLOWHIP_BWI_ACT4 = 4, GLOWHIP_BWI_ACT1 = 5,                 /* k_act_bwd / k_act_bwd1 */
+       GLOWHIP_BWI_CHANMIX = 6, GLOWHIP_BWI_CHANMIX_REDUCE = 7, GLOWHIP_BWI_CHANMIX_WIDE = 8,
+       GLOWHIP_BWI_PRIOR = 9 };
+enum { GLOWHIP_BWD_MAX_JOBS = 8 };
+typedef struct glowhip_bwd_job {
+    const void* a; const void* b; const void* c; const void* d; void* out;
+    int32_t n[6];
+    int64_t stride; double add_mul;
+} glowhip_bwd_job;
+typedef struct glowhip_bwd_probe {
+    int32_t op, N, C, C2, HW, flag, ksize, acc_copies, n_jobs, reserved;
+    int64_t acc_stride, bs[2], per;
+    double inv;
+    float add_scale; int32_t add[8], reserved2;
+    const void* src[7]; void* dst[2]; double* acc[3];
+    glowhip_bwd_job job[GLOWHIP_BWD_MAX_JOBS];
+} glowhip_bwd_probe;
+typedef struct glowhip_bwd_info {
+    int32_t kernel, grid[3];
+    int32_t threads_per_channel;       /* the 16-byte kernels of COUPLING / ACT: HW / 4 */
+    int32_t w_lds, lds_bytes;          /* CHANMIX: matrix staged in LDS; dynamic LDS bytes of the launch */
+    int32_t mix_blocks, rblocks;       /* CHANMIX: pixel blocks; blocks per reduction job (k_chanmix_bwd_reduce) */
+    int32_t plain_stores;              /* CHANMIX: every pixel block owns its accumulator copy (stores, no atomics) */
+    int32_t launches;                  /* kernel launches made (2: the reductions did not ride along) */
+    int32_t reserved;
+} glowhip_bwd_info;
+int glowhip_debug_bwd(const glowhip_bwd_probe* d, glowhip_bwd_info* info, glowhip_stream_t stream);
+
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per
  * convolution).  Writes a NUL-terminated description into buf. */
 int glowhip_plan_describe(const glowhip_plan* plan, char* buf, size_t buf_bytes);

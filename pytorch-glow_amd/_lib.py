@@ -125,7 +125,33 @@ WGI_PS128, WGI_PS64, WGI_PS512 = 0x200, 0x201, 0x202
 WGI_PAIR64, WGI_PAIR128, WGI_TRIO64, WGI_TRIO128 = 0x300, 0x301, 0x400, 0x401
 WGI_SHIFT_EXPAND, WGI_DIRECT1, WGI_DIRECT3, WGI_HALF_TO_FLOAT = 0x500, 0x501, 0x503, 0x600
 
-EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256       # glowhip.h GLOWHIP_EVAL_MAX_*
+BWD_MAX_JOBS = 8      # glowhip.h GLOWHIP_BWD_MAX_JOBS
+
+
+class BwdJob(ctypes.Structure):
+    """Mirror of ``glowhip_bwd_job`` (the testing hook ``glowhip_debug_bwd``)."""
+    _fields_ = [(n, c_void_p) for n in ("a", "b", "c", "d", "out")] + [("n", c_int32 * 6), ("stride", ctypes.c_int64), ("add_mul", ctypes.c_double)]
+
+
+class BwdProbe(ctypes.Structure):
+    """Mirror of ``glowhip_bwd_probe``."""
+    _fields_ = [(n, c_int32) for n in ("op", "N", "C", "C2", "HW", "flag", "ksize", "acc_copies", "n_jobs", "reserved")] + \
+               [("acc_stride", ctypes.c_int64), ("bs", ctypes.c_int64 * 2), ("per", ctypes.c_int64), ("inv", ctypes.c_double),
+                ("add_scale", c_float), ("add", c_int32 * 8), ("reserved2", c_int32),
+                ("src", c_void_p * 7), ("dst", c_void_p * 2), ("acc", c_void_p * 3), ("job", BwdJob * BWD_MAX_JOBS)]
+
+
+class BwdInfo(ctypes.Structure):
+    """Mirror of ``glowhip_bwd_info``."""
+    _fields_ = [("kernel", c_int32), ("grid", c_int32 * 3)] + \
+               [(n, c_int32) for n in ("threads_per_channel", "w_lds", "lds_bytes", "mix_blocks", "rblocks", "plain_stores", "launches", "reserved")]
+
+
+# glowhip.h GLOWHIP_BWD_* (op) and GLOWHIP_BWI_* (kernel)
+BWD_COUPLING, BWD_SPLIT, BWD_ACT, BWD_CHANMIX, BWD_PRIOR, BWD_FLIP, BWD_LOGS_FROM_DW, BWD_FINALIZE = range(8)
+BWI_COUPLING4, BWI_COUPLING1, BWI_SPLIT, BWI_ACT4, BWI_ACT1, BWI_CHANMIX, BWI_CHANMIX_REDUCE, BWI_CHANMIX_WIDE, BWI_PRIOR = range(1, 10)
+
+EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256      # glowhip.h GLOWHIP_EVAL_MAX_*
 
 
 class EvalState(ctypes.Structure):
@@ -234,6 +260,7 @@ SIGNATURES = {
     "glowhip_plan_launch_counts": (c_int, [_P, c_char_p, c_size_t, c_int]),
     "glowhip_debug_force_tail_tile": (None, [c_int]),
     "glowhip_debug_wgrad": (c_int, [POINTER(WgradProbe), POINTER(WgradInfo), _P]),
+    "glowhip_debug_bwd": (c_int, [POINTER(BwdProbe), POINTER(BwdInfo), _P]),
     "glowhip_plan_tape_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_train_workspace_bytes": (c_size_t, [_P, c_int]),
     "glowhip_glow_forward_train": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, _P, _P, _P, c_int, _P, c_size_t, _P,

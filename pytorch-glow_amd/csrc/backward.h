@@ -4,6 +4,10 @@
 
 namespace glowhip {
 
+// What a launcher of the HBM-bound gradient kernels chose (testing: glowhip_debug_bwd fills a glowhip_bwd_info from it; the sweep
+// passes no pointer).  kernel: GLOWHIP_BWI_* of include/glowhip.h; the other fields as in glowhip_bwd_info.
+struct BwdLaunchInfo { int kernel, grid[3], threads_per_channel, w_lds, lds_bytes, mix_blocks, rblocks, plain_stores, launches; };
+
 struct CouplingBwdArgs {
     const float* hout;       // (N,Cout,HW) saved post-scale output of f.4
     const float* z2out; long z_bs;   // second half of the step output (z2')
@@ -16,7 +20,7 @@ struct CouplingBwdArgs {
     int N, Ch, Cout, HW, affine;
     int acc_copies = 1; long acc_stride = 0;   // as in ChanMixBwdArgs: workgroup b adds into copy b % acc_copies (k_coupling_bwd4)
 };
-int launch_coupling_bwd(const CouplingBwdArgs& a, hipStream_t s);
+int launch_coupling_bwd(const CouplingBwdArgs& a, hipStream_t s, BwdLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
 
 struct SplitBwdArgs {
     const float* hout;       // (N,2Ch,HW) saved prior conv output
@@ -27,10 +31,10 @@ struct SplitBwdArgs {
     double* acc_b; double* acc_l;
     int N, Ch, HW;
 };
-int launch_split_bwd(const SplitBwdArgs& a, hipStream_t s);
+int launch_split_bwd(const SplitBwdArgs& a, hipStream_t s, BwdLaunchInfo* info = nullptr);
 
 int launch_act_bwd(float* g, const float* h, const float* e, int N, int Cm, int HW, double* acc_b, double* acc_l,
-                   hipStream_t s);
+                   hipStream_t s, BwdLaunchInfo* info = nullptr);
 
 struct ChanMixBwdArgs {
     const float* x; long x_bs;       // step input
@@ -53,7 +57,7 @@ struct ChanMixBwdArgs {
 struct WgradReduceJobs;
 // reduce != null: the split-K reductions of the FlowStep's weight-gradient GEMMs run in the same launch (k_chanmix_bwd_reduce)
 // C > CHANMIX_BWD_NARROW_C: k_chanmix_bwd_wide (pixel blocks x channel slices) -- gx must not alias gy, add_part is refused
-int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce = nullptr);
+int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce = nullptr, BwdLaunchInfo* info = nullptr);
 constexpr int CHANMIX_BWD_NARROW_C = 192;      // k_chanmix_bwd's three C x 65 LDS arrays: 150 KB of a CU's 160
 constexpr int CHANMIX_BWD_MAX_C = 512;         // (the forward mixer's limit, launch_chanmix)
 constexpr int CHANMIX_BWD_WIDE_PX = 32;        // pixels of a k_chanmix_bwd_wide workgroup
@@ -105,7 +109,7 @@ int launch_split_inv_bwd(const SplitInvBwdArgs& a, hipStream_t s);
 int launch_relu_bwd(float* g, const float* h, const float* e, int N, int Cm, int HW, hipStream_t s);      // k_act_bwd without accumulators
 
 int launch_prior_bwd(const float* z, const float* mean, const float* logs, long ml_bs, const float* gld,
-                     const float* gz_in, float* gz, int N, long per, hipStream_t s);
+                     const float* gz_in, float* gz, int N, long per, hipStream_t s, BwdLaunchInfo* info = nullptr);
 int launch_weight_flipT(const float* w, float* wT, int Cout, int Cin, int ksize, hipStream_t s);
 int launch_wgrad_direct(const float* gy, const float* x, long x_bs, float* dw, int N, int Cin, int H, int W, int Cout,
                         int ksize, hipStream_t s);

@@ -166,18 +166,29 @@ __global__ void __launch_bounds__(256) k_coupling_bwd4(CouplingBwdArgs a) {
     }
 }
 
-int launch_coupling_bwd(const CouplingBwdArgs& a, hipStream_t s) {
+static void bwd_report(BwdLaunchInfo* info, int kernel, const dim3& grid) {
+    if (!info) return;
+    *info = BwdLaunchInfo{};
+    info->kernel = kernel; info->grid[0] = (int)grid.x; info->grid[1] = (int)grid.y; info->grid[2] = (int)grid.z; info->launches = 1;
+}
+
+int launch_coupling_bwd(const CouplingBwdArgs& a, hipStream_t s, BwdLaunchInfo* info) {
     if (a.N == 0) return GLOWHIP_OK;
     const bool pow2 = a.HW >= 4 && (a.HW & (a.HW - 1)) == 0;
     const bool aligned = a.g_bs % 4 == 0 && a.z_bs % 4 == 0 && ((size_t)a.g2 & 15) == 0 && ((size_t)a.gy2 & 15) == 0 &&
                          ((size_t)a.z2out & 15) == 0 && ((size_t)a.hout & 15) == 0 && ((size_t)a.gpre & 15) == 0;
     if (pow2 && aligned) {
-        hipLaunchKernelGGL(k_coupling_bwd4, dim3((unsigned)(((long)a.Ch * a.HW + 1023) / 1024), a.N), dim3(256), 0, s, a);
+        const dim3 grid((unsigned)(((long)a.Ch * a.HW + 1023) / 1024), a.N);
+        hipLaunchKernelGGL(k_coupling_bwd4, grid, dim3(256), 0, s, a);
         GH_LAUNCH_CHECK("k_coupling_bwd4");
+        bwd_report(info, GLOWHIP_BWI_COUPLING4, grid);
+        if (info) info->threads_per_channel = a.HW >> 2;
         return GLOWHIP_OK;
     }
-    hipLaunchKernelGGL(k_coupling_bwd, dim3(cdiv(a.HW, 256), a.Ch, a.N), dim3(256), 0, s, a);
+    const dim3 grid(cdiv(a.HW, 256), a.Ch, a.N);
+    hipLaunchKernelGGL(k_coupling_bwd, grid, dim3(256), 0, s, a);
     GH_LAUNCH_CHECK("k_coupling_bwd");
+    bwd_report(info, GLOWHIP_BWI_COUPLING1, grid);
     return GLOWHIP_OK;
 }
 
@@ -221,10 +232,12 @@ __global__ void __launch_bounds__(256) k_split_bwd(SplitBwdArgs a) {
     }
 }
 
-int launch_split_bwd(const SplitBwdArgs& a, hipStream_t s) {
+int launch_split_bwd(const SplitBwdArgs& a, hipStream_t s, BwdLaunchInfo* info) {
     if (a.N == 0) return GLOWHIP_OK;
-    hipLaunchKernelGGL(k_split_bwd, dim3(cdiv(a.HW, 256), a.Ch, a.N), dim3(256), 0, s, a);
+    const dim3 grid(cdiv(a.HW, 256), a.Ch, a.N);
+    hipLaunchKernelGGL(k_split_bwd, grid, dim3(256), 0, s, a);
     GH_LAUNCH_CHECK("k_split_bwd");
+    bwd_report(info, GLOWHIP_BWI_SPLIT, grid);
     return GLOWHIP_OK;
 }
 
@@ -337,16 +350,19 @@ int launch_half_to_float(const void* src_half, float* dst, int N, int R, int HW,
 }
 
 int launch_act_bwd(float* g, const float* h, const float* e, int N, int Cm, int HW, double* acc_b, double* acc_l,
-                   hipStream_t s) {
+                   hipStream_t s, BwdLaunchInfo* info) {
     if (N == 0) return GLOWHIP_OK;
     const bool pow2 = HW >= 4 && (HW & (HW - 1)) == 0;
+    const long per_img = (long)Cm * HW;
+    const dim3 grid = pow2 ? dim3((unsigned)((per_img + 1023) / 1024), N) : dim3(cdiv(HW, 256), Cm, N);
     if (pow2) {
-        const long per_img = (long)Cm * HW;
-        hipLaunchKernelGGL(k_act_bwd, dim3((unsigned)((per_img + 1023) / 1024), N), dim3(256), 0, s, g, h, e, Cm, HW, per_img, acc_b, acc_l);
+        hipLaunchKernelGGL(k_act_bwd, grid, dim3(256), 0, s, g, h, e, Cm, HW, per_img, acc_b, acc_l);
     } else {
-        hipLaunchKernelGGL(k_act_bwd1, dim3(cdiv(HW, 256), Cm, N), dim3(256), 0, s, g, h, e, Cm, HW, acc_b, acc_l);
+        hipLaunchKernelGGL(k_act_bwd1, grid, dim3(256), 0, s, g, h, e, Cm, HW, acc_b, acc_l);
     }
     GH_LAUNCH_CHECK("k_act_bwd");
+    bwd_report(info, pow2 ? GLOWHIP_BWI_ACT4 : GLOWHIP_BWI_ACT1, grid);
+    if (info && pow2) info->threads_per_channel = HW >> 2;
     return GLOWHIP_OK;
 }
 
@@ -666,7 +682,7 @@ __global__ void __launch_bounds__(256) k_chanmix_bwd_wide(ChanMixBwdArgs a) {
     }
 }
 
-int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce) {
+int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduceJobs* reduce, BwdLaunchInfo* info) {
     GH_REQUIRE(a.C > 0 && a.C <= CHANMIX_BWD_MAX_C, "chanmix backward: C=%d unsupported (1..%d)", a.C, CHANMIX_BWD_MAX_C);
     const long total = (long)a.N * a.HW;
     if (total == 0) return reduce ? launch_wgrad_reduce_batched(*reduce, s) : GLOWHIP_OK;
@@ -680,8 +696,14 @@ int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduce
         const size_t lds = chanmix_bwd_wide_lds(a.C, a.matrix != nullptr);
         if (lds > 32 * 1024)
             (void)hipFuncSetAttribute((const void*)k_chanmix_bwd_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_chanmix_bwd_wide, dim3(cdiv(total, CW_PX), cdiv(a.C, CW_SL)), dim3(256), lds, s, a);
+        const dim3 grid(cdiv(total, CW_PX), cdiv(a.C, CW_SL));
+        hipLaunchKernelGGL(k_chanmix_bwd_wide, grid, dim3(256), lds, s, a);
         GH_LAUNCH_CHECK("k_chanmix_bwd_wide");
+        bwd_report(info, GLOWHIP_BWI_CHANMIX_WIDE, grid);
+        if (info) {
+            info->lds_bytes = (int)lds; info->mix_blocks = (int)grid.x; info->plain_stores = (int)grid.x <= a.acc_copies;
+            info->launches = reduce && reduce->n > 0 ? 2 : 1;
+        }
         return GLOWHIP_OK;
     }
     size_t lds = (size_t)3 * a.C * CB_LD * sizeof(float);
@@ -697,8 +719,14 @@ int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduce
         for (int i = 0; i < reduce->n; ++i) rblocks = std::max(rblocks, (long)cdiv((long)reduce->job[i].Mreal * ((reduce->job[i].Nreal + 3) / 4), 256));
         if (lds > 32 * 1024)
             (void)hipFuncSetAttribute((const void*)k_chanmix_bwd_reduce, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_chanmix_bwd_reduce, dim3((unsigned)(mix_blocks + rblocks * reduce->n)), dim3(256), lds, s, b, *reduce, mix_blocks, (int)rblocks);
+        const dim3 grid((unsigned)(mix_blocks + rblocks * reduce->n));
+        hipLaunchKernelGGL(k_chanmix_bwd_reduce, grid, dim3(256), lds, s, b, *reduce, mix_blocks, (int)rblocks);
         GH_LAUNCH_CHECK("k_chanmix_bwd_reduce");
+        bwd_report(info, GLOWHIP_BWI_CHANMIX_REDUCE, grid);
+        if (info) {
+            info->w_lds = b.w_lds; info->lds_bytes = (int)lds; info->mix_blocks = mix_blocks; info->rblocks = (int)rblocks;
+            info->plain_stores = mix_blocks <= b.acc_copies;
+        }
         return GLOWHIP_OK;
     }
     if (reduce) GH_TRY(launch_wgrad_reduce_batched(*reduce, s));
@@ -706,6 +734,11 @@ int launch_chanmix_bwd(const ChanMixBwdArgs& a, hipStream_t s, const WgradReduce
         (void)hipFuncSetAttribute((const void*)k_chanmix_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_chanmix_bwd, dim3(mix_blocks), dim3(256), lds, s, b);
     GH_LAUNCH_CHECK("k_chanmix_bwd");
+    bwd_report(info, GLOWHIP_BWI_CHANMIX, dim3(mix_blocks));
+    if (info) {
+        info->w_lds = b.w_lds; info->lds_bytes = (int)lds; info->mix_blocks = mix_blocks; info->plain_stores = mix_blocks <= b.acc_copies;
+        info->launches = reduce && reduce->n > 0 ? 2 : 1;
+    }
     return GLOWHIP_OK;
 }
 
@@ -724,10 +757,12 @@ __global__ void __launch_bounds__(256) k_prior_bwd(const float* __restrict__ z, 
 }
 
 int launch_prior_bwd(const float* z, const float* mean, const float* logs, long ml_bs, const float* gld,
-                     const float* gz_in, float* gz, int N, long per, hipStream_t s) {
+                     const float* gz_in, float* gz, int N, long per, hipStream_t s, BwdLaunchInfo* info) {
     if (N == 0 || per == 0) return GLOWHIP_OK;
-    hipLaunchKernelGGL(k_prior_bwd, dim3(cdiv(per, 256), N), dim3(256), 0, s, z, mean, logs, ml_bs, gld, gz_in, gz, per);
+    const dim3 grid(cdiv(per, 256), N);
+    hipLaunchKernelGGL(k_prior_bwd, grid, dim3(256), 0, s, z, mean, logs, ml_bs, gld, gz_in, gz, per);
     GH_LAUNCH_CHECK("k_prior_bwd");
+    bwd_report(info, GLOWHIP_BWI_PRIOR, grid);
     return GLOWHIP_OK;
 }
 
@@ -855,3 +890,118 @@ int launch_gld_from_nll(const float* nll_grad, float* gld, int N, double inv, hi
 }
 
 }  // namespace glowhip
+
+using namespace glowhip;
+
+// a host job table on the device for one launch of the testing hook below
+template <class J>
+static int with_jobs_on_device(const J* host, int n, hipStream_t s, int (*launch)(const J*, int, const void*, hipStream_t), const void* extra) {
+    J* dev = nullptr;
+    GH_REQUIRE(hipMalloc((void**)&dev, sizeof(J) * n) == hipSuccess, "debug_bwd: no device memory for the job table");
+    int rc = hipMemcpy(dev, host, sizeof(J) * n, hipMemcpyHostToDevice) == hipSuccess ? launch(dev, n, extra, s) : GLOWHIP_ELAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == GLOWHIP_OK) rc = GLOWHIP_ELAUNCH;      // (the table outlives the launch)
+    (void)hipFree(dev);
+    return rc;
+}
+
+// Testing hook (include/glowhip.h): one launch of the launchers above on the caller's operands.  No second path: it decodes the
+// probe, calls the launcher the sweep calls, and copies what the launcher reported.
+extern "C" int glowhip_debug_bwd(const glowhip_bwd_probe* d, glowhip_bwd_info* info, glowhip_stream_t stream) {
+    GH_REQUIRE(d && info, "debug_bwd: null probe / info");
+    hipStream_t s = (hipStream_t)stream;
+    *info = glowhip_bwd_info{};
+    BwdLaunchInfo li{};
+    auto report = [&]() {
+        info->kernel = li.kernel; info->grid[0] = li.grid[0]; info->grid[1] = li.grid[1]; info->grid[2] = li.grid[2];
+        info->threads_per_channel = li.threads_per_channel; info->w_lds = li.w_lds; info->lds_bytes = li.lds_bytes;
+        info->mix_blocks = li.mix_blocks; info->rblocks = li.rblocks; info->plain_stores = li.plain_stores; info->launches = li.launches;
+    };
+    auto F = [&](int i) { return (const float*)d->src[i]; };
+    GH_REQUIRE(d->N >= 0 && d->n_jobs >= 0 && d->n_jobs <= GLOWHIP_BWD_MAX_JOBS, "debug_bwd: bad batch / job count");
+    switch (d->op) {
+    case GLOWHIP_BWD_COUPLING: {
+        GH_REQUIRE(d->C > 0 && d->HW > 0 && d->C2 == (d->flag ? 2 * d->C : d->C) && d->acc_copies >= 1, "debug_bwd: coupling shape");
+        GH_REQUIRE(d->src[0] && (d->src[1] || !d->flag) && d->src[2] && d->src[3] && (d->src[4] || !d->flag) && d->dst[0] && d->dst[1] && d->acc[0] && d->acc[1],
+                   "debug_bwd: coupling null operand / output");
+        CouplingBwdArgs a{F(0), F(1), (long)d->bs[0], F(2), (long)d->bs[1], (float*)d->dst[0], (float*)d->dst[1], F(3), F(4), d->acc[0], d->acc[1],
+                          d->N, d->C, d->C2, d->HW, d->flag};
+        a.acc_copies = d->acc_copies; a.acc_stride = (long)d->acc_stride;
+        GH_TRY(launch_coupling_bwd(a, s, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_BWD_SPLIT: {
+        GH_REQUIRE(d->C > 0 && d->HW > 0, "debug_bwd: split shape");
+        GH_REQUIRE(d->src[0] && d->src[1] && d->src[3] && d->src[4] && d->dst[0] && d->dst[1] && d->acc[0] && d->acc[1], "debug_bwd: split null operand / output");
+        const SplitBwdArgs a{F(0), F(1), (long)d->bs[0], (float*)d->dst[0], (long)d->bs[1], (float*)d->dst[1], F(3), F(4), d->acc[0], d->acc[1], d->N, d->C, d->HW};
+        GH_TRY(launch_split_bwd(a, s, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_BWD_ACT:
+        GH_REQUIRE(d->C > 0 && d->HW > 0 && d->src[0] && d->src[3] && d->dst[0] && d->acc[0] && d->acc[1], "debug_bwd: act arguments");
+        GH_TRY(launch_act_bwd((float*)d->dst[0], F(0), F(3), d->N, d->C, d->HW, d->acc[0], d->acc[1], s, &li));
+        report();
+        return GLOWHIP_OK;
+    case GLOWHIP_BWD_CHANMIX: {
+        GH_REQUIRE(d->HW > 0 && d->n_jobs <= 3 && d->acc_copies >= 1, "debug_bwd: chanmix shape");
+        GH_REQUIRE(d->src[0] && d->src[1] && d->src[2] && d->src[3] && !(d->src[4] && d->src[5]) && d->dst[0] && (d->acc[0] || !d->src[4]) && d->acc[1] && d->acc[2],
+                   "debug_bwd: chanmix null operand / output");
+        ChanMixBwdArgs a{};
+        a.x = F(0); a.x_bs = (long)d->bs[0]; a.gy = F(1); a.gx = (float*)d->dst[0]; a.g_bs = (long)d->bs[1]; a.bias = F(2); a.scale = F(3);
+        a.matrix = F(4); a.gather_inv = (const int32_t*)d->src[5];
+        a.acc_w = d->acc[0]; a.acc_b = d->acc[1]; a.acc_l = d->acc[2];
+        a.N = d->N; a.C = d->C; a.HW = d->HW; a.acc_copies = d->acc_copies; a.acc_stride = (long)d->acc_stride;
+        if (d->src[6]) {
+            const int32_t* g = d->add;      // C, MS, tiles, R, NI, lpxt, H, W
+            GH_REQUIRE(g[0] > 0 && g[0] <= d->C && g[1] >= 1 && g[2] >= 1 && g[3] >= 1 && (g[3] & (g[3] - 1)) == 0 && g[4] >= 1 && g[5] >= 0 &&
+                       g[7] >= 1 && (g[7] & (g[7] - 1)) == 0 && g[6] * g[7] == d->HW, "debug_bwd: add_part geometry");
+            a.add_part = F(6); a.add_scale = d->add_scale;
+            a.add_C = g[0]; a.add_MS = g[1]; a.add_tiles = g[2]; a.add_R = g[3]; a.add_NI = g[4]; a.add_lpxt = g[5]; a.add_H = g[6]; a.add_W = g[7];
+        }
+        WgradReduceJobs rj{};
+        rj.n = d->n_jobs;
+        for (int i = 0; i < rj.n; ++i) {
+            const glowhip_bwd_job& j = d->job[i];
+            GH_REQUIRE(j.a && j.out && j.n[0] >= 1 && j.n[3] >= 1 && j.n[4] >= 1 && j.n[3] <= j.n[1] && j.n[4] <= j.n[2] && j.n[2] % 64 == 0, "debug_bwd: reduce job %d", i);
+            rj.job[i] = WgradReduceJob{(const float*)j.a, (float*)j.out, j.n[0], j.n[1], j.n[2], j.n[3], j.n[4], j.n[5]};
+        }
+        GH_TRY(launch_chanmix_bwd(a, s, rj.n ? &rj : nullptr, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_BWD_PRIOR:
+        GH_REQUIRE(d->per > 0 && d->src[0] && d->src[4] && d->dst[0], "debug_bwd: prior arguments");
+        GH_TRY(launch_prior_bwd(F(0), F(1), F(2), (long)d->bs[0], F(4), F(5), (float*)d->dst[0], d->N, (long)d->per, s, &li));
+        report();
+        return GLOWHIP_OK;
+    case GLOWHIP_BWD_FLIP:
+        GH_REQUIRE(d->C > 0 && d->C2 > 0 && (d->ksize == 1 || d->ksize == 3) && d->src[0] && d->dst[0], "debug_bwd: flipT arguments");
+        return launch_weight_flipT(F(0), (float*)d->dst[0], d->C, d->C2, d->ksize, s);
+    case GLOWHIP_BWD_LOGS_FROM_DW: {
+        GH_REQUIRE(d->n_jobs >= 1, "debug_bwd: no jobs");
+        LogsJob jobs[GLOWHIP_BWD_MAX_JOBS];
+        for (int i = 0; i < d->n_jobs; ++i) {
+            const glowhip_bwd_job& j = d->job[i];
+            GH_REQUIRE(j.a && j.b && j.c && j.d && j.out && j.n[0] >= 1 && j.n[0] <= 512 && j.n[1] >= 1, "debug_bwd: logs job %d", i);
+            jobs[i] = LogsJob{(const float*)j.a, (const float*)j.b, (const float*)j.c, (const double*)j.d, (float*)j.out, j.n[0], j.n[1]};
+        }
+        return with_jobs_on_device<LogsJob>(jobs, d->n_jobs, s,
+            [](const LogsJob* dev, int n, const void*, hipStream_t st) { return launch_logs_from_dw_batched(dev, n, st); }, nullptr);
+    }
+    case GLOWHIP_BWD_FINALIZE: {
+        GH_REQUIRE(d->n_jobs >= 1 && d->src[0] && d->dst[0] && d->acc[0], "debug_bwd: finalize arguments");
+        GradJob jobs[GLOWHIP_BWD_MAX_JOBS];
+        for (int i = 0; i < d->n_jobs; ++i) {
+            const glowhip_bwd_job& j = d->job[i];
+            GH_REQUIRE(!j.out || (j.a && j.n[0] >= 1 && j.n[2] >= 1 && (!j.b || (j.n[1] >= 1 && j.n[0] == j.n[1] * j.n[1]))), "debug_bwd: finalize job %d", i);
+            jobs[i] = GradJob{(const double*)j.a, (float*)j.out, j.n[0], j.add_mul, (const float*)j.b, j.n[1], j.n[2], (long)j.stride};
+        }
+        GH_TRY(launch_gld_from_nll(F(0), (float*)d->dst[0], d->N, d->inv, s));
+        GH_TRY(launch_sum_gld((const float*)d->dst[0], d->N, d->acc[0], s));
+        return with_jobs_on_device<GradJob>(jobs, d->n_jobs, s,
+            [](const GradJob* dev, int n, const void* gsum, hipStream_t st) { return launch_grad_finalize_batched(dev, n, (const double*)gsum, st); }, d->acc[0]);
+    }
+    }
+    GH_REQUIRE(false, "debug_bwd: unknown op %d", d->op);
+}
