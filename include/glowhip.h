@@ -783,6 +783,55 @@ typedef struct glowhip_bwd_info {
 } glowhip_bwd_info;
 int glowhip_debug_bwd(const glowhip_bwd_probe* d, glowhip_bwd_info* info, glowhip_stream_t stream);
 
+/* Testing hook: ONE launch of an exact-fp32 convolution kernel (csrc/conv_mfma.hip, conv_mfma_first.hip, conv_direct.hip) on operands
+ * the caller lays out, through the launchers the plan itself calls -- tests/test_gpu_conv_kernels.py holds every instance to fp64
+ * with it.  Not part of the operator surface.  All pointers are device pointers except the probe itself; strides are in elements.
+ *   WIDE    the image of w (Cout, Cin, k, k) is built by the plan's REPACK_WIDE job (launch_pack_batched) into `image`, then
+ *           launch_conv_mfma_wide(x, x_bs, image, post_bias, post_scale, y, N, Cin, H, W, Cout, ksize, stream, relu, scratch,
+ *           scratch_floats); scratch may be NULL (no split-K).  transposed (ksize 1 only): w is the forward weight (Cin, Cout), which
+ *           is the K-major image of the input-gradient GEMM as it stands: passed to the launcher directly, as the training sweep does
+ *   FIRST   the image is built by the REPACK_FIRST job with fold_bias / fold_logs (both or neither) and `transposed` (w is then the
+ *           forward weight (Cin, Cout, 3, 3) of which this is the input-gradient convolution), then launch_conv_mfma_first(x, x_bs,
+ *           image, image + 9 Cin Cout, y, N, Cin, H, W, Cout, stream, relu)
+ *   DIRECT  launch_conv_direct on w in its reference layout with bias, post_bias, post_logs, post_scale (each may be NULL)
+ *   TAIL    conv_mfma_tail_pack(w, Cin, Cout, paired, image) -- paired as the mode implies -- then launch_conv_mfma_tail on a
+ *           TailConvArgs of x, x_bs, image, bias, scale = post_scale, mode (the TailMode values 0..6 of csrc/conv_mfma.h: PLAIN,
+ *           AFFINE_FWD, AFFINE_REV, ADD_FWD, ADD_REV, SPLIT_FWD, SPLIT_REV), z2_in / z2_out with their strides, zeros (NULL or
+ *           >= 16 bytes of zeros, 16-byte aligned), hout (NULL or (N, Cout, HW)) and an empty rng; the forced tile and the split /
+ *           no-DMA switches of glowhip_debug_force_tail_tile hold as they do for a plan.  acc (NULL, or 2 N 64-bit words): zeroed
+ *           with launch_zero_acc before the launch and turned into term[n] (N floats) with launch_finalize after it, as
+ *           glowhip_gaussian_logp and the plan do it
+ * A NULL `image` in WIDE / FIRST / TAIL launches nothing: info->image_bytes alone is filled, with what the plan allocates for that
+ * image.  The hook waits for the stream in WIDE / FIRST (its one-job table is freed before it returns).  Whatever a launcher refuses
+ * is refused here: GLOWHIP_EINVAL, no launch. */
+enum { GLOWHIP_CONV_WIDE = 0, GLOWHIP_CONV_FIRST = 1, GLOWHIP_CONV_DIRECT = 2, GLOWHIP_CONV_TAIL = 3 };
+/* glowhip_conv_info.kernel: the kernel that ran */
+enum { GLOWHIP_CVI_WIDE = 1,        /* k_conv_wide<ksize, tile, tile, 32>, with k_splitk_finish behind it when splits > 1 */
+       GLOWHIP_CVI_GEMM_GLDS = 2,   /* k_gemm_glds */
+       GLOWHIP_CVI_FIRST = 3,       /* k_conv_first<tile, W> */
+       GLOWHIP_CVI_DIRECT = 4,      /* k_conv_direct<ksize, 8> */
+       GLOWHIP_CVI_TAIL = 5,        /* k_conv_tail<mb, ...> (register-staged), tile pixels per workgroup */
+       GLOWHIP_CVI_TAIL_DMA = 6 };  /* k_conv_tail_dma<1, ..., W> */
+typedef struct glowhip_conv_probe {
+    int32_t op, N, Cin, H, W, Cout, ksize, relu, transposed, mode;
+    int64_t x_bs, scratch_floats, z2_in_bs, z2_out_bs;
+    const float* x; const float* w; const float* bias; const float* post_bias; const float* post_logs; const float* post_scale;
+    const float* fold_bias; const float* fold_logs;
+    float* image; float* scratch; float* y;
+    const float* z2_in; float* z2_out; float* hout; const float* zeros; void* acc; float* term;      /* TAIL */
+} glowhip_conv_probe;
+typedef struct glowhip_conv_info {
+    int32_t kernel, ksize;
+    int32_t tile;                      /* WIDE: 64 / 128 (k_gemm_glds: 128); FIRST: pixels per workgroup BN; TAIL: TP */
+    int32_t splits;                    /* WIDE: split-K slices S (1: none); TAIL: waves that share the reduction, WK */
+    int32_t mb;                        /* FIRST: output-channel tiles per workgroup MB; TAIL: MT (grid[1] holds the rest) */
+    int32_t grid[3];
+    int32_t launches;                  /* kernel launches the launcher made (2: k_splitk_finish followed) */
+    int32_t paired;                    /* TAIL: the paired row map */
+    int64_t image_bytes;
+} glowhip_conv_info;
+int glowhip_debug_conv(const glowhip_conv_probe* d, glowhip_conv_info* info, glowhip_stream_t stream);
+
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per
  * convolution).  Writes a NUL-terminated description into buf. */
 int glowhip_plan_describe(const glowhip_plan* plan, char* buf, size_t buf_bytes);

@@ -151,6 +151,25 @@ class BwdInfo(ctypes.Structure):
 BWD_COUPLING, BWD_SPLIT, BWD_ACT, BWD_CHANMIX, BWD_PRIOR, BWD_FLIP, BWD_LOGS_FROM_DW, BWD_FINALIZE = range(8)
 BWI_COUPLING4, BWI_COUPLING1, BWI_SPLIT, BWI_ACT4, BWI_ACT1, BWI_CHANMIX, BWI_CHANMIX_REDUCE, BWI_CHANMIX_WIDE, BWI_PRIOR = range(1, 10)
 
+class ConvProbe(ctypes.Structure):
+    """Mirror of ``glowhip_conv_probe`` (the testing hook ``glowhip_debug_conv``)."""
+    _fields_ = [(n, c_int32) for n in ("op", "N", "Cin", "H", "W", "Cout", "ksize", "relu", "transposed", "mode")] + \
+               [(n, ctypes.c_int64) for n in ("x_bs", "scratch_floats", "z2_in_bs", "z2_out_bs")] + \
+               [(n, c_void_p) for n in ("x", "w", "bias", "post_bias", "post_logs", "post_scale", "fold_bias", "fold_logs", "image", "scratch", "y",
+                                        "z2_in", "z2_out", "hout", "zeros", "acc", "term")]
+
+
+class ConvInfo(ctypes.Structure):
+    """Mirror of ``glowhip_conv_info``."""
+    _fields_ = [(n, c_int32) for n in ("kernel", "ksize", "tile", "splits", "mb")] + [("grid", c_int32 * 3), ("launches", c_int32), ("paired", c_int32),
+                                                                                     ("image_bytes", ctypes.c_int64)]
+
+
+# glowhip.h GLOWHIP_CONV_* (op), GLOWHIP_CVI_* (kernel) and the TailMode values of csrc/conv_mfma.h
+CONV_WIDE, CONV_FIRST, CONV_DIRECT, CONV_TAIL = range(4)
+CVI_WIDE, CVI_GEMM_GLDS, CVI_FIRST, CVI_DIRECT, CVI_TAIL, CVI_TAIL_DMA = range(1, 7)
+TAIL_PLAIN, TAIL_AFFINE_FWD, TAIL_AFFINE_REV, TAIL_ADD_FWD, TAIL_ADD_REV, TAIL_SPLIT_FWD, TAIL_SPLIT_REV = range(7)
+
 EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256      # glowhip.h GLOWHIP_EVAL_MAX_*
 
 
@@ -261,6 +280,7 @@ SIGNATURES = {
     "glowhip_debug_force_tail_tile": (None, [c_int]),
     "glowhip_debug_wgrad": (c_int, [POINTER(WgradProbe), POINTER(WgradInfo), _P]),
     "glowhip_debug_bwd": (c_int, [POINTER(BwdProbe), POINTER(BwdInfo), _P]),
+    "glowhip_debug_conv": (c_int, [POINTER(ConvProbe), POINTER(ConvInfo), _P]),
     "glowhip_plan_tape_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_train_workspace_bytes": (c_size_t, [_P, c_int]),
     "glowhip_glow_forward_train": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, _P, _P, _P, c_int, _P, c_size_t, _P,

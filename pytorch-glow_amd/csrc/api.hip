@@ -3,6 +3,7 @@
 #include <stdio.h>
 
 #include "kernels.h"
+#include "conv_mfma.h"
 #include "invconv_lu.h"
 #include "debug_switches.h"
 
@@ -170,6 +171,110 @@ int glowhip_gaussian_logp(const float* x, long x_stride, const float* mean, cons
     GH_TRY(launch_zero_acc(acc, N, s));
     GH_TRY(launch_gaussian_logp(x, x_stride, mean, logs, ml_stride, N, C, HW, acc, s));
     return launch_finalize(in, acc, nullptr, 1.0, 0.0, 1.0, out, nullptr, N, s);
+}
+
+// one weight image through the plan's own image kernel (launch_pack_batched on a one-job table); waits for the stream, since the
+// table is freed here
+static int debug_conv_image(RepackJob r, float* image, hipStream_t s) {
+    RepackJob* dev = nullptr;
+    GH_REQUIRE(hipMalloc((void**)&dev, sizeof(RepackJob)) == hipSuccess, "debug_conv: no device memory for the job table");
+    const int n_kind[4] = {1, 0, 0, 0};
+    int rc = hipMemcpy(dev, &r, sizeof(RepackJob), hipMemcpyHostToDevice) == hipSuccess
+                 ? launch_pack_batched(nullptr, 0, dev, n_kind, 0, image, s, s) : GLOWHIP_ELAUNCH;
+    if (hipStreamSynchronize(s) != hipSuccess && rc == GLOWHIP_OK) rc = GLOWHIP_ELAUNCH;
+    (void)hipFree(dev);
+    return rc;
+}
+
+// Testing hook (include/glowhip.h): one launch of an exact-fp32 convolution launcher on the caller's operands.  No second path: it
+// decodes the probe, builds the weight image with the plan's repack job, calls the launcher the plan calls, and copies what the
+// launcher reported.
+int glowhip_debug_conv(const glowhip_conv_probe* d, glowhip_conv_info* info, glowhip_stream_t stream) {
+    GH_REQUIRE(d && info, "debug_conv: null probe / info");
+    hipStream_t s = (hipStream_t)stream;
+    *info = glowhip_conv_info{};
+    ConvLaunchInfo li{};
+    auto report = [&]() {
+        info->kernel = li.kernel; info->ksize = li.ksize; info->tile = li.tile; info->splits = li.splits; info->mb = li.mb;
+        info->grid[0] = li.grid[0]; info->grid[1] = li.grid[1]; info->grid[2] = li.grid[2]; info->launches = li.launches;
+    };
+    GH_REQUIRE(d->N >= 0 && d->Cin > 0 && d->Cout > 0 && d->H > 0 && d->W > 0, "debug_conv: bad shape");
+    GH_REQUIRE(d->x_bs >= (int64_t)d->Cin * d->H * d->W, "debug_conv: batch stride below one sample");
+    switch (d->op) {
+    case GLOWHIP_CONV_WIDE: {
+        GH_REQUIRE(conv_mfma_wide_supported(d->Cin, d->H, d->W, d->Cout, d->ksize), "conv_mfma_wide: unsupported shape");
+        // transposed (1x1 only): w is the forward weight (Cin, Cout), which in its reference layout already is the K-major image of the
+        // input-gradient GEMM -- the training sweep passes it to the launcher as it is, and so does the hook (no image, no repack)
+        GH_REQUIRE(!d->transposed || d->ksize == 1, "debug_conv: the wide image has a transposed source form for 1x1 only");
+        info->image_bytes = d->transposed ? 0 : (int64_t)conv_mfma_wide_packed_bytes(d->Cin, d->Cout, d->ksize);
+        if (!d->image && !d->transposed) return GLOWHIP_OK;
+        GH_REQUIRE(d->x && d->w && d->y && d->scratch_floats >= 0, "debug_conv: wide null operand / output");
+        const float* wt = d->w;
+        if (!d->transposed) {
+            RepackJob r{};
+            r.kind = REPACK_WIDE; r.w = d->w; r.Cin = d->Cin; r.Cout = d->Cout;
+            r.K = d->Cin * d->ksize * d->ksize; r.Kpad = wide_kpad(d->Cin, d->ksize);
+            GH_TRY(debug_conv_image(r, d->image, s));
+            wt = d->image;
+        }
+        GH_TRY(launch_conv_mfma_wide(d->x, (long)d->x_bs, wt, d->post_bias, d->post_scale, d->y, d->N, d->Cin, d->H, d->W, d->Cout,
+                                     d->ksize, s, d->relu, d->scratch, (size_t)d->scratch_floats, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_CONV_FIRST: {
+        GH_REQUIRE(conv_mfma_first_supported(d->Cin, d->H, d->W, d->Cout), "conv_mfma_first: unsupported shape");
+        GH_REQUIRE(!d->fold_bias == !d->fold_logs, "debug_conv: the folded ActNorm is a bias and a logs table, or neither");
+        info->image_bytes = (int64_t)conv_mfma_first_packed_bytes(d->Cin, d->Cout);
+        if (!d->image) return GLOWHIP_OK;
+        GH_REQUIRE(d->x && d->w && d->y, "debug_conv: first null operand / output");
+        RepackJob r{};
+        r.kind = REPACK_FIRST; r.w = d->w; r.Cin = d->Cin; r.Cout = d->Cout; r.fold_bias = d->fold_bias; r.fold_logs = d->fold_logs;
+        r.transposed = d->transposed ? 1 : 0;
+        GH_TRY(debug_conv_image(r, d->image, s));
+        GH_TRY(launch_conv_mfma_first(d->x, (long)d->x_bs, d->image, d->image + (size_t)9 * d->Cin * d->Cout, d->y, d->N, d->Cin, d->H, d->W,
+                                      d->Cout, s, d->relu, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_CONV_DIRECT: {
+        GH_REQUIRE(d->x && d->w && d->y, "debug_conv: direct null operand / output");
+        ConvArgs a{d->x, (long)d->x_bs, d->w, d->bias, d->post_bias, d->post_logs, d->post_scale, d->relu, d->y, d->N, d->Cin, d->H, d->W,
+                   d->Cout, d->ksize};
+        GH_TRY(launch_conv_direct(a, s, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_CONV_TAIL: {
+        GH_REQUIRE(d->mode >= TAIL_PLAIN && d->mode <= TAIL_SPLIT_REV, "debug_conv: unknown tail mode %d", d->mode);
+        GH_REQUIRE(conv_mfma_tail_supported(d->Cin, d->H, d->W, d->Cout), "conv_mfma_tail: unsupported shape");
+        const int paired = tail_paired(d->mode);
+        GH_REQUIRE(!paired || d->Cout % 2 == 0, "conv_mfma_tail: paired mode needs an even Cout");
+        info->image_bytes = (int64_t)conv_mfma_tail_packed_bytes(d->Cin, d->Cout);
+        if (!d->image) return GLOWHIP_OK;
+        const long chw = (long)(paired ? d->Cout / 2 : d->Cout) * d->H * d->W;
+        GH_REQUIRE(d->x && d->w && (d->z2_in || d->mode == TAIL_PLAIN) && (d->z2_out || d->mode == TAIL_SPLIT_FWD), "debug_conv: tail null operand / output");
+        GH_REQUIRE((!d->z2_in || d->z2_in_bs >= chw) && (!d->z2_out || d->z2_out_bs >= chw), "debug_conv: tail batch stride below one sample");
+        GH_REQUIRE(!d->acc == !d->term, "debug_conv: the accumulator and its finalised term come together");
+        GH_REQUIRE(!d->zeros || ((size_t)d->zeros & 15) == 0, "debug_conv: the zero block is 16-byte aligned");
+        TailConvArgs a{};
+        a.x = d->x; a.x_bs = (long)d->x_bs; a.wp = d->image; a.bias = d->bias; a.scale = d->post_scale;
+        a.N = d->N; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.Cout = d->Cout; a.mode = d->mode;
+        a.z2_in = d->z2_in; a.z2_in_bs = (long)d->z2_in_bs; a.z2_out = d->z2_out; a.z2_out_bs = (long)d->z2_out_bs;
+        a.acc = (unsigned long long*)d->acc; a.zeros = d->zeros; a.hout = d->hout;
+        GH_TRY(conv_mfma_tail_check(a));
+        GH_TRY(conv_mfma_tail_pack(d->w, d->Cin, d->Cout, paired, d->image, s));
+        if (d->acc) GH_TRY(launch_zero_acc(a.acc, d->N, s));
+        GH_TRY(launch_conv_mfma_tail(a, s, &li));
+        if (d->acc) GH_TRY(launch_finalize(nullptr, a.acc, nullptr, 1.0, 0.0, 1.0, d->term, nullptr, d->N, s));
+        report();
+        info->paired = li.paired;
+        return GLOWHIP_OK;
+    }
+    default: break;
+    }
+    GH_REQUIRE(false, "debug_conv: unknown op %d", d->op);
+    return GLOWHIP_EINVAL;
 }
 
 }  // extern "C"

@@ -171,6 +171,12 @@ __device__ __forceinline__ float relu_(float v) { return v < 0.f ? 0.f : v; }
 #define GH_STAMP_VAL(i, v) do { } while (0)
 #endif
 
+// What a launcher of the exact-fp32 convolution kernels chose (testing: glowhip_debug_conv fills a glowhip_conv_info from it; every
+// production caller passes nothing).  kernel: GLOWHIP_CVI_*; tile: 64 / 128 (wide: the square block tile, first: BN; tail: the pixels
+// per workgroup TP); splits: split-K slices S (wide) / K-split waves WK (tail); mb: output-channel tiles per workgroup (first: MB,
+// tail: MT); launches: kernel launches made; paired: the tail's row map
+struct ConvLaunchInfo { int kernel, ksize, tile, splits, mb, grid[3], launches, paired; };
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(256) k_conv_direct(ConvArgs a) {
     }
 }
 
-int launch_conv_direct(const ConvArgs& a, hipStream_t s) {
+int launch_conv_direct(const ConvArgs& a, hipStream_t s, ConvLaunchInfo* info) {
     GH_REQUIRE(a.ksize == 1 || a.ksize == 3, "conv2d: kernel size %d unsupported (1 or 3)", a.ksize);
     GH_REQUIRE(a.Cin > 0 && a.Cout > 0 && a.H > 0 && a.W > 0, "conv2d: empty shape");
     if (a.N == 0) return GLOWHIP_OK;
@@ -66,6 +66,7 @@ int launch_conv_direct(const ConvArgs& a, hipStream_t s) {
     if (a.ksize == 3) hipLaunchKernelGGL((k_conv_direct<3, OB>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_conv_direct<1, OB>), grid, dim3(256), 0, s, a);
     GH_LAUNCH_CHECK("k_conv_direct");
+    if (info) *info = ConvLaunchInfo{GLOWHIP_CVI_DIRECT, a.ksize, 0, 1, 0, {(int)grid.x, (int)grid.y, (int)grid.z}, 1};
     return GLOWHIP_OK;
 }
 

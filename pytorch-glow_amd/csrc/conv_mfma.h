@@ -15,14 +15,16 @@ size_t conv_mfma_wide_packed_bytes(int Cin, int Cout, int ksize);
 // reduction split the reduction over workgroups (partial sums there, summed in a fixed order by a second small kernel)
 int launch_conv_mfma_wide(const float* x, long x_bs, const float* wt, const float* post_bias, const float* post_scale,
                           float* y, int N, int Cin, int H, int W, int Cout, int ksize, hipStream_t s, int relu = 1,
-                          float* splitk_scratch = nullptr, size_t splitk_floats = 0);
+                          float* splitk_scratch = nullptr, size_t splitk_floats = 0,
+                          ConvLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
 
 // f.0 with a stationary LDS pixel window (conv_mfma_first.hip): Cin a multiple of 6 (C/2 of every Glow level).
 bool conv_mfma_first_supported(int Cin, int H, int W, int Cout);
 size_t conv_mfma_first_packed_bytes(int Cin, int Cout);
 // wf: packed image (weights * exp(3 logs), then bias * exp(3 logs)) produced by the REPACK_FIRST job
 int launch_conv_mfma_first(const float* x, long x_bs, const float* wf, const float* bias_scaled, float* y, int N,
-                           int Cin, int H, int W, int Cout, hipStream_t s, int relu = 1);
+                           int Cin, int H, int W, int Cout, hipStream_t s, int relu = 1,
+                           ConvLaunchInfo* info = nullptr);     // non-null: what was launched (testing)
 
 // "Tail" convolution: 3x3, few output channels (f.4 / Split2d prior), with the coupling / prior
 // arithmetic and the per-sample log-det reduction fused into the epilogue.
@@ -63,13 +65,15 @@ __host__ __device__ inline int tail_row_channel(int m, int Cout, int paired) {
     const int c = 2 * g + (r & 1);
     return c < Cout / 2 ? 2 * c + (r >> 1) : -1;
 }
+inline bool tail_paired(int mode) { return mode != TAIL_PLAIN && mode != TAIL_ADD_FWD && mode != TAIL_ADD_REV; }   // the row map a mode takes
 inline int tail_chunks(int Cin) { return (Cin + TAIL_CK - 1) / TAIL_CK; }
 inline int wide_kpad(int Cin, int ksize) { return (Cin * ksize * ksize + 31) / 32 * 32; }
 bool conv_mfma_tail_supported(int Cin, int H, int W, int Cout);
 size_t conv_mfma_tail_packed_bytes(int Cin, int Cout);
 // paired=1: output channels come in (even, odd) = (shift|mean, scale|logs) pairs (affine coupling, Split2d)
 int conv_mfma_tail_pack(const float* w, int Cin, int Cout, int paired, float* wp, hipStream_t s);
-int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s);
+int conv_mfma_tail_check(const TailConvArgs& a);   // GLOWHIP_OK, or what launch_conv_mfma_tail would refuse `a` with (no launch)
+int launch_conv_mfma_tail(const TailConvArgs& a, hipStream_t s, ConvLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
 bool conv_mfma_tail_takes_dma(const TailConvArgs& a);   // which of the two tail kernels launch_conv_mfma_tail picks for `a`
 int launch_tail_dma_narrow(const TailConvArgs& a, int paired, hipStream_t s, int TP, int Y);  // W in {8,16}
 int launch_tail_dma_wide(const TailConvArgs& a, int paired, hipStream_t s, int TP, int Y);    // W in {32,64,128}

@@ -397,7 +397,8 @@ __global__ void __launch_bounds__(256) k_splitk_finish(const float* __restrict__
 
 template <int KS, int BMN>
 static int launch_wide_cfg(const float* x, long x_bs, const float* wt, const float* bias, const float* scale, float* y,
-                           int N, int Cin, int H, int W, int Cout, hipStream_t s, int relu, float* scratch, size_t scratch_floats) {
+                           int N, int Cin, int H, int W, int Cout, hipStream_t s, int relu, float* scratch, size_t scratch_floats,
+                           ConvLaunchInfo* info) {
     const long total_px = (long)N * H * W;
     const int tiles = (Cout / BMN) * (int)((total_px + BMN - 1) / BMN);
     const int K = Cin * KS * KS;
@@ -416,12 +417,13 @@ static int launch_wide_cfg(const float* x, long x_bs, const float* wt, const flo
         hipLaunchKernelGGL(k_splitk_finish, dim3(cdiv(per / 4, 256)), dim3(256), 0, s, scratch, S, per, bias, scale, relu, y, Cout, H * W);
         GH_LAUNCH_CHECK("k_splitk_finish");
     }
+    if (info) *info = ConvLaunchInfo{GLOWHIP_CVI_WIDE, KS, BMN, S, 0, {tiles, S, 1}, S > 1 ? 2 : 1};
     return GLOWHIP_OK;
 }
 
 int launch_conv_mfma_wide(const float* x, long x_bs, const float* wt, const float* post_bias, const float* post_scale,
                           float* y, int N, int Cin, int H, int W, int Cout, int ksize, hipStream_t s, int relu,
-                          float* splitk_scratch, size_t splitk_floats) {
+                          float* splitk_scratch, size_t splitk_floats, ConvLaunchInfo* info) {
     GH_REQUIRE(conv_mfma_wide_supported(Cin, H, W, Cout, ksize), "conv_mfma_wide: unsupported shape");
     if (N == 0) return GLOWHIP_OK;
     const int t = pick_wide_tile(Cout, (long)N * H * W);
@@ -435,14 +437,15 @@ int launch_conv_mfma_wide(const float* x, long x_bs, const float* wt, const floa
         hipLaunchKernelGGL(k_gemm_glds, dim3((unsigned)((Cout / GL_BM) * (total_px / GL_BN))), dim3(256), lds, s, x, x_bs, wt,
                            post_bias, post_scale, y, N, Cin, H * W, Cout, relu);
         GH_LAUNCH_CHECK("k_gemm_glds");
+        if (info) *info = ConvLaunchInfo{GLOWHIP_CVI_GEMM_GLDS, 1, 128, 1, 0, {(int)((Cout / GL_BM) * (total_px / GL_BN)), 1, 1}, 1};
         return GLOWHIP_OK;
     }
     if (ksize == 1) {
-        if (t == 128) return launch_wide_cfg<1, 128>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats);
-        return launch_wide_cfg<1, 64>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats);
+        if (t == 128) return launch_wide_cfg<1, 128>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats, info);
+        return launch_wide_cfg<1, 64>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats, info);
     }
-    if (t == 128) return launch_wide_cfg<3, 128>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats);
-    return launch_wide_cfg<3, 64>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats);
+    if (t == 128) return launch_wide_cfg<3, 128>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats, info);
+    return launch_wide_cfg<3, 64>(x, x_bs, wt, post_bias, post_scale, y, N, Cin, H, W, Cout, s, relu, splitk_scratch, splitk_floats, info);
 }
 
 // ================================================================================================

@@ -187,7 +187,7 @@ k_conv_first(const float* __restrict__ X, long x_bs, const float* __restrict__ W
 }
 
 int launch_conv_mfma_first(const float* x, long x_bs, const float* wf_, const float* bias_scaled, float* y, int N,
-                           int Cin, int H, int W, int Cout, hipStream_t s, int relu) {
+                           int Cin, int H, int W, int Cout, hipStream_t s, int relu, ConvLaunchInfo* info) {
     GH_REQUIRE(conv_mfma_first_supported(Cin, H, W, Cout), "conv_mfma_first: unsupported shape");
     if (N == 0) return GLOWHIP_OK;
     const int HW = H * W;
@@ -212,6 +212,7 @@ int launch_conv_mfma_first(const float* x, long x_bs, const float* wf_, const fl
         hipLaunchKernelGGL((k_conv_first<bn, wf>), dim3(grid), dim3(256), lds, s, x, x_bs, wf_, bias_scaled, y, N,   \
                            Cin, H, W, Cout, g, relu);                                                                \
         GH_LAUNCH_CHECK("k_conv_first");                                                                             \
+        if (info) *info = ConvLaunchInfo{GLOWHIP_CVI_FIRST, 3, bn, 1, MB, {(int)grid, 1, 1}, 1};                     \
         return GLOWHIP_OK;                                                                                           \
     }
     GH_FIRST_CASE(128, 32) GH_FIRST_CASE(64, 32) GH_FIRST_CASE(128, 16) GH_FIRST_CASE(64, 16) GH_FIRST_CASE(64, 8)

@@ -152,6 +152,6 @@ struct ConvArgs {
     float* y;                // (N,Cout,H,W) contiguous
     int N, Cin, H, W, Cout, ksize;
 };
-int launch_conv_direct(const ConvArgs& a, hipStream_t s);
+int launch_conv_direct(const ConvArgs& a, hipStream_t s, ConvLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
 
 }  // namespace glowhip
