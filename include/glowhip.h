@@ -691,8 +691,8 @@ void glowhip_debug_force_tail_tile(int pixels_and_flags);
  * out, through the launchers the backward sweep itself calls -- tests/test_gpu_wgrad.py holds every instance to fp64 with it.
  * Not part of the operator surface.  All pointers are device pointers; the layouts are those of the launchers (csrc/backward.h).
  *   op GLOWHIP_WGRAD_MFMA:   gemm[0] through launch_wgrad_mfma with every argument below (taps[0].operand < 0: no gathered operand)
- *   op GLOWHIP_WGRAD_PAIR:   gemm[0] = f.4 (A = g_pre, B = h2 fp16, Mpad = m4, Npad = hidden), gemm[1] = f.0 (A = g_u0, B = y1,
- *                            Mpad = hidden, Npad = n0); taps[0] / taps[1] their gathered tensors; tiled4 / tiled0 = gemm[].tiled;
+ *   op GLOWHIP_WGRAD_PAIR:   launch_wgrad_group on gemm[0] = f.4 (A = g_pre, B = h2 fp16, Mpad = m4, Npad = hidden), gemm[1] = f.0
+ *                            (A = g_u0, B = y1, Mpad = hidden, Npad = n0); taps[0] / taps[1] their gathered tensors;
  *                            then launch_wgrad_reduce_batched on the jobs the launcher returned
  *   op GLOWHIP_WGRAD_TRIO:   the same with gemm[2] = f.2 (A = g_u2, B = h1 fp16, hidden x hidden)
  *   op GLOWHIP_WGRAD_SHIFT_EXPAND:  gemm[0].A (batch stride a_bs) -> gemm[0].dw, taps[0] = (C, H, W, sign), rows_pad = gemm[0].Mpad

@@ -118,38 +118,40 @@ int launch_shift_expand(const float* src, long src_bs, float* out, int N, int C,
                         hipStream_t s);
 bool wgrad_mfma_supported(int HW, int Mpad, int Npad);
 size_t wgrad_mfma_partial_floats(int Mpad, int Npad, int N, int HW);
-// operand (0: A, 1: B) of launch_wgrad_mfma given as the (N, C, H, W) tensor whose shift-expanded rows (c * 9 + tap) it stands for
+// operand (0: A, 1: B) of a weight-gradient GEMM given as the (N, C, H, W) tensor whose shift-expanded rows (c * 9 + tap) it stands for
 // (what launch_shift_expand would write): the GEMM's loader gathers them itself.  The operand pointer / batch stride are the tensor's.
+// operand < 0: none, both operands are plain.
 struct WgradTaps { int operand, C, H, W, sign; };
+// WgradGemm::layout (f16-pipe kernel, plain operands; the values are those of glowhip_wgrad_gemm.tiled and of the kernels' WgArgs)
+constexpr int WGRAD_A_TILED = 1;       // A / B is pixel-tile-major [pixel / 32][rows][pixel % 32] over the batch's pixels (what the taping /
+constexpr int WGRAD_B_TILED = 2;       // backward k_cnet write, sh.h), rows = Mpad / Npad; its batch stride is unused
+constexpr int WGRAD_A_PRESCALED = 4;   // A holds g * sh_scale * 2^11 (the backward k_cnet's g_u2 / g_u0); row sums and dW come out as for g
+// One weight-gradient GEMM: partial[split] = A B^T over a slice of the batch's pixels, dw = their sum in the layer's weight layout
+// (wgrad_reduce.h: mode).  The fields of the public glowhip_wgrad_gemm, plus the taps.
+struct WgradGemm {
+    const float* A; long a_bs; const float* B; long b_bs;   // (Mpad, HW) / (Npad, HW) per image, batch strides in elements
+    float* partial; float* dw;
+    int Mpad, Npad, Mreal, Nreal, mode;
+    double* rowsum = nullptr;          // (f16-pipe kernel) rowsum[m] += sum over all pixels of A's row m -- the bias gradient when A = g_u
+    WgradTaps taps{-1, 0, 0, 1, 0};
+    int b_valid = 0;                   // > 0 (f16-pipe kernel, plain B): only that many rows of B exist, the rest of the column tile is zero
+    int b_half = 0;                    // 1 (f16-pipe kernel, plain B): B points at an fp16 tensor (the taped h1 / h2), b_bs in elements
+    int layout = 0;                    // OR of WGRAD_A_TILED / WGRAD_B_TILED / WGRAD_A_PRESCALED
+};
+// what all GEMMs of a launch share.  sh_scale > 0: f16-pipe kernels, the gradient operand A pre-scaled by it; 0: the fp32 pipe
+struct WgradBatch { int N, HW; float sh_scale; };
 struct WgradReduceJob;
 // What a weight-gradient launcher chose for one GEMM (testing: glowhip_debug_wgrad fills a glowhip_wgrad_info from it; the
 // sweep passes no pointer).  instance: GLOWHIP_WGI_* of include/glowhip.h; blocks: workgroups of this GEMM, `live` of them with a tile.
 struct WgradLaunchInfo { int instance, splits, ktiles_per_split, blocks, live; };
-int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, float* partial, float* dw, int N, int HW,
-                      int Mpad, int Npad, int Mreal, int Nreal, int mode, hipStream_t s, float sh_scale = 0.f,   // sh_scale > 0: f16-pipe kernel, gradient operand A pre-scaled by it
-                      double* rowsum = nullptr,    // (f16-pipe kernel) rowsum[m] += sum over all pixels of A's row m -- the bias gradient when A = g_u
-                      const WgradTaps* taps = nullptr,
-                      struct WgradReduceJob* defer = nullptr,    // non-null: skip the split-K reduction, describe it in *defer instead
-                      int b_valid = 0,    // > 0 (f16-pipe kernel, plain B): only that many rows of B exist, the rest of the column tile is zero
-                      int b_half = 0,     // 1 (f16-pipe kernel, plain B): B points at an fp16 tensor (the taped h1 / h2), b_bs in elements
-                      int tiled = 0,      // bit 0 / bit 1 (f16-pipe kernel, plain operand): A / B is pixel-tile-major [pixel / 32][rows][pixel % 32]
-                                          // over the batch's pixels (what the taping / backward k_cnet write, sh.h), rows = Mpad / Npad; its batch stride is unused
-                                          // bit 2: A holds g * sh_scale * 2^11 (the backward k_cnet's g_u2 / g_u0); row sums and dW come out as for g
-                      WgradLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
-// f.4's + f.0's GEMMs of one FlowStep as one launch (wgrad_mfma.hip); GLOWHIP_EINVAL (nothing launched) for shapes it does not take
+// defer != null: skip the split-K reduction, describe it in *defer instead;  info != null: what was launched (testing)
+int launch_wgrad_mfma(const WgradGemm& g, const WgradBatch& b, hipStream_t s, WgradReduceJob* defer = nullptr, WgradLaunchInfo* info = nullptr);
+// The GEMMs of one FlowStep behind the backward k_cnet as ONE launch (wgrad_mfma.hip): g[0] = f.4's (A = gathered g_pre, B = h2 fp16
+// pixel-tile-major), g[1] = f.0's (A = g_u0 pixel-tile-major and pre-scaled, B = gathered y1) and, n == 3, g[2] = f.2's (A = g_u2,
+// B = h1 fp16, both pixel-tile-major, A pre-scaled).  GLOWHIP_EINVAL (nothing launched) for anything else; the caller asks
+// wgrad_pair_ok for the shapes first.  The reduction of g[i] is described in *defer[i]; info[i] <- g[i]'s share of the launch.
 bool wgrad_pair_ok(int HW, int m4, int hid, int n0);
-int launch_wgrad_pair(const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
-                      const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
-                      int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0, int tiled4,
-                      int tiled0, struct WgradReduceJob* rj4, struct WgradReduceJob* rj0, hipStream_t s,
-                      WgradLaunchInfo* info = nullptr);      // non-null: info[0] <- f.4's GEMM, info[1] <- f.0's (testing)
-// ... and f.2's (A = g_u2, B = h1 fp16, both pixel-tile-major, A pre-scaled) as the third
-int launch_wgrad_trio(const float* gu2, const void* h1_half, float* partial2, float* dw2, double* rowsum2,
-                      const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
-                      const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
-                      int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0,
-                      struct WgradReduceJob* rj2, struct WgradReduceJob* rj4, struct WgradReduceJob* rj0, hipStream_t s,
-                      WgradLaunchInfo* info = nullptr);      // non-null: info[0] <- f.4's GEMM, info[1] <- f.0's, info[2] <- f.2's (testing)
+int launch_wgrad_group(const WgradGemm* g, int n, const WgradBatch& b, WgradReduceJob* const* defer, hipStream_t s, WgradLaunchInfo* info = nullptr);
 // fp16 pixel-tile-major [pixel / 32][R][pixel % 32] -> fp32 (N, R, HW): a taped hidden tensor for the per-layer backward kernels
 int launch_half_to_float(const void* src_half, float* dst, int N, int R, int HW, hipStream_t s);
 struct WgradReduceJob { const float* partial; float* dw; int splits, Mpad, Npad, Mreal, Nreal, mode; };

@@ -145,13 +145,17 @@ static bool wgrad_fast(const LayerPlan& L) {
     return d.kind == GLOWHIP_LAYER_FLOWSTEP && (d.H * d.W) % 32 == 0 && d.hidden % 128 == 0;
 }
 
+// padded sizes of a layer's 3x3 weight-gradient GEMMs: rows of f.4's A (Cout x 9 taps), columns of f.0's B (C / 2 x 9 taps)
+struct WgradPads { int m4, n0; };
+static WgradPads wgrad_pads(const LayerPlan& L) { return WgradPads{round_up(L.Cout * 9, 128), round_up((L.d.C / 2) * 9, 64)}; }
+
 static void wgrad_scratch_floats(const glowhip_plan* p, int N, size_t* col, size_t* partial) {
     *col = 0; *partial = 0;
     for (const LayerPlan& L : p->layers) {
         if (!wgrad_fast(L)) continue;
         const glowhip_layer_desc& d = L.d;
         const int HW = d.H * d.W, hid = d.hidden;
-        const int m4 = round_up(L.Cout * 9, 128), n0 = round_up((d.C / 2) * 9, 64);
+        const auto [m4, n0] = wgrad_pads(L);
         *col = std::max(*col, (size_t)N * std::max(m4, n0) * HW);
         *partial = std::max(*partial, wgrad_mfma_partial_floats(hid, hid, N, HW));
         *partial = std::max(*partial, wgrad_mfma_partial_floats(m4, hid, N, HW));
@@ -447,12 +451,40 @@ static ChanMixBwdArgs chanmix_bwd_args(const LayerPlan& L, const void* packed, i
 enum class WgradRoute { trio, pair, taps, expanded };
 static WgradRoute wgrad_route(const LayerPlan& L, int N) {
     const glowhip_layer_desc& d = L.d;
-    const int HW = d.H * d.W, m4 = round_up(L.Cout * 9, 128), n0 = round_up((d.C / 2) * 9, 64);
+    const int HW = d.H * d.W;
+    const auto [m4, n0] = wgrad_pads(L);
     if (d.W < 4 || (d.W & (d.W - 1)) != 0) return WgradRoute::expanded;
     if (!wgrad_pair_ok(HW, m4, d.hidden, n0)) return WgradRoute::taps;
     // short pixel axes (<= 512 k-tiles of 32 pixels): f.2's GEMM joins the launch as well -- at 12 - 18 pixel slices instead of 32
     // its workgroups' loops are two to three times as long and a third of the partial tiles is left
     return (long)N * HW / 32 <= 512 ? WgradRoute::trio : WgradRoute::pair;
+}
+
+// The three weight-gradient GEMMs of FlowStep L behind its backward k_cnet launch, in launch_wgrad_group's order (f.4, f.0, f.2),
+// on the operands that launch and the tape hand over; their partial tiles in the three regions behind w.partial.
+//   dW4[o][i][tap] = sum_p g_pre[o][p - d(tap)] * h2[i][p]        dW0[o][i][tap] = sum_p g_u0[o][p] * y1[i][p + d(tap)]
+// The 3x3 layers' shift-expanded operands are gathered by the GEMM's loader (WgradTaps); the bias gradients are row sums of g_u.
+static void cnet_wgrad_gemms(const LayerPlan& L, const glowhip_layer_grads& G, const StepTape& T, const StepAcc& A, const TrainWs& w,
+                             WgradGemm g[3]) {
+    const glowhip_layer_desc& d = L.d;
+    const int HW = d.H * d.W, Ch = d.C / 2, hid = d.hidden;
+    const long hb = (long)hid * HW;
+    const auto [m4, n0] = wgrad_pads(L);
+    g[0] = WgradGemm{w.gpre, (long)L.Cout * HW, T.h2, hb, w.partial, G.f4_w, m4, hid, L.Cout * 9, hid, 1};
+    g[0].taps = WgradTaps{0, L.Cout, d.H, d.W, -1}; g[0].b_half = 1; g[0].layout = WGRAD_B_TILED;
+    g[1] = WgradGemm{w.gh1, hb, T.out, (long)d.C * HW, w.partial + 2 * w.partial_floats, G.f0_w, hid, n0, hid, Ch * 9, 0};
+    g[1].taps = WgradTaps{1, Ch, d.H, d.W, +1}; g[1].rowsum = A.b0; g[1].layout = WGRAD_A_TILED | WGRAD_A_PRESCALED;
+    g[2] = WgradGemm{w.gh2, hb, T.h1, hb, w.partial + w.partial_floats, G.f2_w, hid, hid, hid, hid, 0};
+    g[2].rowsum = A.b2; g[2].b_half = 1; g[2].layout = WGRAD_A_TILED | WGRAD_B_TILED | WGRAD_A_PRESCALED;
+}
+// the gathered operand of g written out by launch_shift_expand into `col`, g a GEMM on that plain operand
+static int expand_taps(WgradGemm& g, float* col, int N, int HW, hipStream_t s) {
+    const WgradTaps t = g.taps;
+    const bool a = t.operand == 0;
+    const int rows = a ? g.Mpad : g.Npad;
+    GH_TRY(launch_shift_expand(a ? g.A : g.B, a ? g.a_bs : g.b_bs, col, N, t.C, t.H, t.W, rows, t.sign, s));
+    (a ? g.A : g.B) = col; (a ? g.a_bs : g.b_bs) = (long)rows * HW; g.taps.operand = -1;
+    return GLOWHIP_OK;
 }
 
 static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in, const char* tape,
@@ -566,60 +598,38 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
             if (fastw && bwd_cnet(p, L, li, G, N, (size_t)N * p->max_hidden)) {
                 // The input-gradient chain as ONE k_cnet launch (launch_cnet_bwd); the bias gradients are row sums inside the
                 // weight-gradient GEMMs that read g_u2 / g_u0 anyway, the log-scale gradients follow from dW and db (backward.h LogsJob).
-                const int m4 = round_up(L.Cout * 9, 128), n0 = round_up(Ch * 9, 64);
                 const WgradRoute route = wgrad_route(L, N);
-                // (the 3x3 layers' shift-expanded operands are gathered by the GEMM's loader: WgradTaps -- or, `expanded`, written out first)
-                const WgradTaps t4{0, L.Cout, d.H, d.W, -1}, t0{1, Ch, d.H, d.W, +1};
-                float* const part4 = w.partial; float* const part2 = w.partial + w.partial_floats; float* const part0 = w.partial + 2 * w.partial_floats;
-                WgradReduceJobs rj{};      // the three split-K reductions of this step run as one launch at its end
+                const WgradBatch wb{N, HW, sh_grad_scale};
+                WgradGemm gm[3];           // f.4's, f.0's, f.2's
+                cnet_wgrad_gemms(L, G, T, A, w, gm);
+                WgradReduceJobs rj{};      // the three split-K reductions of this step run as one launch at its end, in the order f.4, f.2, f.0
                 rj.n = 3;
-                auto wgrad_f4 = [&]() {      // dW4[o][i][tap] = sum_p g_pre[o][p - d(tap)] * h2[i][p]
-                    const bool ex = route == WgradRoute::expanded;
-                    if (ex) GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, m4, -1, s));
+                WgradReduceJob* const defer[3] = {&rj.job[0], &rj.job[2], &rj.job[1]};
+                auto wgrad_alone = [&](int i) {      // GEMM i in a launch of its own; `expanded`: its gathered operand written out first
+                    WgradGemm q = gm[i];
+                    if (route == WgradRoute::expanded && q.taps.operand >= 0) GH_TRY(expand_taps(q, w.col, N, HW, s));
                     ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    return launch_wgrad_mfma(ex ? w.col : w.gpre, (long)(ex ? m4 : L.Cout) * HW, h2, (long)hid * HW, part4, G.f4_w, N, HW, m4, hid,
-                                             L.Cout * 9, hid, 1, s, sh_grad_scale, nullptr, ex ? nullptr : &t4, &rj.job[0], 0, 1, 2);
-                };
-                auto wgrad_f2 = [&]() {
-                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    return launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, part2, G.f2_w, N, HW, hid, hid, hid, hid, 0, s,
-                                             sh_grad_scale, A.b2, nullptr, &rj.job[1], 0, 1, 7);
-                };
-                auto wgrad_f0 = [&]() {      // dW0[o][i][tap] = sum_p g_u0[o][p] * y1[i][p + d(tap)]
-                    const bool ex = route == WgradRoute::expanded;
-                    if (ex) GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, n0, +1, s));
-                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    return launch_wgrad_mfma(w.gh1, (long)hid * HW, ex ? w.col : out, ex ? (long)n0 * HW : chw, part0, G.f0_w, N, HW, hid, n0,
-                                             hid, Ch * 9, 0, s, sh_grad_scale, A.b0, ex ? nullptr : &t0, &rj.job[2], 0, 0, 5);
+                    return launch_wgrad_mfma(q, wb, s, defer[i]);
                 };
                 // f.4's GEMM does not depend on the chain below, but where it shares a launch with f.0's (and f.2's), which do, it
                 // waits for it; alone it runs here
-                if (route == WgradRoute::taps || route == WgradRoute::expanded) GH_TRY(wgrad_f4());
+                if (route == WgradRoute::taps || route == WgradRoute::expanded) GH_TRY(wgrad_alone(0));
                 CnetPending pend{};
                 GH_TRY(launch_cnet_bwd(p, L, packed, N, T, w, sh_grad_scale, &pend, s));
                 // (its finishing step -- g_y1 += the partial sums -- rides in k_chanmix_bwd below)
-                switch (route) {
-                case WgradRoute::trio: {      // all three GEMMs side by side in one launch
+                if (route == WgradRoute::trio) {      // all three GEMMs side by side in one launch
                     count_launch(p, "k_wgrad(trio)");
                     ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    GH_TRY(launch_wgrad_trio(w.gh2, h1, part2, G.f2_w, A.b2, w.gpre, (long)L.Cout * HW, h2, part4, G.f4_w, m4, L.Cout * 9,
-                                             w.gh1, out, chw, part0, G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, A.b0, t4, t0,
-                                             &rj.job[1], &rj.job[0], &rj.job[2], s));
-                    break;
-                }
-                case WgradRoute::pair: {      // f.2's alone, then f.4's and f.0's in one launch
-                    GH_TRY(wgrad_f2());
-                    count_launch(p, "k_wgrad(pair)");
-                    ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
-                    GH_TRY(launch_wgrad_pair(w.gpre, (long)L.Cout * HW, h2, part4, G.f4_w, m4, L.Cout * 9, w.gh1, out, chw, part0,
-                                             G.f0_w, n0, Ch * 9, N, HW, hid, sh_grad_scale, A.b0, t4, t0, 2, 5, &rj.job[0], &rj.job[2], s));
-                    break;
-                }
-                case WgradRoute::taps:
-                case WgradRoute::expanded:
-                    GH_TRY(wgrad_f2());
-                    GH_TRY(wgrad_f0());
-                    break;
+                    GH_TRY(launch_wgrad_group(gm, 3, wb, defer, s));
+                } else {
+                    GH_TRY(wgrad_alone(2));
+                    if (route == WgradRoute::pair) {      // f.2's alone, then f.4's and f.0's in one launch
+                        count_launch(p, "k_wgrad(pair)");
+                        ScopedTimer tw(p, GLOWHIP_K_WGRAD, 1, s);
+                        GH_TRY(launch_wgrad_group(gm, 2, wb, defer, s));
+                    } else {
+                        GH_TRY(wgrad_alone(1));
+                    }
                 }
                 // (the three reductions ride in the mixer backward's launch below: k_chanmix_bwd_reduce)
                 ChanMixBwdArgs mb = chanmix_bwd_args(L, packed, N, xin, g, g, A);      // (C <= 96 here, tape_cnet: never the wide kernel)
@@ -630,31 +640,31 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                 continue;
             }
             const bool half_tape = li < (int)p->tape_has_masks.size() && p->tape_has_masks[li];
-            const float wscale = train_sh_enabled(p) ? sh_grad_scale : 0.f;
+            const WgradBatch wb{N, HW, train_sh_enabled(p) ? sh_grad_scale : 0.f};      // (0: the fp32 pipe)
+            const WgradPads pad = wgrad_pads(L);
+            const long hb = (long)hid * HW;
             GH_TRY(tape_to_f32(h2, half_tape, L, N, w, s));
             if (fastw) {   // dW4[o][i][tap] = sum_p g_pre[o][p - d(tap)] * h2[i][p]
-                const int m4 = round_up(L.Cout * 9, 128);
-                GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, m4, -1, s));
-                GH_TRY(launch_wgrad_mfma(w.col, (long)m4 * HW, h2, (long)hid * HW, w.partial, G.f4_w, N, HW, m4, hid, L.Cout * 9, hid, 1, s, wscale));
+                GH_TRY(launch_shift_expand(w.gpre, (long)L.Cout * HW, w.col, N, L.Cout, d.H, d.W, pad.m4, -1, s));
+                GH_TRY(launch_wgrad_mfma(WgradGemm{w.col, (long)pad.m4 * HW, h2, hb, w.partial, G.f4_w, pad.m4, hid, L.Cout * 9, hid, 1}, wb, s));
             } else {
-                GH_TRY(launch_wgrad_direct(w.gpre, h2, (long)hid * HW, G.f4_w, N, hid, d.H, d.W, L.Cout, 3, s));
+                GH_TRY(launch_wgrad_direct(w.gpre, h2, hb, G.f4_w, N, hid, d.H, d.W, L.Cout, 3, s));
             }
             GH_TRY(dgrad_f4(L, packed, N, w, s));
             GH_TRY(launch_act_bwd(w.gh2, h2, at<float>(packed, L.f2_scale), N, hid, HW, A.b2, A.l2, s));
             GH_TRY(tape_to_f32(h1, half_tape, L, N, w, s));
             // (c) f.2 (1x1)
             if (fastw) {
-                GH_TRY(launch_wgrad_mfma(w.gh2, (long)hid * HW, h1, (long)hid * HW, w.partial, G.f2_w, N, HW, hid, hid, hid, hid, 0, s, wscale));
+                GH_TRY(launch_wgrad_mfma(WgradGemm{w.gh2, hb, h1, hb, w.partial, G.f2_w, hid, hid, hid, hid, 0}, wb, s));
             } else {
-                GH_TRY(launch_wgrad_direct(w.gh2, h1, (long)hid * HW, G.f2_w, N, hid, d.H, d.W, hid, 1, s));
+                GH_TRY(launch_wgrad_direct(w.gh2, h1, hb, G.f2_w, N, hid, d.H, d.W, hid, 1, s));
             }
             GH_TRY(dgrad_f2(L, N, w, s));
             GH_TRY(launch_act_bwd(w.gh1, h1, at<float>(packed, L.f0_scale), N, hid, HW, A.b0, A.l0, s));
             // (d) f.0: input is y1 = first half of the step output
             if (fastw) {   // dW0[o][i][tap] = sum_p g_u0[o][p] * y1[i][p + d(tap)]
-                const int n0 = round_up(Ch * 9, 64);
-                GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, n0, +1, s));
-                GH_TRY(launch_wgrad_mfma(w.gh1, (long)hid * HW, w.col, (long)n0 * HW, w.partial, G.f0_w, N, HW, hid, n0, hid, Ch * 9, 0, s, wscale));
+                GH_TRY(launch_shift_expand(out, chw, w.col, N, Ch, d.H, d.W, pad.n0, +1, s));
+                GH_TRY(launch_wgrad_mfma(WgradGemm{w.gh1, hb, w.col, (long)pad.n0 * HW, w.partial, G.f0_w, hid, pad.n0, hid, Ch * 9, 0}, wb, s));
             } else {
                 GH_TRY(launch_wgrad_direct(w.gh1, out, chw, G.f0_w, N, Ch, d.H, d.W, hid, 3, s));
             }
@@ -678,13 +688,13 @@ static int backward_sweep(glowhip_plan* p, const void* packed, const float* x_in
                             at<float>(packed, L.f4_scale), w.gld, a4b, a4l, N, Ch, HW};
             GH_TRY(launch_split_bwd(sb, s));
             {   // Conv2dZeros weight gradient: the split-K GEMM of the FlowSteps (A = gathered taps of g_pre, B = z1's Ch rows)
-                const int m4 = round_up(L.Cout * 9, 128);
+                const int m4 = wgrad_pads(L).m4;
                 const bool mf = train_sh_enabled(p) && G.f4_w && HW % 32 == 0 && Ch <= 64 && d.W >= 4 && (d.W & (d.W - 1)) == 0 &&
                                 wgrad_mfma_partial_floats(m4, 64, N, HW) <= w.partial_floats;
                 if (mf) {
-                    const WgradTaps t4{0, L.Cout, d.H, d.W, -1};
-                    GH_TRY(launch_wgrad_mfma(w.gpre, (long)L.Cout * HW, xin, chw, w.partial, G.f4_w, N, HW, m4, 64, L.Cout * 9, Ch, 1, s,
-                                             sh_grad_scale, nullptr, &t4, nullptr, Ch));
+                    WgradGemm q{w.gpre, (long)L.Cout * HW, xin, chw, w.partial, G.f4_w, m4, 64, L.Cout * 9, Ch, 1};
+                    q.taps = WgradTaps{0, L.Cout, d.H, d.W, -1}; q.b_valid = Ch;
+                    GH_TRY(launch_wgrad_mfma(q, WgradBatch{N, HW, sh_grad_scale}, s));
                 } else {
                     GH_TRY(launch_wgrad_direct(w.gpre, xin, chw, G.f4_w, N, Ch, d.H, d.W, L.Cout, 3, s));
                 }

@@ -931,107 +931,77 @@ bool wgrad_pair_ok(int HW, int m4, int hid, int n0) {
     return wgrad_mfma_supported(HW, m4, hid) && wgrad_mfma_supported(HW, hid, n0) && hid % 128 == 0 && (n0 == 64 || n0 % 128 == 0);
 }
 
-// f.4's and f.0's weight-gradient GEMMs of one FlowStep (both behind the backward k_cnet, both with a gathered 3x3 operand) as ONE
-// launch (k_wgrad_gemm_pair): the ~512 workgroups that fill the chip are shared out by MFMA work, so each GEMM is cut into half
-// as many pixel slices as it would take alone -- half the partial tiles to write and to reduce.  The caller asks wgrad_pair_ok first;
-// shapes outside it are an error here (GLOWHIP_EINVAL, nothing launched).
-//   f.4: A = gathered g_pre (t4: Cout x 9 rows -> m4), B = h2 fp16 (hid rows);   f.0: A = g_u0 (hid rows, pre-scaled), B = gathered y1 (t0 -> n0)
-int launch_wgrad_pair(const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
-                      const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
-                      int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0, int tiled4,
-                      int tiled0, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s, WgradLaunchInfo* info) {
-    const bool ok = sh_scale > 0.f && N > 0 && wgrad_pair_ok(HW, m4, hid, n0) && t4.operand == 0 && t1_ok(t4, HW) && t0.operand == 1 && t1_ok(t0, HW) &&
-                    tiled4 == 2 && tiled0 == 5;
-    GH_REQUIRE(ok, "wgrad grouped launch: shapes outside wgrad_pair_ok / operands not as documented");
-    const int total = (int)((long)N * HW / 32);
-    const int bn0 = n0 == 64 ? 64 : 128;
-    const int tiles4 = (m4 / 128) * (hid / 128), tiles0 = (hid / 128) * (n0 / bn0);
-    // MFMAs per k-tile: f.4 two per product (fp16 B), f.0 three
-    const double w4 = 2.0 * m4 * hid, w0 = 3.0 * hid * n0;
-    auto slices = [&](int tiles, double share, int* per) {
-        int sp = std::max(1, std::min(total, (int)(512.0 * share / tiles + 0.5)));
-        *per = (total + sp - 1) / sp;
-        return (total + *per - 1) / *per;
-    };
-    int per4, per0;
-    const int sp4 = slices(tiles4, w4 / (w4 + w0), &per4), sp0 = slices(tiles0, w0 / (w4 + w0), &per0);
-    const int nb4 = (tiles4 * sp4 + 7) / 8 * 8, nb0 = tiles0 * sp0;      // (f.0's blocks start on XCD 0: xcd_remap)
-    WgArgs a4{gpre, gpre_bs, reinterpret_cast<const float*>(h2_half), (long)hid * HW, partial4, HW, m4, hid, total, per4, sh_scale, sh_scale, nullptr,
-              t4.C, t4.H, t4.W, t4.sign, hid, tiled4, tiles4 * sp4};
-    WgArgs a0{gu0, (long)hid * HW, y1, y1_bs, partial0, HW, hid, n0, total, per0, sh_scale, SH_LO_INV, rowsum0,
-              t0.C, t0.H, t0.W, t0.sign, n0, tiled0, nb0};
-    // (blocks tiles4 * sp4 .. nb4 of f.4's range have no tile: the body's split index runs past its k-tiles and they only write
-    // nothing -- see the guard in the wrapper)
-    a4.nblocks = nb4;
-    if (bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_pair<64>, dim3(nb4 + nb0), dim3(256), 0, s, a4, a0, tiles4 * sp4);
-    else hipLaunchKernelGGL(k_wgrad_gemm_pair<128>, dim3(nb4 + nb0), dim3(256), 0, s, a4, a0, tiles4 * sp4);
-    GH_LAUNCH_CHECK("k_wgrad_gemm_pair");
-    if (info) {
-        const int inst = bn0 == 64 ? GLOWHIP_WGI_PAIR64 : GLOWHIP_WGI_PAIR128;
-        info[0] = WgradLaunchInfo{inst, sp4, per4, nb4, tiles4 * sp4};
-        info[1] = WgradLaunchInfo{inst, sp0, per0, nb0, nb0};
-    }
-    *rj4 = WgradReduceJob{partial4, dw4, sp4, m4, hid, m4_real, hid, 1};
-    *rj0 = WgradReduceJob{partial0, dw0, sp0, hid, n0, hid, n0_real, 0};
-    return GLOWHIP_OK;
+// the kernel arguments of GEMM g cut into slices of `per` k-tiles, on `nblocks` workgroups
+static WgArgs wg_args(const WgradGemm& g, const WgradBatch& b, int per, int nblocks) {
+    const bool t = g.taps.operand >= 0;
+    return WgArgs{g.A, g.a_bs, g.B, g.b_bs, g.partial, b.HW, g.Mpad, g.Npad, (int)((long)b.N * b.HW / 32), per, b.sh_scale,
+                  (g.layout & WGRAD_A_PRESCALED) ? SH_LO_INV : b.sh_scale, g.rowsum, t ? g.taps.C : 0, t ? g.taps.H : 0, t ? g.taps.W : 1,
+                  t ? g.taps.sign : 0, g.b_valid > 0 ? g.b_valid : g.Npad, g.layout, nblocks};
 }
 
-// The same with f.2's GEMM (A = g_u2, B = h1 fp16, both pixel-tile-major; wgrad_ps_body) as the third: k_wgrad_gemm_trio.
-int launch_wgrad_trio(const float* gu2, const void* h1_half, float* partial2, float* dw2, double* rowsum2,
-                      const float* gpre, long gpre_bs, const void* h2_half, float* partial4, float* dw4, int m4, int m4_real,
-                      const float* gu0, const float* y1, long y1_bs, float* partial0, float* dw0, int n0, int n0_real,
-                      int N, int HW, int hid, float sh_scale, double* rowsum0, const WgradTaps& t4, const WgradTaps& t0,
-                      WgradReduceJob* rj2, WgradReduceJob* rj4, WgradReduceJob* rj0, hipStream_t s, WgradLaunchInfo* info) {
-    const bool ok = sh_scale > 0.f && N > 0 && wgrad_pair_ok(HW, m4, hid, n0) && t4.operand == 0 && t1_ok(t4, HW) && t0.operand == 1 && t1_ok(t0, HW);
+// The weight-gradient GEMMs of one FlowStep behind the backward k_cnet as ONE launch: f.4's and f.0's (both with a gathered 3x3
+// operand; k_wgrad_gemm_pair) and, n == 3, f.2's (wgrad_ps_body; k_wgrad_gemm_trio).  The ~512 workgroups that fill the chip are
+// shared out by MFMA work, so each GEMM is cut into fewer pixel slices than it would take alone -- fewer partial tiles to write
+// and to reduce.  Anything but the documented shapes and operand forms is an error (GLOWHIP_EINVAL, nothing launched).
+int launch_wgrad_group(const WgradGemm* g, int n, const WgradBatch& b, WgradReduceJob* const* defer, hipStream_t s, WgradLaunchInfo* info) {
+    // the form of member i (f.4, f.0, f.2): gathered operand (-1: none), layout, reduction mode, fp16 B
+    static constexpr struct { int taps, layout, mode, b_half; } form[3] = {
+        {0, WGRAD_B_TILED, 1, 1}, {1, WGRAD_A_TILED | WGRAD_A_PRESCALED, 0, 0}, {-1, WGRAD_A_TILED | WGRAD_B_TILED | WGRAD_A_PRESCALED, 0, 1}};
+    const int hid = g[0].Npad;
+    bool ok = (n == 2 || n == 3) && b.sh_scale > 0.f && b.N > 0 && wgrad_pair_ok(b.HW, g[0].Mpad, hid, g[1].Npad) && g[1].Mpad == hid &&
+              (n == 2 || (g[2].Mpad == hid && g[2].Npad == hid)) && !g[0].rowsum;
+    for (int i = 0; ok && i < n; ++i)
+        ok = g[i].layout == form[i].layout && g[i].mode == form[i].mode && g[i].b_half == form[i].b_half && g[i].b_valid <= 0 &&
+             (form[i].taps < 0 ? g[i].taps.operand < 0 : g[i].taps.operand == form[i].taps && t1_ok(g[i].taps, b.HW));
     GH_REQUIRE(ok, "wgrad grouped launch: shapes outside wgrad_pair_ok / operands not as documented");
-    const int total = (int)((long)N * HW / 32);
-    const int bn0 = n0 == 64 ? 64 : 128;
-    const int tiles2 = (hid / 128) * (hid / 128), tiles4 = (m4 / 128) * (hid / 128), tiles0 = (hid / 128) * (n0 / bn0);
+    const int total = (int)((long)b.N * b.HW / 32);
+    const int bn0 = g[1].Npad == 64 ? 64 : 128;
     // Shares by MFMAs per k-tile: two per product with an fp16 B (f.2, f.4), three for f.0.  (By measured cost per (workgroup,
     // k-tile) -- 1.37 us for f.2's kernel, 2.4 - 2.7 us for the gathering ones -- the launch got slower: f.2's steps slow down
     // next to gathering workgroups on the same CU.  With long pixel axes (level 1 of config B: 2 048 k-tiles) the launch is slower
     // than f.2 and the pair one after the other either way, 185 vs 87 + 73 us: the caller takes it only for short ones.)
-    const double w2 = 2.0 * hid * hid, w4 = 2.0 * m4 * hid, w0 = 3.0 * hid * n0, wsum = w2 + w4 + w0;
-    auto slices = [&](int tiles, double share, int* per) {
-        int sp = std::max(1, std::min(total, (int)(512.0 * share / tiles + 0.5)));
-        *per = (total + sp - 1) / sp;
-        return (total + *per - 1) / *per;
-    };
-    int per2, per4, per0;
-    const int sp2 = slices(tiles2, w2 / wsum, &per2), sp4 = slices(tiles4, w4 / wsum, &per4), sp0 = slices(tiles0, w0 / wsum, &per0);
-    const int live2 = tiles2 * sp2, live4 = tiles4 * sp4, nb2 = (live2 + 7) / 8 * 8, nb4 = (live4 + 7) / 8 * 8, nb0 = tiles0 * sp0;
-    const long hb = (long)hid * HW;
-    WgArgs a2{gu2, hb, reinterpret_cast<const float*>(h1_half), hb, partial2, HW, hid, hid, total, per2, sh_scale, SH_LO_INV, rowsum2,
-              0, 0, 1, 0, hid, 7, nb2};
-    WgArgs a4{gpre, gpre_bs, reinterpret_cast<const float*>(h2_half), hb, partial4, HW, m4, hid, total, per4, sh_scale, sh_scale, nullptr,
-              t4.C, t4.H, t4.W, t4.sign, hid, 2, nb4};
-    WgArgs a0{gu0, hb, y1, y1_bs, partial0, HW, hid, n0, total, per0, sh_scale, SH_LO_INV, rowsum0,
-              t0.C, t0.H, t0.W, t0.sign, n0, 5, nb0};
-    if (bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_trio<64>, dim3(nb2 + nb4 + nb0), dim3(256), 0, s, a2, a4, a0, live2, live4);
-    else hipLaunchKernelGGL(k_wgrad_gemm_trio<128>, dim3(nb2 + nb4 + nb0), dim3(256), 0, s, a2, a4, a0, live2, live4);
-    GH_LAUNCH_CHECK("k_wgrad_gemm_trio");
-    if (info) {
-        const int inst = bn0 == 64 ? GLOWHIP_WGI_TRIO64 : GLOWHIP_WGI_TRIO128;
-        info[0] = WgradLaunchInfo{inst, sp4, per4, nb4, live4};
-        info[1] = WgradLaunchInfo{inst, sp0, per0, nb0, nb0};
-        info[2] = WgradLaunchInfo{inst, sp2, per2, nb2, live2};
+    int tiles[3], splits[3], per[3], live[3] = {}, nb[3] = {};
+    double work[3], wsum = 0.0;
+    for (int i = 0; i < n; ++i) {
+        tiles[i] = (g[i].Mpad / 128) * (g[i].Npad / (i == 1 ? bn0 : 128));
+        work[i] = (g[i].b_half ? 2.0 : 3.0) * g[i].Mpad * g[i].Npad;
+        wsum += work[i];
     }
-    *rj2 = WgradReduceJob{partial2, dw2, sp2, hid, hid, hid, hid, 0};
-    *rj4 = WgradReduceJob{partial4, dw4, sp4, m4, hid, m4_real, hid, 1};
-    *rj0 = WgradReduceJob{partial0, dw0, sp0, hid, n0, hid, n0_real, 0};
+    WgArgs a[3];
+    for (int i = 0; i < n; ++i) {
+        const int want = std::max(1, std::min(total, (int)(512.0 * (work[i] / wsum) / tiles[i] + 0.5)));
+        per[i] = (total + want - 1) / want;
+        splits[i] = (total + per[i] - 1) / per[i];
+        live[i] = tiles[i] * splits[i];
+        // f.0's blocks are the last of the grid and start on XCD 0 (xcd_remap): the ranges before them are rounded up to multiples of
+        // 8, their blocks past `live` have no tile (the guard in the kernel)
+        nb[i] = i == 1 ? live[i] : (live[i] + 7) / 8 * 8;
+        a[i] = wg_args(g[i], b, per[i], nb[i]);
+    }
+    const dim3 grid(nb[2] + nb[0] + nb[1]);      // f.2's blocks first, then f.4's, then f.0's
+    if (n == 2 && bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_pair<64>, grid, dim3(256), 0, s, a[0], a[1], live[0]);
+    else if (n == 2) hipLaunchKernelGGL(k_wgrad_gemm_pair<128>, grid, dim3(256), 0, s, a[0], a[1], live[0]);
+    else if (bn0 == 64) hipLaunchKernelGGL(k_wgrad_gemm_trio<64>, grid, dim3(256), 0, s, a[2], a[0], a[1], live[2], live[0]);
+    else hipLaunchKernelGGL(k_wgrad_gemm_trio<128>, grid, dim3(256), 0, s, a[2], a[0], a[1], live[2], live[0]);
+    GH_LAUNCH_CHECK(n == 3 ? "k_wgrad_gemm_trio" : "k_wgrad_gemm_pair");
+    const int inst = n == 3 ? (bn0 == 64 ? GLOWHIP_WGI_TRIO64 : GLOWHIP_WGI_TRIO128) : (bn0 == 64 ? GLOWHIP_WGI_PAIR64 : GLOWHIP_WGI_PAIR128);
+    for (int i = 0; i < n; ++i) {
+        if (info) info[i] = WgradLaunchInfo{inst, splits[i], per[i], nb[i], live[i]};
+        *defer[i] = WgradReduceJob{g[i].partial, g[i].dw, splits[i], g[i].Mpad, g[i].Npad, g[i].Mreal, g[i].Nreal, g[i].mode};
+    }
     return GLOWHIP_OK;
 }
 
-int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, float* partial, float* dw, int N, int HW,
-                      int Mpad, int Npad, int Mreal, int Nreal, int mode, hipStream_t s, float sh_scale, double* rowsum,
-                      const WgradTaps* taps, WgradReduceJob* defer, int b_valid, int b_half, int tiled, WgradLaunchInfo* info) {
-    const bool ps = tiled & 4;          // bit 2: A holds g * sh_scale * 2^11 (the backward k_cnet's g_u2 / g_u0)
-    const float a_pre = ps ? SH_LO_INV : sh_scale;
+int launch_wgrad_mfma(const WgradGemm& g, const WgradBatch& b, hipStream_t s, WgradReduceJob* defer, WgradLaunchInfo* info) {
+    const int N = b.N, HW = b.HW, Mpad = g.Mpad, Npad = g.Npad, b_valid = g.b_valid, b_half = g.b_half, tiled = g.layout;
+    const float sh_scale = b.sh_scale;
+    const WgradTaps* const taps = g.taps.operand >= 0 ? &g.taps : nullptr;
+    const bool ps = tiled & WGRAD_A_PRESCALED;
     GH_REQUIRE(!ps || !(taps && taps->operand == 0), "wgrad_mfma: a pre-scaled A is a plain one");
-    GH_REQUIRE(!tiled || (sh_scale > 0.f && !(tiled & ~7) && !((tiled & 1) && taps && taps->operand == 0) &&
-                          !((tiled & 2) && ((taps && taps->operand == 1) || b_valid > 0))),
+    GH_REQUIRE(!tiled || (sh_scale > 0.f && !(tiled & ~(WGRAD_A_TILED | WGRAD_B_TILED | WGRAD_A_PRESCALED)) && !((tiled & WGRAD_A_TILED) && taps && taps->operand == 0) &&
+                          !((tiled & WGRAD_B_TILED) && ((taps && taps->operand == 1) || b_valid > 0))),
                "wgrad_mfma: the pixel-tile-major layout is for plain operands of the split-half kernel");
-    GH_REQUIRE(!rowsum || sh_scale > 0.f, "wgrad_mfma: row sums only on the split-half kernel");
+    GH_REQUIRE(!g.rowsum || sh_scale > 0.f, "wgrad_mfma: row sums only on the split-half kernel");
     GH_REQUIRE(!b_half || (sh_scale > 0.f && b_valid <= 0 && !(taps && taps->operand == 1)), "wgrad_mfma: an fp16 operand B needs the split-half kernel and a plain B");
     GH_REQUIRE(b_valid <= 0 || (sh_scale > 0.f && taps && taps->operand == 0 && Npad == 64), "wgrad_mfma: b_valid only with gathered A and a 64-column B");
     GH_REQUIRE(!taps || (sh_scale > 0.f && taps->H * taps->W == HW && taps->W >= 4 && (taps->W & (taps->W - 1)) == 0 &&
@@ -1047,23 +1017,21 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
     int splits = std::max(1, std::min(total, ((wide ? 256 : 512) + tiles - 1) / tiles));   // 2 workgroups per CU (wide: 1, of twice the waves)
     const int per = (total + splits - 1) / splits;
     splits = (total + per - 1) / per;
-    const int vC = taps ? taps->C : 0, vH = taps ? taps->H : 0, vW = taps ? taps->W : 1, vs = taps ? taps->sign : 0;
-    const WgArgs wa{A, a_bs, B, b_bs, partial, HW, Mpad, Npad, total, per, sh_scale, a_pre, rowsum, vC, vH, vW, vs,
-                    b_valid > 0 ? b_valid : Npad, tiled, tiles * splits};
+    const WgArgs wa = wg_args(g, b, per, tiles * splits);
     int inst = 0;      // GLOWHIP_WGI_* of the instance launched (reported through `info` only)
 #define GH_WGI(bn, va, vb, bv, bh) (GLOWHIP_WGI_SH | ((bn) == 64 ? GLOWHIP_WGI_BN64 : 0) | ((va) ? GLOWHIP_WGI_VA : 0) | ((vb) ? GLOWHIP_WGI_VB : 0) | \
                                     ((bv) ? GLOWHIP_WGI_BV : 0) | ((bh) ? GLOWHIP_WGI_BH : 0))
 #define GH_WG(bn, va, vb) do { inst = GH_WGI(bn, va, vb, false, false); hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, vb>), dim3(tiles * splits), dim3(256), 0, s, wa); } while (0)
 #define GH_WGH(bn, va) do { inst = GH_WGI(bn, va, false, false, true); hipLaunchKernelGGL((k_wgrad_gemm_sh<bn, va, false, false, true>), dim3(tiles * splits), dim3(256), 0, s, wa); } while (0)
     if (b_half && ps && wide) {        // ... with 256-column tiles and eight waves, one workgroup per CU
-        GH_REQUIRE((tiled & 3) == 3, "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
+        GH_REQUIRE((tiled & WGRAD_A_TILED) && (tiled & WGRAD_B_TILED), "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
         constexpr int lds256 = wgrad_sh_lds_bytes<256, true>();
         (void)hipFuncSetAttribute((const void*)k_wgrad_gemm_ps512, hipFuncAttributeMaxDynamicSharedMemorySize, lds256);
         inst = GLOWHIP_WGI_PS512;
         hipLaunchKernelGGL(k_wgrad_gemm_ps512, dim3(tiles * splits), dim3(512), lds256, s, wa);
     } else
     if (b_half && ps) {                // f.2 behind the backward k_cnet: its own kernel
-        GH_REQUIRE((tiled & 3) == 3, "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
+        GH_REQUIRE((tiled & WGRAD_A_TILED) && (tiled & WGRAD_B_TILED), "wgrad_mfma: f.2's kernel reads pixel-tile-major operands");
         inst = bn128 ? GLOWHIP_WGI_PS128 : GLOWHIP_WGI_PS64;
         if (bn128) hipLaunchKernelGGL(k_wgrad_gemm_ps<128>, dim3(tiles * splits), dim3(256), 0, s, wa);
         else hipLaunchKernelGGL(k_wgrad_gemm_ps<64>, dim3(tiles * splits), dim3(256), 0, s, wa);
@@ -1091,21 +1059,21 @@ int launch_wgrad_mfma(const float* A, long a_bs, const float* B, long b_bs, floa
 #undef GH_WGI
     else if (bn128) {
         inst = GLOWHIP_WGI_F32_128;
-        hipLaunchKernelGGL(k_wgrad_gemm<128>, dim3(tiles * splits), dim3(256), 0, s, A, a_bs, B, b_bs, partial, HW, Mpad, Npad,
+        hipLaunchKernelGGL(k_wgrad_gemm<128>, dim3(tiles * splits), dim3(256), 0, s, g.A, g.a_bs, g.B, g.b_bs, g.partial, HW, Mpad, Npad,
                            total, per);
     } else {
         inst = GLOWHIP_WGI_F32_64;
-        hipLaunchKernelGGL(k_wgrad_gemm<64>, dim3(tiles * splits), dim3(256), 0, s, A, a_bs, B, b_bs, partial, HW, Mpad, Npad,
+        hipLaunchKernelGGL(k_wgrad_gemm<64>, dim3(tiles * splits), dim3(256), 0, s, g.A, g.a_bs, g.B, g.b_bs, g.partial, HW, Mpad, Npad,
                            total, per);
     }
     GH_LAUNCH_CHECK("k_wgrad_gemm");
     if (info) *info = WgradLaunchInfo{inst, splits, per, tiles * splits, tiles * splits};
     if (defer) {       // the caller reduces later (launch_wgrad_reduce_batched): `partial` must stay untouched until then
-        *defer = WgradReduceJob{partial, dw, splits, Mpad, Npad, Mreal, Nreal, mode};
+        *defer = WgradReduceJob{g.partial, g.dw, splits, Mpad, Npad, g.Mreal, g.Nreal, g.mode};
         return GLOWHIP_OK;
     }
-    hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv((long)Mreal * ((Nreal + 3) / 4), 256)), dim3(256), 0, s, partial, dw, splits, Mpad, Npad,
-                       Mreal, Nreal, mode);
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3(cdiv((long)g.Mreal * ((g.Nreal + 3) / 4), 256)), dim3(256), 0, s, g.partial, g.dw, splits, Mpad, Npad,
+                       g.Mreal, g.Nreal, g.mode);
     GH_LAUNCH_CHECK("k_wgrad_reduce");
     return GLOWHIP_OK;
 }
@@ -1123,11 +1091,6 @@ extern "C" int glowhip_debug_wgrad(const glowhip_wgrad_probe* d, glowhip_wgrad_i
     const int ngemm = d->op == GLOWHIP_WGRAD_MFMA ? 1 : d->op == GLOWHIP_WGRAD_PAIR ? 2 : d->op == GLOWHIP_WGRAD_TRIO ? 3 : 0;
     GH_REQUIRE(d->N >= 0 && d->HW > 0, "debug_wgrad: bad batch / map size");
     const glowhip_wgrad_gemm* g = d->gemm;
-    auto taps = [&](int i) { return WgradTaps{d->taps[i].operand, d->taps[i].C, d->taps[i].H, d->taps[i].W, d->taps[i].sign}; };
-    auto report = [&](int i, const WgradLaunchInfo& li) {
-        info->instance[i] = li.instance; info->splits[i] = li.splits; info->ktiles_per_split[i] = li.ktiles_per_split;
-        info->blocks[i] = li.blocks; info->live[i] = li.live;
-    };
     if (ngemm) {
         bool query = false;
         for (int i = 0; i < ngemm; ++i) {
@@ -1136,42 +1099,28 @@ extern "C" int glowhip_debug_wgrad(const glowhip_wgrad_probe* d, glowhip_wgrad_i
             query = query || !g[i].partial;
         }
         if (query) return GLOWHIP_OK;
-        for (int i = 0; i < ngemm; ++i) GH_REQUIRE(g[i].A && g[i].B && g[i].dw, "debug_wgrad: null operand / output");
-    }
-    switch (d->op) {
-    case GLOWHIP_WGRAD_MFMA: {
-        const WgradTaps t = taps(0);
-        WgradLaunchInfo li{};
-        GH_TRY(launch_wgrad_mfma((const float*)g[0].A, (long)g[0].a_bs, (const float*)g[0].B, (long)g[0].b_bs, g[0].partial, g[0].dw, d->N, d->HW,
-                                 g[0].Mpad, g[0].Npad, g[0].Mreal, g[0].Nreal, g[0].mode, s, d->sh_scale, g[0].rowsum, t.operand >= 0 ? &t : nullptr,
-                                 nullptr, g[0].b_valid, g[0].b_half, g[0].tiled, &li));
-        report(0, li);
-        return GLOWHIP_OK;
-    }
-    case GLOWHIP_WGRAD_PAIR:
-    case GLOWHIP_WGRAD_TRIO: {
-        const bool trio = d->op == GLOWHIP_WGRAD_TRIO;
-        const int hid = g[0].Npad;
-        GH_REQUIRE(g[1].Mpad == hid && (!trio || (g[2].Mpad == hid && g[2].Npad == hid)), "debug_wgrad: the grouped GEMMs share one hidden width");
-        GH_REQUIRE(!trio || (g[0].tiled == 2 && g[1].tiled == 5 && g[2].tiled == 7), "debug_wgrad: the three-GEMM launch has fixed operand layouts");
-        const WgradTaps t4 = taps(0), t0 = taps(1);
+        WgradGemm q[3];      // probe.gemm[i] + probe.taps[i] (f.2 has none) as the launchers' description
+        for (int i = 0; i < ngemm; ++i) {
+            GH_REQUIRE(g[i].A && g[i].B && g[i].dw, "debug_wgrad: null operand / output");
+            q[i] = WgradGemm{(const float*)g[i].A, (long)g[i].a_bs, (const float*)g[i].B, (long)g[i].b_bs, g[i].partial, g[i].dw,
+                             g[i].Mpad, g[i].Npad, g[i].Mreal, g[i].Nreal, g[i].mode};
+            q[i].rowsum = g[i].rowsum; q[i].b_valid = g[i].b_valid; q[i].b_half = g[i].b_half; q[i].layout = g[i].tiled;
+            if (i < 2) q[i].taps = WgradTaps{d->taps[i].operand, d->taps[i].C, d->taps[i].H, d->taps[i].W, d->taps[i].sign};
+        }
+        const WgradBatch wb{d->N, d->HW, d->sh_scale};
         WgradLaunchInfo li[3] = {};
         WgradReduceJobs rj{};
-        if (trio) {
-            rj.n = 3;
-            GH_TRY(launch_wgrad_trio((const float*)g[2].A, g[2].B, g[2].partial, g[2].dw, g[2].rowsum, (const float*)g[0].A, (long)g[0].a_bs, g[0].B,
-                                     g[0].partial, g[0].dw, g[0].Mpad, g[0].Mreal, (const float*)g[1].A, (const float*)g[1].B, (long)g[1].b_bs,
-                                     g[1].partial, g[1].dw, g[1].Npad, g[1].Nreal, d->N, d->HW, hid, d->sh_scale, g[1].rowsum, t4, t0,
-                                     &rj.job[2], &rj.job[0], &rj.job[1], s, li));
-        } else {
-            rj.n = 2;
-            GH_TRY(launch_wgrad_pair((const float*)g[0].A, (long)g[0].a_bs, g[0].B, g[0].partial, g[0].dw, g[0].Mpad, g[0].Mreal,
-                                     (const float*)g[1].A, (const float*)g[1].B, (long)g[1].b_bs, g[1].partial, g[1].dw, g[1].Npad, g[1].Nreal,
-                                     d->N, d->HW, hid, d->sh_scale, g[1].rowsum, t4, t0, g[0].tiled, g[1].tiled, &rj.job[0], &rj.job[1], s, li));
+        rj.n = ngemm;
+        WgradReduceJob* const defer[3] = {&rj.job[0], &rj.job[1], &rj.job[2]};
+        if (ngemm == 1) GH_TRY(launch_wgrad_mfma(q[0], wb, s, nullptr, li));
+        else GH_TRY(launch_wgrad_group(q, ngemm, wb, defer, s, li));
+        for (int i = 0; i < ngemm; ++i) {
+            info->instance[i] = li[i].instance; info->splits[i] = li[i].splits; info->ktiles_per_split[i] = li[i].ktiles_per_split;
+            info->blocks[i] = li[i].blocks; info->live[i] = li[i].live;
         }
-        for (int i = 0; i < rj.n; ++i) report(i, li[i]);
-        return launch_wgrad_reduce_batched(rj, s);
+        return ngemm == 1 ? GLOWHIP_OK : launch_wgrad_reduce_batched(rj, s);
     }
+    switch (d->op) {
     case GLOWHIP_WGRAD_SHIFT_EXPAND:
         GH_REQUIRE(g[0].A && g[0].dw && d->taps[0].C > 0 && d->taps[0].H * d->taps[0].W == d->HW && g[0].Mpad >= 9 * d->taps[0].C &&
                    (d->taps[0].sign == 1 || d->taps[0].sign == -1), "debug_wgrad: shift_expand arguments");

@@ -388,7 +388,7 @@ def reduce_cases():
 # the grouped launches: f.4's and f.0's GEMMs (k_wgrad_gemm_pair), with f.2's as the third (k_wgrad_gemm_trio)
 # ---------------------------------------------------------------------------------------------------------------------
 def expected_group_splits(total, hid, m4, n0, trio):
-    """The share arithmetic of launch_wgrad_pair / _trio: ((splits, per) of f.4, of f.0, of f.2 or None, and the fractional parts of
+    """The share arithmetic of launch_wgrad_group: ((splits, per) of f.4, of f.0, of f.2 or None, and the fractional parts of
     512 share / tiles that decided the rounding).  For choosing shapes and for the host yardstick; the GPU tests assert what
     glowhip_wgrad_info reports against it."""
     bn0 = 64 if n0 == 64 else 128
