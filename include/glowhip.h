@@ -678,7 +678,7 @@ enum {
     GLOWHIP_DBG_CNET_ROWS_SHIFT     = 22,         /* bits 22..24 = 1, 2 or 4: that many row splits of k_cnet (value << SHIFT) */
     GLOWHIP_DBG_CNET_128_ONLY       = 0x2000000,  /* k_cnet with 128-pixel tiles only */
     GLOWHIP_DBG_CNET_64             = 0x4000000,  /* k_cnet with 64-pixel tiles wherever supported */
-    GLOWHIP_DBG_CNET_CHAIN          = 0x8000000,  /* a FlowStep's finishing inside the next FlowStep's k_cnet (off by default: measured slower) */
+    /* 0x8000000: reserved, formerly GLOWHIP_DBG_CNET_CHAIN (removed; last present in commit dbe339a) */
     GLOWHIP_DBG_CFINISH_BLOCK_ORDER = 0x10000000, /* the finishing kernel takes its pixel chunks in block order, not the XCD-affine order (A/B) */
     GLOWHIP_DBG_PACK_ONE_STREAM     = 0x20000000, /* glowhip_plan_pack entirely on the caller's stream, no side-stream fork (A/B) */
     GLOWHIP_DBG_TRAIN_PER_LAYER_FWD = 0x40000000, /* glowhip_glow_forward_train on the per-layer kernels, no taping k_cnet (A/B, parity tests) */

@@ -210,7 +210,6 @@ class DBG(enum.IntFlag):
     LU_WORKGROUP = 0x200000
     CNET_128_ONLY = 0x2000000
     CNET_64 = 0x4000000
-    CNET_CHAIN = 0x8000000
     CFINISH_BLOCK_ORDER = 0x10000000
     PACK_ONE_STREAM = 0x20000000
     TRAIN_PER_LAYER_FWD = 0x40000000

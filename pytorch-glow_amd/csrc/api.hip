@@ -40,7 +40,6 @@ void glowhip_debug_force_tail_tile(int v) {
     d.cnet_rows = (v >> GLOWHIP_DBG_CNET_ROWS_SHIFT) & 7;
     d.cnet_128_only = bit(GLOWHIP_DBG_CNET_128_ONLY);
     d.cnet_64 = bit(GLOWHIP_DBG_CNET_64);
-    d.cnet_chain = bit(GLOWHIP_DBG_CNET_CHAIN);
     d.cfinish_block_order = bit(GLOWHIP_DBG_CFINISH_BLOCK_ORDER);
     d.pack_one_stream = bit(GLOWHIP_DBG_PACK_ONE_STREAM);
     d.pack_unfused = bit(GLOWHIP_DBG_PACK_UNFUSED);

@@ -18,7 +18,7 @@
 //     stays busy through what used to be separate phases.
 // Output: the partial sums `hpart` / `hup` / `hdn` of k_cnet at MS = 1 with 128-pixel tiles -- k_cfinish does not know the difference.
 // Instances (launch_cnet1w): product forward / inverse, the training step's taping forward (MODE 1) and its input-gradient launch
-// (MODE 2: the transposed network) for the C = 12 levels; no chained prologue, no row split (the workgroup owns all h2 rows of its
+// (MODE 2: the transposed network) for the C = 12 levels; no row split (the workgroup owns all h2 rows of its
 // tile), one group of f.4 output channels.
 #include "sh.h"
 #include <algorithm>
@@ -887,7 +887,6 @@ static int cnet1w_instance(const CnetArgs& a, const CnetGeo& g) {      // 0: non
 }
 
 bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g) {
-    if (a.pre_on) return false;
     if ((a.tape_h1 || a.bwd) && (!a.tape_h1 || !a.tape_h2 || !a.mask1 || !a.mask2 || g.HW % 128 != 0)) return false;      // taping / backward: whole 32-pixel tiles of the batch per wave
     if (g.NI != 1) return false;                     // (tiles of whole small images stay on k_cnet: no level that large has them)
     const int inst = cnet1w_instance(a, g);

@@ -31,8 +31,8 @@ __device__ __forceinline__ FinSrc fin_src(const CnetPending& p, int N, int H, in
 // Partial sums of h = f(z1) for coupling channel c at pixel p of image n: (se, so) = the shift (and, affine, the scale logit) before
 // bias and exp(3 logs).  Every load is unconditional (clamped index, selected value), so a caller that gathers several elements
 // before using any has all of their loads in flight together.
-// (a function, not a plain dereference at the six call sites: written that way, the chained-prologue instances of k_cnet come out
-// with their gather loads scheduled differently from the code that was measured)
+// (a function, not a plain dereference at the six call sites: it dates from k_cnet's window-time finishing, removed since -- see
+// docs/DESIGN_HISTORY.md, "The chained k_cnet prologue" -- and stays so that k_cfinish and k_chanmix_bwd remain the measured code)
 __device__ __forceinline__ float fin_ld(const float* p) { return *p; }
 template <int MSV, bool HALO = true>      // MSV > 0: f.MS known at compile time (loops unrolled: every load of the element in
                                           // flight at once); HALO = false: the caller knows f.halos is false

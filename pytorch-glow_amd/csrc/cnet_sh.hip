@@ -40,7 +40,6 @@ namespace glowhip {
 
 // (FinSrc, fin_src, fin_gather_t: cnet_fin.h -- shared with the backward's k_chanmix_bwd)
 
-// PRE: the launch may finish the previous step while it builds its window (a.pre_on); without it none of that code is compiled in
 // NG: f.4 output-channel groups (compile time: with one group nothing of the group loop survives -- as a run-time count it kept
 // the h2 accumulators alive through P4 and cost the level-1 instance 88 bytes of spills)
 // MODE 1 (TAPE), the training forward (plan_train.hip): h1 and h2 also go to memory as FP16, pixel-tile-major
@@ -56,7 +55,7 @@ namespace glowhip {
 // weights, 1x1 hidden -> hidden with f.2's, 3x3 hidden -> C/2 with f.0's): x = d L / d(f.4 output), the "activation" of the
 // first two layers is  g_u = g_h * (h > 0) * exp(3 logs)  (the scale folded into the weight image's rows, the mask from the
 // tape's bit masks), and g_u2 / g_u0 go to memory as fp32, pixel-tile-major like the tape, for the weight-gradient GEMMs.  Needs HW % 32 == 0.
-template <int HID, int MS, int UPW, int PXT, bool PRE, int NG = 1, int MODE = 0>
+template <int HID, int MS, int UPW, int PXT, int NG = 1, int MODE = 0>
 __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     constexpr bool TAPE = MODE == 1, BWD = MODE == 2, STORE = MODE != 0;
 #ifdef CN_DBG_NOF32
@@ -70,7 +69,6 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     constexpr bool MSKST = TAPE;
 #endif
     const long P_all = (long)a.N * g.HW;          // pixels of the batch (row stride of the bit masks)
-    const bool pre_on = PRE && a.pre_on;
     constexpr int NPT = PXT / 32;                    // pixel tiles of the workgroup: 4 (128 pixels) or 2 (64 pixels)
     constexpr int ADEPTH = (HID / MS / 32) * NPT / 8 == 8 ? 1 : 2;       // prefetch distance of P2's A fragments (k-steps)
     constexpr bool MIXSPLIT = PXT == 64 && NG == 1;  // v_fma_mix_f32 in the split epilogues where registers are to spare (sh.h)
@@ -103,7 +101,6 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     float* t_rs2 = t_b0 + HID;
     float* t_b2 = t_rs2 + MR;
     float* t_rs4 = t_b2 + MR;
-    long long* ld_slot = reinterpret_cast<long long*>((reinterpret_cast<size_t>(t_rs4 + g.Mpad4) + 7) & ~(size_t)7);   // [8 waves][2]
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -167,77 +164,24 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     const int nwin = g.NI * g.Wpx;
     const int nslots = g.nchunk * nwin;
     // window slot e -> (inside the image?, address of its first channel); the address is always valid (clamped)
-    int slot_r, slot_c, slot_sub;      // window row / column / sub-image of the slot slot_src was last asked about
     auto slot_src = [&](int e, bool& in, int& ch) {
         // (three divisions by run-time constants, on the way to the kernel's FIRST loads: one v_mul_hi each instead of ~25 instructions)
         ch = (int)__umulhi((unsigned)e, g.m_nwin);
         const int rem = e - ch * nwin;
         const int sub = (int)__umulhi((unsigned)rem, g.m_Wpx), wp = rem - sub * g.Wpx;
         const int r = (int)__umulhi((unsigned)wp, g.m_WP), c = wp - r * g.WP;
-        slot_r = r; slot_c = c; slot_sub = sub;
         const int yy = y0 - 1 + r, xx = c - 1;
         const long n = n0 + sub;
         in = yy >= 0 && yy < H && xx >= 0 && xx < W && n < a.N;
         return a.x + (n < a.N ? n : (long)a.N - 1) * a.x_bs + min(max(yy, 0), H - 1) * W + min(max(xx, 0), W - 1);
     };
-    // With `pre`: the window pixels that lie inside an image, as a compact list k = (sub-image * nrows + row) * W + x over the window
-    // rows [rlo, rlo + nrows); KP = that count rounded up to whole waves.
-    const int rlo = y0 == 0 ? 1 : 0;
-    const int nrows = min(g.R + 2, H - y0 + 1) - rlo;
-    const int nin = g.NI * nrows * W;
-    const int KP = (nin + 63) & ~63;
-    const int per_sub = nrows << g.wshift;
-    // pixel k of the list -> image n, pixel index p, own pixel of this tile?
-    auto pix = [&](int k, long& n, int& p, bool& own, int& sub) {
-        sub = k >= per_sub ? 1 : 0;
-        const int kk = k - sub * per_sub;
-        const int r = rlo + (kk >> g.wshift);                     // window row
-        n = n0 + sub;
-        p = (y0 - 1 + r) * W + (kk & (W - 1));
-        own = r >= 1 && r <= g.R;
-        return k < nin && n < a.N;
-    };
-    // ---- the first round of global loads is REQUESTED before the tables are copied (one trip to memory for both): the window
-    // values, or -- chained launch -- everything the finishing of the previous step reads
-    constexpr int PU = 3;      // elements per thread and round of the finishing
-    const FinSrc pf = pre_on ? fin_src(a.pre, a.N, H, W, HW, g.wshift) : FinSrc{};
-    const int pCh = pf.paired ? pf.Cout / 2 : pf.Cout, pC = 2 * pCh;
-    const int ptotal = pCh * KP;
-    float pse[PU], pso[PU], pzin[PU], pz1[PU], pkb[PU][4], pkm[PU][4];      // pkb: f.4 bias / scale (even, odd); pkm: mixer bias / scale
-    int pcc[PU], pkq[PU];
-    auto pre_gather = [&](int e0, auto halo_c) {
-        constexpr bool HALO = decltype(halo_c)::value;
-#pragma unroll
-        for (int u = 0; u < PU; ++u) {
-            const int e = min(e0 + 512 * u, ptotal - 1);
-            const int c = __builtin_amdgcn_readfirstlane(e / KP);           // (a wave's 64 elements share the channel: 64 | KP)
-            const int k = e - c * KP;
-            long n; int p, sub; bool own;
-            const bool ok = pix(k, n, p, own, sub);
-            const long nc = ok ? n : n0;
-            const int pc = ok ? p : (y0 - 1 + rlo) * W;                     // (clamped: a pixel of the list's first row)
-            const float* zp = a.pre.z + nc * a.pre.z_bs;
-            pz1[u] = zp[(long)c * HW + pc];
-            pzin[u] = zp[(long)(pCh + c) * HW + pc];
-            fin_gather_t<MS, HALO>(pf, nc, c, pc, pse[u], pso[u]);       // (pre.MS == MS: checked by the launcher)
-            pcc[u] = c; pkq[u] = k;
-            const int ce = pf.paired ? 2 * c : c, co = ce + (pf.paired ? 1 : 0);
-            pkb[u][0] = pf.bias[ce]; pkb[u][1] = pf.scale[ce]; pkb[u][2] = pf.bias[co]; pkb[u][3] = pf.scale[co];
-            const bool an = !a.pre_mix.reverse && a.pre_mix.C;
-            pkm[u][0] = an ? a.pre_mix.bias[c] : 0.f; pkm[u][1] = an ? a.pre_mix.scale[c] : 1.f;
-            pkm[u][2] = an ? a.pre_mix.bias[pCh + c] : 0.f; pkm[u][3] = an ? a.pre_mix.scale[pCh + c] : 1.f;
-        }
-    };
+    // ---- the first round of global loads, the window values, is REQUESTED before the tables are copied (one trip to memory for both)
     float v0[8];
-    if (!pre_on) {     // (chained launches build the window from the state they finish themselves)
+    {
         bool in; int ch;
         const float* xin = slot_src(min(tid, nslots - 1), in, ch);
 #pragma unroll
         for (int q = 0; q < 8; ++q) v0[q] = xin[(long)min(ch * 8 + q, a.Cin - 1) * HW];
-    } else if (pf.halos) {
-        pre_gather(tid, std::true_type{});
-    } else {
-        pre_gather(tid, std::false_type{});
     }
     // The activations travel NEGATED from the first epilogue on (sh.h nrelu_bits): h1 and h2 sit in LDS as -h1, -h2, the h2 and T
     // accumulators hold the negated sums.  So the tables carry the signs: f.0 (-rs0, -b0) turns the true accumulator into -t;
@@ -265,138 +209,12 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     for (int i = 0; i < N2; ++i)
         if (tid + 512 * i < MR) { t_rs2[tid + 512 * i] = canon_nan(tv2[i]); t_b2[tid + 512 * i] = canon_nan(-tvb[i]); }
     if (tid < g.Mpad4) t_rs4[tid] = canon_nan(-tv4);
-    float* nz = nullptr;     // with `pre`: z1 of the freshly finished state, fp32 [Cin][KP]
-    if (pre_on) {
-        // ---- finish the PREVIOUS step on the window pixels: coupling (+ log-det for the tile's own pixels), then the channel mixer;
-        // the result of the own pixels goes to pre_z_new, z1 of all of them to `nz` (hbuf is free at this point).  Same arithmetic
-        // as k_cfinish, bit for bit.  Built for latency: ONE round of global loads (requested above), the mixer's matrix staged in
-        // LDS meanwhile and read as wave-uniform 16-byte broadcasts, log-det terms summed per wave (fixed point: any grouping
-        // gives the same bits).
-        const FinSrc& f = pf;
-        const int Ch = pCh, C = pC;
-        float* pv = reinterpret_cast<float*>(hbuf);          // [C][KP] staged values
-        nz = pv + C * KP;
-        const int CP = (C + 3) & ~3;                          // matrix row stride (16-byte aligned rows)
-        float* pm = nz + a.Cin * KP;                          // [C][CP]
-        if (a.pre_mix.matrix)
-            for (int e = tid; e < C * C; e += 512) { const int o = e / C; pm[o * CP + (e - o * C)] = a.pre_mix.matrix[e]; }
-        GH_STAMP(22);
-        long long ldq[2] = {0, 0};
-        for (int e0 = tid; e0 < ptotal; e0 += 512 * PU) {
-            if (e0 != tid) {                                  // (a second round only for shapes beyond the product's)
-                if (f.halos) pre_gather(e0, std::true_type{}); else pre_gather(e0, std::false_type{});
-            }
-#pragma unroll
-            for (int u = 0; u < PU; ++u) {
-                if (e0 + 512 * u >= ptotal) continue;
-                const int c = pcc[u], k = pkq[u];
-                long n; int p, sub; bool own;
-                const bool ok = pix(k, n, p, own, sub);
-                float v1 = 0.f, v2 = 0.f;
-                if (ok) {
-                    long long lq = 0;
-                    float bad = 0.f;
-                    const float zres = fin_apply_k(f, pse[u], pso[u], pzin[u], pkb[u][0], pkb[u][1], pkb[u][2], pkb[u][3], lq, bad);
-                    if (own && blockIdx.y == 0) {            // own pixel (not a halo row), once per tile: counts for the log-det
-                        if (bad != 0.f) fix_flag_nonfinite(a.acc, n, a.N, bad);
-                        ldq[sub] += lq;
-                    }
-                    if (!a.pre_mix.reverse && a.pre_mix.C) {             // ActNorm of the mixer on both halves, staged for its matrix / gather
-                        v1 = (pz1[u] + pkm[u][0]) * pkm[u][1];
-                        v2 = (zres + pkm[u][2]) * pkm[u][3];
-                    } else { v1 = pz1[u]; v2 = zres; }
-                }
-                pv[c * KP + k] = v1;
-                pv[(Ch + c) * KP + k] = v2;
-            }
-        }
-        if (f.paired && blockIdx.y == 0) {                    // per-wave sums of the fixed-point terms, one atomic per wave and image
-#pragma unroll
-            for (int sb = 0; sb < 2; ++sb) {
-                if (sb >= g.NI) continue;
-                long long v = ldq[sb];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-                if (lane == 0) ld_slot[wid * 2 + sb] = v;     // added to the sample's accumulator at the END of the kernel: an
-                                                              // atomic in flight here would sit in front of every later wait
-            }
-        }
-        GH_STAMP(23);
-        __syncthreads();
-        GH_STAMP(24);
-        // mixer: item = (group of OB output channels, 64 pixels); the matrix rows of a wave's output channels are wave-uniform
-        constexpr int OB = 6;
-        const int npb = KP >> 6, nog = (C + OB - 1) / OB;
-        for (int it = wid; it < nog * npb; it += 8) {
-            const int og = it / npb, pb = it - og * npb;
-            const int k = pb * 64 + lane;
-            float r[OB], osc[OB], obi[OB];
-            const bool rev = a.pre_mix.reverse && a.pre_mix.C;
-#pragma unroll
-            for (int j = 0; j < OB; ++j) {        // inverse ActNorm of the outputs (reverse flow): requested before the products
-                const int o = min(og * OB + j, C - 1);
-                osc[j] = rev ? a.pre_mix.scale[o] : 1.f;
-                obi[j] = rev ? a.pre_mix.bias[o] : 0.f;
-            }
-            if (a.pre_mix.matrix) {   // same operation order as k_chanmix / k_cfinish: r = fma(m[o][i], v[i], r), i ascending
-#pragma unroll
-                for (int j = 0; j < OB; ++j) r[j] = 0.f;
-                const float* mrow[OB];
-#pragma unroll
-                for (int j = 0; j < OB; ++j) mrow[j] = pm + min(og * OB + j, C - 1) * CP;
-                int i = 0;
-                for (; i + 4 <= C; i += 4) {
-                    float vi[4];
-#pragma unroll
-                    for (int t = 0; t < 4; ++t) vi[t] = pv[(i + t) * KP + k];
-#pragma unroll
-                    for (int j = 0; j < OB; ++j) {
-                        const f32x4_t m4 = *reinterpret_cast<const f32x4_t*>(mrow[j] + i);
-#pragma unroll
-                        for (int t = 0; t < 4; ++t) r[j] = fmaf(m4[t], vi[t], r[j]);
-                    }
-                }
-                for (; i < C; ++i) {
-                    const float vi = pv[i * KP + k];
-#pragma unroll
-                    for (int j = 0; j < OB; ++j) r[j] = fmaf(mrow[j][i], vi, r[j]);
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < OB; ++j) {
-                    const int o = min(og * OB + j, C - 1);
-                    r[j] = pv[(a.pre_mix.gather ? a.pre_mix.gather[o] : o) * KP + k];
-                }
-            }
-            long n; int p, sub; bool own;
-            const bool ok = pix(k, n, p, own, sub);
-            const bool wr = ok && own && blockIdx.y == 0;
-            float* zo = a.pre_z_new + (wr ? n : n0) * a.pre_z_new_bs + (wr ? p : 0);
-#pragma unroll
-            for (int j = 0; j < OB; ++j) {
-                const int o = og * OB + j;
-                if (rev) r[j] = r[j] * osc[j] - obi[j];
-                if (o < C && wr) zo[(long)o * HW] = r[j];
-            }
-#pragma unroll
-            for (int j = 0; j < OB; ++j) {
-                const int o = og * OB + j;
-                if (o < a.Cin && o < C) nz[o * KP + k] = ok ? r[j] : 0.f;
-            }
-        }
-        GH_STAMP(25);
-        __syncthreads();
-    }
     GH_STAMP(26);
     for (int e = tid; e < nslots; e += 512) {
         bool in; int ch;
         const float* xin = slot_src(e, in, ch);
         float v[8];
-        if (nz) {
-            const int k = in ? ((slot_sub * nrows + slot_r - rlo) << g.wshift) + slot_c - 1 : 0;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) v[q] = nz[min(ch * 8 + q, a.Cin - 1) * KP + k];
-        } else if (e == tid) {      // (nz == nullptr <=> !pre_on: v0 was loaded)
+        if (e == tid) {      // (requested above)
 #pragma unroll
             for (int q = 0; q < 8; ++q) v[q] = v0[q];
         } else {
@@ -1069,10 +887,6 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
         if (pass + 1 < g.npass) __syncthreads();
     }
     }      // output-channel groups
-    if (pre_on && blockIdx.y == 0 && lane < g.NI && (a.pre.mode == TAIL_AFFINE_FWD || a.pre.mode == TAIL_AFFINE_REV)) {
-        const long long v = ld_slot[wid * 2 + lane];         // (written by this wave's lane 0 in the window phase)
-        if (v != 0 && n0 + lane < a.N) atomicAdd(a.acc + (n0 + lane), (unsigned long long)v);
-    }
     GH_STAMP(21);
     GH_WG_END();
 }
@@ -1173,9 +987,8 @@ size_t cnet_scratch_floats_per_sample(int H, int W, int Cout) {
 template <int HID, int MS, int UPW, int PXT>
 static int launch_cnet_inst2(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {     // two groups of f.4 output channels (C = 96)
     const size_t lds = cnet_lds_bytes(g, HID);
-    GH_REQUIRE(!a.pre_on, "cnet: no chained launch with output-channel groups");
-    (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT, false, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT, false, 2>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
+    (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT, 2>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet");
     return GLOWHIP_OK;
 }
@@ -1183,13 +996,8 @@ static int launch_cnet_inst2(const CnetArgs& a, const CnetGeo& g, hipStream_t s)
 template <int HID, int MS, int UPW, int PXT>
 static int launch_cnet_inst(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
     const size_t lds = cnet_lds_bytes(g, HID);
-    if (a.pre_on) {
-        (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT, true>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
-    } else {
-        (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT, false>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
-    }
+    (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet");
     return GLOWHIP_OK;
 }
@@ -1218,7 +1026,7 @@ static bool cnet_select(const CnetArgs& a, CnetChoice* out) {
     if (sw.cnet_64) use64 = ok64;              // testing: 64-pixel tiles wherever they exist
     // k_cnet1w (one wave per SIMD, cnet1w_sh.hip): which launches may go to it at all (the shape's say is cnet1w_takes), and whether
     // the 128-pixel tiles it needs may be preferred for it
-    const bool c1w_kind = !a.pre_on && !sw.no_cnet1w && !(a.bwd && sw.no_cnet1w_bwd);      // (no_cnet1w_bwd: no backward instance, A/B)
+    const bool c1w_kind = !sw.no_cnet1w && !(a.bwd && sw.no_cnet1w_bwd);      // (no_cnet1w_bwd: no backward instance, A/B)
     const bool c1w_tile = c1w_kind && ok128 && !sw.cnet_64;
     // taping / backward launches: the 128-pixel instance is at the register limit and spills once the stores and the sign words
     // are in (184 B); 64-pixel tiles measured 2 % faster on the training step
@@ -1259,8 +1067,8 @@ bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N) {
 template <int HID, int MS, int PXT, int MODE>
 static int launch_cnet_tape(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
     const size_t lds = cnet_lds_bytes(g, HID);
-    (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, 1, PXT, false, 1, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((k_cnet<HID, MS, 1, PXT, false, 1, MODE>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
+    (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, 1, PXT, 1, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((k_cnet<HID, MS, 1, PXT, 1, MODE>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet (taping)");
     return GLOWHIP_OK;
 }
@@ -1273,9 +1081,8 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     GH_REQUIRE(cnet_select(a, &c), "cnet: unsupported shape");
     const CnetGeo& g = c.g;
     const int ms = c.ms, upw = c.upw;
-    GH_REQUIRE(!a.pre_on || a.pre.MS == ms, "cnet: a chained launch needs the previous step's row split");
     const bool tape = a.tape_h1 != nullptr;
-    GH_REQUIRE(!tape || (a.tape_h2 && a.mask1 && a.mask2 && !a.pre_on && g.HW % 32 == 0 &&
+    GH_REQUIRE(!tape || (a.tape_h2 && a.mask1 && a.mask2 && g.HW % 32 == 0 &&
                          cnet_tape_instance(a.hidden, ms, upw, g.pxt, g.ng)),
                "cnet: no taping / backward instance for this launch");
     int rc = GLOWHIP_EINVAL;
@@ -1305,8 +1112,7 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     if (out) {
         out->scratch = a.scratch; out->MS = ms; out->tiles = g.tiles; out->R = g.R; out->NI = g.NI; out->lpxt = g.lpxt;
         out->bias = a.bias; out->scale = a.scale; out->mode = a.mode; out->Cout = a.Cout;
-        out->z = a.pre_on ? a.pre_z_new : a.z_in;
-        out->z_bs = a.pre_on ? a.pre_z_new_bs : a.z_in_bs;
+        out->z = a.z_in; out->z_bs = a.z_in_bs;
         out->one_wave = c.one_wave ? 1 : 0;
     }
     return GLOWHIP_OK;
@@ -1346,18 +1152,6 @@ int launch_cnet(const CnetArgs& a, hipStream_t s) {
     CnetPending p{};
     GH_TRY(launch_cnet_main(a, s, &p));
     return launch_cnet_finish(a, p, s);
-}
-
-// window-time finishing stages [C][window] + [C][C] + [Cin][window] floats in the (then idle) activation buffer
-bool cnet_pre_supported(int Cin, int H, int W, int hidden, int Cout, int C) {
-    if (C > 96 || cnet_groups(Cout) != 1) return false;
-    for (int pxt : {128, 64}) {
-        CnetGeo g;
-        if (!cnet_geo(Cin, H, W, hidden, Cout, 0, pxt, &g)) continue;
-        const size_t kp = ((size_t)g.NI * (g.R + 2) * W + 63) / 64 * 64;      // upper bound of the in-image window pixels
-        if (((size_t)C * kp + (size_t)Cin * kp + (size_t)C * (C + 3) + 32) * sizeof(float) > (size_t)CN_HBUF) return false;
-    }
-    return true;
 }
 
 }  // namespace glowhip

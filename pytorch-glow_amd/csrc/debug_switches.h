@@ -23,7 +23,6 @@ struct DebugSwitches {
     int cnet_rows = 0;               // row splits of k_cnet: 0 automatic, else 1 / 2 / 4
     bool cnet_128_only = false;      // 128-pixel tiles wherever they exist
     bool cnet_64 = false;            // 64-pixel tiles wherever they exist
-    bool cnet_chain = false;         // a step's finishing inside the next step's k_cnet (off by default: measured slower)
     bool cfinish_block_order = false;   // the finishing kernel takes its pixel chunks in block order, not the XCD-affine order
     bool no_cnet1w = false;          // no k_cnet1w (one wave per SIMD): k_cnet takes its launches
     bool no_cnet1w_bwd = false;      // no backward instance of k_cnet1w

@@ -150,35 +150,25 @@ static int run_dnet_reverse(glowhip_plan* p, const void* packed, int li, int lj,
 }
 
 // ---- the one-kernel coupling network (cnet_sh.hip).  A FlowStep is k_cnet (partial sums of h = f(z1)) + a finishing step
-// (coupling, log-det, channel mixer); the finishing step of step k runs either as its own kernel or inside step k+1's k_cnet
-// while that builds its window ("pending").
+// (coupling, log-det, channel mixer), which runs as its own kernel right behind it.
 // which instance of k_cnet ran (run-time evidence for the tests): "variant:k_cnet<hidden,row split,pixel tile>"
 static void count_cnet_variant(glowhip_plan* p, const CnetArgs& c, const CnetPending& pend) {
     char name[64];
     snprintf(name, sizeof name, "variant:k_cnet%s<%d,%d,%d>", pend.one_wave ? "1w" : "", c.hidden, pend.MS, 1 << pend.lpxt);
     count_launch(p, name);
 }
-// One FlowStep's k_cnet launch (`pending`: it also finishes the previous step) and, with `finish`, this step's finishing kernel.
-static int run_cnet_step(glowhip_plan* p, const CnetArgs& c, bool pending, bool finish, CnetPending* pend, hipStream_t s) {
+// One FlowStep's k_cnet launch and its finishing kernel.
+static int run_cnet_step(glowhip_plan* p, const CnetArgs& c, hipStream_t s) {
+    CnetPending pend{};
     {
         ScopedTimer t(p, GLOWHIP_K_CNET, 1, s);
-        count_launch(p, pending ? "k_cnet+prev_finish" : "k_cnet");
-        GH_TRY(launch_cnet_main(c, s, pend));
-        count_cnet_variant(p, c, *pend);
+        count_launch(p, "k_cnet");
+        GH_TRY(launch_cnet_main(c, s, &pend));
+        count_cnet_variant(p, c, pend);
     }
-    if (!finish) return GLOWHIP_OK;
     ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
     count_launch(p, c.mix.C ? "k_cfinish+mixer" : "k_cfinish");
-    return launch_cnet_finish(c, *pend, s);
-}
-// may the finishing step of layer A run inside layer B's k_cnet?  (Off by default: the window-time finishing costs a workgroup
-// ~25 k cycles of dependent global round trips with 8 waves, more than the ~10 us finishing kernel it saves; kept behind
-// glowhip_debug_force_tail_tile(0x8000000) with its bitwise-equality test.)
-static bool cnet_chain(const glowhip_plan* p, const LayerPlan& A, const LayerPlan& B) {
-    const glowhip_layer_desc& a = A.d; const glowhip_layer_desc& b = B.d;
-    return debug_switches().cnet_chain && !debug_switches().no_mixer_fusion && a.kind == GLOWHIP_LAYER_FLOWSTEP && b.kind == GLOWHIP_LAYER_FLOWSTEP &&
-           cnet_runs(p, A) && cnet_runs(p, B) && a.C == b.C && a.H == b.H && a.W == b.W && a.coupling == b.coupling &&
-           cnet_pre_supported(b.C / 2, b.H, b.W, b.hidden, B.Cout, b.C);
+    return launch_cnet_finish(c, pend, s);
 }
 
 // The coupling network of a FlowStep that neither k_cnet nor the deep-level kernels take (odd hidden widths, tiny images, the
@@ -316,8 +306,6 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
     SqueezeFold fold{};      // set by a skipped squeeze layer, consumed by the next layer's k_chanmix
     const int nl = (int)p->layers.size();
     bool premixed = false;   // `cur` already holds this step's ActNorm + permutation output (applied by the previous tail)
-    bool pending = false;    // the previous FlowStep's k_cnet has run, its finishing step has not (cnet_chain)
-    CnetPending pend{};
     int scr_i = 0;
     long cur_bs = 0;         // batch stride of `cur` when it is Split2d's z1 left where it lies (0: dense)
     // does the Squeeze2d at layer `ls` fold into the next layer's mixer?
@@ -356,7 +344,7 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 if (li != nl - 1) dst = w.bufB;
             }
             const int Ch = d.C / 2;
-            if (d.kind == GLOWHIP_LAYER_FLOWSTEP && dnet_runs(p, L) && !premixed && !pending) {
+            if (d.kind == GLOWHIP_LAYER_FLOWSTEP && dnet_runs(p, L) && !premixed) {
                 // ---- deep level: the whole run of same-shape FlowSteps on the per-layer SH2 kernels (dnet_sh.hip)
                 const int lj = dnet_run_end(p, li, +1);
                 float* S = other_buf(w, cur);
@@ -367,40 +355,30 @@ static int run_forward(glowhip_plan* p, const void* packed, const float* x, cons
                 continue;
             }
             if (d.kind == GLOWHIP_LAYER_FLOWSTEP && cnet_runs(p, L)) {
-                // ---- k_cnet path.  `cur` holds the input of this step's mixer, or -- `premixed` -- its output, or -- `pending` --
-                // the state the PREVIOUS step's k_cnet read, whose finishing (coupling + this step's mixer) this launch does itself
+                // ---- k_cnet path.  `cur` holds the input of this step's mixer, or -- `premixed` -- its output
                 float* scratch = (scr_i ^= 1) ? w.h1 : w.h2;
                 CnetArgs c = cnet_base(L, packed, N, 0, scratch, w.acc);
-                if (pending) {
-                    float* nxt = other_buf(w, cur);
-                    c.pre_on = 1; c.pre = pend; c.pre_mix = mixer_fwd(L, packed); c.pre_z_new = nxt; c.pre_z_new_bs = chw;
-                    cur = nxt;
-                } else {
-                    if (!premixed) {
-                        ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
-                        apply_fold(m, fold);
-                        GH_TRY(run_chanmix(p, m, s));
-                        cur = dst;
-                    }
-                    c.x = cur; c.x_bs = chw; c.z_in = cur; c.z_in_bs = chw;
+                if (!premixed) {
+                    ChanMixArgs m = chanmix_fwd_args(L, packed, N, cur, chw, dst);
+                    apply_fold(m, fold);
+                    GH_TRY(run_chanmix(p, m, s));
+                    cur = dst;
                 }
+                c.x = cur; c.x_bs = chw; c.z_in = cur; c.z_in_bs = chw;
                 premixed = false;
-                const bool chain = li + 1 < nl && cnet_chain(p, L, p->layers[li + 1]);
+                // the step is finished right behind its k_cnet: with the NEXT step's mixer when that is a same-shape FlowStep
                 float* out = (li == nl - 1) ? z_out : const_cast<float*>(cur);
-                if (!chain) {   // the step is finished right behind its k_cnet: with the NEXT step's mixer when that is a same-shape FlowStep
-                    c.z_out = out; c.z_out_bs = chw;
-                    if (li + 1 < nl - 1 && !debug_switches().no_mixer_fusion && d.C <= 96) {
-                        const LayerPlan& Ln = p->layers[li + 1];
-                        const glowhip_layer_desc& dn = Ln.d;
-                        if (dn.kind == GLOWHIP_LAYER_FLOWSTEP && dn.C == d.C && dn.H == d.H && dn.W == d.W) {
-                            c.mix = mixer_fwd(Ln, packed);
-                            premixed = true;
-                        }
+                c.z_out = out; c.z_out_bs = chw;
+                if (li + 1 < nl - 1 && !debug_switches().no_mixer_fusion && d.C <= 96) {
+                    const LayerPlan& Ln = p->layers[li + 1];
+                    const glowhip_layer_desc& dn = Ln.d;
+                    if (dn.kind == GLOWHIP_LAYER_FLOWSTEP && dn.C == d.C && dn.H == d.H && dn.W == d.W) {
+                        c.mix = mixer_fwd(Ln, packed);
+                        premixed = true;
                     }
                 }
-                GH_TRY(run_cnet_step(p, c, pending, !chain, &pend, s));
-                pending = chain;
-                if (!chain) cur = out;
+                GH_TRY(run_cnet_step(p, c, s));
+                cur = out;
                 continue;
             }
             if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
@@ -446,8 +424,6 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
     const float* cur = z;
     const int nl = (int)p->layers.size();
     int ke = 0;
-    bool pending = false;    // as in run_forward
-    CnetPending pend{};
     int scr_i = 0;
     for (int li = nl - 1; li >= 0; --li) {
         const LayerPlan& L = p->layers[li];
@@ -465,7 +441,7 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
             GH_TRY(launch_squeeze(cur, nullptr, dst, N, d.C * 4, d.H / 2, d.W / 2, 2, 1, s));
         } else if (d.kind == GLOWHIP_LAYER_FLOWSTEP) {
             float* z2 = dst + (long)Ch * HW;
-            if (dnet_runs(p, L) && !pending) {
+            if (dnet_runs(p, L)) {
                 const int lj = dnet_run_end(p, li, -1);
                 float* S = other_buf(w, cur);
                 GH_TRY(run_dnet_reverse(p, packed, li, lj, cur, S, N, w, s));
@@ -475,37 +451,21 @@ static int run_reverse(glowhip_plan* p, const void* packed, const float* z, cons
                 continue;
             }
             if (cnet_runs(p, L)) {
-                // coupling^-1, permutation^-1 and ActNorm^-1 by the finishing step -- run by the next-executed step's k_cnet where
-                // the two chain, by the finishing kernel otherwise
+                // coupling^-1, permutation^-1 and ActNorm^-1 by the finishing kernel
                 float* scratch = (scr_i ^= 1) ? w.h1 : w.h2;
                 CnetArgs c = cnet_base(L, packed, N, 1, scratch, w.acc);
-                if (pending) {
-                    float* nxt = other_buf(w, cur);
-                    c.pre_on = 1; c.pre = pend; c.pre_mix = mixer_rev(p->layers[li + 1], packed); c.pre_z_new = nxt; c.pre_z_new_bs = chw;
-                    cur = nxt;
-                } else {
-                    c.x = cur; c.x_bs = chw; c.z_in = cur; c.z_in_bs = chw;
-                }
-                const bool chain = d.C <= 96 && li - 1 >= 0 && cnet_chain(p, L, p->layers[li - 1]) && p->layers[li - 1].d.C <= 96;
-                float* fout = nullptr;
-                if (!chain && d.C <= 96) {
-                    fout = (li == 0) ? x_out : other_buf(w, cur);
+                c.x = cur; c.x_bs = chw; c.z_in = cur; c.z_in_bs = chw;
+                if (d.C <= 96) {
+                    float* fout = (li == 0) ? x_out : other_buf(w, cur);
                     c.z_out = fout; c.z_out_bs = chw; c.mix = mixer_rev(L, packed);
-                }
-                GH_TRY(run_cnet_step(p, c, pending, fout != nullptr, &pend, s));      // (its mixer is set: the finishing counts as "k_cfinish+mixer")
-                pending = chain;
-                if (fout) {
+                    GH_TRY(run_cnet_step(p, c, s));      // (its mixer is set: the finishing counts as "k_cfinish+mixer")
                     cur = fout;
-                } else if (!chain) {
+                } else {
                     // wider than the finishing kernel's mixer (additive coupling, 96 < C <= 112: L.cnet holds, the fused mixer
                     // does not): coupling^-1 alone by the finishing kernel, then permutation^-1 + ActNorm^-1 by k_chanmix
                     float* mid = other_buf(w, cur);
                     c.z_out = mid; c.z_out_bs = chw;
-                    {
-                        ScopedTimer t(p, GLOWHIP_K_CFINISH, 0, s);
-                        count_launch(p, "k_cfinish");
-                        GH_TRY(launch_cnet_finish(c, pend, s));
-                    }
+                    GH_TRY(run_cnet_step(p, c, s));
                     float* out = (li == 0) ? x_out : other_buf(w, mid);
                     ChanMixArgs m = chanmix_rev_args(L, packed, N, mid, mid + (long)Ch * HW, chw, out);
                     GH_TRY(run_chanmix(p, m, s));

@@ -126,8 +126,8 @@ int cnet_groups(int Cout);            // f.4 runs in that many groups of Cout / 
 size_t cnet_w4_bytes(int hidden, int Cout);   // all groups' images, one after the other
 size_t cnet_scratch_floats(int N, int H, int W, int Cout);   // partial-sum scratch (floats) for batch N; <= N * the per-sample bound
 size_t cnet_scratch_floats_per_sample(int H, int W, int Cout);
-// What a k_cnet launch leaves behind for whoever finishes the step -- the finishing kernel, or the NEXT step's k_cnet while it
-// builds its window: the partial sums of h = f(z1) in `scratch`, how they are tiled, and the coupling they feed.
+// What a k_cnet launch leaves behind for the finishing kernel (launch_cnet_main hands it to launch_cnet_finish): the partial sums
+// of h = f(z1) in `scratch`, how they are tiled, and the coupling they feed.
 struct CnetPending {
     const float* scratch; int MS, tiles, R, NI, lpxt;
     const float* bias; const float* scale;       // f.4 bias (Cout), exp(3 logs) (Cout) of that step
@@ -139,7 +139,7 @@ struct CnetPending {
 //   forward: the NEXT step's  y = M ((z + bias) * scale);   reverse: THIS step's  x = (M z) * scale - bias
 struct CnetMixer { int C, reverse; const float* bias; const float* scale; const float* matrix; const int32_t* gather; };
 struct CnetArgs {
-    const float* x; long x_bs;                   // z1: channels [0, Cin) of (N, *, H, W), batch stride x_bs (unused with `pre`)
+    const float* x; long x_bs;                   // z1: channels [0, Cin) of (N, *, H, W), batch stride x_bs
     const void* w0; const void* w2; const void* w4;   // SH2 images (REPACK_SH2_FIRST / _GEMM / _TAIL)
     int N, Cin, H, W, hidden, Cout;
     float* scratch;                              // cnet_scratch_floats(N, ...) floats
@@ -150,10 +150,6 @@ struct CnetArgs {
     float* z_out; long z_out_bs;                 // result (may be z_in: a workgroup reads all of its own pixels before it writes)
     unsigned long long* acc;
     CnetMixer mix;                               // applied by this step's finishing kernel (mix.C = 0: only z2 is updated)
-    // ---- optional: finish the PREVIOUS step while the window is built (one launch per FlowStep instead of two).  The
-    // workgroup applies `pre`'s coupling and `pre_mix` to every window pixel (its own and the halo), takes z1 of the result as its
-    // f.0 input and writes the result of its OWN pixels to pre_z_new (a buffer other than pre.z: neighbours still read that).
-    int pre_on; CnetPending pre; CnetMixer pre_mix; float* pre_z_new; long pre_z_new_bs;
     // ---- optional: the training tape (plan_train.hip).  k_cnet stores h1 = relu(f.0 ...) and h2 = relu(f.2 ...) as FP16
     // (N, hidden, H, W) from its epilogues (the pointers are typed float* for the backward launch, which stores fp32 through them); the finishing kernel stores hout = (f.4 + bias) * exp(3 logs) as (N, Cout, H, W) and,
     // when it mixes out of place (z_out != z_in), ALSO writes the coupled z2 back into z_in -- which then holds this step's
@@ -169,14 +165,13 @@ struct CnetArgs {
     // ---- k_cnet / k_cnet1w take (CnetArgs, CnetGeo) as kernel arguments: the geometry starts at offset sizeof(CnetArgs), and the
     // kernels read it with 16- and 32-byte scalar loads.  The size is held at a multiple of 128 bytes (asserted below) so that those
     // loads keep their places inside 64-byte lines (docs/DESIGN_HISTORY.md, "Fused finishing and the row-split ...": measured)
-    char pad_to_128[8];
+    char pad_to_128[24];
 };
 static_assert(sizeof(CnetArgs) % 128 == 0, "CnetGeo follows CnetArgs in the kernel arguments: keep it on a 128-byte boundary (pad_to_128)");
 int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out);            // k_cnet only; *out describes its partial sums
 int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s);     // the finishing kernel for those sums
 int launch_cnet(const CnetArgs& a, hipStream_t s);                                   // both
 bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N);        // a taping instance of k_cnet exists for the shape
-bool cnet_pre_supported(int Cin, int H, int W, int hidden, int Cout, int C);         // window-time finishing fits the LDS
 
 // ---- FlowSteps of the deep levels (C >= 192, a few hundred pixels per launch): one launch per LAYER, rows split over workgroups,
 // activations between the launches as ready-made SH2 B operands in L2 (dnet_sh.hip) -------------------------------------------

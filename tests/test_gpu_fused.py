@@ -25,7 +25,7 @@ def path(request):
 
 
 def ncnet(counts):
-    return counts.get("k_cnet", 0) + counts.get("k_cnet+prev_finish", 0)
+    return counts.get("k_cnet", 0)
 
 
 def nfinish(counts):
@@ -204,31 +204,30 @@ def test_cnet_every_row_split(ms, image, L, hidden, batch):
         assert f"variant:k_cnet<512,{ms},64>" in got, (ms, got)
 
 
-@pytest.mark.parametrize("tile", [0x2000000, 0x4000000])
-@pytest.mark.parametrize("chained", [True, False])
-def test_cnet_tile_sizes_and_chaining(tile, chained):
-    """128- and 64-pixel tiles forced (the heuristic picks by grid size), each with the finishing step as its own kernel (the
-    default) and chained into the next FlowStep's launch (0x8000000): the two orders of evaluation must agree BIT FOR BIT -- same arithmetic, log-det terms
-    summed as fixed point -- and both match the oracle."""
-    outs = []
-    CHAIN = _lib.DBG.CNET_CHAIN
-    for flags in [tile | (CHAIN if chained else 0), tile | (0 if chained else CHAIN)]:
-        with _lib.debug_flags(flags):
-            cfg = O.default_cfg(image_shape=(32, 32, 3), hidden_channels=128, K=3, L=2, batch=5)
-            sd = O.seeded_state_dict(cfg, seed=77, invconv_perturb=0.02)
-            g = torch.Generator().manual_seed(77)
-            x = torch.rand(5, 3, 32, 32, generator=g); noise = torch.rand(5, 3, 32, 32, generator=g) / 256
-            glow = make_glow(cfg, sd, 5)
-            plan = glow.flow.plan_for(dev(x)); plan.launch_counts(reset=True)
-            z, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
-            counts = plan.launch_counts(reset=True)
-            xr = glow.reverse_flow(z, None, eps=[torch.zeros(5, 6, 16, 16, device=z.device)])
-            outs.append((z.clone(), nll.clone(), xr.clone(), counts))
-    (z0, n0, x0, c0), (z1, n1, x1, c1) = outs
-    assert ("k_cnet+prev_finish" in c0) != ("k_cnet+prev_finish" in c1), (c0, c1)
-    assert torch.equal(z0, z1) and torch.equal(n0, n1) and torch.equal(x0, x1)
+@pytest.mark.parametrize("px", [128, 64])
+def test_cnet_tile_sizes(px):
+    """128- and 64-pixel tiles forced (the heuristic picks by grid size): z and nll of the forward pass and the way back (the decode
+    of the oracle's z, the split half drawn as zeros) match the oracle, and the run-time counters say that every k_cnet launch, both
+    ways, ran the forced tile's instance."""
+    cfg = O.default_cfg(image_shape=(32, 32, 3), hidden_channels=128, K=3, L=2, batch=5)
+    sd = O.seeded_state_dict(cfg, seed=77, invconv_perturb=0.02)
+    g = torch.Generator().manual_seed(77)
+    x = torch.rand(5, 3, 32, 32, generator=g); noise = torch.rand(5, 3, 32, 32, generator=g) / 256
+    eps = [torch.zeros(5, 6, 16, 16)]
     z_ref, nll_ref, _ = O.glow_forward(x, noise, sd, cfg)
-    close(z0, z_ref, 1e-4, what="z"); close(n0, nll_ref, 1e-4, what="nll")
+    x_ref = O.glow_reverse(z_ref, sd, cfg, eps)
+    with _lib.debug_flags(_lib.DBG.CNET_128_ONLY if px == 128 else _lib.DBG.CNET_64):
+        glow = make_glow(cfg, sd, 5)
+        plan = glow.flow.plan_for(dev(x)); plan.launch_counts(reset=True)
+        z, nll, _ = glow.normal_flow(dev(x), None, noise=dev(noise))
+        fwd = plan.launch_counts(reset=True)
+        xr = glow.reverse_flow(dev(z_ref), None, eps=[dev(e) for e in eps])
+        rev = plan.launch_counts(reset=True)
+    close(z, z_ref, 1e-4, what="z"); close(nll, nll_ref, 1e-4, what="nll"); close(xr, x_ref, 1e-4, what="decode")
+    for counts in (fwd, rev):      # six FlowSteps each way, every one on the forced tile's instance (hidden 128, any row split)
+        variants = {k: v for k, v in counts.items() if k.startswith("variant:")}
+        assert ncnet(counts) == 6 and sum(variants.values()) == 6, counts
+        assert all(k.startswith("variant:k_cnet<128,") and k.endswith(f",{px}>") for k in variants), (px, variants)
 
 
 @pytest.mark.parametrize("case", range(14))
