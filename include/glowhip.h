@@ -832,6 +832,59 @@ typedef struct glowhip_conv_info {
 } glowhip_conv_info;
 int glowhip_debug_conv(const glowhip_conv_probe* d, glowhip_conv_info* info, glowhip_stream_t stream);
 
+/* Testing hook: ONE launch of the fp32 code between the MFMA launches of a forward / decode / training step -- the finishing kernel
+ * of the coupling network (csrc/cnet_sh.hip k_cfinish, csrc/cnet_fin.h), the channel mixer (csrc/pointwise.hip) and the deep levels'
+ * finishing and first launches (csrc/dnet_sh.hip k_dn_fin, k_dn_prep) -- on operands the caller lays out, through the launchers
+ * the plan itself calls; tests/test_gpu_fin_kernels.py holds every instance to fp64 with it.  Not part of the operator surface.  All
+ * pointers are device pointers except the probe itself; strides are in elements.  Operands per op (unused ones NULL / 0):
+ *   CFINISH  N, C (channels of the state = 2 Ch), H, W, Cout, hidden, mode (TailMode 1..4: AFFINE_FWD, AFFINE_REV, ADD_FWD, ADD_REV),
+ *            MS (row-split copies in the scratch), tile (64 / 128 pixels per k_cnet tile); scratch (the partial sums k_cnet would have
+ *            left: csrc/cnet_fin.h documents the layout), scratch_floats (what the caller allocated: refused below the plan's own
+ *            size, which info reports), bias / scale (f.4 bias, exp(3 logs): Cout each), z_in / z_out with z_in_bs / z_out_bs, acc
+ *            ((2 + ACC_EXTRA) N 64-bit words: accumulator row 0, the flag row, ACC_EXTRA more accumulator rows; zeroed by the caller),
+ *            the mixer (mix_C = 0: none) and tape_hout.  The tiling (R, NI, tiles, lpxt) comes from cnet_geo(Ch, H, W, hidden, Cout,
+ *            N, tile) through the helper launch_cnet_main fills its hand-over with; then launch_cnet_finish.  Block order:
+ *            GLOWHIP_DBG_CFINISH_BLOCK_ORDER of glowhip_debug_force_tail_tile, as for a plan.  A NULL scratch launches nothing:
+ *            info reports the tiling and the plan's scratch size alone
+ *   CHANMIX  every field of ChanMixArgs (csrc/kernels.h): in_a / in_b with in_a_bs / in_b_bs and Ca, out / out_bs, mix_bias /
+ *            mix_scale / mix_matrix / mix_gather, mix_reverse, N, C, HW (H and W are not read), sq_src / sq_u8 / sq_div / sq_noise /
+ *            sq_W / sq_bs and the Philox draw rng_on / rng_seed / rng_call / rng_scale; then launch_chanmix
+ *   DN_FIN   a DnetLevel (N, C, H, W, hidden, Cout, state with z_in_bs = its batch stride, dn_scratch) over caller memory; ks, bias /
+ *            scale, mode, acc ((2 + ACC_EXTRA) N words as above), mix_bias / mix_scale = the next step's ActNorm (NULL: none) and
+ *            want_u; then dnet_finish
+ *   DN_PREP  the same level; src / src_bs, mix_bias / mix_scale, mix_reverse; then dnet_prep
+ * In the two DN ops info reports where dn_carve puts `part`, `u` and `ypad` inside the level scratch (byte offsets; plane sizes in
+ * fp16 elements) and the level's scratch bytes (scratch_bytes); a NULL dn_scratch launches nothing and fills only those.
+ * Whatever a launcher refuses is refused here: GLOWHIP_EINVAL, no launch. */
+enum { GLOWHIP_FIN_CFINISH = 0, GLOWHIP_FIN_CHANMIX = 1, GLOWHIP_FIN_DN_FIN = 2, GLOWHIP_FIN_DN_PREP = 3 };
+/* glowhip_fin_info.kernel: the kernel that ran */
+enum { GLOWHIP_FNI_CFINISH = 1,         /* k_cfinish<pxb, msv, halo> */
+       GLOWHIP_FNI_CHANMIX16 = 2, GLOWHIP_FNI_CHANMIX64 = 3, GLOWHIP_FNI_CHANMIX_WIDE = 4,
+       GLOWHIP_FNI_DN_FIN = 5, GLOWHIP_FNI_DN_PREP = 6 };
+typedef struct glowhip_fin_probe {
+    int32_t op, N, C, H, W, HW, Cout, hidden, mode, MS, tile, ks, want_u, Ca;
+    int32_t mix_C, mix_reverse, sq_u8, sq_W, rng_on, reserved;
+    float sq_div, rng_scale;
+    uint64_t rng_seed, rng_call;
+    int64_t z_in_bs, z_out_bs, in_a_bs, in_b_bs, out_bs, sq_bs, src_bs, scratch_floats;
+    const float* scratch; const float* bias; const float* scale; const float* z_in; float* z_out; void* acc; float* tape_hout;
+    const float* mix_bias; const float* mix_scale; const float* mix_matrix; const int32_t* mix_gather;
+    const float* in_a; const float* in_b; float* out; const void* sq_src; const float* sq_noise;
+    float* state; void* dn_scratch; const float* src;
+} glowhip_fin_probe;
+typedef struct glowhip_fin_info {
+    int32_t kernel, grid[3], lds_bytes;
+    int32_t pxb, msv, halo;            /* CFINISH: the template arguments of the instance */
+    int32_t xcd_affine;                /* CFINISH: the launch took its pixel chunks in the XCD-affine order */
+    int32_t stage_matrix;              /* CHANMIX (k_chanmix<16 / 64>): the matrix goes through LDS */
+    int32_t R, NI, tiles, lpxt;        /* CFINISH: the tiling the hook derived */
+    int32_t reserved;
+    int64_t scratch_floats;            /* CFINISH: the floats the plan allocates for this launch's partial sums */
+    int64_t scratch_bytes;             /* DN: the bytes of the level scratch for N samples */
+    int64_t part_off, u_off, ypad_off, u_plane, ypad_plane;      /* DN */
+} glowhip_fin_info;
+int glowhip_debug_fin(const glowhip_fin_probe* d, glowhip_fin_info* info, glowhip_stream_t stream);
+
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per
  * convolution).  Writes a NUL-terminated description into buf. */
 int glowhip_plan_describe(const glowhip_plan* plan, char* buf, size_t buf_bytes);

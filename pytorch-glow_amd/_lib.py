@@ -170,6 +170,30 @@ CONV_WIDE, CONV_FIRST, CONV_DIRECT, CONV_TAIL = range(4)
 CVI_WIDE, CVI_GEMM_GLDS, CVI_FIRST, CVI_DIRECT, CVI_TAIL, CVI_TAIL_DMA = range(1, 7)
 TAIL_PLAIN, TAIL_AFFINE_FWD, TAIL_AFFINE_REV, TAIL_ADD_FWD, TAIL_ADD_REV, TAIL_SPLIT_FWD, TAIL_SPLIT_REV = range(7)
 
+
+
+class FinProbe(ctypes.Structure):
+    """Mirror of ``glowhip_fin_probe`` (the testing hook ``glowhip_debug_fin``)."""
+    _fields_ = [(n, c_int32) for n in ("op", "N", "C", "H", "W", "HW", "Cout", "hidden", "mode", "MS", "tile", "ks", "want_u", "Ca",
+                                       "mix_C", "mix_reverse", "sq_u8", "sq_W", "rng_on", "reserved")] + \
+               [("sq_div", c_float), ("rng_scale", c_float), ("rng_seed", ctypes.c_uint64), ("rng_call", ctypes.c_uint64)] + \
+               [(n, ctypes.c_int64) for n in ("z_in_bs", "z_out_bs", "in_a_bs", "in_b_bs", "out_bs", "sq_bs", "src_bs", "scratch_floats")] + \
+               [(n, c_void_p) for n in ("scratch", "bias", "scale", "z_in", "z_out", "acc", "tape_hout", "mix_bias", "mix_scale", "mix_matrix",
+                                        "mix_gather", "in_a", "in_b", "out", "sq_src", "sq_noise", "state", "dn_scratch", "src")]
+
+
+class FinInfo(ctypes.Structure):
+    """Mirror of ``glowhip_fin_info``."""
+    _fields_ = [("kernel", c_int32), ("grid", c_int32 * 3)] + \
+               [(n, c_int32) for n in ("lds_bytes", "pxb", "msv", "halo", "xcd_affine", "stage_matrix", "R", "NI", "tiles", "lpxt", "reserved")] + \
+               [(n, ctypes.c_int64) for n in ("scratch_floats", "scratch_bytes", "part_off", "u_off", "ypad_off", "u_plane", "ypad_plane")]
+
+
+# glowhip.h GLOWHIP_FIN_* (op) and GLOWHIP_FNI_* (kernel); csrc/common.h ACC_EXTRA
+FIN_CFINISH, FIN_CHANMIX, FIN_DN_FIN, FIN_DN_PREP = range(4)
+FNI_CFINISH, FNI_CHANMIX16, FNI_CHANMIX64, FNI_CHANMIX_WIDE, FNI_DN_FIN, FNI_DN_PREP = range(1, 7)
+ACC_EXTRA = 7
+
 EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256      # glowhip.h GLOWHIP_EVAL_MAX_*
 
 
@@ -280,6 +304,7 @@ SIGNATURES = {
     "glowhip_debug_wgrad": (c_int, [POINTER(WgradProbe), POINTER(WgradInfo), _P]),
     "glowhip_debug_bwd": (c_int, [POINTER(BwdProbe), POINTER(BwdInfo), _P]),
     "glowhip_debug_conv": (c_int, [POINTER(ConvProbe), POINTER(ConvInfo), _P]),
+    "glowhip_debug_fin": (c_int, [POINTER(FinProbe), POINTER(FinInfo), _P]),
     "glowhip_plan_tape_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_train_workspace_bytes": (c_size_t, [_P, c_int]),
     "glowhip_glow_forward_train": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, _P, _P, _P, c_int, _P, c_size_t, _P,

@@ -4,6 +4,7 @@
 
 #include "kernels.h"
 #include "conv_mfma.h"
+#include "cnet_geo.h"
 #include "invconv_lu.h"
 #include "debug_switches.h"
 
@@ -273,6 +274,102 @@ int glowhip_debug_conv(const glowhip_conv_probe* d, glowhip_conv_info* info, glo
     default: break;
     }
     GH_REQUIRE(false, "debug_conv: unknown op %d", d->op);
+    return GLOWHIP_EINVAL;
+}
+
+// Testing hook (include/glowhip.h): one launch of the finishing kernel, the channel mixer or the deep levels' FIN / PREP on the
+// caller's operands.  No second path: it decodes the probe, derives the tiling with the producer's own code, calls the launcher the
+// plan calls, and copies what the launcher reported.
+int glowhip_debug_fin(const glowhip_fin_probe* d, glowhip_fin_info* info, glowhip_stream_t stream) {
+    GH_REQUIRE(d && info, "debug_fin: null probe / info");
+    hipStream_t s = (hipStream_t)stream;
+    *info = glowhip_fin_info{};
+    FinLaunchInfo li{};
+    auto report = [&]() {
+        info->kernel = li.kernel; info->grid[0] = li.grid[0]; info->grid[1] = li.grid[1]; info->grid[2] = li.grid[2];
+        info->lds_bytes = li.lds_bytes; info->pxb = li.pxb; info->msv = li.msv; info->halo = li.halo; info->xcd_affine = li.xcd_affine;
+        info->stage_matrix = li.stage_matrix;
+    };
+    GH_REQUIRE(d->N > 0 && d->C > 0, "debug_fin: bad shape N=%d C=%d", d->N, d->C);
+    switch (d->op) {
+    case GLOWHIP_FIN_CFINISH: {
+        GH_REQUIRE(d->mode >= TAIL_AFFINE_FWD && d->mode <= TAIL_ADD_REV, "debug_fin: coupling modes only (mode %d)", d->mode);
+        const bool paired = d->mode == TAIL_AFFINE_FWD || d->mode == TAIL_AFFINE_REV;
+        GH_REQUIRE(d->C % 2 == 0 && d->Cout == (paired ? d->C : d->C / 2), "debug_fin: Cout=%d does not fit C=%d in mode %d", d->Cout, d->C, d->mode);
+        GH_REQUIRE(d->tile == 64 || d->tile == 128, "debug_fin: k_cnet tiles are 64 or 128 pixels (tile %d)", d->tile);
+        GH_REQUIRE(d->MS == 1 || d->MS == 2 || d->MS == 4, "debug_fin: row split %d", d->MS);
+        GH_REQUIRE(d->H > 0 && d->W > 0, "debug_fin: bad map");
+        CnetGeo g;
+        GH_REQUIRE(cnet_geo(d->C / 2, d->H, d->W, d->hidden, d->Cout, d->N, d->tile, &g), "cnet: unsupported shape");
+        CnetPending p{};
+        cnet_pending_tiling(g, d->MS, &p);
+        info->R = p.R; info->NI = p.NI; info->tiles = p.tiles; info->lpxt = p.lpxt;
+        info->scratch_floats = (int64_t)cnet_scratch_floats(d->N, d->H, d->W, d->Cout);
+        if (!d->scratch) return GLOWHIP_OK;
+        const long chw = (long)d->C * d->H * d->W;
+        GH_REQUIRE(d->scratch_floats >= info->scratch_floats, "debug_fin: scratch below the plan's %ld floats", (long)info->scratch_floats);
+        GH_REQUIRE(d->bias && d->scale && d->z_in && d->z_out && d->acc, "debug_fin: cfinish null operand / output");
+        GH_REQUIRE(d->z_in_bs >= chw && d->z_out_bs >= chw, "debug_fin: batch stride below one sample");
+        GH_REQUIRE(d->mix_C == 0 || (d->mix_bias && d->mix_scale), "debug_fin: a mixer has its ActNorm tables");
+        GH_REQUIRE(!(d->mix_matrix && d->mix_gather), "debug_fin: a mixer is a matrix, a gather or neither");
+        p.scratch = d->scratch; p.bias = d->bias; p.scale = d->scale; p.mode = d->mode; p.Cout = d->Cout; p.z = d->z_in; p.z_bs = (long)d->z_in_bs;
+        CnetArgs a{};
+        a.N = d->N; a.Cin = d->C / 2; a.H = d->H; a.W = d->W; a.hidden = d->hidden; a.Cout = d->Cout; a.mode = d->mode;
+        a.z_in = d->z_in; a.z_in_bs = (long)d->z_in_bs; a.z_out = d->z_out; a.z_out_bs = (long)d->z_out_bs;
+        a.acc = (unsigned long long*)d->acc; a.tape_hout = d->tape_hout;
+        a.mix = CnetMixer{d->mix_C, d->mix_reverse, d->mix_bias, d->mix_scale, d->mix_matrix, d->mix_gather};
+        GH_TRY(launch_cnet_finish(a, p, s, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_FIN_CHANMIX: {
+        GH_REQUIRE(d->HW > 0 && d->Ca >= 0 && d->Ca <= d->C, "debug_fin: chanmix bad shape");
+        GH_REQUIRE(d->out && (d->sq_src || ((d->in_a || d->Ca == 0) && (d->in_b || d->Ca == d->C))), "debug_fin: chanmix null operand / output");
+        GH_REQUIRE(!d->mix_bias == !d->mix_scale, "debug_fin: the ActNorm is a bias and a scale table, or neither");
+        GH_REQUIRE(!(d->mix_matrix && d->mix_gather), "debug_fin: a mixer is a matrix, a gather or neither");
+        GH_REQUIRE(d->out_bs >= (long)d->C * d->HW && (d->sq_src || ((d->Ca == 0 || d->in_a_bs >= (long)d->Ca * d->HW) &&
+                   (d->Ca == d->C || d->in_b_bs >= (long)(d->C - d->Ca) * d->HW))), "debug_fin: batch stride below one sample");
+        GH_REQUIRE(!d->sq_src || (d->sq_W > 0 && d->sq_W % 2 == 0 && d->HW % (d->sq_W / 2) == 0 && (d->sq_bs == 0 || d->sq_bs >= (long)d->C * d->HW) &&
+                                  (!d->sq_u8 || d->sq_div > 0.f)), "debug_fin: bad squeezed view");
+        ChanMixArgs a{};
+        // (a half without channels is never read: it gets the other half's valid address, as the plan passes one tensor twice)
+        a.in_a = d->in_a ? d->in_a : d->in_b; a.in_a_bs = (long)d->in_a_bs; a.in_b = d->in_b ? d->in_b : d->in_a; a.in_b_bs = (long)d->in_b_bs; a.Ca = d->Ca;
+        a.out = d->out; a.out_bs = (long)d->out_bs; a.bias = d->mix_bias; a.scale = d->mix_scale; a.matrix = d->mix_matrix; a.gather = d->mix_gather;
+        a.reverse = d->mix_reverse; a.N = d->N; a.C = d->C; a.HW = d->HW;
+        a.sq_src = d->sq_src; a.sq_u8 = d->sq_u8; a.sq_div = d->sq_div; a.sq_noise = d->sq_noise; a.sq_W = d->sq_W; a.sq_bs = (long)d->sq_bs;
+        a.sq_rng = RngSpec{d->rng_on, (unsigned long long)d->rng_seed, (unsigned long long)d->rng_call, d->rng_scale};
+        if (a.sq_src) { a.in_a = a.in_b = reinterpret_cast<const float*>(d->sq_src); }      // (pointers the kernel forms but never reads)
+        GH_TRY(launch_chanmix(a, s, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_FIN_DN_FIN:
+    case GLOWHIP_FIN_DN_PREP: {
+        GH_REQUIRE(d->H > 0 && d->W > 0 && dnet_supported(d->C, d->H, d->W, d->hidden, d->Cout), "dnet: unsupported shape");
+        DnetLevel L{d->N, d->C, d->H, d->W, d->hidden, d->Cout, d->state, (long)d->z_in_bs, d->dn_scratch};
+        DnetScratchLayout lay;
+        dnet_scratch_layout(L, &lay);
+        info->part_off = lay.part_off; info->u_off = lay.u_off; info->ypad_off = lay.ypad_off; info->u_plane = lay.u_plane; info->ypad_plane = lay.ypad_plane;
+        info->scratch_bytes = (int64_t)d->N * (int64_t)dnet_scratch_bytes_per_sample(d->C, d->H, d->W, d->hidden, d->Cout);
+        if (!d->dn_scratch) return GLOWHIP_OK;
+        GH_REQUIRE(d->state && d->z_in_bs >= (long)d->C * d->H * d->W, "debug_fin: dnet state / batch stride");
+        GH_REQUIRE(!d->mix_bias == !d->mix_scale, "debug_fin: the ActNorm is a bias and a scale table, or neither");
+        if (d->op == GLOWHIP_FIN_DN_FIN) {
+            GH_REQUIRE(d->mode >= TAIL_AFFINE_FWD && d->mode <= TAIL_ADD_REV, "debug_fin: coupling modes only (mode %d)", d->mode);
+            const bool paired = d->mode == TAIL_AFFINE_FWD || d->mode == TAIL_AFFINE_REV;
+            GH_REQUIRE(d->Cout == (paired ? d->C : d->C / 2), "debug_fin: Cout=%d does not fit C=%d in mode %d", d->Cout, d->C, d->mode);
+            GH_REQUIRE(d->ks >= 1 && d->ks <= DNET_KS_MAX && d->bias && d->scale && d->acc, "debug_fin: dn_fin ks / null operand");
+            GH_TRY(dnet_finish(L, d->ks, d->bias, d->scale, d->mode, (unsigned long long*)d->acc, d->mix_bias, d->mix_scale, d->want_u, s, &li));
+        } else {
+            GH_REQUIRE(d->src && d->src_bs >= (long)d->C * d->H * d->W, "debug_fin: dn_prep source / batch stride");
+            GH_TRY(dnet_prep(L, d->src, (long)d->src_bs, d->mix_bias, d->mix_scale, d->mix_reverse, s, &li));
+        }
+        report();
+        return GLOWHIP_OK;
+    }
+    default: break;
+    }
+    GH_REQUIRE(false, "debug_fin: unknown op %d", d->op);
     return GLOWHIP_EINVAL;
 }
 

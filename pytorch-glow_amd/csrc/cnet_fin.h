@@ -131,8 +131,12 @@ struct CfinArgs {
 // state this kernel writes -- runs on XCD t % 8.  So block b = 8 s + x takes a pixel chunk of a tile t with t % 8 == x: partial
 // sums and state then travel between kernels through ONE XCD's L2 instead of through memory (halo rows excepted).
 // lr = log2(chunks per k_cnet tile).
+// The 256-pixel instances ALWAYS run in block order: k_cnet's tiles are 64 or 128 pixels (lpxt <= 7), a 256-pixel chunk spans two
+// tiles or more, and k_cfinish takes the affine order only for lpxt >= log2(PXB) = 8.  Nothing is lost: such a chunk has no one
+// XCD to be near.
+__host__ __device__ __forceinline__ bool cfin_whole_groups(int nblk, int lr) { return (nblk & ((8 << lr) - 1)) == 0; }
 __device__ __forceinline__ int cfin_chunk(int b, int nblk, int lr) {
-    if (nblk & ((8 << lr) - 1)) return b;                 // not whole groups of 8 tiles: identity
+    if (!cfin_whole_groups(nblk, lr)) return b;           // not whole groups of 8 tiles: identity
     const int x = b & 7, s = b >> 3;
     return ((((s >> lr) << 3) + x) << lr) + (s & ((1 << lr) - 1));
 }

@@ -28,6 +28,9 @@ __host__ __device__ inline int cnet_trow(int M9) {   // T row stride (floats): m
 // geometry of a launch with pxt-pixel tiles (false: the shape has none); N = 0: shape check only
 bool cnet_geo(int Cin, int H, int W, int hidden, int Cout, int N, int pxt, CnetGeo* out);
 
+// MS, tiles, R, NI, lpxt of the hand-over a launch with this geometry and row split leaves to the finishing kernel
+void cnet_pending_tiling(const CnetGeo& g, int ms, CnetPending* out);
+
 // ---- k_cnet1w (cnet1w_sh.hip): may this launch run on it (no row split), and the launch itself (same partial-sum layout as k_cnet
 // at MS = 1 with 128-pixel tiles: the finishing kernel does not know the difference)
 bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g128);

@@ -1073,6 +1073,12 @@ static int launch_cnet_tape(const CnetArgs& a, const CnetGeo& g, hipStream_t s) 
     return GLOWHIP_OK;
 }
 
+// the tiling half of a hand-over: how a launch with geometry g and row split ms tiles its partial sums (launch_cnet_main, and the
+// testing hook glowhip_debug_fin, whose geometry therefore cannot drift from the producer's)
+void cnet_pending_tiling(const CnetGeo& g, int ms, CnetPending* out) {
+    out->MS = ms; out->tiles = g.tiles; out->R = g.R; out->NI = g.NI; out->lpxt = g.lpxt;
+}
+
 int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     GH_REQUIRE(a.mode == TAIL_AFFINE_FWD || a.mode == TAIL_AFFINE_REV || a.mode == TAIL_ADD_FWD || a.mode == TAIL_ADD_REV,
                "cnet: coupling modes only");
@@ -1110,7 +1116,8 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     if (rc == GLOWHIP_EINVAL) set_error("cnet: no kernel instance for hidden=%d ms=%d upw=%d tile=%d", a.hidden, ms, upw, g.pxt);
     GH_TRY(rc);
     if (out) {
-        out->scratch = a.scratch; out->MS = ms; out->tiles = g.tiles; out->R = g.R; out->NI = g.NI; out->lpxt = g.lpxt;
+        out->scratch = a.scratch;
+        cnet_pending_tiling(g, ms, out);
         out->bias = a.bias; out->scale = a.scale; out->mode = a.mode; out->Cout = a.Cout;
         out->z = a.z_in; out->z_bs = a.z_in_bs;
         out->one_wave = c.one_wave ? 1 : 0;
@@ -1118,7 +1125,7 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     return GLOWHIP_OK;
 }
 
-int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s) {
+int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s, FinLaunchInfo* info) {
     if (a.N == 0) return GLOWHIP_OK;
     const int HW = a.H * a.W;
     CfinArgs f{p, a.mix, a.z_out, a.z_out_bs, a.acc, a.N, a.H, a.W, HW, __builtin_ctz(a.W), debug_switches().cfinish_block_order ? 0 : 1, a.tape_hout};
@@ -1138,10 +1145,17 @@ int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s) {
             (void)hipFuncSetAttribute((const void*)k_cfinish<px, m, h>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds); \
         hipLaunchKernelGGL((k_cfinish<px, m, h>), dim3((unsigned)(total_px / px)), dim3(256), flds, s, f);                    \
         launched = true;                                                                                                      \
+        if (info) {                                                                                                           \
+            const int lpxb = px == 256 ? 8 : (px == 64 ? 6 : 4);      /* (k_cfinish's LPXB) */                                 \
+            *info = FinLaunchInfo{GLOWHIP_FNI_CFINISH, {(int)(total_px / px), 1, 1}, (int)flds, px, m, h ? 1 : 0,             \
+                                  f.xcd_affine && p.lpxt >= lpxb && cfin_whole_groups((int)(total_px / px), p.lpxt - lpxb) ? 1 : 0, 0}; \
+        }                                                                                                                     \
     }
     GH_CF(16, 1, false) GH_CF(16, 1, true) GH_CF(16, 2, false) GH_CF(16, 2, true) GH_CF(16, 4, false) GH_CF(16, 4, true)
     GH_CF(64, 1, false) GH_CF(64, 1, true) GH_CF(64, 2, false) GH_CF(64, 2, true) GH_CF(64, 4, false) GH_CF(64, 4, true)
-    GH_CF(256, 1, false) GH_CF(256, 1, true) GH_CF(256, 2, false) GH_CF(256, 2, true)
+    // (256 pixels per workgroup need HW % 256 == 0, and a map without halo rows is one whole tile or less, HW <= 128: the 256-pixel
+    // instances exist with halo rows only)
+    GH_CF(256, 1, true) GH_CF(256, 2, true)
 #undef GH_CF
     GH_REQUIRE(launched, "cnet: no finishing kernel for row split %d", p.MS);
     GH_LAUNCH_CHECK("k_cfinish");

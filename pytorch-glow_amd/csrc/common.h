@@ -177,6 +177,11 @@ __device__ __forceinline__ float relu_(float v) { return v < 0.f ? 0.f : v; }
 // tail: MT); launches: kernel launches made; paired: the tail's row map
 struct ConvLaunchInfo { int kernel, ksize, tile, splits, mb, grid[3], launches, paired; };
 
+// What a launcher of the fp32 finishing / channel-mixer kernels chose (testing: glowhip_debug_fin fills a glowhip_fin_info from it;
+// every production caller passes nothing).  kernel: GLOWHIP_FNI_*; pxb / msv / halo: k_cfinish's template arguments; xcd_affine: the
+// launch took its chunks in the XCD-affine order (cnet_fin.h cfin_chunk); stage_matrix: k_chanmix's matrix goes through LDS
+struct FinLaunchInfo { int kernel, grid[3], lds_bytes, pxb, msv, halo, xcd_affine, stage_matrix; };
+
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 

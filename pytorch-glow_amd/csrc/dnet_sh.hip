@@ -371,6 +371,13 @@ static DnScratch dn_carve(const DnetLevel& L, void* base) {
     return d;
 }
 
+void dnet_scratch_layout(const DnetLevel& L, DnetScratchLayout* out) {
+    const DnScratch d = dn_carve(L, L.scratch);
+    const char* base = (const char*)L.scratch;
+    out->part_off = (long)((const char*)d.part - base); out->u_off = (long)((const char*)d.u - base);
+    out->ypad_off = (long)((const char*)d.ypad - base); out->u_plane = d.u_plane; out->ypad_plane = d.y_plane;
+}
+
 // zero two 16-byte aligned ranges (n16a, n16b: their sizes in 16-byte words)
 __global__ void __launch_bounds__(256) k_dn_zero(uint4* __restrict__ a, long n16a, uint4* __restrict__ b, long n16b) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n16a + n16b; i += (long)gridDim.x * 256) {
@@ -391,7 +398,8 @@ int dnet_level_begin(const DnetLevel& L, hipStream_t s) {
     return GLOWHIP_OK;
 }
 
-int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an_bias, const float* an_scale, int reverse, hipStream_t s) {
+int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an_bias, const float* an_scale, int reverse, hipStream_t s,
+              FinLaunchInfo* info) {
     const DnScratch d = dn_carve(L, L.scratch);
     const int P = L.N * L.H * L.W;
     DnPrepArgs a{};
@@ -401,6 +409,7 @@ int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an
     else { a.Csh = L.C / 2; a.out_sh = d.ypad; a.out_plane = d.y_plane; a.out_slots = d.SLN; a.out_padded = 1; }
     hipLaunchKernelGGL(k_dn_prep, dim3((P + 63) / 64, (L.C / 4 + 3) / 4), dim3(256), 0, s, a);
     GH_LAUNCH_CHECK("k_dn_prep");
+    if (info) *info = FinLaunchInfo{GLOWHIP_FNI_DN_PREP, {(P + 63) / 64, (L.C / 4 + 3) / 4, 1}, 0, 0, 0, 0, 0, 0};
     return GLOWHIP_OK;
 }
 
@@ -444,7 +453,7 @@ int dnet_coupling_net(const DnetLevel& L, const void* w0, const void* w2, const 
 }
 
 int dnet_finish(const DnetLevel& L, int ks, const float* f4_bias, const float* f4_scale, int mode, unsigned long long* acc,
-                const float* u_bias, const float* u_scale, int want_u, hipStream_t s) {
+                const float* u_bias, const float* u_scale, int want_u, hipStream_t s, FinLaunchInfo* info) {
     const DnScratch d = dn_carve(L, L.scratch);
     const int P = L.N * L.H * L.W;
     DnFinArgs a{};
@@ -453,6 +462,7 @@ int dnet_finish(const DnetLevel& L, int ks, const float* f4_bias, const float* f
     a.u_bias = u_bias; a.u_scale = u_scale; a.u = want_u ? d.u : nullptr; a.u_plane = d.u_plane; a.u_slots = P;
     hipLaunchKernelGGL(k_dn_fin, dim3((P + 63) / 64, (L.C / 8 + 3) / 4), dim3(256), 0, s, a);
     GH_LAUNCH_CHECK("k_dn_fin");
+    if (info) *info = FinLaunchInfo{GLOWHIP_FNI_DN_FIN, {(P + 63) / 64, (L.C / 8 + 3) / 4, 1}, 0, 0, 0, 0, 0, 0};
     return GLOWHIP_OK;
 }
 

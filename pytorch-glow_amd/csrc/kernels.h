@@ -42,7 +42,7 @@ struct ChanMixArgs {
     const void* sq_src; int sq_u8; float sq_div; const float* sq_noise; RngSpec sq_rng; int sq_W;
     long sq_bs;            // batch stride of sq_src in elements, 0 = dense (C/4 * 4 HW); the noise tensor / draw is always dense
 };
-int launch_chanmix(const ChanMixArgs& a, hipStream_t s);
+int launch_chanmix(const ChanMixArgs& a, hipStream_t s, FinLaunchInfo* info = nullptr);      // non-null: what was launched (testing)
 bool chanmix_squeeze_foldable(int C);      // the squeezed-view input (ChanMixArgs::sq_src) is served for this channel count
 
 int launch_add_const_logdet(const float* in, float* out, int N, const float* term_a, float mul_a, int count_a,

@@ -591,26 +591,37 @@ __global__ void __launch_bounds__(256) k_chanmix_wide(ChanMixArgs a) {
 
 bool chanmix_squeeze_foldable(int C) { return C % 4 == 0 && (size_t)C * C * sizeof(float) <= 48 * 1024; }
 
-int launch_chanmix(const ChanMixArgs& a, hipStream_t s) {
+int launch_chanmix(const ChanMixArgs& a, hipStream_t s, FinLaunchInfo* info) {
     GH_REQUIRE(a.C > 0 && a.C <= 512, "channel mixer: C=%d unsupported (1..512)", a.C);
     const long total = (long)a.N * a.HW;
     if (total == 0) return GLOWHIP_OK;
     GH_REQUIRE(!a.sq_src || (chanmix_squeeze_foldable(a.C) && !a.reverse), "channel mixer: the squeezed-view input needs the LDS-matrix kernel, forward");
     if ((size_t)a.C * a.C * sizeof(float) > 48 * 1024) {
-        // output slices over gridDim.y only when the output does not alias an input (other workgroups read the same pixels)
-        const float* o_lo = a.out; const float* o_hi = a.out + (long)a.N * a.out_bs;
-        const bool alias = (a.in_a >= o_lo && a.in_a < o_hi) || (a.in_b >= o_lo && a.in_b < o_hi);
+        // output slices over gridDim.y only when the output does not overlap an input (other workgroups read the same pixels).  A
+        // symmetric test of the address ranges: an output that starts INSIDE an input (out = in_a + HW, channels shifted by one)
+        // overlaps it as much as an input that starts inside the output
+        auto overlaps = [&](const float* in, long bs, int ch) {
+            if (ch <= 0) return false;
+            const float* i_hi = in + (long)(a.N - 1) * bs + (long)ch * a.HW;
+            const float* o_hi = a.out + (long)(a.N - 1) * a.out_bs + (long)a.C * a.HW;
+            return in < o_hi && a.out < i_hi;
+        };
+        const bool alias = overlaps(a.in_a, a.in_a_bs, a.Ca) || overlaps(a.in_b, a.in_b_bs, a.C - a.Ca);
         const size_t lds = ((size_t)a.C * 16 + (size_t)32 * a.C) * sizeof(float);
         if (lds > 32 * 1024) (void)hipFuncSetAttribute((const void*)k_chanmix_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_chanmix_wide, dim3(cdiv(total, 16), alias ? 1 : cdiv(a.C, 32)), dim3(256), lds, s, a);
+        const dim3 grid(cdiv(total, 16), alias ? 1 : cdiv(a.C, 32));
+        hipLaunchKernelGGL(k_chanmix_wide, grid, dim3(256), lds, s, a);
         GH_LAUNCH_CHECK("k_chanmix_wide");
+        if (info) *info = FinLaunchInfo{GLOWHIP_FNI_CHANMIX_WIDE, {(int)grid.x, (int)grid.y, 1}, (int)lds, 0, 0, 0, 0, 0};
         return GLOWHIP_OK;
     }
     const int stage = (size_t)a.C * a.C * sizeof(float) <= 48 * 1024;   // C <= 110: the matrix fits next to the pixel tile
     const size_t mbytes = stage ? (size_t)a.C * a.C * sizeof(float) : 0;
     if (total < 16384 && a.C >= 16 && stage) {   // deep levels: 16 pixels x 16 output groups per workgroup
-        hipLaunchKernelGGL(k_chanmix<16>, dim3(cdiv(total, 16)), dim3(256), (size_t)a.C * 16 * sizeof(float) + mbytes, s, a, stage);
+        const size_t lds16 = (size_t)a.C * 16 * sizeof(float) + mbytes;
+        hipLaunchKernelGGL(k_chanmix<16>, dim3(cdiv(total, 16)), dim3(256), lds16, s, a, stage);
         GH_LAUNCH_CHECK("k_chanmix");
+        if (info) *info = FinLaunchInfo{GLOWHIP_FNI_CHANMIX16, {cdiv(total, 16), 1, 1}, (int)lds16, 0, 0, 0, 0, stage};
         return GLOWHIP_OK;
     }
     const size_t lds = (size_t)a.C * 64 * sizeof(float) + mbytes;
@@ -618,6 +629,7 @@ int launch_chanmix(const ChanMixArgs& a, hipStream_t s) {
         (void)hipFuncSetAttribute((const void*)k_chanmix<64>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(k_chanmix<64>, dim3(cdiv(total, 64)), dim3(256), lds, s, a, stage);
     GH_LAUNCH_CHECK("k_chanmix");
+    if (info) *info = FinLaunchInfo{GLOWHIP_FNI_CHANMIX64, {cdiv(total, 64), 1, 1}, (int)lds, 0, 0, 0, 0, stage};
     return GLOWHIP_OK;
 }
 

@@ -169,7 +169,7 @@ struct CnetArgs {
 };
 static_assert(sizeof(CnetArgs) % 128 == 0, "CnetGeo follows CnetArgs in the kernel arguments: keep it on a 128-byte boundary (pad_to_128)");
 int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out);            // k_cnet only; *out describes its partial sums
-int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s);     // the finishing kernel for those sums
+int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s, FinLaunchInfo* info = nullptr);     // the finishing kernel for those sums (info: what was launched, testing)
 int launch_cnet(const CnetArgs& a, hipStream_t s);                                   // both
 bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N);        // a taping instance of k_cnet exists for the shape
 
@@ -186,7 +186,8 @@ size_t dnet_scratch_bytes_per_sample(int C, int H, int W, int hidden, int Cout);
 int dnet_level_begin(const DnetLevel& L, hipStream_t s);      // zero the padded operands' borders (once per level and call)
 // first launch of a level: forward u = SH2((src + an_bias) * an_scale); reverse: src's first C/2 channels as the padded F0 operand;
 // both copy src into L.state when it lives elsewhere
-int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an_bias, const float* an_scale, int reverse, hipStream_t s);
+int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an_bias, const float* an_scale, int reverse, hipStream_t s,
+              FinLaunchInfo* info = nullptr);      // info (here and in dnet_finish): what was launched (testing)
 // MIX: state <- W u (forward; w_image = SH2_GEMM image of W) or (W^-1 u) * post_scale - post_bias (reverse); want_pad: also the
 // first C/2 channels as the padded operand of the next F0
 int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, const float* post_bias, int want_pad, hipStream_t s);
@@ -195,6 +196,10 @@ int dnet_coupling_net(const DnetLevel& L, const void* w0_sh2_first, const void* 
 // FIN: coupling (mode = TailMode) on L.state in place + log-det; want_u: the next MIX's operand, with the next step's ActNorm
 // (u_bias / u_scale, forward) or plain (null, reverse)
 int dnet_finish(const DnetLevel& L, int ks, const float* f4_bias, const float* f4_scale, int mode, unsigned long long* acc,
-                const float* u_bias, const float* u_scale, int want_u, hipStream_t s);
+                const float* u_bias, const float* u_scale, int want_u, hipStream_t s, FinLaunchInfo* info = nullptr);
+// where the level's scratch holds the f.4 partial sums, the MIX operand u and the padded F0 operand (byte offsets from L.scratch;
+// plane = fp16 elements between the hi and the lo plane) -- for the testing hook glowhip_debug_fin, which lays them out itself
+struct DnetScratchLayout { long part_off, u_off, ypad_off, u_plane, ypad_plane; };
+void dnet_scratch_layout(const DnetLevel& L, DnetScratchLayout* out);
 
 }  // namespace glowhip
