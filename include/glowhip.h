@@ -507,6 +507,36 @@ int glowhip_restore_objective(const float* x, const float* target, const float* 
                               int N, int C, int H, int W, int pool, float* grad_x, float* loss_out, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The restoration objective observed through a point-spread function (PSF): deblurring, and super-resolution as blur then decimate.
+ * THE definition of the operator.  Per sample n and channel c, with k the sample's PSF of kh x kw taps (kh, kw odd, 1 .. 15),
+ * ah = (kh - 1) / 2, aw = (kw - 1) / 2:
+ *     (B x)[c,i,j] = sum_{a,b} k[a,b] * x[c, i + ah - a, j + aw - b]         (x = 0 outside the image)
+ *     A = P B                                                                (P: the pool x pool average pool, as above)
+ *     loss_out[n] = inv_wsum[n] * sum w (A x - t)^2
+ *     grad_x      = 2 inv_wsum[n] * B^T P^T (w (A x - t))
+ *     resid       = w (A x - t)                                              (N,C,H/pool,W/pool): scratch AND output
+ * B is a true convolution: k is the image a point source leaves (a single 1 at (i0, j0) blurs to k centred there); it is
+ * F.conv2d with the flipped kernel, depthwise.  The same PSF serves every channel of a sample; psf_stride == 0 means one PSF
+ * (kh*kw floats, row-major) for the whole batch, otherwise sample n's starts at psf + n * psf_stride (>= kh*kw).  The call does not
+ * normalise the PSF.  Zero padding is the only border rule: a caller who wants the border treated honestly gives weight 0 to the
+ * measurement cells whose footprint leaves the image.  x, target, weight, inv_wsum, grad_x, loss_out and the NULL defaults are as
+ * for glowhip_restore_objective, which this call leaves untouched.
+ * ONE launch, one workgroup per sample, three phases separated by workgroup barriers: B x into grad_x[n] (as scratch) from x tiles
+ * staged with their halo in LDS; glowhip_restore_objective's own loops over it (resid and the fp64 loss, in the same fixed order:
+ * bitwise the same run to run, no atomics); B^T P^T from resid tiles staged the same way.  The two gathers are one routine, with the
+ * taps flipped and as given: exact transposes of each other as linear maps.  With pool == 1 and a 1x1 PSF holding 1.0f, loss_out
+ * and grad_x are bit-identical to glowhip_restore_objective's on the same inputs (placed so that both take the same access path).
+ * inv_wsum[n] == 0: exact zeros in grad_x[n] and resid[n] and loss 0, whatever x[n] holds.  A non-finite x[n] reaches no other
+ * sample's outputs.  x, grad_x and resid must not overlap.  No allocation, no host sync, capturable.
+ * GLOWHIP_EINVAL with a message and no device call: a NULL x, target, grad_x, psf or resid; kh or kw even, < 1 or > 15; psf_stride
+ * neither 0 nor >= kh*kw; pool < 1; H or W not divisible by pool; C*H*W >= 2^31.  N == 0 returns GLOWHIP_OK. */
+int glowhip_restore_objective_psf(const float* x, const float* target, const float* weight, const float* inv_wsum,
+                                  const float* psf, long psf_stride /* 0: one PSF for the batch; else >= kh*kw */, int kh, int kw,
+                                  int N, int C, int H, int W, int pool,
+                                  float* resid /* scratch AND output: (N,C,H/pool,W/pool) = w (A x - t) */,
+                                  float* grad_x, float* loss_out, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Posterior sampling: a Metropolis-adjusted Langevin (MALA) chain over the latents of an inverse problem, one independent chain
  * per sample, and the Welford moments of its images (csrc/posterior.hip; numpy restatement tests/posterior_oracle.py).
  * THE definition.  Per sample n, theta = all latent leaves of that sample (leaf 0 = z, leaf 1 + k = eps[k] in decode order):

@@ -141,15 +141,36 @@ class Inferer:
                 history.append(loss.detach())
         return lat.detach(), [float(v) for v in torch.stack(history).cpu()] if history else []
 
-    def _problem(self, measurement, weight, pool, init, chains=1):
-        """``(measurement batch, weight broadcast to it, pool, start latents)`` of `restore` / `posterior`: ``init`` None = ``encode_full``
-        of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement."""
+    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid"):
+        """``(measurement batch, weight broadcast to it, pool, start latents, psf)`` of `restore` / `posterior`: ``init`` None =
+        ``encode_full`` of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement
+        (and a single PSF).  With a ``psf``, ``border="valid"`` multiplies the weight (None = ones) by
+        `network.restore.psf_valid_weight`; every refusal of a PSF is raised before any device work."""
+        from .restore import check_psf_shape, psf_valid_weight
+        if psf is not None:
+            psf = torch.as_tensor(psf, dtype=torch.float32)
+            if border not in ("valid", "zero"):
+                raise ValueError(f"border = {border!r}: 'valid' or 'zero'")
+            if not torch.is_tensor(measurement):
+                raise TypeError("takes a tensor; image decoding (cv2 / PIL) is outside this package")
+            kh, kw = check_psf_shape(psf.shape, 1 if measurement.dim() == 3 else len(measurement))
+            band = None
+            if border == "valid":
+                band = psf_valid_weight(tuple(measurement.shape)[-2:], kh, kw, int(pool))
+                if not bool(band.any()):
+                    raise ValueError(f"border='valid': a psf of {kh} x {kw} taps leaves no cell of the "
+                                     f"{tuple(measurement.shape)[-2:]} measurement (pool {int(pool)}) whose footprint is inside the image")
         meas = self._batch(measurement).float().contiguous()
         pool = int(pool)
         if chains < 1 or (chains > 1 and meas.shape[0] != 1):
             raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {meas.shape[0]} runs one chain each)")
         if weight is not None:
             weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
+        if psf is not None:
+            psf = psf.to(self.device).contiguous()
+            if band is not None:
+                band = band.to(self.device)
+                weight = band.expand_as(meas).contiguous() if weight is None else weight * band
         if init is None:
             start = meas if pool <= 1 else meas.repeat_interleave(pool, dim=-2).repeat_interleave(pool, dim=-1)
             init = self.encode_full(start)
@@ -158,10 +179,12 @@ class Inferer:
             meas, weight = rep(meas), None if weight is None else rep(weight)
             if len(init) == 1:
                 init = Latents(rep(init.z), [rep(e) for e in init.eps])
-        return meas, weight, pool, init
+            if psf is not None and psf.dim() == 3:
+                psf = rep(psf)
+        return meas, weight, pool, init, psf
 
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
-                graph=True, exact=False):
+                graph=True, exact=False, psf=None, border="valid"):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
         image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
         super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
@@ -183,17 +206,26 @@ class Inferer:
         ``graph``: iterations after the first run as ONE hipGraph launch each (a failed capture falls back to the eager loop;
         the reason is in ``RestoreInfo.graph_error``).  ``exact``: the whole fit on the exact-fp32 kernel family.  With ``exact``
         off and ``glow.range_check`` on, a fit whose norm history holds a non-finite value is run once more from the same start on
-        the exact family (``fallback=1``); non-finite there too: ``finite=False``.  Nothing raises; one host sync, at the end."""
+        the exact family (``fallback=1``); non-finite there too: ``finite=False``.  Nothing raises; one host sync, at the end.
+
+        ``psf``: deblurring (and, with ``pool>1``, super-resolution as blur then decimate) -- the decode is observed through the
+        point-spread function before the pool, ``A = P B`` with ``B`` the zero-padded convolution by ``psf`` (include/glowhip.h,
+        glowhip_restore_objective_psf).  Anything ``torch.as_tensor`` takes, of shape (kh,kw) -- one PSF for the batch -- or
+        (N,kh,kw), sides odd and at most 15, the same for every channel, not normalised.  ``border="valid"`` (the default) gives
+        weight 0 to the measurement cells whose footprint leaves the image (`network.restore.psf_valid_weight`: ceil(ah / pool)
+        rows and ceil(aw / pool) columns at each edge), before ``inv_wsum`` is formed; ``border="zero"`` leaves the weight alone
+        and takes the kernel's zero padding as the truth.  An even side, a side above 15, a wrong leading dimension or a band that
+        leaves no cell raise ValueError before any device work.  ``init=None`` stays ``encode_full`` of the measurement."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
-        meas, weight, pool, init = self._problem(measurement, weight, pool, init)
+        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
-                        max_grad_norm=max_grad_norm, graph=graph)
+                        max_grad_norm=max_grad_norm, graph=graph, psf=psf)
         info = fit.run(exact=exact)
         return fit.latents(), info
 
     def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
-                  seed=None, init=None, graph=True, adapt_rate=0.5):
+                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid"):
         """Draws from the posterior of the latents given ``measurement`` -- what else is consistent with it, and how sure the model
         is of each pixel -- by a Metropolis-adjusted Langevin chain on the device (`network.posterior.LatentMALA`):
 
@@ -212,19 +244,22 @@ class Inferer:
         (``pool>1``: of its pixel-repeated upsampling).  A model with a learned or class-conditional top prior raises ValueError:
         the prior term assumes a standard-normal top latent.  A proposal whose decode is not finite (outside the fp16 pairs' range
         of the product kernels) is rejected on the device and counted; a start whose own decode is not finite gives
-        ``finite=False`` and runs no iteration.  Nothing else raises; one host sync at the start state, one read at the end."""
+        ``finite=False`` and runs no iteration.  Nothing else raises; one host sync at the start state, one read at the end.
+
+        ``psf`` / ``border``: the measurement is a blurred image, as for `restore`; with ``chains=K`` a single PSF is repeated as
+        the measurement is."""
         from .model import sampler_position
         from .posterior import LatentMALA
         from .restore import check_prior_weight
         check_prior_weight(self.graph, 1.0)
-        meas, weight, pool, init = self._problem(measurement, weight, pool, init, chains=int(chains))
+        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border)
         if seed is None:
             seed, call = sampler_position(advance=True)
             call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)
         else:
             seed, call = int(seed) & (2 ** 64 - 1), 0
         chain = LatentMALA(self.graph, meas, weight=weight, pool=pool, noise_std=noise_std, init=init, steps=steps, burn_in=burn_in,
-                           thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call)
+                           thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call, psf=psf)
         info = chain.run()
         return chain.latents(), info
 

@@ -9,7 +9,11 @@ The pieces: `restore_objective` (glowhip_restore_objective, csrc/restore.hip: th
 respect to the image, one launch), `FlowPlan.decode` / `decode_vjp` (the image and J^T of that gradient) and the fused Adam step
 (`training.HipAdam`), whose weight decay IS the prior term: the update kernel adds prior_weight * p to the gradient, the gradient of
 prior_weight * 1/2 ||p||^2.  `LatentFit` runs them as a device-resident loop -- no autograd, no host sync, the histories on the
-device -- and, with ``graph=True``, as one hipGraph launch per iteration."""
+device -- and, with ``graph=True``, as one hipGraph launch per iteration.
+
+Deblurring: with a point-spread function ``psf`` the decode is observed through A = P B, B the zero-padded convolution by the PSF
+(glowhip_restore_objective_psf; include/glowhip.h has the definition).  Only `LatentLoop._evaluate` knows: decode, `decode_vjp`,
+the optimiser, the MALA launches, the capture protocol and the histories are the same with and without one."""
 import contextlib
 from dataclasses import dataclass
 from typing import Optional
@@ -22,15 +26,49 @@ from ..training import HipAdam, HyperRing
 from .latents import Latents
 
 
-def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None):
+PSF_MAX = 15       # the largest side of a point-spread function (csrc/restore.hip)
+
+
+def check_psf_shape(shape, n, what="psf"):
+    """``(kh, kw)`` of a PSF of shape (kh,kw) or (n,kh,kw): both sides odd and at most `PSF_MAX`; ValueError otherwise."""
+    shape = tuple(shape)
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != n):
+        raise ValueError(f"{what} of shape {shape}: expected (kh, kw) or ({n}, kh, kw)")
+    kh, kw = shape[-2:]
+    if not all(1 <= k <= PSF_MAX and k % 2 == 1 for k in (kh, kw)):
+        raise ValueError(f"{what} of {kh} x {kw} taps: both sides must be odd and at most {PSF_MAX}")
+    return kh, kw
+
+
+def psf_valid_weight(meas_shape, kh, kw, pool=1):
+    """The band mask of ``border="valid"`` as a CPU fp32 tensor of the measurement's last two dimensions (h, w): 1 where every x the
+    cell's footprint reads -- its pool x pool patch widened by (kh-1)/2 rows and (kw-1)/2 columns on each side -- lies inside the
+    image, 0 elsewhere: ceil(ah / pool) rows at the top and at the bottom, ceil(aw / pool) columns at the left and at the right."""
+    h, w = (int(v) for v in tuple(meas_shape)[-2:])
+    pool = int(pool)
+    rh, rw = -(-((kh - 1) // 2) // pool), -(-((kw - 1) // 2) // pool)
+    m = torch.zeros((h, w), dtype=torch.float32)
+    if h > 2 * rh and w > 2 * rw:
+        m[rh:h - rh, rw:w - rw] = 1.0
+    return m
+
+
+def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None, psf=None, resid_out=None):
     """``(loss (N,), grad_x)`` of the data term for images ``x`` (N,C,H,W): glowhip_restore_objective.  ``target`` / ``weight``
     (N,C,H/pool,W/pool; weight None = ones), ``inv_wsum`` (N,; None = 1 / elements of one measurement).  Contiguous fp32 device
-    tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write."""
-    for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out)):
+    tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write.
+
+    ``psf`` (kh,kw) or (N,kh,kw), sides odd and at most 15: the image is observed through that point-spread function before the
+    pool (glowhip_restore_objective_psf; include/glowhip.h has the definition), one for the batch or one per sample, not
+    normalised.  ``resid_out`` (N,C,H/pool,W/pool): where that call leaves w (A x - t) -- its scratch, allocated when None.
+    ``psf=None`` is the call above, unchanged."""
+    for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out),
+                    ("psf", psf), ("resid_out", resid_out)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
             raise _lib.GlowHipError(f"restore_objective: {name} must be a contiguous fp32 tensor on the device of x")
     n, c, h, w = x.shape
     pool = int(pool)
+    mshape = None
     if pool >= 1 and h % pool == 0 and w % pool == 0:      # (anything else is the C call's to refuse)
         mshape = (n, c, h // pool, w // pool)
         if tuple(target.shape) != mshape or (weight is not None and tuple(weight.shape) != mshape):
@@ -41,8 +79,21 @@ def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out
     loss = torch.empty(n, dtype=torch.float32, device=x.device) if loss_out is None else loss_out
     if tuple(grad.shape) != tuple(x.shape) or loss.numel() != n:
         raise _lib.GlowHipError("restore_objective: grad_out must have the shape of x, loss_out one value per sample")
-    _lib.check(_lib.lib().glowhip_restore_objective(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), n, c, h, w,
-                                                    pool, _lib.ptr(grad), _lib.ptr(loss), _lib.stream_ptr(x.device)))
+    if psf is None:
+        if resid_out is not None:
+            raise _lib.GlowHipError("restore_objective: resid_out belongs to the call with a psf")
+        _lib.check(_lib.lib().glowhip_restore_objective(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), n, c, h, w,
+                                                        pool, _lib.ptr(grad), _lib.ptr(loss), _lib.stream_ptr(x.device)))
+        return loss, grad
+    if psf.dim() not in (2, 3) or (psf.dim() == 3 and psf.shape[0] != n):
+        raise _lib.GlowHipError(f"restore_objective: psf of shape {tuple(psf.shape)}: expected (kh, kw) or ({n}, kh, kw)")
+    kh, kw = psf.shape[-2:]                                # (their parity and range are the C call's to refuse)
+    resid = torch.empty_like(target) if resid_out is None else resid_out
+    if mshape is not None and tuple(resid.shape) != mshape:
+        raise _lib.GlowHipError(f"restore_objective: resid_out must have shape {mshape}")
+    _lib.check(_lib.lib().glowhip_restore_objective_psf(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum),
+                                                        _lib.ptr(psf), kh * kw if psf.dim() == 3 else 0, kh, kw, n, c, h, w, pool,
+                                                        _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss), _lib.stream_ptr(x.device)))
     return loss, grad
 
 
@@ -73,7 +124,7 @@ def check_prior_weight(glow, prior_weight):
 
 class LatentLoop:
     """What the device-resident loops over the latents of a measurement share -- `LatentFit` here, `posterior.LatentMALA`: the
-    problem (``target``, ``weight``, ``pool``, the plan of the full-resolution image, the start leaves ``_start``, the static
+    problem (``target``, ``weight``, ``pool``, the optional point-spread function ``psf``, the plan of the full-resolution image, the start leaves ``_start``, the static
     ``image`` and its gradient ``grad_x``), one evaluation of it, and an iteration as either Python-enqueued launches
     (`step_eager`) or one hipGraph launch (`capture` once, after at least one eager iteration -- lazy allocations, packed weights
     -- then `step_captured`), by the package's one capture protocol (`_capture.Capture`).  Same kernels and same bits either way.
@@ -81,7 +132,7 @@ class LatentLoop:
     A subclass supplies ``inv_wsum`` (the per-sample factor of the data term), ``_body(captured)`` (the iteration), `reset`, and,
     where a replay has a host side, ``_capturing()`` / ``_signature()`` / ``_replay_host()``."""
 
-    def __init__(self, glow, measurement, weight, pool, init, steps, graph):
+    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None):
         self.glow, self.pool, self.steps, self.want_graph = glow, int(pool), int(steps), bool(graph)
         meas = _lib.require_device_tensor(measurement, "measurement")
         dev = self.device = meas.device
@@ -97,6 +148,13 @@ class LatentLoop:
         self._start = [t.float().contiguous().clone() for t in init.to(dev).detach().tensors()]
         self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
         self.grad_x = torch.empty_like(self.image)
+        # the point-spread function (None: the image is observed directly) and the objective's scratch w (A x - t): one buffer,
+        # because every evaluation of a loop runs on one stream, one after the other
+        self.psf = self.resid = None
+        if psf is not None:
+            self.psf = _lib.require_device_tensor(psf, "psf").to(dev).clone()
+            check_psf_shape(self.psf.shape, n)
+            self.resid = torch.empty_like(self.target)
         self._capture = None
         self.graph_error = None
         self._iterations = 0         # run since construction (a reset does not take the lazy allocations back)
@@ -104,10 +162,12 @@ class LatentLoop:
     # ------------------------------------------------------------------ the iteration
     def _evaluate(self, leaves, image, loss, grads):
         """`FlowPlan.decode` of ``leaves`` into ``image``; `restore_objective` (per-sample loss into ``loss``, its image gradient
-        into ``grad_x``); `FlowPlan.decode_vjp` of that into ``grads``."""
+        into ``grad_x``; through ``psf`` when the loop has one, with ``resid`` as its scratch); `FlowPlan.decode_vjp` of that into
+        ``grads``."""
         plan = self.plan
         plan.decode(leaves[0], leaves[1:], out=image)
-        restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss)
+        restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss,
+                          psf=self.psf, resid_out=self.resid)
         plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
 
     def _capturing(self):            # the context of a recording (the fit: its optimiser's)
@@ -118,7 +178,9 @@ class LatentLoop:
 
     def _signature(self):
         """What a captured iteration reaches through the plan and an eager call in between could have moved or rebuilt: no pack is
-        inside, so the parameters' versions and the family count, and the workspaces of the decode and of its VJP."""
+        inside, so the parameters' versions and the family count, and the workspaces of the decode and of its VJP.  ``psf`` and
+        ``resid`` need no entry: like ``target`` and ``weight`` they are this loop's own static buffers, allocated once in the
+        constructor and never rebound, so a recorded launch always reaches them."""
         return self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
 
     @torch.no_grad()
@@ -183,14 +245,16 @@ class LatentFit(LatentLoop):
     The data term is normalised per sample, so each image of a batch is its own problem; what still couples the batch is the norm
     clip (``max_grad_norm``: one total norm) and the skip of an iteration whose norm is not finite (all samples or none).  A skipped
     iteration still counts in the bias corrections (the host never looks): harmless, because a fit with a skipped iteration is
-    either run again on the exact-fp32 family or reported ``finite=False``."""
+    either run again on the exact-fp32 family or reported ``finite=False``.
+
+    ``psf`` (kh,kw) or (N,kh,kw), a device tensor: the measurement is the decode blurred by it (`LatentLoop`)."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
-                 graph=True):
+                 graph=True, psf=None):
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
-        super().__init__(glow, measurement, weight, pool, init, steps, graph)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf)
         self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
         n, dev = self.n, self.device
         # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
