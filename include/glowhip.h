@@ -915,6 +915,58 @@ typedef struct glowhip_fin_info {
 } glowhip_fin_info;
 int glowhip_debug_fin(const glowhip_fin_probe* d, glowhip_fin_info* info, glowhip_stream_t stream);
 
+/* Testing hook: ONE SH2 weight image (csrc/pack.hip) or ONE launch of the one-kernel coupling network  h = f.4(relu(f.2(relu(f.0(z1)))))
+ * (network/module.py:300-319; the coupling it feeds: network/model.py:105-150) on split-fp16 operands (csrc/sh.h "SH2":
+ * csrc/cnet_sh.hip k_cnet, csrc/cnet1w_sh.hip k_cnet1w) on operands the caller lays out, through the pack code and the launcher the
+ * plan itself calls -- tests/test_gpu_sh2_kernels.py holds every forward and taping instance to fp64 with it.  Not part of the
+ * operator surface.  All pointers are device pointers except the probe itself; strides are in elements.
+ *   IMAGE  one image of w into `image`, through the RepackJob fields csrc/plan_build.hip fills (add_sh2_first / _gemm / _tail): kind
+ *          (GLOWHIP_SH2_GEMM: w (Cout, Cin); _FIRST: w (Cout, Cin, 3, 3), K = cnet_g0(Cin) groups; _TAIL: w (Cout, Cin, 3, 3), Kpad =
+ *          cnet_mpad4(Cout) rows, always k-permuted), kperm (GEMM), fold_bias / fold_logs (GEMM / FIRST; NULL: none), and
+ *          launch_pack_batched with the block counts the plan derives.  transposed: w is the FORWARD weight ((Cin, Cout) or
+ *          (Cin, Cout, 3, 3)); launch_flipT_batched first writes its transposed, tap-flipped copy into `flip` (Cout Cin ks floats) and
+ *          the image is packed from there, as the plan does for the backward images.  The hook waits for the stream (its job tables
+ *          are freed before it returns).  A NULL image launches nothing: info->image_bytes alone
+ *   CNET   launch_cnet_main on a CnetArgs of x / x_bs, the images w0 / w2 / w4, N, Cin, H, W, hidden, Cout, mode (TailMode 1..4),
+ *          scratch; optional tape_h1 / tape_h2 / mask1 / mask2 with in_scale / out_scale, and bwd.  No finishing launch.  The
+ *          switches of glowhip_debug_force_tail_tile hold as they do for a plan.  scratch_floats (what the caller allocated) is
+ *          refused below the plan's own size, which info reports.  A NULL scratch launches nothing: info reports the instance the
+ *          launch would take, its grid, LDS bytes, hand-over tiling and the plan's scratch size alone
+ *   DN_MIX a DnetLevel (N, C = Cin, H, W, hidden, Cout, state with x_bs = its batch stride, dn_scratch) over caller memory, in which the
+ *          caller has laid the u operand (glowhip_debug_fin's DN ops report the layout); dnet_level_begin, then dnet_mix(w0 = the
+ *          SH2_GEMM image of W, or of W^-1 with post_scale / post_bias; want_pad).  info: <RT, PT, NPF> and grid in dn_*[0]
+ *   DN_NET the same level; dnet_coupling_net(w0, w2, w4) = F0, F2, F4 on the padded z1 operand.  dnet_level_begin zeroes BOTH padded
+ *          operands whole, so it is not called here: the caller lays ypad (zero border included) and zero-fills h2pad, whose
+ *          interior F2 writes, as dnet_level_begin leaves them.  info: ks, the three launches in dn_*[0..2], part_off
+ * In the two DN ops a NULL dn_scratch launches nothing and reports scratch_bytes and part_off alone.
+ * Whatever the launcher refuses is refused here: GLOWHIP_EINVAL, no launch. */
+enum { GLOWHIP_SH2_IMAGE = 0, GLOWHIP_SH2_CNET = 1, GLOWHIP_SH2_DN_MIX = 2, GLOWHIP_SH2_DN_NET = 3 };
+enum { GLOWHIP_SH2_GEMM = 3, GLOWHIP_SH2_FIRST = 4, GLOWHIP_SH2_TAIL = 5 };      /* probe.kind: the REPACK_SH2_* kinds of csrc/kernels.h */
+/* glowhip_sh2_info.kernel: the kernel that ran */
+enum { GLOWHIP_S2I_CNET = 1,        /* k_cnet<hid, ms, upw, pxt, ng, mode> */
+       GLOWHIP_S2I_CNET1W = 2 };    /* k_cnet1w<hid, g0, nrt4, mode> */
+typedef struct glowhip_sh2_probe {
+    int32_t op, kind, N, Cin, H, W, hidden, Cout, mode, bwd, kperm, transposed, want_pad, reserved;
+    float in_scale, out_scale;
+    int64_t x_bs, scratch_floats;
+    const float* w; const float* fold_bias; const float* fold_logs; float* flip; void* image;      /* IMAGE */
+    const float* x; const void* w0; const void* w2; const void* w4; float* scratch;                  /* CNET */
+    void* tape_h1; void* tape_h2; void* mask1; void* mask2;
+    float* state; void* dn_scratch; const float* post_scale; const float* post_bias;                 /* DN_MIX / DN_NET */
+} glowhip_sh2_probe;
+typedef struct glowhip_sh2_info {
+    int32_t kernel, hid, ms, upw, pxt, ng, mode, g0, nrt4;      /* the instance's template arguments (upw: k_cnet only; g0 / nrt4 always) */
+    int32_t grid[3], lds_bytes;
+    int32_t MS, tiles, R, NI, lpxt;    /* the hand-over tiling (CnetPending) */
+    int32_t Kp, M;                     /* IMAGE: padded k and rows of the image */
+    int32_t dn_launches, ks;           /* DN: k_dn_gemm launches made; DN_NET: K-split copies F4 left in `part` */
+    int32_t dn_rt[3], dn_pt[3], dn_npf[3], dn_grid[9];      /* DN: k_dn_gemm<8, RT, PT, NPF> and grid (x, y, z) per launch */
+    int64_t part_off, scratch_bytes;   /* DN: where `part` lies in the level scratch (bytes); the level scratch for N samples */
+    int64_t scratch_floats;            /* CNET: the floats the plan allocates for this launch's partial sums */
+    int64_t image_bytes;               /* IMAGE */
+} glowhip_sh2_info;
+int glowhip_debug_sh2(const glowhip_sh2_probe* d, glowhip_sh2_info* info, glowhip_stream_t stream);
+
 /* Introspection for tests / benchmarks: which kernels a plan will launch ("mfma" or "direct" per
  * convolution).  Writes a NUL-terminated description into buf. */
 int glowhip_plan_describe(const glowhip_plan* plan, char* buf, size_t buf_bytes);

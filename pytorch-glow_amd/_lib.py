@@ -194,6 +194,27 @@ FIN_CFINISH, FIN_CHANMIX, FIN_DN_FIN, FIN_DN_PREP = range(4)
 FNI_CFINISH, FNI_CHANMIX16, FNI_CHANMIX64, FNI_CHANMIX_WIDE, FNI_DN_FIN, FNI_DN_PREP = range(1, 7)
 ACC_EXTRA = 7
 
+class Sh2Probe(ctypes.Structure):
+    """Mirror of ``glowhip_sh2_probe`` (the testing hook ``glowhip_debug_sh2``)."""
+    _fields_ = [(n, c_int32) for n in ("op", "kind", "N", "Cin", "H", "W", "hidden", "Cout", "mode", "bwd", "kperm", "transposed", "want_pad", "reserved")] + \
+               [("in_scale", c_float), ("out_scale", c_float), ("x_bs", ctypes.c_int64), ("scratch_floats", ctypes.c_int64)] + \
+               [(n, c_void_p) for n in ("w", "fold_bias", "fold_logs", "flip", "image", "x", "w0", "w2", "w4", "scratch",
+                                        "tape_h1", "tape_h2", "mask1", "mask2", "state", "dn_scratch", "post_scale", "post_bias")]
+
+
+class Sh2Info(ctypes.Structure):
+    """Mirror of ``glowhip_sh2_info``."""
+    _fields_ = [(n, c_int32) for n in ("kernel", "hid", "ms", "upw", "pxt", "ng", "mode", "g0", "nrt4")] + \
+               [("grid", c_int32 * 3)] + [(n, c_int32) for n in ("lds_bytes", "MS", "tiles", "R", "NI", "lpxt", "Kp", "M", "dn_launches", "ks")] + \
+               [("dn_rt", c_int32 * 3), ("dn_pt", c_int32 * 3), ("dn_npf", c_int32 * 3), ("dn_grid", c_int32 * 9)] + \
+               [(n, ctypes.c_int64) for n in ("part_off", "scratch_bytes", "scratch_floats", "image_bytes")]
+
+
+# glowhip.h GLOWHIP_SH2_* (op, image kind) and GLOWHIP_S2I_* (kernel)
+SH2_IMAGE, SH2_CNET, SH2_DN_MIX, SH2_DN_NET = range(4)
+SH2_GEMM, SH2_FIRST, SH2_TAIL = 3, 4, 5
+S2I_CNET, S2I_CNET1W = 1, 2
+
 EVAL_MAX_LEVELS, EVAL_MAX_BINS = 16, 256      # glowhip.h GLOWHIP_EVAL_MAX_*
 
 
@@ -305,6 +326,7 @@ SIGNATURES = {
     "glowhip_debug_bwd": (c_int, [POINTER(BwdProbe), POINTER(BwdInfo), _P]),
     "glowhip_debug_conv": (c_int, [POINTER(ConvProbe), POINTER(ConvInfo), _P]),
     "glowhip_debug_fin": (c_int, [POINTER(FinProbe), POINTER(FinInfo), _P]),
+    "glowhip_debug_sh2": (c_int, [POINTER(Sh2Probe), POINTER(Sh2Info), _P]),
     "glowhip_plan_tape_bytes": (c_size_t, [_P, c_int]),
     "glowhip_plan_train_workspace_bytes": (c_size_t, [_P, c_int]),
     "glowhip_glow_forward_train": (c_int, [_P, _P, _P, _P, _P, _P, c_long, c_int, _P, _P, _P, c_int, _P, c_size_t, _P,

@@ -2,6 +2,8 @@
 #include <stdarg.h>
 #include <stdio.h>
 
+#include <algorithm>
+
 #include "kernels.h"
 #include "conv_mfma.h"
 #include "cnet_geo.h"
@@ -370,6 +372,115 @@ int glowhip_debug_fin(const glowhip_fin_probe* d, glowhip_fin_info* info, glowhi
     default: break;
     }
     GH_REQUIRE(false, "debug_fin: unknown op %d", d->op);
+    return GLOWHIP_EINVAL;
+}
+
+// Testing hook (include/glowhip.h): one SH2 weight image through the plan's pack code, or one launch_cnet_main on the caller's
+// operands.  No second path: it decodes the probe, fills the RepackJob / CnetArgs fields the plan fills, calls what the plan calls,
+// and copies what the launcher reported.
+int glowhip_debug_sh2(const glowhip_sh2_probe* d, glowhip_sh2_info* info, glowhip_stream_t stream) {
+    GH_REQUIRE(d && info, "debug_sh2: null probe / info");
+    hipStream_t s = (hipStream_t)stream;
+    *info = glowhip_sh2_info{};
+    GH_REQUIRE(d->Cin > 0 && d->Cout > 0, "debug_sh2: bad shape Cin=%d Cout=%d", d->Cin, d->Cout);
+    switch (d->op) {
+    case GLOWHIP_SH2_IMAGE: {
+        GH_REQUIRE(d->kind == REPACK_SH2_GEMM || d->kind == REPACK_SH2_FIRST || d->kind == REPACK_SH2_TAIL, "debug_sh2: unknown image kind %d", d->kind);
+        GH_REQUIRE(d->kind != REPACK_SH2_TAIL || (!d->fold_bias && !d->fold_logs), "debug_sh2: the tail image folds nothing");
+        GH_REQUIRE(d->kind == REPACK_SH2_FIRST || d->Cin % 8 == 0, "debug_sh2: k of a GEMM / tail image comes in groups of 8 (Cin=%d)", d->Cin);
+        GH_REQUIRE((!d->kperm && d->kind != REPACK_SH2_TAIL) || d->Cin % 32 == 0, "debug_sh2: a k-permuted image has whole 32-k blocks (Cin=%d)", d->Cin);
+        RepackJob r{};
+        r.kind = d->kind; r.Cin = d->Cin; r.Cout = d->Cout; r.fold_bias = d->fold_bias; r.fold_logs = d->fold_logs;
+        int n_kind[4] = {0, 0, 0, 0}, tail_blocks = 1, first_blocks = 2;
+        if (d->kind == REPACK_SH2_GEMM) { r.K = d->Cin; r.kperm = d->kperm ? 1 : 0; info->Kp = d->Cin; info->M = d->Cout; n_kind[1] = 1; }
+        else if (d->kind == REPACK_SH2_FIRST) {
+            r.K = cnet_g0(d->Cin); info->Kp = r.K * 8; info->M = d->Cout; n_kind[2] = 1;
+            if (d->Cin >= 64) first_blocks = std::max(2, std::min(16, (d->Cout + 31) / 32));
+        } else { r.Kpad = cnet_mpad4(d->Cout); r.kperm = 1; info->Kp = d->Cin; info->M = r.Kpad; n_kind[3] = 1; tail_blocks = (d->Cout + 7) / 8; }
+        info->image_bytes = (int64_t)sh2_image_bytes(info->Kp, info->M);
+        if (!d->image) return GLOWHIP_OK;
+        GH_REQUIRE(d->w && (!d->transposed || d->flip), "debug_sh2: image null weight / flip buffer");
+        const int ks = d->kind == REPACK_SH2_GEMM ? 1 : 9;
+        struct Tables { FlipJob f[3]; RepackJob r; } t{};
+        r.w = d->transposed ? d->flip : d->w;
+        t.r = r;
+        // (flip jobs come in triples, one launch per member: three times the one job, with its tile count)
+        for (int k = 0; k < 3; ++k) t.f[k] = FlipJob{d->w, 0, d->Cin, d->Cout, ks};      // forward weight (Cin rows, Cout columns) -> (Cout, Cin)
+        const int tiles = ((d->Cin + 31) / 32) * ((d->Cout + 31) / 32);
+        const int tiles3[3] = {tiles, tiles, tiles};
+        Tables* dev = nullptr;
+        GH_REQUIRE(hipMalloc((void**)&dev, sizeof(Tables)) == hipSuccess, "debug_sh2: no device memory for the job tables");
+        // (a blocking copy: it is complete before the launches below are queued on s, whatever stream s is; t lives on this frame)
+        int rc = hipMemcpy(dev, &t, sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess ? GLOWHIP_OK : GLOWHIP_ELAUNCH;
+        if (rc == GLOWHIP_OK && d->transposed) rc = launch_flipT_batched(dev->f, 3, tiles3, d->flip, s);
+        if (rc == GLOWHIP_OK) rc = launch_pack_batched(nullptr, 0, &dev->r, n_kind, tail_blocks, d->image, s, s, first_blocks);
+        if (hipStreamSynchronize(s) != hipSuccess && rc == GLOWHIP_OK) rc = GLOWHIP_ELAUNCH;
+        (void)hipFree(dev);
+        return rc;
+    }
+    case GLOWHIP_SH2_CNET: {
+        GH_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0, "debug_sh2: bad shape N=%d map %dx%d", d->N, d->H, d->W);
+        CnetArgs a{};
+        a.x = d->x; a.x_bs = (long)d->x_bs; a.w0 = d->w0; a.w2 = d->w2; a.w4 = d->w4;
+        a.N = d->N; a.Cin = d->Cin; a.H = d->H; a.W = d->W; a.hidden = d->hidden; a.Cout = d->Cout; a.mode = d->mode;
+        a.scratch = d->scratch;
+        a.tape_h1 = (float*)d->tape_h1; a.tape_h2 = (float*)d->tape_h2; a.mask1 = (unsigned short*)d->mask1; a.mask2 = (unsigned short*)d->mask2;
+        a.in_scale = d->in_scale; a.out_scale = d->out_scale; a.bwd = d->bwd ? 1 : 0;
+        CnetLaunchInfo li{};
+        CnetPending p{};
+        auto report = [&]() {
+            info->kernel = li.one_wave ? GLOWHIP_S2I_CNET1W : GLOWHIP_S2I_CNET;
+            info->hid = li.hid; info->ms = li.ms; info->upw = li.upw; info->pxt = li.pxt; info->ng = li.ng; info->mode = li.mode;
+            info->g0 = li.g0; info->nrt4 = li.nrt4;
+            info->grid[0] = li.grid[0]; info->grid[1] = li.grid[1]; info->grid[2] = li.grid[2]; info->lds_bytes = li.lds_bytes;
+            info->MS = p.MS; info->tiles = p.tiles; info->R = p.R; info->NI = p.NI; info->lpxt = p.lpxt;
+            info->scratch_floats = (int64_t)cnet_scratch_floats(d->N, d->H, d->W, d->Cout);
+        };
+        // the choice alone first (nothing is launched in a dry run): every refusal of the launcher is made before any operand is looked at
+        li.dry_run = 1;
+        GH_TRY(launch_cnet_main(a, s, &p, &li));
+        report();
+        if (!d->scratch) return GLOWHIP_OK;
+        GH_REQUIRE(d->scratch_floats >= info->scratch_floats, "debug_sh2: scratch below the plan's %ld floats", (long)info->scratch_floats);
+        GH_REQUIRE(d->x && d->w0 && d->w2 && d->w4, "debug_sh2: cnet null operand");
+        GH_REQUIRE(d->x_bs >= (int64_t)d->Cin * d->H * d->W, "debug_sh2: batch stride below one sample");
+        GH_REQUIRE(!d->bwd || d->tape_h1, "debug_sh2: a backward launch stores its gradient tensors");
+        li = CnetLaunchInfo{};
+        GH_TRY(launch_cnet_main(a, s, &p, &li));
+        report();
+        return GLOWHIP_OK;
+    }
+    case GLOWHIP_SH2_DN_MIX:
+    case GLOWHIP_SH2_DN_NET: {
+        GH_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && dnet_supported(d->Cin, d->H, d->W, d->hidden, d->Cout), "dnet: unsupported shape");
+        DnetLevel L{d->N, d->Cin, d->H, d->W, d->hidden, d->Cout, d->state, (long)d->x_bs, d->dn_scratch};
+        DnetScratchLayout lay;
+        dnet_scratch_layout(L, &lay);
+        info->part_off = lay.part_off;
+        info->scratch_bytes = (int64_t)d->N * (int64_t)dnet_scratch_bytes_per_sample(d->Cin, d->H, d->W, d->hidden, d->Cout);
+        if (!d->dn_scratch) return GLOWHIP_OK;
+        GH_REQUIRE(d->w0 && d->state && d->x_bs >= (int64_t)d->Cin * d->H * d->W, "debug_sh2: dnet null operand / batch stride");
+        DnLaunchInfo li{};
+        if (d->op == GLOWHIP_SH2_DN_MIX) {
+            GH_REQUIRE(!d->post_scale == !d->post_bias, "debug_sh2: the reverse mixer has a scale and a bias table, or neither");
+            GH_TRY(dnet_level_begin(L, s));
+            GH_TRY(dnet_mix(L, d->w0, d->post_scale, d->post_bias, d->want_pad ? 1 : 0, s, &li));
+        } else {
+            GH_REQUIRE(d->w2 && d->w4, "debug_sh2: dn_net null image");
+            int ks = 0;
+            GH_TRY(dnet_coupling_net(L, d->w0, d->w2, d->w4, &ks, s, &li));
+            info->ks = ks;
+        }
+        info->dn_launches = li.n;
+        for (int k = 0; k < li.n; ++k) {
+            info->dn_rt[k] = li.rt[k]; info->dn_pt[k] = li.pt[k]; info->dn_npf[k] = li.npf[k];
+            for (int q = 0; q < 3; ++q) info->dn_grid[3 * k + q] = li.grid[k][q];
+        }
+        return GLOWHIP_OK;
+    }
+    default: break;
+    }
+    GH_REQUIRE(false, "debug_sh2: unknown op %d", d->op);
     return GLOWHIP_EINVAL;
 }
 

@@ -363,7 +363,7 @@ __global__ void __launch_bounds__(256) k_cnet1w(CnetArgs a, CnetGeo g) {
         }
         // (signs: the activations travel NEGATED from the first epilogue on -- sh.h nrelu_bits, cnet_sh.hip)
 #pragma unroll
-        for (int i = 0; i < N0; ++i) t_rs0[tid + NT * i] = canon_nan(-tv0[i]);
+        for (int i = 0; i < N0; ++i) t_rs0[tid + NT * i] = canon_nan(0.f - tv0[i]);      // (0 - b: a zero bias becomes +0 -- cnet_sh.hip, the same table)
 #pragma unroll
         for (int i = 0; i < N2; ++i) { t_rs2[tid + NT * i] = canon_nan(tv2[i]); t_b2[tid + NT * i] = canon_nan(-tvb[i]); }
         if (tid < MP4) t_rs4[tid] = canon_nan(-tv4);
@@ -896,9 +896,16 @@ bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g) {
     return true;
 }
 
-int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
+int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, hipStream_t s, CnetLaunchInfo* info) {
     const size_t lds = cnet1w_lds_bytes(g, a.hidden);
-    switch (cnet1w_instance(a, g)) {
+    const int inst = cnet1w_instance(a, g);
+    if (info && inst) {
+        info->one_wave = 1; info->hid = 512; info->g0 = inst == 4 ? 18 : 10; info->nrt4 = inst == 4 ? 2 : 4; info->mode = inst >> 1;
+        info->ms = 1; info->upw = 0; info->pxt = 128; info->ng = 1;
+        info->grid[0] = g.tiles; info->grid[1] = info->grid[2] = 1; info->lds_bytes = (int)lds;
+        if (info->dry_run) return GLOWHIP_OK;
+    }
+    switch (inst) {
     case 1:
         (void)hipFuncSetAttribute((const void*)k_cnet1w<512, 10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((k_cnet1w<512, 10, 4>), dim3(g.tiles), dim3(256), lds, s, a, g);

@@ -34,6 +34,6 @@ void cnet_pending_tiling(const CnetGeo& g, int ms, CnetPending* out);
 // ---- k_cnet1w (cnet1w_sh.hip): may this launch run on it (no row split), and the launch itself (same partial-sum layout as k_cnet
 // at MS = 1 with 128-pixel tiles: the finishing kernel does not know the difference)
 bool cnet1w_takes(const CnetArgs& a, const CnetGeo& g128);
-int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, hipStream_t s);
+int launch_cnet1w(const CnetArgs& a, const CnetGeo& g, hipStream_t s, CnetLaunchInfo* info = nullptr);      // info: sh.h (testing)
 
 }  // namespace glowhip

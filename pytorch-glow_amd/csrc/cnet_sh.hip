@@ -186,7 +186,10 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     // The activations travel NEGATED from the first epilogue on (sh.h nrelu_bits): h1 and h2 sit in LDS as -h1, -h2, the h2 and T
     // accumulators hold the negated sums.  So the tables carry the signs: f.0 (-rs0, -b0) turns the true accumulator into -t;
     // f.2 (rs2, -b2) turns the negated accumulator into -t; f.4's row scale -rs4 turns the negated T back.  canon_nan: a NaN
-    // from memory gets the sign bit the hardware's own NaNs have.
+    // from memory gets the sign bit the hardware's own NaNs have.  f.0's negated bias is 0 - b: with -b a zero bias is -0, a
+    // pre-activation of exactly zero comes out as +0 * -rs + -0 = -0, and the sign word (the sign bit of -h) then says h > 0 where
+    // h = 0 -- the backward passed a gradient where torch's ReLU passes none.  With +0 the sum is +0 in every such case (round to
+    // nearest gives +0 for x - x and for -0 + +0).  f.2 multiplies a +0 accumulator by a positive scale: +0 + -0 = +0 as it stands.
     // ALL table values are requested here, in the same round as the window values and the first A sets, from clamped addresses, and
     // stored afterwards: as three copy loops every iteration was a round trip of its own (load, s_waitcnt vmcnt(0) -- which also
     // waited for everything requested before -- store): four to five serialised trips to L2 in front of the window, 4.8 k - 6.7 k
@@ -204,7 +207,7 @@ __global__ void __launch_bounds__(512) k_cnet(CnetArgs a, CnetGeo g) {
     __builtin_amdgcn_sched_barrier(0);            // (hipcc sinks the last request behind the first store otherwise: one more trip)
 #pragma unroll
     for (int i = 0; i < N0; ++i)
-        if (tid + 512 * i < 2 * HID) t_rs0[tid + 512 * i] = canon_nan(-tv0[i]);
+        if (tid + 512 * i < 2 * HID) t_rs0[tid + 512 * i] = canon_nan(0.f - tv0[i]);      // (0 - b, not -b: a zero bias becomes +0, see below)
 #pragma unroll
     for (int i = 0; i < N2; ++i)
         if (tid + 512 * i < MR) { t_rs2[tid + 512 * i] = canon_nan(tv2[i]); t_b2[tid + 512 * i] = canon_nan(-tvb[i]); }
@@ -984,9 +987,19 @@ size_t cnet_scratch_floats_per_sample(int H, int W, int Cout) {
     return (size_t)CN_MAXMS * ((size_t)Cout * H * W + (size_t)2 * tiles * Cout * W);
 }
 
+// the instance a launcher is about to launch, for the testing hook (sh.h CnetLaunchInfo); true: a dry run, launch nothing
+static bool cnet_report(CnetLaunchInfo* info, int hid, int ms, int upw, int pxt, int ng, int mode, const CnetGeo& g, size_t lds) {
+    if (!info) return false;
+    info->one_wave = 0; info->hid = hid; info->ms = ms; info->upw = upw; info->pxt = pxt; info->ng = ng; info->mode = mode;
+    info->g0 = g.G; info->nrt4 = g.NRT4;
+    info->grid[0] = g.tiles; info->grid[1] = ms; info->grid[2] = 1; info->lds_bytes = (int)lds;
+    return info->dry_run != 0;
+}
+
 template <int HID, int MS, int UPW, int PXT>
-static int launch_cnet_inst2(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {     // two groups of f.4 output channels (C = 96)
+static int launch_cnet_inst2(const CnetArgs& a, const CnetGeo& g, hipStream_t s, CnetLaunchInfo* info) {     // two groups of f.4 output channels (C = 96)
     const size_t lds = cnet_lds_bytes(g, HID);
+    if (cnet_report(info, HID, MS, UPW, PXT, 2, 0, g, lds)) return GLOWHIP_OK;
     (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT, 2>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet");
@@ -994,8 +1007,9 @@ static int launch_cnet_inst2(const CnetArgs& a, const CnetGeo& g, hipStream_t s)
 }
 
 template <int HID, int MS, int UPW, int PXT>
-static int launch_cnet_inst(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
+static int launch_cnet_inst(const CnetArgs& a, const CnetGeo& g, hipStream_t s, CnetLaunchInfo* info) {
     const size_t lds = cnet_lds_bytes(g, HID);
+    if (cnet_report(info, HID, MS, UPW, PXT, 1, 0, g, lds)) return GLOWHIP_OK;
     (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, UPW, PXT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((k_cnet<HID, MS, UPW, PXT>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet");
@@ -1065,8 +1079,9 @@ bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N) {
 }
 
 template <int HID, int MS, int PXT, int MODE>
-static int launch_cnet_tape(const CnetArgs& a, const CnetGeo& g, hipStream_t s) {
+static int launch_cnet_tape(const CnetArgs& a, const CnetGeo& g, hipStream_t s, CnetLaunchInfo* info) {
     const size_t lds = cnet_lds_bytes(g, HID);
+    if (cnet_report(info, HID, MS, 1, PXT, 1, MODE, g, lds)) return GLOWHIP_OK;
     (void)hipFuncSetAttribute((const void*)k_cnet<HID, MS, 1, PXT, 1, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL((k_cnet<HID, MS, 1, PXT, 1, MODE>), dim3(g.tiles, MS), dim3(512), lds, s, a, g);
     GH_LAUNCH_CHECK("k_cnet (taping)");
@@ -1079,7 +1094,7 @@ void cnet_pending_tiling(const CnetGeo& g, int ms, CnetPending* out) {
     out->MS = ms; out->tiles = g.tiles; out->R = g.R; out->NI = g.NI; out->lpxt = g.lpxt;
 }
 
-int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
+int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out, CnetLaunchInfo* info) {
     GH_REQUIRE(a.mode == TAIL_AFFINE_FWD || a.mode == TAIL_AFFINE_REV || a.mode == TAIL_ADD_FWD || a.mode == TAIL_ADD_REV,
                "cnet: coupling modes only");
     if (a.N == 0) return GLOWHIP_OK;
@@ -1093,17 +1108,17 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
                "cnet: no taping / backward instance for this launch");
     int rc = GLOWHIP_EINVAL;
     if (c.one_wave) {
-        GH_TRY(launch_cnet1w(a, g, s));
+        GH_TRY(launch_cnet1w(a, g, s, info));
         rc = GLOWHIP_OK;
     }
 #define GH_CNT(hid, m, px)                                                                                     \
     if (rc == GLOWHIP_EINVAL && tape && a.hidden == hid && ms == m && g.pxt == px)                             \
-        rc = a.bwd ? launch_cnet_tape<hid, m, px, 2>(a, g, s) : launch_cnet_tape<hid, m, px, 1>(a, g, s);
+        rc = a.bwd ? launch_cnet_tape<hid, m, px, 2>(a, g, s, info) : launch_cnet_tape<hid, m, px, 1>(a, g, s, info);
     GH_CNT(512, 1, 128) GH_CNT(512, 2, 128) GH_CNT(512, 4, 128) GH_CNT(512, 1, 64) GH_CNT(512, 2, 64) GH_CNT(512, 4, 64)
     GH_CNT(256, 1, 128) GH_CNT(256, 2, 128) GH_CNT(256, 1, 64) GH_CNT(256, 2, 64) GH_CNT(128, 1, 128) GH_CNT(128, 1, 64)
 #undef GH_CNT
-#define GH_CN(hid, m, u, px) if (rc == GLOWHIP_EINVAL && !tape && g.ng == 1 && a.hidden == hid && ms == m && upw == u && g.pxt == px) rc = launch_cnet_inst<hid, m, u, px>(a, g, s);
-#define GH_CN2(hid, m, u, px) if (!tape && g.ng == 2 && a.hidden == hid && ms == m && upw == u && g.pxt == px) rc = launch_cnet_inst2<hid, m, u, px>(a, g, s);
+#define GH_CN(hid, m, u, px) if (rc == GLOWHIP_EINVAL && !tape && g.ng == 1 && a.hidden == hid && ms == m && upw == u && g.pxt == px) rc = launch_cnet_inst<hid, m, u, px>(a, g, s, info);
+#define GH_CN2(hid, m, u, px) if (!tape && g.ng == 2 && a.hidden == hid && ms == m && upw == u && g.pxt == px) rc = launch_cnet_inst2<hid, m, u, px>(a, g, s, info);
     GH_CN2(512, 1, 1, 64) GH_CN2(512, 2, 1, 64) GH_CN2(512, 4, 1, 64) GH_CN2(256, 1, 1, 64) GH_CN2(256, 2, 1, 64) GH_CN2(128, 1, 1, 64)
 #undef GH_CN2
     GH_CN(512, 1, 1, 128) GH_CN(512, 2, 1, 128) GH_CN(512, 4, 1, 128) GH_CN(256, 1, 1, 128) GH_CN(256, 2, 1, 128) GH_CN(256, 4, 1, 128)
@@ -1111,7 +1126,8 @@ int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out) {
     GH_CN(512, 2, 2, 128) GH_CN(512, 4, 2, 128) GH_CN(256, 1, 2, 128) GH_CN(256, 2, 2, 128) GH_CN(256, 4, 2, 128) GH_CN(128, 1, 2, 128)
     GH_CN(128, 2, 2, 128) GH_CN(64, 1, 2, 128)
     GH_CN(512, 1, 1, 64) GH_CN(512, 2, 1, 64) GH_CN(512, 4, 1, 64) GH_CN(256, 1, 1, 64) GH_CN(256, 2, 1, 64) GH_CN(128, 1, 1, 64)
-    GH_CN(512, 1, 2, 64) GH_CN(512, 2, 2, 64) GH_CN(512, 4, 2, 64) GH_CN(256, 1, 2, 64) GH_CN(256, 2, 2, 64) GH_CN(128, 1, 2, 64)
+    // (no <*, *, 2, 64>: two T units per wave need NU4 * KS > 8, and a 64-pixel tile's unit holds two row tiles -- NU4 <= 8, with KS = 1
+    // from NU4 = 5 on.  tests/test_sh2_oracle_host.py enumerates the selection and finds none)
 #undef GH_CN
     if (rc == GLOWHIP_EINVAL) set_error("cnet: no kernel instance for hidden=%d ms=%d upw=%d tile=%d", a.hidden, ms, upw, g.pxt);
     GH_TRY(rc);

@@ -333,7 +333,7 @@ size_t dnet_scratch_bytes_per_sample(int C, int H, int W, int hidden, int Cout) 
     return 4 * ((size_t)C * HW + (size_t)(C / 2) * SL + (size_t)hidden * HW + (size_t)hidden * SL + (size_t)DNET_KS_MAX * Cout * HW) + 8 * 256;
 }
 
-static int dn_launch_gemm(const DnGemmArgs& a, hipStream_t s) {
+static int dn_launch_gemm(const DnGemmArgs& a, hipStream_t s, DnLaunchInfo* info = nullptr) {
     // 32-row tiles unless the launch has pixels to spare (every row tile re-reads the B operand from L2, every weight is read once
     // either way): more workgroups, and -- with fewer registers per operand set -- more k-steps of weights in flight per wave
     const bool pt2 = a.P > 32, rt2 = a.M % 64 == 0 && a.P >= 512;
@@ -347,6 +347,11 @@ static int dn_launch_gemm(const DnGemmArgs& a, hipStream_t s) {
             attr_set = true;                                                                                                        \
         }                                                                                                                           \
         hipLaunchKernelGGL((k_dn_gemm<8, RT, PT, NPF>), grid, dim3(512), lds, s, a);                                                \
+    }
+    if (info && info->n < 3) {
+        const int k = info->n++;
+        info->rt[k] = rt2 && pt2 ? 2 : 1; info->pt[k] = pt2 ? 2 : 1; info->npf[k] = rt2 && pt2 ? 4 : (pt2 ? 6 : 8);
+        info->grid[k][0] = (int)grid.x; info->grid[k][1] = (int)grid.y; info->grid[k][2] = (int)grid.z;
     }
     if (rt2 && pt2) DN_GO(2, 2, 4) else if (pt2) DN_GO(1, 2, 6) else DN_GO(1, 1, 8)
 #undef DN_GO
@@ -415,7 +420,8 @@ int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an
 
 // MIX of one step: forward y = W u (+ y1 padded for F0); reverse x = (W^-1 u) * exp(-3 logs) - bias (+ x1 padded for the next
 // executed step's F0 when `want_pad`)
-int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, const float* post_bias, int want_pad, hipStream_t s) {
+int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, const float* post_bias, int want_pad, hipStream_t s,
+             DnLaunchInfo* info) {
     const DnScratch d = dn_carve(L, L.scratch);
     const int P = L.N * L.H * L.W;
     DnGemmArgs g{};
@@ -424,11 +430,11 @@ int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, c
     g.N = L.N; g.H = L.H; g.W = L.W; g.P = P; g.ksplit = 1; g.epi = DN_EPI_MIX;
     g.out_sh = want_pad ? d.ypad : nullptr; g.out_plane = d.y_plane; g.out_slots = d.SLN; g.out_padded = 1; g.out_rows_sh = L.C / 2;
     g.out_f32 = L.state; g.out_bs = L.state_bs; g.post_scale = post_scale; g.post_bias = post_bias;
-    return dn_launch_gemm(g, s);
+    return dn_launch_gemm(g, s, info);
 }
 
 // F0 -> F2 -> F4 of one step: partial sums of h = f(z1) from the padded z1 operand
-int dnet_coupling_net(const DnetLevel& L, const void* w0, const void* w2, const void* w4, int* ks_out, hipStream_t s) {
+int dnet_coupling_net(const DnetLevel& L, const void* w0, const void* w2, const void* w4, int* ks_out, hipStream_t s, DnLaunchInfo* info) {
     const DnScratch d = dn_carve(L, L.scratch);
     const int P = L.N * L.H * L.W, Ch = L.C / 2;
     DnGemmArgs g{};
@@ -437,19 +443,19 @@ int dnet_coupling_net(const DnetLevel& L, const void* w0, const void* w2, const 
     g.A = (const _Float16*)w0; g.M = L.hidden; g.Kg = cnet_g0(Ch);
     g.B = d.ypad; g.b_plane = d.y_plane; g.b_slots = d.SLN; g.taps = 1; g.nchunk_b = Ch / 8;
     g.epi = DN_EPI_ACT; g.out_sh = d.h1; g.out_plane = d.h1_plane; g.out_slots = P; g.out_padded = 0; g.out_rows_sh = L.hidden;
-    GH_TRY(dn_launch_gemm(g, s));
+    GH_TRY(dn_launch_gemm(g, s, info));
     // F2: 1x1, hidden -> hidden
     g.A = (const _Float16*)w2; g.Kg = L.hidden / 8;
     g.B = d.h1; g.b_plane = d.h1_plane; g.b_slots = P; g.taps = 0;
     g.out_sh = d.h2pad; g.out_plane = d.h2_plane; g.out_slots = d.SLN; g.out_padded = 1;
-    GH_TRY(dn_launch_gemm(g, s));
+    GH_TRY(dn_launch_gemm(g, s, info));
     // F4: 3x3, hidden -> Cout, K split over workgroups
     g.A = (const _Float16*)w4; g.M = L.Cout; g.Kg = cnet_g0(L.hidden);
     g.B = d.h2pad; g.b_plane = d.h2_plane; g.b_slots = d.SLN; g.taps = 1; g.nchunk_b = L.hidden / 8;
     g.epi = DN_EPI_PARTIAL; g.out_sh = nullptr; g.out_f32 = d.part;
     g.ksplit = dn_ksplit(L.Cout, P, g.Kg / 2);
     *ks_out = g.ksplit;
-    return dn_launch_gemm(g, s);
+    return dn_launch_gemm(g, s, info);
 }
 
 int dnet_finish(const DnetLevel& L, int ks, const float* f4_bias, const float* f4_scale, int mode, unsigned long long* acc,

@@ -168,7 +168,11 @@ struct CnetArgs {
     char pad_to_128[24];
 };
 static_assert(sizeof(CnetArgs) % 128 == 0, "CnetGeo follows CnetArgs in the kernel arguments: keep it on a 128-byte boundary (pad_to_128)");
-int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out);            // k_cnet only; *out describes its partial sums
+// What launch_cnet_main chose (testing: glowhip_debug_sh2 fills a glowhip_sh2_info from it; every production caller passes nothing).
+// one_wave: k_cnet1w instead of k_cnet; hid, ms, upw, pxt, ng, mode: k_cnet's template arguments (k_cnet1w: hid, mode and g0, nrt4);
+// dry_run (set by the caller): everything is decided and reported, every refusal is made, nothing is launched
+struct CnetLaunchInfo { int dry_run, one_wave, hid, ms, upw, pxt, ng, mode, g0, nrt4, grid[3], lds_bytes; };
+int launch_cnet_main(const CnetArgs& a, hipStream_t s, CnetPending* out, CnetLaunchInfo* info = nullptr);   // k_cnet only; *out describes its partial sums
 int launch_cnet_finish(const CnetArgs& a, const CnetPending& p, hipStream_t s, FinLaunchInfo* info = nullptr);     // the finishing kernel for those sums (info: what was launched, testing)
 int launch_cnet(const CnetArgs& a, hipStream_t s);                                   // both
 bool cnet_tape_supported(int Cin, int H, int W, int hidden, int Cout, int N);        // a taping instance of k_cnet exists for the shape
@@ -190,9 +194,14 @@ int dnet_prep(const DnetLevel& L, const float* src, long src_bs, const float* an
               FinLaunchInfo* info = nullptr);      // info (here and in dnet_finish): what was launched (testing)
 // MIX: state <- W u (forward; w_image = SH2_GEMM image of W) or (W^-1 u) * post_scale - post_bias (reverse); want_pad: also the
 // first C/2 channels as the padded operand of the next F0
-int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, const float* post_bias, int want_pad, hipStream_t s);
+// what the k_dn_gemm launches of dnet_mix (one) / dnet_coupling_net (three: F0, F2, F4) chose (testing: glowhip_debug_sh2; every
+// production caller passes nothing): the template arguments <8, RT, PT, NPF> and the grid of each launch, appended in order
+struct DnLaunchInfo { int n, rt[3], pt[3], npf[3], grid[3][3]; };
+int dnet_mix(const DnetLevel& L, const void* w_image, const float* post_scale, const float* post_bias, int want_pad, hipStream_t s,
+             DnLaunchInfo* info = nullptr);
 // F0 -> F2 -> F4 on the padded z1 operand; *ks_out = number of K-split partial copies F4 left in the scratch
-int dnet_coupling_net(const DnetLevel& L, const void* w0_sh2_first, const void* w2_sh2_gemm, const void* w4_sh2_first, int* ks_out, hipStream_t s);
+int dnet_coupling_net(const DnetLevel& L, const void* w0_sh2_first, const void* w2_sh2_gemm, const void* w4_sh2_first, int* ks_out, hipStream_t s,
+                      DnLaunchInfo* info = nullptr);
 // FIN: coupling (mode = TailMode) on L.state in place + log-det; want_u: the next MIX's operand, with the next step's ActNorm
 // (u_bias / u_scale, forward) or plain (null, reverse)
 int dnet_finish(const DnetLevel& L, int ks, const float* f4_bias, const float* f4_scale, int mode, unsigned long long* acc,

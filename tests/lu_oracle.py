@@ -167,10 +167,9 @@ def apply_bound_sh2(M, v):
       2 * 2^-24 (|M| |v|)        the stored matrix entry against its fp64 value, the output store;
       2^-37 max_k |M_ok| sum_k |v_k|    the weights' absolute floor: 2^-25 at a row scale that puts the row's largest entry in [2^12, 2^13);
       2^-29 sum_k |M_ok|                the activations' floor: 2^-25 at the fixed scale 2^4."""
-    C = M.shape[0]
+    from sh2_oracle import bound_sh2      # (the one SH2 bound: the coupling-network kernels are held to the same function layer by layer)
     aM, av = np.abs(M).astype(np.float64), np.abs(v).astype(np.float64)
-    rel = 3 * 2.0 ** -22 + 3 * C * 2.0 ** -23 + 2 * 2.0 ** -24
-    return rel * (aM @ av) + 2.0 ** -37 * aM.max(axis=1)[:, None] * av.sum(axis=0)[None, :] + 2.0 ** -29 * aM.sum(axis=1)[:, None]
+    return bound_sh2(aM @ av, M.shape[0], aM.max(axis=1)[:, None] * av.sum(axis=0)[None, :], aM.sum(axis=1)[:, None])
 
 
 # ---- routes.  Names are the launch counters of glowhip_plan_launch_counts (csrc/plan_build.hip glowhip_plan_pack_for; csrc/lu.hip
