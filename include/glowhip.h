@@ -318,7 +318,8 @@ int glowhip_plan_set_dequant_stream(glowhip_plan* plan, unsigned long long seed,
  *              with more than 254 Split2d layers are refused; call < 2^56.  The top byte of c3 is never zero, the dequantisation
  *              stream's always is: the two share no counter under one seed.  Streams 128 + leaf (128 .. 247) and 254 belong
  *              to the posterior chain ("Posterior sampling" below: the proposal's draws and the accept test's uniform, call =
- *              the chain's iteration); 248 .. 253 are unassigned.
+ *              the chain's iteration); 248 names the Gaussian sensing matrix of compressed sensing
+ *              ("a dense linear operator" below: call 0, element = flat index in the (M, C, H, W) matrix); 249 .. 253 are unassigned.
  *   element   flat index in the contiguous (N, C, H, W) draw tensor
  *   normals    words (w0, w1) give elements 0, 1 of the group, (w2, w3) elements 2, 3, by Box-Muller in fp32:
  *                u1 = ((w >> 9) + 0.5) * 2^-23, u2 = (w' >> 8) * 2^-24, r = sqrtf(-2 logf(u1)),
@@ -535,6 +536,44 @@ int glowhip_restore_objective_psf(const float* x, const float* target, const flo
                                   int N, int C, int H, int W, int pool,
                                   float* resid /* scratch AND output: (N,C,H/pool,W/pool) = w (A x - t) */,
                                   float* grad_x, float* loss_out, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The restoration objective observed through a dense linear operator: compressed sensing, t = A x + noise with M well below D.
+ * THE definition.  Per sample n, with x[n] flattened to D = C*H*W values in (C,H,W) order and A an (M, D) row-major fp32 matrix
+ * shared by the batch:
+ *     y[n,m]      = sum_d A[m,d] * x[n,d]
+ *     resid[n,m]  = w[n,m] * (y[n,m] - t[n,m])                      (N,M): scratch AND output
+ *     loss_out[n] = inv_wsum[n] * sum_m w[n,m] * (y[n,m] - t[n,m])^2
+ *     grad_x[n,d] = sum_m A[m,d] * u[n,m],    u = 2 * inv_wsum[n] * resid      (the scaling applied to the residual BEFORE A^T, as
+ *                                                                               phase 2 of the PSF kernel does)
+ * x, grad_x: (N, D) contiguous; target, weight, resid: (N, M); inv_wsum: (N).  weight == NULL means all ones, inv_wsum == NULL means
+ * 1 / M; loss_out may be NULL (overwritten, never accumulated into).  The call does not normalise A.  x, grad_x, resid, A and the
+ * scratch must not overlap.
+ * Plain fp32 FMA on the vector pipe; both products are paced by reading A, which each reads from HBM once for any N up to 64.  The
+ * launches (csrc/restore_linear.hip): the forward product over row blocks x D slices of 4 096 columns, a workgroup's A tile held in
+ * registers while it loops over the batch in sample tiles of 4, a slice's partial y into the scratch; one workgroup per sample that
+ * sums the partials in slice order and runs glowhip_restore_objective's own loops over y (the same 16-byte or element path by the
+ * same address rule, the fp64 loss per thread in element order, then wave, then workgroup), writing resid and u; the adjoint product
+ * over column blocks x M slices of 128 rows, one accumulator per sample in each lane; and, where M has more than one slice, the sum
+ * of the slices' partials in slice order.  No atomics, nothing depends on workgroup order: bitwise the same run to run.  Every slice
+ * count and tile shape is a function of (M, D) only, never of N, and no arithmetic of a sample reads another sample's values: sample
+ * n's outputs have the same bits in a batch of 1 and in a batch of 64 (buffers placed alike), and a non-finite x[n] reaches no other
+ * sample's outputs.  inv_wsum[n] == 0: exact zeros in grad_x[n] and resid[n] and loss 0, whatever x[n] holds.  With A the D x D
+ * identity, loss_out and grad_x are bit-identical to glowhip_restore_objective's at pool 1 on the same inputs (placed so that both
+ * take the same access path): products with +-0 and one-term sums round nothing.  The one thing a sum cannot carry is the sign
+ * of an exact zero: where w == 0 and x < t that call returns -0, and here the -0 meets the +0 products of the identity's other
+ * rows (-0 + +0 = +0).  glowhip_restore_objective and glowhip_restore_objective_psf are untouched.
+ * scratch: glowhip_restore_linear_scratch_bytes(N, M, D) bytes at a 16-byte aligned address (the D slices' partial y, u, the M
+ * slices' partial gradients); the size is monotone in each argument, and 0 only on error (see glowhip_last_error).  No allocation,
+ * no host sync, capturable; offsets into A are 64-bit.
+ * GLOWHIP_EINVAL with a message and no device call: a NULL x, target, A, resid or grad_x; M < 1, D < 1, D >= 2^31 or M*D >= 2^40
+ * (or a shape of more than 2^31 workgroups or 2^46 scratch bytes, which no such matrix in memory reaches); N < 0; a scratch that is
+ * NULL, misaligned or too small.  N == 0 returns GLOWHIP_OK. */
+size_t glowhip_restore_linear_scratch_bytes(int N, long M, long D);          /* 0: see last_error */
+int    glowhip_restore_objective_linear(const float* x, const float* target, const float* weight, const float* inv_wsum,
+                                        const float* A, long M, int N, long D,
+                                        float* resid, float* grad_x, float* loss_out,
+                                        void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Posterior sampling: a Metropolis-adjusted Langevin (MALA) chain over the latents of an inverse problem, one independent chain

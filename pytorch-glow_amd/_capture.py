@@ -4,6 +4,8 @@ Each of the five sites (`network.model.GraphedSampler` / `GraphedForward`, `trai
 `network.posterior.LatentMALA`) gives a `Capture` its body and a function that returns its SIGNATURE: a dict of named items --
 addresses, version counters, epochs -- for what ITS captured launches reach and an eager call in between could move or rebuild
 (`FlowPlan.capture_signature`, `_HipOptimizer.capture_signature`).  What a stale graph costs -- an error, a recapture -- is the site's."""
+import gc
+
 import torch
 
 from . import _lib
@@ -28,7 +30,8 @@ class Capture:
     """``body`` recorded once on a side stream, by the sequence every site follows: the side stream joins the current one;
     ``warmup`` eager runs of the body on it (the inference graphs: workspace, job tables, lazy inits -- the other sites have an eager
     step behind them instead); a device synchronise; ``plan.pack_sync()``, so nothing of an earlier pack is left for the captured
-    calls to join; the recording, under ``torch.no_grad()``.  Nothing runs during the recording."""
+    calls to join; the recording, under ``torch.no_grad()`` and with Python's cycle collector off.  Nothing runs
+    during the recording."""
 
     def __init__(self, plan, body, signature, warmup=0):
         dev = plan.device
@@ -40,12 +43,23 @@ class Capture:
                     for _ in range(warmup):
                         body()
                 torch.cuda.current_stream(dev).wait_stream(side)
+            # No garbage collection inside the recording.  A finished loop and its `Capture` are a reference cycle (the body and
+            # the signature close over the loop), so the graph and the side stream of an earlier fit die only when the cycle
+            # collector runs -- and the body's thousands of small host objects make it run inside the recording, where destroying
+            # a graph or a stream aborts the process (torch.cuda.graph used to collect on entry and no longer does by default).
+            # Keep the collector off until the recording has ended; what is dead dies after it, as it did before.
             torch.cuda.synchronize(dev)
             plan.pack_sync()
             self.graph = torch.cuda.CUDAGraph()
-            # (thread_local: a DataLoader's pinning thread may touch the device while this thread captures)
-            with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
-                body()
+            collecting = gc.isenabled()
+            gc.disable()
+            try:
+                # (thread_local: a DataLoader's pinning thread may touch the device while this thread captures)
+                with torch.cuda.graph(self.graph, stream=side, capture_error_mode="thread_local"):
+                    body()
+            finally:
+                if collecting:
+                    gc.enable()
         self.replay = self.graph.replay
         self._signature, self._then = signature, signature()
 

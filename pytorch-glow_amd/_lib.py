@@ -344,6 +344,8 @@ SIGNATURES = {
     "glowhip_grad_accumulate": (c_int, [POINTER(GradSeg), c_int, c_int, c_float, _P]),
     "glowhip_restore_objective": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, _P]),
     "glowhip_restore_objective_psf": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
+    "glowhip_restore_linear_scratch_bytes": (c_size_t, [c_int, c_long, c_long]),
+    "glowhip_restore_objective_linear": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_long, _P, _P, _P, _P, c_size_t, _P]),
     "glowhip_mala_scratch_bytes": (c_size_t, [POINTER(MalaSeg), c_int, c_int, c_int]),
     "glowhip_mala_init": (c_int, [_P, _P, c_int, c_float, c_float, _P]),
     "glowhip_mala_propose": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),

@@ -141,12 +141,51 @@ class Inferer:
                 history.append(loss.detach())
         return lat.detach(), [float(v) for v in torch.stack(history).cpu()] if history else []
 
-    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid"):
+    def _linear_problem(self, measurement, weight, pool, init, chains, psf, operator):
+        """`_problem` with a dense ``operator`` (M,C,H,W): the measurement is (N, M) -- (M,) for one problem -- and so is the weight;
+        ``init`` None = all-zero latents, the prior's mode (there is no image to encode); ``chains`` > 1 repeats a single measurement
+        and shares the one operator.  Every refusal is a ValueError raised before any device work."""
+        from .restore import check_operator_shape
+        if psf is not None or int(pool) != 1:
+            raise ValueError("operator: a dense operator excludes psf, and pool must be 1")
+        if not torch.is_tensor(operator) or not torch.is_tensor(measurement):
+            raise TypeError("operator and measurement are tensors (network.restore.gaussian_operator makes an operator on the device)")
+        m, _ = check_operator_shape(operator.shape, self.graph.flow.in_chw)
+        if measurement.dim() not in (1, 2) or measurement.shape[-1] != m:
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)}: expected (N, {m}) or ({m},) with this operator")
+        n = 1 if measurement.dim() == 1 else measurement.shape[0]
+        if weight is not None:
+            wshape = tuple(weight.shape) if torch.is_tensor(weight) else tuple(torch.as_tensor(weight).shape)
+            if len(wshape) not in (1, 2) or wshape[-1] != m or (len(wshape) == 2 and wshape[0] not in (1, n)):
+                raise ValueError(f"weight of shape {wshape}: expected ({n}, {m}) or ({m},) with this operator")
+        if chains < 1 or (chains > 1 and n != 1):
+            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {n} runs one chain each)")
+        if operator.dtype != torch.float32 or not operator.is_contiguous() or not operator.is_cuda:
+            raise ValueError("operator must be a contiguous fp32 tensor on the device (it is held by reference, never copied)")
+        meas = measurement.reshape(n, m).to(self.device).float().contiguous()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand(n, m).contiguous()
+        if chains > 1:
+            meas = meas.expand(chains, m).contiguous()
+            weight = None if weight is None else weight.expand(chains, m).contiguous()
+            n = chains
+        if init is None:
+            plan = self.graph.flow.plan_for(tuple(operator.shape[1:]), self.device)
+            zeros = lambda chw: torch.zeros((n,) + tuple(chw), dtype=torch.float32, device=self.device)
+            init = Latents(zeros(plan.out_chw), [zeros(chw) for chw in plan.split_chw])
+        elif chains > 1 and len(init) == 1:
+            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
+            init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        return meas, weight, 1, init, None
+
+    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid", operator=None):
         """``(measurement batch, weight broadcast to it, pool, start latents, psf)`` of `restore` / `posterior`: ``init`` None =
         ``encode_full`` of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement
         (and a single PSF).  With a ``psf``, ``border="valid"`` multiplies the weight (None = ones) by
         `network.restore.psf_valid_weight`; every refusal of a PSF is raised before any device work."""
         from .restore import check_psf_shape, psf_valid_weight
+        if operator is not None:
+            return self._linear_problem(measurement, weight, pool, init, chains, psf, operator)
         if psf is not None:
             psf = torch.as_tensor(psf, dtype=torch.float32)
             if border not in ("valid", "zero"):
@@ -184,7 +223,7 @@ class Inferer:
         return meas, weight, pool, init, psf
 
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
-                graph=True, exact=False, psf=None, border="valid"):
+                graph=True, exact=False, psf=None, border="valid", operator=None):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
         image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
         super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
@@ -215,17 +254,26 @@ class Inferer:
         weight 0 to the measurement cells whose footprint leaves the image (`network.restore.psf_valid_weight`: ceil(ah / pool)
         rows and ceil(aw / pool) columns at each edge), before ``inv_wsum`` is formed; ``border="zero"`` leaves the weight alone
         and takes the kernel's zero padding as the truth.  An even side, a side above 15, a wrong leading dimension or a band that
-        leaves no cell raise ValueError before any device work.  ``init=None`` stays ``encode_full`` of the measurement."""
+        leaves no cell raise ValueError before any device work.  ``init=None`` stays ``encode_full`` of the measurement.
+
+        ``operator``: compressed sensing -- the decode, flattened in (C,H,W) order, is observed through a dense matrix,
+        ``measurement = A x + noise`` (include/glowhip.h, glowhip_restore_objective_linear).  A contiguous fp32 DEVICE tensor of
+        shape (M, C, H, W) with (C, H, W) the model's image shape, shared by the batch, not normalised and held by reference: do
+        not write to it during the fit (`network.restore.gaussian_operator` makes the standard N(0, 1/M) matrix on the device).
+        ``measurement`` and ``weight`` are then (N, M), or (M,) for one problem.  ``operator`` together with ``psf`` or
+        ``pool != 1``, a measurement or weight whose last dimension is not M, and an operator that is not 4-D or not of the model's
+        image shape raise ValueError before any device work.  ``init=None`` starts from all-zero latents, the prior's mode: there
+        is no image to encode."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
-        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border)
+        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border, operator=operator)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
-                        max_grad_norm=max_grad_norm, graph=graph, psf=psf)
+                        max_grad_norm=max_grad_norm, graph=graph, psf=psf, operator=operator)
         info = fit.run(exact=exact)
         return fit.latents(), info
 
     def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
-                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid"):
+                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None):
         """Draws from the posterior of the latents given ``measurement`` -- what else is consistent with it, and how sure the model
         is of each pixel -- by a Metropolis-adjusted Langevin chain on the device (`network.posterior.LatentMALA`):
 
@@ -247,19 +295,23 @@ class Inferer:
         ``finite=False`` and runs no iteration.  Nothing else raises; one host sync at the start state, one read at the end.
 
         ``psf`` / ``border``: the measurement is a blurred image, as for `restore`; with ``chains=K`` a single PSF is repeated as
-        the measurement is."""
+        the measurement is.  ``operator``: the measurement (N, M) or (M,) is the decode seen through a dense matrix (M,C,H,W), as for
+        `restore`; ``chains=K`` repeats the measurement and shares the one operator, and ``init=None`` starts every chain from the
+        all-zero latents."""
         from .model import sampler_position
         from .posterior import LatentMALA
         from .restore import check_prior_weight
         check_prior_weight(self.graph, 1.0)
-        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border)
+        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border,
+                                                      operator=operator)
         if seed is None:
             seed, call = sampler_position(advance=True)
             call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)
         else:
             seed, call = int(seed) & (2 ** 64 - 1), 0
         chain = LatentMALA(self.graph, meas, weight=weight, pool=pool, noise_std=noise_std, init=init, steps=steps, burn_in=burn_in,
-                           thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call, psf=psf)
+                           thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call, psf=psf,
+                           operator=operator)
         info = chain.run()
         return chain.latents(), info
 

@@ -13,8 +13,13 @@ device -- and, with ``graph=True``, as one hipGraph launch per iteration.
 
 Deblurring: with a point-spread function ``psf`` the decode is observed through A = P B, B the zero-padded convolution by the PSF
 (glowhip_restore_objective_psf; include/glowhip.h has the definition).  Only `LatentLoop._evaluate` knows: decode, `decode_vjp`,
-the optimiser, the MALA launches, the capture protocol and the histories are the same with and without one."""
+the optimiser, the MALA launches, the capture protocol and the histories are the same with and without one.
+
+Compressed sensing: with a dense ``operator`` A of shape (M, C, H, W) the measurement is (N, M), t = A x + noise with x the flattened
+decode (glowhip_restore_objective_linear, csrc/restore_linear.hip; `gaussian_operator` makes the standard i.i.d. N(0, 1/M) matrix on
+the device from the sampler's stream 248).  Again only `LatentLoop._evaluate` knows."""
 import contextlib
+import math
 from dataclasses import dataclass
 from typing import Optional
 
@@ -53,7 +58,44 @@ def psf_valid_weight(meas_shape, kh, kw, pool=1):
     return m
 
 
-def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None, psf=None, resid_out=None):
+OPERATOR_STREAM = 248      # the sampler stream that names a Gaussian sensing matrix (include/glowhip.h: the stream table)
+
+
+def check_operator_shape(shape, image_shape=None, what="operator"):
+    """``(M, D)`` of an operator of shape (M, C, H, W); ``image_shape`` (C, H, W): the image it must observe.  ValueError otherwise."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 4 or min(shape) < 1:
+        raise ValueError(f"{what} of shape {shape}: expected (M, C, H, W)")
+    if image_shape is not None and shape[1:] != tuple(int(v) for v in image_shape):
+        raise ValueError(f"{what} of shape {shape} does not observe images of shape {tuple(image_shape)}")
+    return shape[0], shape[1] * shape[2] * shape[3]
+
+
+def linear_scratch(n, m, d, device):
+    """The scratch of glowhip_restore_objective_linear for a batch of ``n``: a uint8 device tensor of
+    glowhip_restore_linear_scratch_bytes(n, m, d) bytes."""
+    need = int(_lib.lib().glowhip_restore_linear_scratch_bytes(int(n), int(m), int(d)))
+    if need == 0:
+        _lib.check(-1)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def gaussian_operator(m, image_shape, seed, device):
+    """The standard compressed-sensing matrix, i.i.d. N(0, 1/m), as an (m, C, H, W) fp32 tensor made ON the device: stream 248 of
+    the sampler's generator at ``(seed, call = 0)``, element = flat index, times ``float32(1 / sqrt(m))`` (glowhip_normal_noise).
+    The matrix is named by ``(m, image_shape, seed)``: it never crosses PCIe, and tests/linear_oracle.py restates it on the CPU."""
+    m = int(m)
+    shape = (m,) + tuple(int(v) for v in image_shape)
+    check_operator_shape(shape)
+    out = torch.empty(shape, dtype=torch.float32, device=device)
+    std = float(torch.tensor(1.0 / math.sqrt(m), dtype=torch.float32))
+    _lib.check(_lib.lib().glowhip_normal_noise(_lib.ptr(out), out.numel(), int(seed) & (2 ** 64 - 1), 0, OPERATOR_STREAM, std,
+                                               _lib.stream_ptr(out.device)))
+    return out
+
+
+def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None, psf=None, resid_out=None,
+                      operator=None, scratch=None):
     """``(loss (N,), grad_x)`` of the data term for images ``x`` (N,C,H,W): glowhip_restore_objective.  ``target`` / ``weight``
     (N,C,H/pool,W/pool; weight None = ones), ``inv_wsum`` (N,; None = 1 / elements of one measurement).  Contiguous fp32 device
     tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write.
@@ -61,13 +103,23 @@ def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out
     ``psf`` (kh,kw) or (N,kh,kw), sides odd and at most 15: the image is observed through that point-spread function before the
     pool (glowhip_restore_objective_psf; include/glowhip.h has the definition), one for the batch or one per sample, not
     normalised.  ``resid_out`` (N,C,H/pool,W/pool): where that call leaves w (A x - t) -- its scratch, allocated when None.
-    ``psf=None`` is the call above, unchanged."""
+    ``psf=None`` is the call above, unchanged.
+
+    ``operator`` (M,C,H,W): the image is observed through that dense matrix, y = A x with x flattened in (C,H,W) order
+    (glowhip_restore_objective_linear); ``target`` / ``weight`` / ``resid_out`` are then (N, M), ``psf`` must be None and ``pool``
+    1.  The operator is read where it is and not normalised.  ``scratch``: a uint8 device tensor of at least
+    glowhip_restore_linear_scratch_bytes(N, M, C H W) bytes (`linear_scratch`), allocated when None.  ``operator=None`` is every
+    call above, unchanged."""
     for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out),
-                    ("psf", psf), ("resid_out", resid_out)):
+                    ("psf", psf), ("resid_out", resid_out), ("operator", operator)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
             raise _lib.GlowHipError(f"restore_objective: {name} must be a contiguous fp32 tensor on the device of x")
     n, c, h, w = x.shape
     pool = int(pool)
+    if operator is not None:
+        return _restore_objective_linear(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch)
+    if scratch is not None:
+        raise _lib.GlowHipError("restore_objective: scratch belongs to the call with an operator")
     mshape = None
     if pool >= 1 and h % pool == 0 and w % pool == 0:      # (anything else is the C call's to refuse)
         mshape = (n, c, h // pool, w // pool)
@@ -94,6 +146,34 @@ def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out
     _lib.check(_lib.lib().glowhip_restore_objective_psf(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum),
                                                         _lib.ptr(psf), kh * kw if psf.dim() == 3 else 0, kh, kw, n, c, h, w, pool,
                                                         _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss), _lib.stream_ptr(x.device)))
+    return loss, grad
+
+
+def _restore_objective_linear(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch):
+    """`restore_objective` with an operator (its tensors are already known to be contiguous fp32 on the device of x)."""
+    n = x.shape[0]
+    if psf is not None or pool != 1:
+        raise _lib.GlowHipError("restore_objective: an operator excludes psf, and pool must be 1")
+    if operator.dim() != 4 or tuple(operator.shape[1:]) != tuple(x.shape[1:]):
+        raise _lib.GlowHipError(f"restore_objective: operator of shape {tuple(operator.shape)}: expected (M,) + {tuple(x.shape[1:])}")
+    m, d = operator.shape[0], operator[0].numel()
+    for name, t in (("target", target), ("weight", weight), ("resid_out", resid_out)):
+        if t is not None and tuple(t.shape) != (n, m):
+            raise _lib.GlowHipError(f"restore_objective: {name} must have shape {(n, m)} with this operator")
+    if inv_wsum is not None and inv_wsum.numel() != n:
+        raise _lib.GlowHipError(f"restore_objective: inv_wsum holds {inv_wsum.numel()} values for a batch of {n}")
+    grad = torch.empty_like(x) if grad_out is None else grad_out
+    loss = torch.empty(n, dtype=torch.float32, device=x.device) if loss_out is None else loss_out
+    if tuple(grad.shape) != tuple(x.shape) or loss.numel() != n:
+        raise _lib.GlowHipError("restore_objective: grad_out must have the shape of x, loss_out one value per sample")
+    resid = torch.empty_like(target) if resid_out is None else resid_out
+    if scratch is None:
+        scratch = linear_scratch(n, m, d, x.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.device == x.device):
+        raise _lib.GlowHipError("restore_objective: scratch must be a contiguous uint8 tensor on the device of x")
+    _lib.check(_lib.lib().glowhip_restore_objective_linear(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum),
+                                                           _lib.ptr(operator), m, n, d, _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss),
+                                                           _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(x.device)))
     return loss, grad
 
 
@@ -124,22 +204,38 @@ def check_prior_weight(glow, prior_weight):
 
 class LatentLoop:
     """What the device-resident loops over the latents of a measurement share -- `LatentFit` here, `posterior.LatentMALA`: the
-    problem (``target``, ``weight``, ``pool``, the optional point-spread function ``psf``, the plan of the full-resolution image, the start leaves ``_start``, the static
+    problem (``target``, ``weight``, ``pool``, the optional point-spread function ``psf`` or dense ``operator``, the plan of the full-resolution image, the start leaves ``_start``, the static
     ``image`` and its gradient ``grad_x``), one evaluation of it, and an iteration as either Python-enqueued launches
     (`step_eager`) or one hipGraph launch (`capture` once, after at least one eager iteration -- lazy allocations, packed weights
     -- then `step_captured`), by the package's one capture protocol (`_capture.Capture`).  Same kernels and same bits either way.
 
     A subclass supplies ``inv_wsum`` (the per-sample factor of the data term), ``_body(captured)`` (the iteration), `reset`, and,
-    where a replay has a host side, ``_capturing()`` / ``_signature()`` / ``_replay_host()``."""
+    where a replay has a host side, ``_capturing()`` / ``_signature()`` / ``_replay_host()``.
 
-    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None):
+    ``operator`` (M,C,H,W), a contiguous fp32 device tensor: the measurement is (N, M) and the image shape is the operator's.  The
+    loop holds the operator BY REFERENCE -- a sensing matrix is hundreds of MB; it is not copied -- so the caller must not write
+    to it (or free it) while a fit or a chain that uses it is alive.  ``resid`` and the call's scratch ``op_scratch`` are the loop's own."""
+
+    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None, operator=None):
         self.glow, self.pool, self.steps, self.want_graph = glow, int(pool), int(steps), bool(graph)
         meas = _lib.require_device_tensor(measurement, "measurement")
         dev = self.device = meas.device
-        n, c, h, w = meas.shape
         if self.pool < 1:
             raise ValueError(f"pool = {pool}")
-        self.plan = plan = glow.flow.plan_for((c, h * self.pool, w * self.pool), dev)
+        if operator is not None:
+            if psf is not None or self.pool != 1:
+                raise ValueError("an operator excludes psf, and pool must be 1")
+            op = _lib.require_device_tensor(operator, "operator")
+            if op is not operator or op.device != dev:      # (never a copy of a matrix of hundreds of MB behind the caller's back)
+                raise ValueError("operator must be a contiguous fp32 tensor on the device of the measurement")
+            m, d = check_operator_shape(op.shape)
+            if meas.dim() != 2 or meas.shape[1] != m:
+                raise ValueError(f"measurement of shape {tuple(meas.shape)}: expected (N, {m}) with this operator")
+            n, image_chw = meas.shape[0], tuple(op.shape[1:])
+        else:
+            n, c, h, w = meas.shape
+            image_chw = (c, h * self.pool, w * self.pool)
+        self.plan = plan = glow.flow.plan_for(image_chw, dev)
         if tuple(init.z.shape) != (n,) + plan.out_chw or len(init.eps) != plan.n_split:
             raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
         self.n = n
@@ -155,6 +251,12 @@ class LatentLoop:
             self.psf = _lib.require_device_tensor(psf, "psf").to(dev).clone()
             check_psf_shape(self.psf.shape, n)
             self.resid = torch.empty_like(self.target)
+        # the dense operator (by reference), its residual and the scratch of its call: static buffers like the above
+        self.operator = self.op_scratch = None
+        if operator is not None:
+            self.operator = op
+            self.resid = torch.empty_like(self.target)
+            self.op_scratch = linear_scratch(n, m, d, dev)
         self._capture = None
         self.graph_error = None
         self._iterations = 0         # run since construction (a reset does not take the lazy allocations back)
@@ -162,12 +264,12 @@ class LatentLoop:
     # ------------------------------------------------------------------ the iteration
     def _evaluate(self, leaves, image, loss, grads):
         """`FlowPlan.decode` of ``leaves`` into ``image``; `restore_objective` (per-sample loss into ``loss``, its image gradient
-        into ``grad_x``; through ``psf`` when the loop has one, with ``resid`` as its scratch); `FlowPlan.decode_vjp` of that into
-        ``grads``."""
+        into ``grad_x``; through ``psf`` or ``operator`` when the loop has one, with ``resid`` -- and ``op_scratch`` -- as its scratch);
+        `FlowPlan.decode_vjp` of that into ``grads``."""
         plan = self.plan
         plan.decode(leaves[0], leaves[1:], out=image)
         restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss,
-                          psf=self.psf, resid_out=self.resid)
+                          psf=self.psf, resid_out=self.resid, operator=self.operator, scratch=self.op_scratch)
         plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
 
     def _capturing(self):            # the context of a recording (the fit: its optimiser's)
@@ -178,9 +280,10 @@ class LatentLoop:
 
     def _signature(self):
         """What a captured iteration reaches through the plan and an eager call in between could have moved or rebuilt: no pack is
-        inside, so the parameters' versions and the family count, and the workspaces of the decode and of its VJP.  ``psf`` and
-        ``resid`` need no entry: like ``target`` and ``weight`` they are this loop's own static buffers, allocated once in the
-        constructor and never rebound, so a recorded launch always reaches them."""
+        inside, so the parameters' versions and the family count, and the workspaces of the decode and of its VJP.  ``psf``,
+        ``resid`` and ``op_scratch`` need no entry: like ``target`` and ``weight`` they are this loop's own static buffers, allocated
+        once in the constructor and never rebound, so a recorded launch always reaches them; ``operator`` is the caller's tensor,
+        held here for the loop's life, which the caller must leave alone (`LatentLoop`)."""
         return self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
 
     @torch.no_grad()
@@ -247,18 +350,19 @@ class LatentFit(LatentLoop):
     iteration still counts in the bias corrections (the host never looks): harmless, because a fit with a skipped iteration is
     either run again on the exact-fp32 family or reported ``finite=False``.
 
-    ``psf`` (kh,kw) or (N,kh,kw), a device tensor: the measurement is the decode blurred by it (`LatentLoop`)."""
+    ``psf`` (kh,kw) or (N,kh,kw), a device tensor: the measurement is the decode blurred by it (`LatentLoop`).  ``operator``
+    (M,C,H,W): the measurement (N, M) is the decode seen through that dense matrix, held by reference (`LatentLoop`)."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
-                 graph=True, psf=None):
+                 graph=True, psf=None, operator=None):
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
-        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator)
         self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
         n, dev = self.n, self.device
         # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
-        self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=(1, 2, 3)).clamp(min=1.0)
+        self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=tuple(range(1, self.weight.dim()))).clamp(min=1.0)
         self.loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_hist = torch.zeros((self.steps, n), dtype=torch.float32, device=dev)
