@@ -576,6 +576,51 @@ int    glowhip_restore_objective_linear(const float* x, const float* target, con
                                         void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Blind deblurring: the PSF as an unknown of the fit -- the gradient of the data term of glowhip_restore_objective_psf with
+ * respect to the taps of the PSF, and the softmax that keeps an estimate on the simplex (csrc/restore_blind.hip; fp64 restatement
+ * tests/blind_oracle.py).  THE definition.  Notation as for glowhip_restore_objective_psf; per sample n, k the kh x kw PSF,
+ * ah = (kh - 1) / 2, aw = (kw - 1) / 2, v = resid = w (A x - t) at measurement resolution, inv = inv_wsum[n] (NULL: that call's
+ * default 1 / (C (H/pool) (W/pool))):
+ *     u[c,i,j]   = (2 inv * v[c, i/pool, j/pool]) * (1/pool^2)          formed with exactly the two roundings phase 2 of the PSF kernel uses
+ *     g_k[n,a,b] = sum_{c,i,j} u[c,i,j] * x[c, i + ah - a, j + aw - b]     (x = 0 outside the image)   = d loss[n] / d k[a,b]
+ * For a PSF shared by the batch (psf_stride == 0), g_k = sum_n g_k[n], in sample order.  With k = softmax(theta) over the kh*kw taps
+ * of one PSF,
+ *     g_theta[q] = k[q] * (g_k[q] - sum_r k[r] g_k[r])
+ * The softmax gives taps >= 0 that sum to 1: it fixes the scale ambiguity between PSF and image without a projection step.  A
+ * translation ambiguity remains (a shifted PSF and the oppositely shifted image explain the same measurement): the centre of the
+ * start PSF and the valid-band weights select the solution.
+ *
+ * glowhip_psf_from_logits: psf[p] = softmax(logits[p]) for n_psf PSFs of kh*kw taps, both dense.  The max is subtracted, the
+ * exponentials and their sum are taken in fp64 in tap order, one rounding to fp32 per tap.  One launch, one workgroup per PSF.
+ * GLOWHIP_EINVAL: a NULL pointer, kh or kw even, < 1 or > 15, n_psf < 0.  n_psf == 0 returns GLOWHIP_OK.
+ *
+ * glowhip_restore_psf_grad runs after glowhip_restore_objective_psf on the same x, resid and inv_wsum.  grad_psf and grad_logits
+ * are dense (n_psf, kh*kw) with n_psf = psf_stride ? N : 1; either may be NULL, not both; psf (with psf_stride as in that call) is
+ * read only for grad_logits.  Overwritten, never accumulated into.  x, resid, the outputs and the scratch must not overlap.
+ * Two launches: the partial launch over samples x (channel, 8-row band, 64-column tile) -- u and the x tile with its zero halo
+ * staged in LDS, a thread owns a tap and a slice of the tile's columns, fp32 fmaf chains of at most 64 terms, everything above a
+ * chain folded in fp64 in a fixed order, kh*kw doubles per workgroup into the scratch -- and the finishing launch, one workgroup per
+ * PSF, which folds the partials in (sample,) channel, band, tile order in fp64, writes grad_psf with one rounding, applies the
+ * softmax backward in fp64 and writes grad_logits with one rounding.
+ * Guarantees.  inv_wsum[n] == 0: sample n contributes exact zeros, whatever x[n] holds.  A non-finite x[n] reaches no other sample's
+ * per-sample output; with a shared PSF it reaches the shared gradient and nothing else.  No atomics, nothing depends on workgroup
+ * order: the same bits run to run.  Every tile, band, slice and group count is a function of (C, H, W, kh, kw, pool) only, never of
+ * N: with per-sample PSFs sample n's gradient has the same bits in a batch of 1 and in a batch of 5 (buffers placed alike).
+ * scratch: glowhip_restore_psf_grad_scratch_bytes(N, C, H, W, kh, kw, pool) bytes at a 16-byte aligned address; the size is monotone
+ * in each argument, and 0 only on error (see glowhip_last_error).  No allocation, no host sync, capturable.
+ * GLOWHIP_EINVAL with a message and no device call: a NULL x or resid, grad_psf and grad_logits both NULL, grad_logits without psf;
+ * kh or kw even, < 1 or > 15; psf_stride neither 0 nor >= kh*kw; N < 0, C, H or W < 1; pool < 1 or not dividing H and W;
+ * C*H*W >= 2^31 (or a shape of more than 2^31 workgroups or 2^46 scratch bytes); a scratch that is NULL, misaligned or too small.
+ * N == 0 returns GLOWHIP_OK. */
+int    glowhip_psf_from_logits(const float* logits, float* psf, int n_psf, int kh, int kw, glowhip_stream_t stream);
+size_t glowhip_restore_psf_grad_scratch_bytes(int N, int C, int H, int W, int kh, int kw, int pool);      /* 0: see last_error */
+int    glowhip_restore_psf_grad(const float* x, const float* resid, const float* inv_wsum,
+                                const float* psf, long psf_stride /* 0: one PSF for the batch; else >= kh*kw */, int kh, int kw,
+                                int N, int C, int H, int W, int pool,
+                                float* grad_psf /* (n_psf, kh*kw) or NULL */, float* grad_logits /* (n_psf, kh*kw) or NULL */,
+                                void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Posterior sampling: a Metropolis-adjusted Langevin (MALA) chain over the latents of an inverse problem, one independent chain
  * per sample, and the Welford moments of its images (csrc/posterior.hip; numpy restatement tests/posterior_oracle.py).
  * THE definition.  Per sample n, theta = all latent leaves of that sample (leaf 0 = z, leaf 1 + k = eps[k] in decode order):

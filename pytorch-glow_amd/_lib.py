@@ -346,7 +346,10 @@ SIGNATURES = {
     "glowhip_restore_objective_psf": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "glowhip_restore_linear_scratch_bytes": (c_size_t, [c_int, c_long, c_long]),
     "glowhip_restore_objective_linear": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_long, _P, _P, _P, _P, c_size_t, _P]),
-    "glowhip_mala_scratch_bytes": (c_size_t, [POINTER(MalaSeg), c_int, c_int, c_int]),
+    "glowhip_psf_from_logits": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "glowhip_restore_psf_grad_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "glowhip_restore_psf_grad": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "glowhip_mala_scratch_bytes":(c_size_t, [POINTER(MalaSeg), c_int, c_int, c_int]),
     "glowhip_mala_init": (c_int, [_P, _P, c_int, c_float, c_float, _P]),
     "glowhip_mala_propose": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "glowhip_mala_energy": (c_int, [POINTER(MalaSeg), c_int, c_int, c_int, _P, _P, c_size_t, _P]),

@@ -178,12 +178,18 @@ class Inferer:
             init = Latents(rep(init.z), [rep(e) for e in init.eps])
         return meas, weight, 1, init, None
 
-    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid", operator=None):
+    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid", operator=None, estimate_psf=None):
         """``(measurement batch, weight broadcast to it, pool, start latents, psf)`` of `restore` / `posterior`: ``init`` None =
         ``encode_full`` of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement
         (and a single PSF).  With a ``psf``, ``border="valid"`` multiplies the weight (None = ones) by
-        `network.restore.psf_valid_weight`; every refusal of a PSF is raised before any device work."""
-        from .restore import check_psf_shape, psf_valid_weight
+        `network.restore.psf_valid_weight`; every refusal of a PSF is raised before any device work.  ``estimate_psf``: ``psf`` is
+        the start of a blind fit -- a pair of ints (kh, kw) is the uniform PSF of that support -- checked and normalised by
+        `network.restore.blind_start`, here, on the host."""
+        from .restore import blind_start, check_psf_shape, psf_valid_weight
+        if estimate_psf is not None:
+            if not torch.is_tensor(measurement):
+                raise TypeError("takes a tensor; image decoding (cv2 / PIL) is outside this package")
+            psf = blind_start(psf, estimate_psf, 1 if measurement.dim() == 3 else len(measurement), operator)
         if operator is not None:
             return self._linear_problem(measurement, weight, pool, init, chains, psf, operator)
         if psf is not None:
@@ -223,7 +229,7 @@ class Inferer:
         return meas, weight, pool, init, psf
 
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
-                graph=True, exact=False, psf=None, border="valid", operator=None):
+                graph=True, exact=False, psf=None, border="valid", operator=None, estimate_psf=None, psf_lr=0.2):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
         image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
         super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
@@ -263,14 +269,63 @@ class Inferer:
         ``measurement`` and ``weight`` are then (N, M), or (M,) for one problem.  ``operator`` together with ``psf`` or
         ``pool != 1``, a measurement or weight whose last dimension is not M, and an operator that is not 4-D or not of the model's
         image shape raise ValueError before any device work.  ``init=None`` starts from all-zero latents, the prior's mode: there
-        is no image to encode."""
+        is no image to encode.
+
+        ``estimate_psf`` = ``"shared"`` / ``"per_sample"``: BLIND deblurring -- the PSF is not known, and is fitted with the latents
+        (one for the batch, or one per image) in the same captured loop, as ``softmax(theta)`` by Adam at ``psf_lr``
+        (`network.restore.LatentFit`; include/glowhip.h, glowhip_restore_psf_grad).  ``psf`` is then the START: a pair of ints
+        ``(kh, kw)`` for the uniform PSF of that support, or taps that are all > 0 (normalised to sum 1).  ``border="valid"`` works
+        as it stands: the band depends on the support only.  The estimate comes back as ``RestoreInfo.psf`` -- on the device,
+        ready for ``posterior(measurement, psf=info.psf)`` -- with ``psf_grad_norm``.  The softmax fixes the scale of the PSF; a
+        shift of the PSF against the image is NOT determined by the measurement: the centred start and the valid band select the
+        solution.  A tap <= 0 in the start, (N,kh,kw) with ``"shared"``, an ``operator`` beside it, an unknown value and no start
+        at all raise ValueError before any device work.  ``estimate_psf=None`` is every call above, unchanged."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
-        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border, operator=operator)
+        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border, operator=operator,
+                                                      estimate_psf=estimate_psf)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
-                        max_grad_norm=max_grad_norm, graph=graph, psf=psf, operator=operator)
+                        max_grad_norm=max_grad_norm, graph=graph, psf=psf, operator=operator, estimate_psf=estimate_psf, psf_lr=psf_lr)
         info = fit.run(exact=exact)
         return fit.latents(), info
+
+    def estimate_psf(self, sharp, blurred, psf=(5, 5), per_sample=False, weight=None, pool=1, border="valid", steps=100, psf_lr=0.2):
+        """Calibration: the point-spread function that turns ``sharp`` (C,H,W or N,C,H,W) into ``blurred`` (the same at
+        H/pool x W/pool) -- the iteration of blind `restore` without the flow (`network.restore.PsfFit`: softmax of the logits,
+        the objective through the PSF, its gradient with respect to the taps, Adam at ``psf_lr``), on the same kernels.  ``psf``: the
+        start, a pair of ints (kh, kw) for the uniform PSF of that support or taps that are all > 0; ``per_sample``: one PSF per
+        image pair instead of one for the batch; ``weight`` / ``border`` as for `restore`.  Returns ``(psf, RestoreInfo)``: the
+        estimate (kh,kw) or (N,kh,kw) on the device, the loss history (steps, N) and the logits' gradient norms.  Eager only: the
+        capture protocol is tied to a flow plan and this loop has none (``captured`` is False).  Every refusal is a ValueError
+        raised before any device work."""
+        from .restore import PsfFit, blind_start, psf_valid_weight
+        if not torch.is_tensor(sharp) or not torch.is_tensor(blurred):
+            raise TypeError("takes tensors; image decoding (cv2 / PIL) is outside this package")
+        if sharp.dim() not in (3, 4) or blurred.dim() != sharp.dim():
+            raise ValueError(f"sharp {tuple(sharp.shape)} and blurred {tuple(blurred.shape)}: two images (C,H,W) or two batches (N,C,H,W)")
+        n, pool = 1 if sharp.dim() == 3 else len(sharp), int(pool)
+        start = blind_start(psf, "per_sample" if per_sample else "shared", n)
+        kh, kw = start.shape[-2:]
+        if border not in ("valid", "zero"):
+            raise ValueError(f"border = {border!r}: 'valid' or 'zero'")
+        want = tuple(sharp.shape[:-2]) + (sharp.shape[-2] // max(pool, 1), sharp.shape[-1] // max(pool, 1))
+        if pool < 1 or sharp.shape[-2] % pool or sharp.shape[-1] % pool or tuple(blurred.shape) != want:
+            raise ValueError(f"blurred of shape {tuple(blurred.shape)}: expected {want} for sharp {tuple(sharp.shape)} at pool {pool}")
+        band = None
+        if border == "valid":
+            band = psf_valid_weight(tuple(blurred.shape)[-2:], kh, kw, pool)
+            if not bool(band.any()):
+                raise ValueError(f"border='valid': a psf of {kh} x {kw} taps leaves no cell of the {tuple(blurred.shape)[-2:]} "
+                                 f"measurement (pool {pool}) whose footprint is inside the image")
+        x, meas = self._batch(sharp).float().contiguous(), self._batch(blurred).float().contiguous()
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32, device=self.device).expand_as(meas).contiguous()
+        if band is not None:
+            band = band.to(self.device)
+            weight = band.expand_as(meas).contiguous() if weight is None else weight * band
+        fit = PsfFit(x, meas, start, weight=weight, pool=pool, steps=steps, psf_lr=psf_lr)
+        info = fit.run()
+        return info.psf, info
 
     def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
                   seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None):

@@ -17,7 +17,12 @@ the optimiser, the MALA launches, the capture protocol and the histories are the
 
 Compressed sensing: with a dense ``operator`` A of shape (M, C, H, W) the measurement is (N, M), t = A x + noise with x the flattened
 decode (glowhip_restore_objective_linear, csrc/restore_linear.hip; `gaussian_operator` makes the standard i.i.d. N(0, 1/M) matrix on
-the device from the sampler's stream 248).  Again only `LatentLoop._evaluate` knows."""
+the device from the sampler's stream 248).  Again only `LatentLoop._evaluate` knows.
+
+Blind deblurring: with ``estimate_psf`` the PSF is one more unknown of the fit, ``psf = softmax(theta)``; the new quantity is the
+gradient of the data term with respect to the taps, a cross-correlation of the decoded image with the residual the objective leaves
+behind (glowhip_restore_psf_grad, csrc/restore_blind.hip; `psf_gradient`, `psf_from_logits`).  `PsfLogits` holds theta and its own
+fused Adam step; `LatentFit` runs it inside the same captured iteration, `PsfFit` without the flow (calibration)."""
 import contextlib
 import math
 from dataclasses import dataclass
@@ -177,19 +182,113 @@ def _restore_objective_linear(x, target, weight, inv_wsum, pool, grad_out, loss_
     return loss, grad
 
 
+ESTIMATE_PSF = (None, "shared", "per_sample")
+
+
+def blind_start(psf, estimate_psf, n, operator=None):
+    """The start of a blind fit, checked on the host before any device work: ``psf`` -- anything `torch.as_tensor` takes, of shape
+    (kh,kw) or (n,kh,kw), or a pair of Python ints (kh, kw) meaning the uniform PSF of that support -- as a CPU fp32 tensor
+    normalised to sum 1 per PSF, of shape (kh,kw) for ``"shared"`` and (n,kh,kw) for ``"per_sample"`` (a single start is repeated).
+    ValueError: an unknown ``estimate_psf``, an ``operator`` beside it, no start, an even or out-of-range side, (n,kh,kw) with
+    ``"shared"``, and a tap that is not a finite value > 0 -- a softmax cannot hold an exact zero."""
+    if estimate_psf not in ESTIMATE_PSF or estimate_psf is None:
+        raise ValueError(f"estimate_psf = {estimate_psf!r}: None, 'shared' or 'per_sample'")
+    if operator is not None:
+        raise ValueError("estimate_psf: a dense operator has no point-spread function to estimate")
+    if psf is None:
+        raise ValueError("estimate_psf needs a start: psf = (kh, kw) for the uniform one, or a tensor of positive taps")
+    if isinstance(psf, (tuple, list)) and len(psf) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in psf):
+        kh, kw = check_psf_shape(psf, n)
+        psf = torch.full((kh, kw), 1.0 / (kh * kw), dtype=torch.float64)
+    k = torch.as_tensor(psf).detach().cpu().double()
+    kh, kw = check_psf_shape(k.shape, n)
+    if k.dim() == 3 and estimate_psf == "shared":
+        raise ValueError(f"estimate_psf='shared' starts from ONE psf (kh, kw), not from {tuple(k.shape)}")
+    if not bool((torch.isfinite(k) & (k > 0)).all()):
+        raise ValueError("estimate_psf: every tap of the start must be > 0 (the estimate is a softmax, which cannot hold an exact zero)")
+    k = k / k.sum(dim=(-2, -1), keepdim=True)
+    if k.dim() == 2 and estimate_psf == "per_sample":
+        k = k.expand(n, kh, kw)
+    return k.float().contiguous()
+
+
+def psf_from_logits(logits, out=None):
+    """``softmax(logits)`` over the taps of each PSF: glowhip_psf_from_logits (the max subtracted, exponentials and sum in fp64 in
+    tap order, one rounding per tap).  ``logits`` (kh,kw) or (n_psf,kh,kw), a contiguous fp32 device tensor; ``out``: the buffer to
+    write, of the same shape."""
+    psf = torch.empty_like(logits) if out is None else out
+    for name, t in (("logits", logits), ("out", psf)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == logits.device):
+            raise _lib.GlowHipError(f"psf_from_logits: {name} must be a contiguous fp32 tensor on the device of the logits")
+    if logits.dim() not in (2, 3) or tuple(psf.shape) != tuple(logits.shape):
+        raise _lib.GlowHipError(f"psf_from_logits: logits of shape {tuple(logits.shape)} (expected (kh, kw) or (n_psf, kh, kw)) and out of the same shape")
+    kh, kw = logits.shape[-2:]
+    _lib.check(_lib.lib().glowhip_psf_from_logits(_lib.ptr(logits), _lib.ptr(psf), logits.shape[0] if logits.dim() == 3 else 1, kh, kw,
+                                                  _lib.stream_ptr(logits.device)))
+    return psf
+
+
+def psf_grad_scratch(shape, kh, kw, pool, device):
+    """The scratch of glowhip_restore_psf_grad for images of ``shape`` (N,C,H,W): a uint8 device tensor."""
+    n, c, h, w = (int(v) for v in shape)
+    need = int(_lib.lib().glowhip_restore_psf_grad_scratch_bytes(n, c, h, w, int(kh), int(kw), int(pool)))
+    if need == 0:
+        _lib.check(-1)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def psf_gradient(x, resid, inv_wsum, psf, pool, *, grad_psf=None, grad_logits=None, scratch=None):
+    """``(grad_psf, grad_logits)`` of the data term with respect to the taps of ``psf`` and to the logits of ``psf = softmax(theta)``:
+    glowhip_restore_psf_grad (include/glowhip.h has the definition), after ``restore_objective(x, ..., psf=psf, resid_out=resid)``
+    on the same ``x`` (N,C,H,W), ``resid`` (N,C,H/pool,W/pool) and ``inv_wsum`` (N,; None = that call's default).  ``psf`` (kh,kw) --
+    shared: the gradient is summed over the batch in sample order -- or (N,kh,kw); both gradients have its shape.  Contiguous fp32
+    device tensors.  ``grad_psf`` / ``grad_logits``: buffers to write; with neither, both are allocated and returned; with one, the
+    other is not computed (None).  ``scratch``: a uint8 device tensor of glowhip_restore_psf_grad_scratch_bytes (`psf_grad_scratch`),
+    allocated when None."""
+    for name, t in (("x", x), ("resid", resid), ("inv_wsum", inv_wsum), ("psf", psf), ("grad_psf", grad_psf), ("grad_logits", grad_logits)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
+            raise _lib.GlowHipError(f"psf_gradient: {name} must be a contiguous fp32 tensor on the device of x")
+    n, c, h, w = x.shape
+    pool = int(pool)
+    if psf is None or psf.dim() not in (2, 3) or (psf.dim() == 3 and psf.shape[0] != n):
+        raise _lib.GlowHipError(f"psf_gradient: psf of shape {None if psf is None else tuple(psf.shape)}: expected (kh, kw) or ({n}, kh, kw)")
+    kh, kw = psf.shape[-2:]                                # (their parity and range are the C call's to refuse)
+    if pool >= 1 and h % pool == 0 and w % pool == 0 and tuple(resid.shape) != (n, c, h // pool, w // pool):
+        raise _lib.GlowHipError(f"psf_gradient: resid must have shape {(n, c, h // pool, w // pool)}")
+    if inv_wsum is not None and inv_wsum.numel() != n:
+        raise _lib.GlowHipError(f"psf_gradient: inv_wsum holds {inv_wsum.numel()} values for a batch of {n}")
+    if grad_psf is None and grad_logits is None:
+        grad_psf, grad_logits = torch.empty_like(psf), torch.empty_like(psf)
+    for name, t in (("grad_psf", grad_psf), ("grad_logits", grad_logits)):
+        if t is not None and t.numel() != psf.numel():
+            raise _lib.GlowHipError(f"psf_gradient: {name} must have the shape of psf")
+    if scratch is None:
+        scratch = psf_grad_scratch(x.shape, kh, kw, pool, x.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.device == x.device):
+        raise _lib.GlowHipError("psf_gradient: scratch must be a contiguous uint8 tensor on the device of x")
+    _lib.check(_lib.lib().glowhip_restore_psf_grad(_lib.ptr(x), _lib.ptr(resid), _lib.ptr(inv_wsum), _lib.ptr(psf),
+                                                   kh * kw if psf.dim() == 3 else 0, kh, kw, n, c, h, w, pool, _lib.ptr(grad_psf),
+                                                   _lib.ptr(grad_logits), _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(x.device)))
+    return grad_psf, grad_logits
+
+
 @dataclass
 class RestoreInfo:
     """What a fit reports.  ``loss`` (steps, N): the per-sample data term BEFORE each iteration's update; ``grad_norm`` (steps,):
     the total norm of the data term's latent gradient (all samples, before clipping; the prior term is not in it).  ``finite``: every
     norm was finite -- when False, the iterations with a non-finite norm were skipped on the device.  ``captured``: the iterations
     after the first ran as hipGraph replays.  ``fallback``: how many times the fit was run again on the exact-fp32 kernel family (0
-    or 1).  ``graph_error``: why a requested capture did not happen."""
+    or 1).  ``graph_error``: why a requested capture did not happen.  A blind fit (``estimate_psf``) adds ``psf``, the estimate --
+    softmax of the final logits, (kh,kw) or (N,kh,kw), on the device -- and ``psf_grad_norm`` (steps,), the norm of the data term's
+    gradient with respect to the logits; ``finite`` then covers both norm histories."""
     loss: torch.Tensor
     grad_norm: torch.Tensor
     finite: bool
     captured: bool
     fallback: int = 0
     graph_error: Optional[str] = None
+    psf: Optional[torch.Tensor] = None
+    psf_grad_norm: Optional[torch.Tensor] = None
 
 
 def check_prior_weight(glow, prior_weight):
@@ -334,6 +433,61 @@ class LatentLoop:
         return replayed
 
 
+class PsfLogits:
+    """The PSF as an unknown of a fit (`LatentFit(estimate_psf=...)`, `PsfFit`): ``theta`` = the logits of ``psf = softmax(theta)``,
+    one row per PSF, started at ``log(start)``; their persistent gradient buffer (bound once as ``theta.grad``); a `training.HipAdam`
+    of their OWN at ``psf_lr`` with weight decay 0 -- the HIP optimiser takes one hyper-parameter set per instance, and theta must
+    not carry the latents' prior term -- with its own `training.HyperRing` and norm word; and the scratch of
+    glowhip_restore_psf_grad.  ``psf`` is the static buffer the objective reads: `forward` fills it from theta, `gradient` takes the
+    gradient of the data term from the objective's leftovers (``image``, ``resid``) into ``theta.grad``, and `update` is theta's
+    fused step, with a device-side skip of its own when the gradient's norm is not finite, and the norm into row ``row`` of
+    ``norm_hist``."""
+
+    def __init__(self, psf, start, image_shape, pool, psf_lr, steps):
+        dev = psf.device
+        self.psf, self.psf_lr, self.pool = psf, float(psf_lr), int(pool)
+        kh, kw = psf.shape[-2:]
+        self._theta0 = torch.log(start.double()).float().to(dev).reshape(-1, kh, kw).contiguous()
+        self.theta = self._theta0.clone().requires_grad_()
+        self.grad = torch.zeros_like(self._theta0)
+        self.theta.grad = self.grad
+        self.optimizer = HipAdam([self.theta], lr=self.psf_lr, weight_decay=0.0)
+        self._token = object()
+        self._ring = HyperRing(3, dev)
+        self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.norm_hist = torch.zeros(int(steps), dtype=torch.float32, device=dev)
+        self.scratch = psf_grad_scratch(image_shape, kh, kw, self.pool, dev)
+
+    def forward(self):
+        psf_from_logits(self.theta.detach().view(self.psf.shape), out=self.psf)
+
+    def gradient(self, image, resid, inv_wsum):
+        psf_gradient(image, resid, inv_wsum, self.psf, self.pool, grad_logits=self.grad, scratch=self.scratch)
+
+    def update(self, row, captured):
+        self.optimizer.fused_step(0.0, 0.0, skip_nonfinite=True, grads_token=self._token,
+                                  hyper_dev=self._ring.words if captured else None, norm_out=self.norm)
+        self.norm_hist.index_copy_(0, row, self.norm)
+
+    def replay_host(self):
+        self.optimizer.replay_step(self._ring, self.psf_lr)
+        torch.autograd.graph.increment_version([self.theta])
+
+    def signature(self):
+        return {"psf " + k: v for k, v in self.optimizer.capture_signature().items()}
+
+    @torch.no_grad()
+    def reset(self):
+        """theta back to its start, the optimiser's state to zero, the history empty; the addresses stay."""
+        self.theta.copy_(self._theta0)
+        self.optimizer.reset_state()
+        self.norm_hist.zero_()
+
+    def estimate(self):
+        """softmax of the current logits, in the shape of ``psf`` (a new tensor)."""
+        return psf_from_logits(self.theta.detach().view(self.psf.shape).clone())
+
+
 class LatentFit(LatentLoop):
     """The device-resident fit.  Owns, beyond `LatentLoop`'s buffers, ``inv_wsum`` = 1 / sum w per sample, the latent leaves --
     ``z`` and every ``eps`` of the start `Latents`, copied -- their persistent gradient buffers (bound once as the leaves'
@@ -351,13 +505,28 @@ class LatentFit(LatentLoop):
     either run again on the exact-fp32 family or reported ``finite=False``.
 
     ``psf`` (kh,kw) or (N,kh,kw), a device tensor: the measurement is the decode blurred by it (`LatentLoop`).  ``operator``
-    (M,C,H,W): the measurement (N, M) is the decode seen through that dense matrix, held by reference (`LatentLoop`)."""
+    (M,C,H,W): the measurement (N, M) is the decode seen through that dense matrix, held by reference (`LatentLoop`).
+
+    ``estimate_psf`` = ``"shared"`` / ``"per_sample"``: blind deblurring -- ``psf`` is only the START (`blind_start`: every tap > 0,
+    normalised to sum 1; (N,kh,kw) with ``"shared"`` raises, (kh,kw) with ``"per_sample"`` is repeated; an ``operator`` beside it
+    raises), and the PSF, as ``softmax(theta)``, is one more unknown of the same loop (`PsfLogits`, ``self.blind``).  An iteration is
+    then: `psf_from_logits` into the loop's static ``psf``; the evaluation above, unchanged; `psf_gradient` from the image and the
+    residual it left into theta's gradient; the latents' fused step as before; theta's fused step at ``psf_lr``; the histories, with
+    theta's gradient norm among them.  The two device-side skips are INDEPENDENT: a non-finite latent norm skips the latents'
+    update, a non-finite theta norm theta's, each without the other -- harmless for the same reason as above, since theta's norm
+    history enters the test that re-runs a fit on the exact family or reports ``finite=False``.  The softmax fixes the scale
+    ambiguity between PSF and image; the translation ambiguity stays, and the centre of the start and the valid-band weights select
+    the solution."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
-                 graph=True, psf=None, operator=None):
+                 graph=True, psf=None, operator=None, estimate_psf=None, psf_lr=0.2):
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
+        start = None
+        if estimate_psf is not None:
+            start = blind_start(psf, estimate_psf, len(measurement), operator)
+            psf = start.to(measurement.device)
         super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator)
         self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
         n, dev = self.n, self.device
@@ -375,25 +544,44 @@ class LatentFit(LatentLoop):
         self.optimizer = HipAdam(self.leaves, lr=self.lr, weight_decay=float(prior_weight or 0.0))
         self._token = object()       # "the gradients are this loop's persistent buffers" (HipAdam._chunk_table)
         self._ring = HyperRing(3, dev)
+        # blind deblurring: theta, its gradient, its own optimiser, ring and norm word, the gradient call's scratch
+        self.blind = None if start is None else PsfLogits(self.psf, start, self.image.shape, self.pool, psf_lr, self.steps)
 
     # ------------------------------------------------------------------ the iteration
     def _body(self, captured):
+        blind = self.blind
+        if blind is not None:
+            blind.forward()
         self._evaluate(self.leaves, self.image, self.loss, self.grads)
+        if blind is not None:        # (before the latents move: the gradient belongs to the image and the residual just evaluated)
+            blind.gradient(self.image, self.resid, self.inv_wsum)
         self.optimizer.fused_step(0.0, self.max_grad_norm, skip_nonfinite=True, grads_token=self._token,
                                   hyper_dev=self._ring.words if captured else None, norm_out=self.norm)
+        if blind is not None:
+            blind.update(self.row, captured)
         self.loss_hist.index_copy_(0, self.row, self.loss.view(1, -1))
         self.norm_hist.index_copy_(0, self.row, self.norm)
         self.row.add_(1).remainder_(self.steps)      # (a loop driven past `steps` iterations wraps around instead of writing outside)
 
     def _capturing(self):
-        return self.optimizer.capturing()
+        if self.blind is None:
+            return self.optimizer.capturing()
+        stack = contextlib.ExitStack()       # both optimisers counted a step that did not run
+        stack.enter_context(self.optimizer.capturing())
+        stack.enter_context(self.blind.optimizer.capturing())
+        return stack
 
     def _signature(self):
-        return {**super()._signature(), **self.optimizer.capture_signature()}
+        """`LatentLoop._signature` and the optimiser's part; a blind fit adds theta's optimiser's.  theta, its gradient, its norm
+        word and history, the ring and the gradient call's scratch are this loop's own static buffers, like ``psf`` and ``resid``."""
+        sig = {**super()._signature(), **self.optimizer.capture_signature()}
+        return sig if self.blind is None else {**sig, **self.blind.signature()}
 
     def _replay_host(self):          # the step count and the 24-byte upload of the iteration's learning rate and bias corrections
         self.optimizer.replay_step(self._ring, self.lr)
         torch.autograd.graph.increment_version(self.leaves)      # (written behind torch's back, as after fused_step)
+        if self.blind is not None:
+            self.blind.replay_host()
 
     # ------------------------------------------------------------------ the fit
     @torch.no_grad()
@@ -405,6 +593,8 @@ class LatentFit(LatentLoop):
         self.row.zero_()
         self.loss_hist.zero_()
         self.norm_hist.zero_()
+        if self.blind is not None:
+            self.blind.reset()
 
     def latents(self):
         """The current latents (copies)."""
@@ -413,9 +603,11 @@ class LatentFit(LatentLoop):
     def _run_once(self):
         self.reset()
         replayed = self._iterate()
-        hist = torch.cat([self.loss_hist.reshape(-1), self.norm_hist]).cpu()      # the loop's one host read
-        n = self.loss_hist.shape[1]
-        return hist[:self.steps * n].view(self.steps, n), hist[self.steps * n:], replayed
+        parts = [self.loss_hist.reshape(-1), self.norm_hist] + ([] if self.blind is None else [self.blind.norm_hist])
+        hist = torch.cat(parts).cpu()                                             # the loop's one host read
+        n, k = self.loss_hist.shape[1], self.steps * self.loss_hist.shape[1]
+        self._psf_norm = None if self.blind is None else hist[k + self.steps:]
+        return hist[:k].view(self.steps, n), hist[k:k + self.steps], replayed
 
     def run(self, exact=False):
         """The whole fit from the start latents: `RestoreInfo`; the result is in `latents()`.  ``exact``: on the exact-fp32 kernel
@@ -429,15 +621,68 @@ class LatentFit(LatentLoop):
         try:
             if exact:
                 plan.set_family(plan.FAMILY_EXACT_FP32)
+            is_finite = lambda norm: bool(torch.isfinite(norm).all()) and (self.blind is None or bool(torch.isfinite(self._psf_norm).all()))
             loss, norm, replayed = self._run_once()
-            finite = bool(torch.isfinite(norm).all())
+            finite = is_finite(norm)
             if not finite and not exact and getattr(self.glow, "range_check", True):
                 fallback = 1
                 plan.set_family(plan.FAMILY_EXACT_FP32)
                 loss, norm, replayed = self._run_once()
-                finite = bool(torch.isfinite(norm).all())
+                finite = is_finite(norm)
         finally:
             plan.set_family(prev)
-        return RestoreInfo(loss=loss, grad_norm=norm, finite=finite, captured=replayed, fallback=fallback, graph_error=self.graph_error)
+        info = RestoreInfo(loss=loss, grad_norm=norm, finite=finite, captured=replayed, fallback=fallback, graph_error=self.graph_error)
+        if self.blind is not None:
+            info.psf, info.psf_grad_norm = self.blind.estimate(), self._psf_norm
+        return info
+
+
+class PsfFit:
+    """Calibration: the PSF that turns ``sharp`` (N,C,H,W) into ``blurred`` (N,C,H/pool,W/pool), by the iteration of a blind
+    `LatentFit` without the flow -- `psf_from_logits`, `restore_objective` with the PSF, `psf_gradient`, theta's fused Adam step
+    (`PsfLogits`) -- on the same kernels, device-resident, one host read at the end.  ``start``: `blind_start`'s result;
+    ``per_sample``: one PSF per image instead of one for the batch.  EAGER ONLY: the package's capture protocol (`_capture.Capture`)
+    is tied to a flow plan, and this loop has none; its iteration is five launches."""
+
+    def __init__(self, sharp, blurred, start, weight=None, pool=1, steps=100, psf_lr=0.2):
+        self.x = _lib.require_device_tensor(sharp, "sharp")
+        self.target = _lib.require_device_tensor(blurred, "blurred")
+        dev, n = self.x.device, self.x.shape[0]
+        self.pool, self.steps = int(pool), int(steps)
+        if self.steps < 1 or self.pool < 1:
+            raise ValueError(f"steps = {steps}, pool = {pool}")
+        if self.x.dim() != 4 or tuple(self.target.shape) != (n, self.x.shape[1], self.x.shape[2] // self.pool, self.x.shape[3] // self.pool):
+            raise ValueError(f"blurred of shape {tuple(self.target.shape)} does not belong to sharp images {tuple(self.x.shape)} at pool {self.pool}")
+        check_psf_shape(start.shape, n)
+        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(self.target).contiguous()
+        self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=(1, 2, 3)).clamp(min=1.0)
+        self.psf = start.to(dev).float().contiguous().clone()
+        self.resid = torch.empty_like(self.target)
+        self.grad_x = torch.empty_like(self.x)
+        self.loss = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.loss_hist = torch.zeros((self.steps, n), dtype=torch.float32, device=dev)
+        self.row = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.blind = PsfLogits(self.psf, start, self.x.shape, self.pool, psf_lr, self.steps)
+
+    @torch.no_grad()
+    def run(self):
+        """``steps`` iterations from the start: `RestoreInfo` -- ``loss`` (steps, N) BEFORE each update, ``grad_norm`` and
+        ``psf_grad_norm`` both theta's gradient norm, ``psf`` the estimate, ``captured`` False."""
+        blind = self.blind
+        blind.reset()
+        self.row.zero_()
+        for _ in range(self.steps):
+            blind.forward()
+            restore_objective(self.x, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=self.loss,
+                              psf=self.psf, resid_out=self.resid)
+            blind.gradient(self.x, self.resid, self.inv_wsum)
+            blind.update(self.row, captured=False)
+            self.loss_hist.index_copy_(0, self.row, self.loss.view(1, -1))
+            self.row.add_(1)
+        n = self.loss_hist.shape[1]
+        hist = torch.cat([self.loss_hist.reshape(-1), blind.norm_hist]).cpu()      # the loop's one host read
+        norm = hist[self.steps * n:]
+        return RestoreInfo(loss=hist[:self.steps * n].view(self.steps, n), grad_norm=norm, finite=bool(torch.isfinite(norm).all()),
+                           captured=False, psf=blind.estimate(), psf_grad_norm=norm)
 
 
