@@ -576,6 +576,51 @@ int    glowhip_restore_objective_linear(const float* x, const float* target, con
                                         void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * The restoration objective observed in the Fourier domain: MRI k-space undersampling, radio interferometry, partial-Fourier
+ * compressed sensing -- a structured operator of O(D log D) work whose only stored part is a mask (csrc/restore_fourier.hip; fp64
+ * restatement tests/fourier_oracle.py).  THE definition.  Per sample n and channel c, F is the unitary 2-D DFT of the H x W plane,
+ *     (F x)[u,v] = 1/sqrt(H W) * sum_{i,j} x[i,j] * exp(-2 pi i (u i / H + v j / W))
+ * which is torch.fft.fft2(norm="ortho"): unshifted, index (0,0) the DC term.
+ *     X[n,c]      = F x[n,c]                                  complex, (H,W)
+ *     resid       = w (X - t)                                 (N,C,H,W,2) interleaved re/im: scratch AND output
+ *     loss_out[n] = inv_wsum[n] * sum_{c,k} w |X - t|^2       fp64, fixed order, no atomics
+ *     grad_x      = 2 inv_wsum[n] * Re( F^H resid )           real (N,C,H,W)
+ * x, grad_x: (N,C,H,W) contiguous; target: (N,C,H,W,2) fp32, the memory of torch.view_as_real on a complex64 tensor; weight: real,
+ * (N,C,H,W), NULL means all ones; inv_wsum: (N), NULL means 1 / (C H W); loss_out may be NULL (overwritten, never accumulated into).
+ * H and W are each a power of two from 2 to 256 (256 is the largest side among the project's configs); H != W is allowed.
+ * THREE launches, whatever the shape -- a separable radix-2 FFT in LDS, fp32, one rounding per operation: the forward rows on tiles
+ * of rows into resid (the intermediate between the passes); the columns on tiles of 32 columns (16 at H = 256; a whole plane does
+ * not fit LDS), where ONE LDS tile sees the forward columns, the scaling, the subtraction, the weighting, the loss partial and the
+ * adjoint columns, so the spectrum makes no round trip through HBM; the adjoint rows from the scratch into grad_x, the workgroup of
+ * a sample's first tile also folding the loss.  Twiddles: evaluated in fp64 and rounded once to fp32, a table built per launch in
+ * LDS.  The column tiles are laid out, and the row tiles XOR-swizzled, against LDS bank conflicts on the strided butterfly stages.
+ * Guarantees.  Tile shapes and the butterfly order are functions of (H, W) only, never of N, and a workgroup works on one plane of
+ * one sample: sample n's outputs have the same bits in a batch of 1 and in a batch of 64 (whatever the buffers' alignment: every
+ * access path is element-wise).  The loss is folded in fp64 in a fixed order -- thread, wave, workgroup, then the partials in index
+ * order; no atomics, nothing depends on workgroup order: bitwise reproducible run to run.  inv_wsum[n] == 0: exact zeros in grad_x[n]
+ * and resid[n] and loss 0, whatever x[n] holds.  A non-finite x[n] reaches no other sample's outputs.  No allocation, no host sync,
+ * capturable.  glowhip_restore_objective, _psf and _linear are untouched.
+ * scratch: glowhip_restore_fourier_scratch_bytes(N, C, H, W) bytes at a 16-byte aligned address (the complex intermediate of the
+ * adjoint and the loss partials); monotone in N and C, and 0 only on error (see glowhip_last_error).
+ * GLOWHIP_EINVAL with a message and no device call: a NULL x, target, resid or grad_x; N < 0 or C < 1; H or W not a power of two
+ * from 2 to 256 (or a batch of more than 2^31 workgroups); a scratch that is NULL, misaligned or too small; x, grad_x and resid
+ * overlapping.  N == 0 returns GLOWHIP_OK.
+ *
+ * glowhip_fourier2d is the transform alone, by the same kernels (two launches): adjoint == 0 maps real `in` (planes,H,W) to complex
+ * `out` (planes,H,W,2) = F in; adjoint == 1 maps complex `in` (planes,H,W,2) to real `out` (planes,H,W) = Re(F^H in).  It makes
+ * measurements and the zero-filled reconstruction without an FFT library.  The adjoint's complex intermediate is taken from and
+ * returned to the stream's memory pool in stream order (no host sync, but not for a captured region; the objective call is).
+ * GLOWHIP_EINVAL: a NULL pointer, planes < 0, a side that is not a power of two from 2 to 256, adjoint outside {0, 1}, in and out
+ * overlapping.  planes == 0 returns GLOWHIP_OK. */
+size_t glowhip_restore_fourier_scratch_bytes(int N, int C, int H, int W);      /* 0: see last_error */
+int    glowhip_restore_objective_fourier(const float* x, const float* target /* (N,C,H,W,2) */, const float* weight,
+                                         const float* inv_wsum, int N, int C, int H, int W,
+                                         float* resid /* scratch AND output: (N,C,H,W,2) = w (F x - t) */,
+                                         float* grad_x, float* loss_out,
+                                         void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+int    glowhip_fourier2d(const float* in, float* out, long planes, int H, int W, int adjoint, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Blind deblurring: the PSF as an unknown of the fit -- the gradient of the data term of glowhip_restore_objective_psf with
  * respect to the taps of the PSF, and the softmax that keeps an estimate on the simplex (csrc/restore_blind.hip; fp64 restatement
  * tests/blind_oracle.py).  THE definition.  Notation as for glowhip_restore_objective_psf; per sample n, k the kh x kw PSF,

@@ -346,6 +346,9 @@ SIGNATURES = {
     "glowhip_restore_objective_psf": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P]),
     "glowhip_restore_linear_scratch_bytes": (c_size_t, [c_int, c_long, c_long]),
     "glowhip_restore_objective_linear": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_long, _P, _P, _P, _P, c_size_t, _P]),
+    "glowhip_restore_fourier_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "glowhip_restore_objective_fourier": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "glowhip_fourier2d": (c_int, [_P, _P, c_long, c_int, c_int, c_int, _P]),
     "glowhip_psf_from_logits": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "glowhip_restore_psf_grad_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "glowhip_restore_psf_grad": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),

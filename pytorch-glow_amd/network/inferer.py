@@ -178,7 +178,50 @@ class Inferer:
             init = Latents(rep(init.z), [rep(e) for e in init.eps])
         return meas, weight, 1, init, None
 
-    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid", operator=None, estimate_psf=None):
+    def _fourier_problem(self, measurement, weight, pool, init, chains, psf, operator, estimate_psf):
+        """`_problem` with ``fourier=True``: the measurement is complex64 (N,C,H,W) -- (C,H,W) for one problem -- or fp32 with a
+        trailing 2, and comes back as the latter; the weight is the real k-space mask, broadcast to (N,C,H,W); ``init`` None =
+        ``encode_full(clamp(fourier2d_adjoint(w t), 0, 1))``, the zero-filled reconstruction; ``chains`` > 1 repeats a single
+        measurement.  Every refusal is a ValueError raised before any device work."""
+        from .restore import as_kspace, check_fourier_shape, fourier2d_adjoint
+        if psf is not None or operator is not None or estimate_psf is not None or int(pool) != 1:
+            raise ValueError("fourier: Fourier-domain measurements exclude psf, operator and estimate_psf, and pool must be 1")
+        real = as_kspace(measurement)
+        if real.dim() not in (4, 5):
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)}: expected complex (C, H, W) or (N, C, H, W), or fp32 with a trailing 2")
+        chw = tuple(int(v) for v in real.shape[-4:-1])
+        check_fourier_shape(chw[1:], "measurement")
+        if chw != tuple(int(v) for v in self.graph.flow.in_chw):
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)} is not the spectrum of this model's images {tuple(self.graph.flow.in_chw)}")
+        n = 1 if real.dim() == 4 else int(real.shape[0])
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32)
+            try:
+                torch.broadcast_shapes(tuple(weight.shape), (n,) + chw)
+                ok = weight.dim() <= 4
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"weight of shape {tuple(weight.shape)} does not broadcast to the k-space of {(n,) + chw}")
+            if bool((weight < 0).any()):      # (a host weight -- `fourier_mask` makes one -- is checked without the device)
+                raise ValueError("weight: a k-space weight must be >= 0")
+        if chains < 1 or (chains > 1 and n != 1):
+            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {n} runs one chain each)")
+        meas = real.reshape((n,) + chw + (2,)).to(self.device).contiguous()
+        if weight is not None:
+            weight = weight.to(self.device).expand((n,) + chw).contiguous()
+        if init is None:
+            start = meas if weight is None else meas * weight.unsqueeze(-1)
+            init = self.encode_full(fourier2d_adjoint(start.contiguous()).clamp_(0.0, 1.0))
+        if chains > 1:
+            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
+            meas, weight = rep(meas), None if weight is None else rep(weight)
+            if len(init) == 1:
+                init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        return meas, weight, 1, init, None
+
+    def _problem(self, measurement, weight, pool, init, chains=1, psf=None, border="valid", operator=None, estimate_psf=None,
+                 fourier=False):
         """``(measurement batch, weight broadcast to it, pool, start latents, psf)`` of `restore` / `posterior`: ``init`` None =
         ``encode_full`` of the measurement (``pool>1``: of its pixel-repeated upsampling); ``chains`` > 1 repeats a single measurement
         (and a single PSF).  With a ``psf``, ``border="valid"`` multiplies the weight (None = ones) by
@@ -186,6 +229,8 @@ class Inferer:
         the start of a blind fit -- a pair of ints (kh, kw) is the uniform PSF of that support -- checked and normalised by
         `network.restore.blind_start`, here, on the host."""
         from .restore import blind_start, check_psf_shape, psf_valid_weight
+        if fourier:
+            return self._fourier_problem(measurement, weight, pool, init, chains, psf, operator, estimate_psf)
         if estimate_psf is not None:
             if not torch.is_tensor(measurement):
                 raise TypeError("takes a tensor; image decoding (cv2 / PIL) is outside this package")
@@ -229,7 +274,7 @@ class Inferer:
         return meas, weight, pool, init, psf
 
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
-                graph=True, exact=False, psf=None, border="valid", operator=None, estimate_psf=None, psf_lr=0.2):
+                graph=True, exact=False, psf=None, border="valid", operator=None, estimate_psf=None, psf_lr=0.2, fourier=False):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
         image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
         super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
@@ -279,13 +324,25 @@ class Inferer:
         ready for ``posterior(measurement, psf=info.psf)`` -- with ``psf_grad_norm``.  The softmax fixes the scale of the PSF; a
         shift of the PSF against the image is NOT determined by the measurement: the centred start and the valid band select the
         solution.  A tap <= 0 in the start, (N,kh,kw) with ``"shared"``, an ``operator`` beside it, an unknown value and no start
-        at all raise ValueError before any device work.  ``estimate_psf=None`` is every call above, unchanged."""
+        at all raise ValueError before any device work.  ``estimate_psf=None`` is every call above, unchanged.
+
+        ``fourier=True``: Fourier-domain measurements (MRI k-space undersampling, interferometry, partial-Fourier compressed
+        sensing) -- ``measurement`` is the unitary 2-D DFT of each channel's plane, `torch.fft.fft2(x, norm="ortho")`: complex64
+        (C,H,W) or (N,C,H,W), or fp32 with a trailing 2; unshifted, index (0,0) the DC term (include/glowhip.h,
+        glowhip_restore_objective_fourier).  ``weight`` is the real k-space mask or weight, broadcast to (N,C,H,W)
+        (`network.restore.fourier_mask` makes the usual undersampling masks); ``inv_wsum[n] = 1 / max(sum w[n], 1)`` as always.
+        H and W must each be a power of two up to 256.  ``init=None`` starts from
+        ``encode_full(clamp(fourier2d_adjoint(w * measurement), 0, 1))``, the zero-filled reconstruction.  ``fourier`` together with
+        ``psf``, ``operator``, ``estimate_psf`` or ``pool != 1``, a side that is not a power of two or is above 256, a measurement
+        that is not the spectrum of the model's image shape, and a negative weight raise ValueError before any device work.
+        ``fourier=False`` is every call above, unchanged."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
         meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border, operator=operator,
-                                                      estimate_psf=estimate_psf)
+                                                      estimate_psf=estimate_psf, fourier=fourier)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
-                        max_grad_norm=max_grad_norm, graph=graph, psf=psf, operator=operator, estimate_psf=estimate_psf, psf_lr=psf_lr)
+                        max_grad_norm=max_grad_norm, graph=graph, psf=psf, operator=operator, estimate_psf=estimate_psf, psf_lr=psf_lr,
+                        fourier=fourier)
         info = fit.run(exact=exact)
         return fit.latents(), info
 
@@ -328,7 +385,7 @@ class Inferer:
         return info.psf, info
 
     def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
-                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None):
+                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None, fourier=False):
         """Draws from the posterior of the latents given ``measurement`` -- what else is consistent with it, and how sure the model
         is of each pixel -- by a Metropolis-adjusted Langevin chain on the device (`network.posterior.LatentMALA`):
 
@@ -352,13 +409,16 @@ class Inferer:
         ``psf`` / ``border``: the measurement is a blurred image, as for `restore`; with ``chains=K`` a single PSF is repeated as
         the measurement is.  ``operator``: the measurement (N, M) or (M,) is the decode seen through a dense matrix (M,C,H,W), as for
         `restore`; ``chains=K`` repeats the measurement and shares the one operator, and ``init=None`` starts every chain from the
-        all-zero latents."""
+        all-zero latents.  ``fourier=True``: the measurement is the decode's unitary 2-D DFT and ``weight`` the k-space mask, as for
+        `restore`; ``noise_std`` is then the standard deviation of EACH of the real and imaginary parts, the energy
+        sum w |F x - measurement|^2 / (2 noise_std^2); ``chains=K`` repeats the one measurement and ``init=None`` starts every chain
+        from the zero-filled reconstruction."""
         from .model import sampler_position
         from .posterior import LatentMALA
         from .restore import check_prior_weight
         check_prior_weight(self.graph, 1.0)
         meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border,
-                                                      operator=operator)
+                                                      operator=operator, fourier=fourier)
         if seed is None:
             seed, call = sampler_position(advance=True)
             call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)
@@ -366,7 +426,7 @@ class Inferer:
             seed, call = int(seed) & (2 ** 64 - 1), 0
         chain = LatentMALA(self.graph, meas, weight=weight, pool=pool, noise_std=noise_std, init=init, steps=steps, burn_in=burn_in,
                            thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call, psf=psf,
-                           operator=operator)
+                           operator=operator, fourier=fourier)
         info = chain.run()
         return chain.latents(), info
 

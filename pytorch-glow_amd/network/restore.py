@@ -22,7 +22,12 @@ the device from the sampler's stream 248).  Again only `LatentLoop._evaluate` kn
 Blind deblurring: with ``estimate_psf`` the PSF is one more unknown of the fit, ``psf = softmax(theta)``; the new quantity is the
 gradient of the data term with respect to the taps, a cross-correlation of the decoded image with the residual the objective leaves
 behind (glowhip_restore_psf_grad, csrc/restore_blind.hip; `psf_gradient`, `psf_from_logits`).  `PsfLogits` holds theta and its own
-fused Adam step; `LatentFit` runs it inside the same captured iteration, `PsfFit` without the flow (calibration)."""
+fused Adam step; `LatentFit` runs it inside the same captured iteration, `PsfFit` without the flow (calibration).
+
+Fourier-domain measurements: with ``fourier=True`` the measurement is the unitary 2-D DFT of each channel's plane, complex
+(N,C,H,W), and ``weight`` the k-space mask (glowhip_restore_objective_fourier, csrc/restore_fourier.hip: a separable radix-2 FFT in
+LDS; sides are powers of two up to 256).  `fourier2d` / `fourier2d_adjoint` are the transform alone, `fourier_mask` the usual
+undersampling masks.  Again only `LatentLoop._evaluate` knows."""
 import contextlib
 import math
 from dataclasses import dataclass
@@ -99,8 +104,97 @@ def gaussian_operator(m, image_shape, seed, device):
     return out
 
 
+FOURIER_MAX = 256      # the largest side of a Fourier-domain problem (csrc/restore_fourier.hip)
+
+
+def check_fourier_shape(hw, what="fourier"):
+    """``(H, W)`` of a plane the transform takes: each side a power of two from 2 to `FOURIER_MAX`; ValueError otherwise."""
+    hw = tuple(int(v) for v in tuple(hw)[-2:])
+    if len(hw) != 2 or not all(2 <= v <= FOURIER_MAX and v & (v - 1) == 0 for v in hw):
+        raise ValueError(f"{what}: a plane of {' x '.join(map(str, hw))}: each side must be a power of two from 2 to {FOURIER_MAX}")
+    return hw
+
+
+def fourier_mask(hw, fraction, kind="lines", center=0.08, seed=0):
+    """An (H, W) 0/1 fp32 undersampling mask in UNSHIFTED k-space (index 0 is DC), made on the host from a generator seeded with
+    ``seed``.  ``"lines"``: the Cartesian MRI mask -- whole rows; the lowest ``center * H`` row frequencies, rows 0..c and
+    H-c..H-1 with c = int(center * H) // 2, are always there, and further rows drawn uniformly without replacement bring the count
+    to ``round(fraction * H)`` (the band alone where it is already more).  ``"points"``: the same with single coefficients -- the
+    block |u| <= int(center * H) // 2, |v| <= int(center * W) // 2, then uniformly drawn coefficients up to
+    ``round(fraction * H * W)``.  ``fraction=1`` is all ones."""
+    h, w = (int(v) for v in hw)
+    if h < 1 or w < 1 or not 0.0 < float(fraction) <= 1.0 or not 0.0 <= float(center) <= 1.0 or kind not in ("lines", "points"):
+        raise ValueError(f"fourier_mask: hw {tuple(hw)}, fraction {fraction!r} in (0, 1], center {center!r} in [0, 1], kind {kind!r} 'lines' or 'points'")
+    gen = torch.Generator().manual_seed(int(seed))
+    low = lambda n: torch.minimum(torch.arange(n), n - torch.arange(n)) <= int(float(center) * n) // 2      # |frequency| <= c
+    if kind == "lines":
+        chosen, total = low(h), h
+    else:
+        chosen, total = (low(h).view(h, 1) & low(w).view(1, w)).reshape(-1), h * w
+    want = int(round(float(fraction) * total))
+    rest = (~chosen).nonzero().view(-1)
+    more = max(0, min(want - int(chosen.sum()), rest.numel()))
+    chosen = chosen.clone()
+    chosen[rest[torch.randperm(rest.numel(), generator=gen)[:more]]] = True
+    mask = chosen.view(h, 1).expand(h, w) if kind == "lines" else chosen.view(h, w)
+    return mask.to(torch.float32).contiguous()
+
+
+def fourier_scratch(n, c, h, w, device):
+    """The scratch of glowhip_restore_objective_fourier for a batch of ``n`` images (c, h, w): a uint8 device tensor of
+    glowhip_restore_fourier_scratch_bytes(n, c, h, w) bytes."""
+    need = int(_lib.lib().glowhip_restore_fourier_scratch_bytes(int(n), int(c), int(h), int(w)))
+    if need == 0:
+        _lib.check(-1)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def as_kspace(k, what="measurement"):
+    """``k`` -- complex64 (..., H, W) or fp32 (..., H, W, 2) -- as its fp32 view (..., H, W, 2), the memory of
+    `torch.view_as_real`; ValueError for anything else."""
+    if not torch.is_tensor(k):
+        raise TypeError(f"{what}: a tensor, complex64 (..., H, W) or fp32 (..., H, W, 2)")
+    if k.is_complex():
+        if k.dtype != torch.complex64:
+            raise ValueError(f"{what}: complex64, not {k.dtype}")
+        return torch.view_as_real(k.contiguous())
+    if k.dtype != torch.float32 or k.dim() < 3 or k.shape[-1] != 2:
+        raise ValueError(f"{what} of shape {tuple(k.shape)} and dtype {k.dtype}: complex64 (..., H, W) or fp32 (..., H, W, 2)")
+    return k
+
+
+def fourier2d(x, out=None):
+    """The unitary 2-D DFT of the last two dimensions of a real fp32 device tensor ``x`` (..., H, W), as complex64 (..., H, W):
+    `torch.fft.fft2(x, norm="ortho")` by glowhip_fourier2d (unshifted, index (0,0) the DC term).  ``out``: an fp32 buffer
+    (..., H, W, 2) to write."""
+    x = _lib.require_device_tensor(x, "x")
+    if x.dim() < 2:
+        raise ValueError(f"fourier2d: x of shape {tuple(x.shape)}")
+    h, w = check_fourier_shape(x.shape, "fourier2d")
+    real = torch.empty(tuple(x.shape) + (2,), dtype=torch.float32, device=x.device) if out is None else out
+    if not (real.is_cuda and real.dtype == torch.float32 and real.is_contiguous() and tuple(real.shape) == tuple(x.shape) + (2,)):
+        raise _lib.GlowHipError("fourier2d: out must be a contiguous fp32 device tensor of the shape of x with a trailing 2")
+    _lib.check(_lib.lib().glowhip_fourier2d(_lib.ptr(x), _lib.ptr(real), x.numel() // (h * w), h, w, 0, _lib.stream_ptr(x.device)))
+    return torch.view_as_complex(real)
+
+
+def fourier2d_adjoint(k, out=None):
+    """``Re(F^H k)``, real fp32 (..., H, W), of a device tensor ``k``, complex64 (..., H, W) or fp32 (..., H, W, 2): the adjoint of
+    `fourier2d` as a map from real images (glowhip_fourier2d with adjoint = 1) -- the zero-filled reconstruction when ``k`` is a
+    masked measurement.  ``out``: the fp32 buffer to write."""
+    real = _lib.require_device_tensor(as_kspace(k, "k"), "k")
+    if real.dim() < 3:
+        raise ValueError(f"fourier2d_adjoint: k of shape {tuple(k.shape)}")
+    h, w = check_fourier_shape(real.shape[:-1], "fourier2d_adjoint")
+    x = torch.empty(real.shape[:-1], dtype=torch.float32, device=real.device) if out is None else out
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == tuple(real.shape[:-1])):
+        raise _lib.GlowHipError("fourier2d_adjoint: out must be a contiguous fp32 device tensor of the shape of k")
+    _lib.check(_lib.lib().glowhip_fourier2d(_lib.ptr(real), _lib.ptr(x), x.numel() // (h * w), h, w, 1, _lib.stream_ptr(x.device)))
+    return x
+
+
 def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None, psf=None, resid_out=None,
-                      operator=None, scratch=None):
+                      operator=None, scratch=None, fourier=False):
     """``(loss (N,), grad_x)`` of the data term for images ``x`` (N,C,H,W): glowhip_restore_objective.  ``target`` / ``weight``
     (N,C,H/pool,W/pool; weight None = ones), ``inv_wsum`` (N,; None = 1 / elements of one measurement).  Contiguous fp32 device
     tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write.
@@ -114,13 +208,21 @@ def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out
     (glowhip_restore_objective_linear); ``target`` / ``weight`` / ``resid_out`` are then (N, M), ``psf`` must be None and ``pool``
     1.  The operator is read where it is and not normalised.  ``scratch``: a uint8 device tensor of at least
     glowhip_restore_linear_scratch_bytes(N, M, C H W) bytes (`linear_scratch`), allocated when None.  ``operator=None`` is every
-    call above, unchanged."""
+    call above, unchanged.
+
+    ``fourier=True``: the image is observed through the unitary 2-D DFT of each channel's plane
+    (glowhip_restore_objective_fourier); ``target`` / ``resid_out`` are then fp32 (N,C,H,W,2) -- `torch.view_as_real` of a
+    complex64 (N,C,H,W) -- ``weight`` the real (N,C,H,W) k-space mask or weight, ``psf`` and ``operator`` must be None and ``pool``
+    1.  ``scratch``: a uint8 device tensor of at least glowhip_restore_fourier_scratch_bytes(N, C, H, W) bytes (`fourier_scratch`),
+    allocated when None.  ``fourier=False`` is every call above, unchanged."""
     for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out),
                     ("psf", psf), ("resid_out", resid_out), ("operator", operator)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
             raise _lib.GlowHipError(f"restore_objective: {name} must be a contiguous fp32 tensor on the device of x")
     n, c, h, w = x.shape
     pool = int(pool)
+    if fourier:
+        return _restore_objective_fourier(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch)
     if operator is not None:
         return _restore_objective_linear(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch)
     if scratch is not None:
@@ -179,6 +281,34 @@ def _restore_objective_linear(x, target, weight, inv_wsum, pool, grad_out, loss_
     _lib.check(_lib.lib().glowhip_restore_objective_linear(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum),
                                                            _lib.ptr(operator), m, n, d, _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss),
                                                            _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(x.device)))
+    return loss, grad
+
+
+def _restore_objective_fourier(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch):
+    """`restore_objective` with ``fourier=True`` (its tensors are already known to be contiguous fp32 on the device of x)."""
+    n, c, h, w = x.shape
+    if psf is not None or operator is not None or pool != 1:
+        raise _lib.GlowHipError("restore_objective: fourier excludes psf and operator, and pool must be 1")
+    for name, t, shape in (("target", target, (n, c, h, w, 2)), ("resid_out", resid_out, (n, c, h, w, 2)), ("weight", weight, (n, c, h, w))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.GlowHipError(f"restore_objective: {name} must have shape {shape} with fourier")
+    if inv_wsum is not None and inv_wsum.numel() != n:
+        raise _lib.GlowHipError(f"restore_objective: inv_wsum holds {inv_wsum.numel()} values for a batch of {n}")
+    grad = torch.empty_like(x) if grad_out is None else grad_out
+    loss = torch.empty(n, dtype=torch.float32, device=x.device) if loss_out is None else loss_out
+    if tuple(grad.shape) != tuple(x.shape) or loss.numel() != n:
+        raise _lib.GlowHipError("restore_objective: grad_out must have the shape of x, loss_out one value per sample")
+    resid = torch.empty_like(target) if resid_out is None else resid_out
+    if scratch is None:
+        if not (2 <= h <= FOURIER_MAX and 2 <= w <= FOURIER_MAX and h & (h - 1) == 0 and w & (w - 1) == 0):      # (let the C call say why)
+            scratch = torch.empty(16, dtype=torch.uint8, device=x.device)
+        else:
+            scratch = fourier_scratch(n, c, h, w, x.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.device == x.device):
+        raise _lib.GlowHipError("restore_objective: scratch must be a contiguous uint8 tensor on the device of x")
+    _lib.check(_lib.lib().glowhip_restore_objective_fourier(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), n, c, h, w,
+                                                            _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss), _lib.ptr(scratch),
+                                                            scratch.numel(), _lib.stream_ptr(x.device)))
     return loss, grad
 
 
@@ -313,10 +443,22 @@ class LatentLoop:
 
     ``operator`` (M,C,H,W), a contiguous fp32 device tensor: the measurement is (N, M) and the image shape is the operator's.  The
     loop holds the operator BY REFERENCE -- a sensing matrix is hundreds of MB; it is not copied -- so the caller must not write
-    to it (or free it) while a fit or a chain that uses it is alive.  ``resid`` and the call's scratch ``op_scratch`` are the loop's own."""
+    to it (or free it) while a fit or a chain that uses it is alive.  ``resid`` and the call's scratch ``op_scratch`` are the loop's own.
 
-    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None, operator=None):
+    ``fourier=True``: the measurement is the unitary 2-D DFT of the decode, complex64 (N,C,H,W) or fp32 with a trailing 2 (kept as
+    the latter); ``weight`` is the real k-space mask or weight, broadcast to (N,C,H,W); sides are powers of two up to 256.  It
+    excludes ``psf``, ``operator`` and ``pool != 1`` (ValueError).  ``resid`` and ``op_scratch`` are static buffers as above."""
+
+    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None, operator=None, fourier=False):
         self.glow, self.pool, self.steps, self.want_graph = glow, int(pool), int(steps), bool(graph)
+        self.fourier = bool(fourier)
+        if self.fourier:
+            if psf is not None or operator is not None or self.pool != 1:
+                raise ValueError("fourier excludes psf, operator and estimate_psf, and pool must be 1")
+            measurement = as_kspace(measurement)
+            if measurement.dim() != 5:
+                raise ValueError(f"measurement of shape {tuple(measurement.shape)}: expected complex (N, C, H, W) or fp32 (N, C, H, W, 2) with fourier")
+            check_fourier_shape(measurement.shape[2:4], "measurement")
         meas = _lib.require_device_tensor(measurement, "measurement")
         dev = self.device = meas.device
         if self.pool < 1:
@@ -331,6 +473,8 @@ class LatentLoop:
             if meas.dim() != 2 or meas.shape[1] != m:
                 raise ValueError(f"measurement of shape {tuple(meas.shape)}: expected (N, {m}) with this operator")
             n, image_chw = meas.shape[0], tuple(op.shape[1:])
+        elif self.fourier:
+            n, image_chw = meas.shape[0], tuple(meas.shape[1:4])
         else:
             n, c, h, w = meas.shape
             image_chw = (c, h * self.pool, w * self.pool)
@@ -339,7 +483,8 @@ class LatentLoop:
             raise ValueError(f"init {init!r} does not belong to a batch of {n} images of shape {plan.in_chw}")
         self.n = n
         self.target = meas.clone()
-        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand_as(meas).contiguous()
+        wshape = meas.shape[:4] if self.fourier else meas.shape      # (the k-space weight is real: one value per coefficient)
+        self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand(wshape).contiguous()
         self._start = [t.float().contiguous().clone() for t in init.to(dev).detach().tensors()]
         self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
         self.grad_x = torch.empty_like(self.image)
@@ -356,6 +501,10 @@ class LatentLoop:
             self.operator = op
             self.resid = torch.empty_like(self.target)
             self.op_scratch = linear_scratch(n, m, d, dev)
+        # Fourier-domain measurements: the residual (the forward pass's intermediate too) and the call's scratch, static as above
+        if self.fourier:
+            self.resid = torch.empty_like(self.target)
+            self.op_scratch = fourier_scratch(n, *image_chw, dev)
         self._capture = None
         self.graph_error = None
         self._iterations = 0         # run since construction (a reset does not take the lazy allocations back)
@@ -368,7 +517,7 @@ class LatentLoop:
         plan = self.plan
         plan.decode(leaves[0], leaves[1:], out=image)
         restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss,
-                          psf=self.psf, resid_out=self.resid, operator=self.operator, scratch=self.op_scratch)
+                          psf=self.psf, resid_out=self.resid, operator=self.operator, scratch=self.op_scratch, fourier=self.fourier)
         plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
 
     def _capturing(self):            # the context of a recording (the fit: its optimiser's)
@@ -383,7 +532,8 @@ class LatentLoop:
         ``resid`` and ``op_scratch`` need no entry: like ``target`` and ``weight`` they are this loop's own static buffers, allocated
         once in the constructor and never rebound, so a recorded launch always reaches them; ``operator`` is the caller's tensor,
         held here for the loop's life, which the caller must leave alone (`LatentLoop`)."""
-        return self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
+        sig = self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
+        return {**sig, "fourier": True} if self.fourier else sig      # (which objective the recording holds)
 
     @torch.no_grad()
     def step_eager(self):
@@ -516,18 +666,22 @@ class LatentFit(LatentLoop):
     update, a non-finite theta norm theta's, each without the other -- harmless for the same reason as above, since theta's norm
     history enters the test that re-runs a fit on the exact family or reports ``finite=False``.  The softmax fixes the scale
     ambiguity between PSF and image; the translation ambiguity stays, and the centre of the start and the valid-band weights select
-    the solution."""
+    the solution.
+
+    ``fourier=True``: the measurement is the decode's unitary 2-D DFT and ``weight`` the k-space mask (`LatentLoop`)."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
-                 graph=True, psf=None, operator=None, estimate_psf=None, psf_lr=0.2):
+                 graph=True, psf=None, operator=None, estimate_psf=None, psf_lr=0.2, fourier=False):
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
+        if fourier and estimate_psf is not None:
+            raise ValueError("fourier excludes psf, operator and estimate_psf, and pool must be 1")
         start = None
         if estimate_psf is not None:
             start = blind_start(psf, estimate_psf, len(measurement), operator)
             psf = start.to(measurement.device)
-        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator, fourier=fourier)
         self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
         n, dev = self.n, self.device
         # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
