@@ -621,6 +621,56 @@ int    glowhip_restore_objective_fourier(const float* x, const float* target /* 
 int    glowhip_fourier2d(const float* in, float* out, long planes, int H, int W, int adjoint, glowhip_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Multi-coil k-space (parallel imaging, SENSE): the Fourier objective above with Q receive coils, each seeing the image through its
+ * own complex sensitivity map (csrc/restore_fourier.hip; fp64 restatement tests/coil_oracle.py).  THE definition.  Per sample n and
+ * image channel c: Q coils with complex sensitivity maps S[q] (H x W), 1 <= Q <= 32; F is the unitary 2-D DFT defined above
+ * (torch.fft.fft2(norm="ortho"), unshifted).
+ *     Y[n,c,q]    = F ( S[q] * x[n,c] )                          complex (H,W); * is the element-wise product
+ *     resid       = w[n,c] * (Y[n,c,q] - t[n,c,q])               (N,C,Q,H,W,2) interleaved re/im: scratch AND output
+ *     loss_out[n] = inv_wsum[n] * sum_{c,q,k} w |Y - t|^2        fp64, fixed order, no atomics
+ *     grad_x[n,c] = 2 inv_wsum[n] * sum_q Re( conj(S[q]) * F^H resid[n,c,q] )     real (N,C,H,W), the sum in coil order q = 0..Q-1
+ * x, grad_x: (N,C,H,W) fp32 contiguous; target: (N,C,Q,H,W,2) fp32, the memory of torch.view_as_real on a complex64 tensor; maps:
+ * (Q,H,W,2) fp32, shared by the batch when maps_stride == 0, or per sample, (N,Q,H,W,2), when maps_stride == Q*H*W*2 (counted in
+ * floats; any other stride is GLOWHIP_EINVAL); the same for every channel; NOT normalised by the kernel.  weight: real (N,C,H,W),
+ * shared by the coils -- the sampling mask; per-coil noise whitening is the caller's job -- NULL means all ones.  inv_wsum: (N), NULL
+ * means 1 / (C Q H W).  loss_out may be NULL.  H and W: each a power of two from 2 to 256, as above.
+ * THREE launches, whatever the shape.  (1) Forward rows on (N C Q planes) x row tiles: the tile is loaded as (S.re x, S.im x) -- two
+ * products, one rounding each -- then the stages of the plain call, into resid.  (2) The column kernel of the plain call on N C Q
+ * planes, with the sample of a plane plane / (C Q) and the weight cell that of plane / Q: forward columns, scaling, subtraction,
+ * weighting, loss partial and adjoint columns on ONE LDS tile.  (3) Adjoint rows with the coil sum on (N C planes) x row tiles: a
+ * workgroup walks q = 0..Q-1 over the same row tile of the Q coil planes in the scratch and every thread adds S.re G.re + S.im G.im
+ * (one rounding per operation) for the elements it owns -- a fixed element <-> thread map -- into fp32 registers, in coil order; it
+ * stores once, times 1/sqrt(H W).  The first tile's workgroup of a sample folds the C Q col_tiles loss partials in index order in
+ * fp64.  No atomics, no fourth launch, nothing depends on workgroup order.
+ * Guarantees.  Tile shapes and the butterfly order are functions of (H, W) only, never of N or Q: sample n's outputs have the same
+ * bits in a batch of 1 and in a batch of 64.  Shared maps and the same maps repeated per sample give the same bits.  Bitwise
+ * reproducible run to run.  inv_wsum[n] == 0: exact zeros in grad_x[n] and resid[n] and loss 0; the spectrum is not read.  A
+ * non-finite x[n] reaches no other sample's outputs.  No allocation, no host sync, capturable.  With Q == 1 and S == 1 + 0i the
+ * loss, grad_x and resid are VALUE-equal to glowhip_restore_objective_fourier's (torch.equal holds): the only bit that can differ is
+ * the sign of a zero -- 0 * x is -0 for x < 0, and +-0 never changes a non-zero sum -- so this is not a claim of bit identity.
+ * glowhip_restore_objective_fourier, glowhip_fourier2d and the other objective entry points keep the bits they had.
+ * scratch: glowhip_restore_coils_scratch_bytes(N, C, Q, H, W) bytes at a 16-byte aligned address (the complex intermediate of the
+ * adjoint, N C Q planes, and the loss partials); monotone in N, C and Q, and 0 only on error (see glowhip_last_error).
+ * GLOWHIP_EINVAL with a message and no device call: a NULL x, target, maps, resid or grad_x; N < 0 or C < 1; Q outside 1..32; a
+ * maps_stride other than 0 and Q*H*W*2; H or W not a power of two from 2 to 256; a grid of more than 2^31 workgroups; a scratch
+ * that is NULL, misaligned or too small; x, grad_x, resid or maps overlapping.  N == 0 returns GLOWHIP_OK.
+ *
+ * glowhip_coils2d is the operator alone (two launches): adjoint == 0 maps real `in` (N,C,H,W) to complex `out` (N,C,Q,H,W,2) =
+ * F (S in); adjoint == 1 maps complex `in` (N,C,Q,H,W,2) to real `out` (N,C,H,W) = sum_q Re( conj(S[q]) F^H in[q] ).  It makes
+ * measurements and the coil-combined zero-filled start without an FFT library.  Like glowhip_fourier2d's adjoint, the adjoint takes
+ * its complex intermediate from the stream's memory pool: not for a captured region.  GLOWHIP_EINVAL as above, and for adjoint
+ * outside {0, 1} and in, maps or out overlapping. */
+size_t glowhip_restore_coils_scratch_bytes(int N, int C, int Q, int H, int W);      /* 0: see last_error */
+int    glowhip_restore_objective_coils(const float* x, const float* target /* (N,C,Q,H,W,2) */, const float* weight,
+                                       const float* inv_wsum, const float* maps /* (Q,H,W,2) or (N,Q,H,W,2) */, long maps_stride,
+                                       int N, int C, int Q, int H, int W,
+                                       float* resid /* scratch AND output: (N,C,Q,H,W,2) = w (F (S x) - t) */,
+                                       float* grad_x, float* loss_out,
+                                       void* scratch, size_t scratch_bytes, glowhip_stream_t stream);
+int    glowhip_coils2d(const float* in, const float* maps, long maps_stride, float* out, int N, int C, int Q, int H, int W,
+                       int adjoint, glowhip_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Blind deblurring: the PSF as an unknown of the fit -- the gradient of the data term of glowhip_restore_objective_psf with
  * respect to the taps of the PSF, and the softmax that keeps an estimate on the simplex (csrc/restore_blind.hip; fp64 restatement
  * tests/blind_oracle.py).  THE definition.  Notation as for glowhip_restore_objective_psf; per sample n, k the kh x kw PSF,

@@ -349,6 +349,9 @@ SIGNATURES = {
     "glowhip_restore_fourier_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "glowhip_restore_objective_fourier": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "glowhip_fourier2d": (c_int, [_P, _P, c_long, c_int, c_int, c_int, _P]),
+    "glowhip_restore_coils_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "glowhip_restore_objective_coils": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
+    "glowhip_coils2d": (c_int, [_P, _P, c_long, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "glowhip_psf_from_logits": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "glowhip_restore_psf_grad_scratch_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "glowhip_restore_psf_grad": (c_int, [_P, _P, _P, _P, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_size_t, _P]),

@@ -16,6 +16,11 @@
 //                        part times 1/sqrt(H W) into grad_x.  The workgroup of a sample's first tile also folds that sample's loss
 //                        partials, in index order, in fp64: no fourth launch
 // glowhip_fourier2d is two of the same kernels (rows then columns; the adjoint columns then rows).
+// Multi-coil k-space (glowhip_restore_objective_coils, glowhip_coils2d): Y[n,c,q] = F (S[q] x[n,c]) with Q complex sensitivity maps,
+// still three launches -- k_coils_rows_fwd loads its tile as (S.re x, S.im x) on N C Q planes; k_fourier_cols<FT_OBJECTIVE, true> is
+// the column kernel on N C Q planes with the weight of plane / Q; k_coils_rows_adj, on N C planes, walks the Q coil planes of its row
+// tile and sums Re(conj(S) G) in registers, in coil order, a fixed element <-> thread map, and folds the loss.  The plain instances
+// compile the coil code out and keep their bits.
 // Twiddles: exp(-i pi k / h) for every stage's half-length h, one contiguous run per stage (L - 1 entries), evaluated in fp64
 // (sincospi on the exact argument k / h) and rounded once to fp32, built per launch in LDS.
 // LDS banks (a wave's 8-byte accesses are served in two halves of 32 lanes; a half is conflict-free when its 32 complex values fall
@@ -193,16 +198,122 @@ __global__ void __launch_bounds__(FT_NT) k_fourier_rows_adj(const float* __restr
     }
 }
 
+// ---- multi-coil (SENSE): Y[n,c,q] = F (S[q] x[n,c]) with Q complex sensitivity maps, the same for every channel ----
+constexpr int FT_COILS_MAX = 32;
+constexpr int FT_ROW_OWN = FT_ROW_ELEMS / FT_NT;      // the most elements of a row tile a thread owns (element e belongs to e % FT_NT)
+
+// real rows times the coil's map -> complex rows.  in: (N C, H, W); maps: (Q, H, W, 2) at n * maps_stride; out: (N C Q, H, W, 2).
+// The tile is loaded as (S.re x, S.im x) -- two products, one rounding each -- and the stages are k_fourier_rows_fwd's
+__global__ void __launch_bounds__(FT_NT) k_coils_rows_fwd(const float* __restrict__ in, const float* __restrict__ maps, long maps_stride,
+                                                          float* __restrict__ out, int lgH, int lgW, int lgR, int C, int Q) {
+    __shared__ float2 tile[FT_ROW_ELEMS];
+    __shared__ float2 tw[FT_MAX];
+    const int W = 1 << lgW, tid = threadIdx.x;
+    const int tiles = 1 << (lgH - lgR);
+    const size_t plane = blockIdx.x >> (lgH - lgR);      // (n C + c) Q + q
+    const size_t nc = plane / (size_t)Q, q = plane - nc * (size_t)Q, n = nc / (size_t)C;
+    const int r0 = (int)(blockIdx.x & (unsigned)(tiles - 1)) << lgR;
+    const size_t base = ((plane << lgH) + (size_t)r0) << lgW;      // the tile's first element of the output
+    const size_t xbase = ((nc << lgH) + (size_t)r0) << lgW;
+    const float* S = maps + n * (size_t)maps_stride + 2 * (((q << lgH) + (size_t)r0) << lgW);
+    const bool a8 = (((size_t)out) & 7) == 0, s8 = (((size_t)maps) & 7) == 0;      // (maps_stride is even)
+    ft_twiddles(tw, W);
+    const int ne = W << lgR;
+    for (int e = tid; e < ne; e += FT_NT) {
+        const int j = e & (W - 1), r = e >> lgW;
+        const float xv = in[xbase + e];
+        const float2 sv = ft_ld2(S + 2 * (size_t)e, s8);
+        tile[ft_row_at(r, ft_bitrev(j, lgW), lgW)] = make_float2(sv.x * xv, sv.y * xv);
+    }
+    __syncthreads();
+    ft_row_stages<false>(tile, tw, lgW, lgR);
+    for (int e = tid; e < ne; e += FT_NT) {
+        const int j = e & (W - 1), r = e >> lgW;
+        ft_st2(out + 2 * (base + e), tile[ft_row_at(r, j, lgW)], a8);
+    }
+}
+
+// complex rows of Q coil planes -> real rows: scale * sum_q Re(conj(S[q]) (the adjoint transform along W)).  in: (N C Q, H, W, 2);
+// out: (N C, H, W).  grid = (N C planes) x row tiles; a workgroup walks q = 0 .. Q - 1 over the same row tile of the Q coil planes,
+// and each thread adds S.re G.re + S.im G.im for the elements it owns (element e of the tile belongs to thread e % FT_NT, whatever q)
+// into fp32 registers, in coil order; one store at the end.  The objective's call (partials given): exact zeros for a sample with
+// inv_wsum[n] == 0, and the workgroup of a sample's first tile folds the sample's C Q col_tiles loss partials in index order
+__global__ void __launch_bounds__(FT_NT) k_coils_rows_adj(const float* __restrict__ in, const float* __restrict__ maps, long maps_stride,
+                                                          float* __restrict__ out, int lgH, int lgW, int lgR, float scale,
+                                                          const float* __restrict__ inv_wsum, int C, int Q, float inv_default,
+                                                          const double* __restrict__ partials, int col_tiles,
+                                                          float* __restrict__ loss_out) {
+    __shared__ float2 tile[FT_ROW_ELEMS];
+    __shared__ float2 tw[FT_MAX];
+    const int W = 1 << lgW, tid = threadIdx.x;
+    const int tiles = 1 << (lgH - lgR);
+    const size_t nc = blockIdx.x >> (lgH - lgR);
+    const size_t n = nc / (size_t)C;
+    const int tix = (int)(blockIdx.x & (unsigned)(tiles - 1));
+    const size_t toff = ((size_t)tix << lgR) << lgW;      // the tile's first element inside its plane
+    const size_t obase = (nc << (lgH + lgW)) + toff;
+    const int ne = W << lgR;
+    if (partials) {      // (uniform)
+        const float inv = inv_wsum ? inv_wsum[n] : inv_default;
+        if (tix == 0 && nc == n * (size_t)C && tid == 0 && loss_out) {
+            double tot = 0.0;
+            const int np = C * Q * col_tiles;
+            const double* ps = partials + n * (size_t)np;
+            for (int i = 0; i < np; ++i) tot += ps[i];
+            loss_out[n] = inv == 0.f ? 0.f : (float)(tot * (double)inv);
+        }
+        if (inv == 0.f) {      // not part of the problem: exact zeros
+            for (int e = tid; e < ne; e += FT_NT) out[obase + e] = 0.f;
+            return;
+        }
+    }
+    const bool a8 = (((size_t)in) & 7) == 0, s8 = (((size_t)maps) & 7) == 0;
+    ft_twiddles(tw, W);
+    float acc[FT_ROW_OWN];
+#pragma unroll
+    for (int i = 0; i < FT_ROW_OWN; ++i) acc[i] = 0.f;
+    for (int q = 0; q < Q; ++q) {
+        const float* src = in + 2 * (((nc * (size_t)Q + (size_t)q) << (lgH + lgW)) + toff);
+        const float* S = maps + n * (size_t)maps_stride + 2 * (((size_t)q << (lgH + lgW)) + toff);
+        for (int e = tid; e < ne; e += FT_NT) {
+            const int j = e & (W - 1), r = e >> lgW;
+            tile[ft_row_at(r, j, lgW)] = ft_ld2(src + 2 * (size_t)e, a8);
+        }
+        __syncthreads();
+        ft_row_stages<true>(tile, tw, lgW, lgR);
+#pragma unroll
+        for (int i = 0; i < FT_ROW_OWN; ++i) {      // (decimation in frequency leaves index j at slot bitrev(j))
+            const int e = tid + i * FT_NT;
+            if (e < ne) {
+                const int j = e & (W - 1), r = e >> lgW;
+                const float2 G = tile[ft_row_at(r, ft_bitrev(j, lgW), lgW)];
+                const float2 sv = ft_ld2(S + 2 * (size_t)e, s8);
+                const float term = sv.x * G.x + sv.y * G.y;
+                acc[i] = acc[i] + term;
+            }
+        }
+        __syncthreads();      // the tile is read: the next coil may load
+    }
+#pragma unroll
+    for (int i = 0; i < FT_ROW_OWN; ++i) {
+        const int e = tid + i * FT_NT;
+        if (e < ne) out[obase + e] = acc[i] * scale;
+    }
+}
+
 enum { FT_OBJECTIVE = 0, FT_FORWARD = 1, FT_ADJOINT = 2 };
+
 
 // the column pass.  FT_FORWARD: src -> dst = scale * (the transform along H); FT_ADJOINT: src -> dst = the adjoint transform along H,
 // unscaled; FT_OBJECTIVE: src = dst_resid = `resid` (the rows' output, overwritten with w (X - t)), the adjoint of 2 inv resid into
 // `dst`, the loss partial of the tile into `partials`.  src may be dst: a workgroup reads its columns before it writes them
-template <int MODE>
+// COILS (the multi-coil objective, planes = N C Q, `C` holds C Q): the weight is shared by the Q coil planes of a channel, so its cell
+// is that of plane / Q; the plain instance compiles this out
+template <int MODE, bool COILS = false>
 __global__ void __launch_bounds__(FT_NT) k_fourier_cols(const float* src, float* dst, int lgH, int lgW, int lgTC, float scale,
                                                         const float* __restrict__ target, const float* __restrict__ weight,
                                                         const float* __restrict__ inv_wsum, int C, float inv_default, float* resid,
-                                                        double* __restrict__ partials) {
+                                                        double* __restrict__ partials, int Q) {
     __shared__ float2 tile[FT_COL_ELEMS];
     __shared__ float2 tw[FT_MAX];
     __shared__ double red[FT_NT / 64];
@@ -249,6 +360,7 @@ __global__ void __launch_bounds__(FT_NT) k_fourier_cols(const float* src, float*
     }
     if (MODE == FT_OBJECTIVE) {
         const bool t8 = ((((size_t)target) | ((size_t)resid)) & 7) == 0;
+        const size_t wshift = COILS ? pbase - ((plane / (size_t)Q) << (lgH + lgW)) : 0;      // from the plane's cell to the weight's
         double acc = 0.0;
         for (int e = tid; e < ne; e += FT_NT) {
             const int c = e & (TC - 1), i = e >> lgTC;
@@ -256,7 +368,7 @@ __global__ void __launch_bounds__(FT_NT) k_fourier_cols(const float* src, float*
             const int p = ft_col_at(i, c, lgTC);
             const float2 X = tile[p];
             const float2 t = ft_ld2(target + 2 * g, t8);
-            const float w = weight ? weight[g] : 1.f;
+            const float w = weight ? weight[g - wshift] : 1.f;
             const float dr = X.x * scale - t.x, di = X.y * scale - t.y;
             const float rr = w * dr, ri = w * di;
             acc += (double)rr * (double)dr;
@@ -354,7 +466,7 @@ extern "C" int glowhip_restore_objective_fourier(const float* x, const float* ta
     hipLaunchKernelGGL(k_fourier_rows_fwd, dim3(g.row_blocks), dim3(FT_NT), 0, s, x, resid, g.lgH, g.lgW, g.lgR);
     GH_LAUNCH_CHECK("k_fourier_rows_fwd");
     hipLaunchKernelGGL(k_fourier_cols<FT_OBJECTIVE>, dim3(g.col_blocks), dim3(FT_NT), 0, s, (const float*)resid, inter, g.lgH, g.lgW,
-                       g.lgTC, g.scale, target, weight, inv_wsum, C, inv_default, resid, partials);
+                       g.lgTC, g.scale, target, weight, inv_wsum, C, inv_default, resid, partials, 1);
     GH_LAUNCH_CHECK("k_fourier_cols");
     hipLaunchKernelGGL(k_fourier_rows_adj, dim3(g.row_blocks), dim3(FT_NT), 0, s, (const float*)inter, grad_x, g.lgH, g.lgW, g.lgR,
                        g.scale, inv_wsum, C, inv_default, (const double*)partials, g.col_tiles, loss_out);
@@ -377,7 +489,7 @@ extern "C" int glowhip_fourier2d(const float* in, float* out, long planes, int H
         hipLaunchKernelGGL(k_fourier_rows_fwd, dim3(g.row_blocks), dim3(FT_NT), 0, s, in, out, g.lgH, g.lgW, g.lgR);
         GH_LAUNCH_CHECK("k_fourier_rows_fwd");
         hipLaunchKernelGGL(k_fourier_cols<FT_FORWARD>, dim3(g.col_blocks), dim3(FT_NT), 0, s, (const float*)out, out, g.lgH, g.lgW,
-                           g.lgTC, g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr);
+                           g.lgTC, g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr, 1);
         GH_LAUNCH_CHECK("k_fourier_cols");
         return GLOWHIP_OK;
     }
@@ -390,7 +502,7 @@ extern "C" int glowhip_fourier2d(const float* in, float* out, long planes, int H
         return GLOWHIP_ELAUNCH;
     }
     hipLaunchKernelGGL(k_fourier_cols<FT_ADJOINT>, dim3(g.col_blocks), dim3(FT_NT), 0, s, in, (float*)inter, g.lgH, g.lgW, g.lgTC,
-                       g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr);
+                       g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr, 1);
     hipError_t e1 = hipGetLastError();
     if (e1 == hipSuccess) {
         hipLaunchKernelGGL(k_fourier_rows_adj, dim3(g.row_blocks), dim3(FT_NT), 0, s, (const float*)inter, out, g.lgH, g.lgW, g.lgR,
@@ -400,6 +512,109 @@ extern "C" int glowhip_fourier2d(const float* in, float* out, long planes, int H
     (void)hipFreeAsync(inter, s);
     if (e1 != hipSuccess) {
         set_error("fourier2d (adjoint): %s", hipGetErrorString(e1));
+        return GLOWHIP_ELAUNCH;
+    }
+    return GLOWHIP_OK;
+}
+
+// ---- multi-coil ----
+// the checks the three coil entry points share: the counts, the stride of the maps and the shapes (planes = N C Q)
+static const char* coils_geo(int N, int C, int Q, int H, int W, long maps_stride, bool with_stride, FtGeo& g) {
+    if (N < 0 || C < 1) return "N < 0 or C < 1";
+    if (Q < 1 || Q > FT_COILS_MAX) return "Q must be from 1 to 32 coils";
+    const char* why = ft_geo((long)N * (long)C * (long)Q, H, W, g);
+    if (why) return why;
+    if (with_stride && maps_stride != 0 && maps_stride != (long)Q * H * W * 2)
+        return "maps_stride must be 0 (maps shared by the batch) or Q*H*W*2 (per sample)";
+    return nullptr;
+}
+
+extern "C" size_t glowhip_restore_coils_scratch_bytes(int N, int C, int Q, int H, int W) {
+    FtGeo g;
+    const char* why = coils_geo(N, C, Q, H, W, 0, false, g);
+    if (why) {
+        set_error("restore_coils_scratch_bytes: %s (N %d, C %d, Q %d, H %d, W %d)", why, N, C, Q, H, W);
+        return 0;
+    }
+    return g.bytes;
+}
+
+extern "C" int glowhip_restore_objective_coils(const float* x, const float* target, const float* weight, const float* inv_wsum,
+                                               const float* maps, long maps_stride, int N, int C, int Q, int H, int W, float* resid,
+                                               float* grad_x, float* loss_out, void* scratch, size_t scratch_bytes,
+                                               glowhip_stream_t stream) {
+    GH_REQUIRE(x && target && maps && resid && grad_x,
+               "restore_objective_coils: null argument (x, target, maps, resid and grad_x are required)");
+    FtGeo g;
+    const char* why = coils_geo(N, C, Q, H, W, maps_stride, true, g);
+    GH_REQUIRE(!why, "restore_objective_coils: %s (N %d, C %d, Q %d, H %d, W %d, maps_stride %ld)", why, N, C, Q, H, W, maps_stride);
+    if (N == 0) return GLOWHIP_OK;
+    GH_REQUIRE(scratch && scratch_bytes >= g.bytes && ((size_t)scratch & 15) == 0,
+               "restore_objective_coils: scratch %p of %zu bytes (16-byte aligned, >= %zu: glowhip_restore_coils_scratch_bytes)",
+               scratch, scratch_bytes, g.bytes);
+    const size_t real_bytes = (size_t)N * (size_t)C * (size_t)H * (size_t)W * 4, resid_bytes = (size_t)g.planes * (size_t)H * (size_t)W * 8;
+    const size_t maps_bytes = (maps_stride ? (size_t)N : (size_t)1) * (size_t)Q * (size_t)H * (size_t)W * 8;
+    GH_REQUIRE(!ft_overlap(x, real_bytes, grad_x, real_bytes) && !ft_overlap(x, real_bytes, resid, resid_bytes) &&
+                   !ft_overlap(grad_x, real_bytes, resid, resid_bytes) && !ft_overlap(maps, maps_bytes, grad_x, real_bytes) &&
+                   !ft_overlap(maps, maps_bytes, resid, resid_bytes) && !ft_overlap(maps, maps_bytes, x, real_bytes),
+               "restore_objective_coils: x, grad_x, resid and maps must not overlap");
+    hipStream_t s = (hipStream_t)stream;
+    float* inter = reinterpret_cast<float*>(scratch);
+    double* partials = reinterpret_cast<double*>(reinterpret_cast<char*>(scratch) + g.off_part);
+    const float inv_default = 1.f / (float)((long)C * Q * H * W);
+    const unsigned adj_blocks = g.row_blocks / (unsigned)Q;      // (N C planes) x row tiles
+    hipLaunchKernelGGL(k_coils_rows_fwd, dim3(g.row_blocks), dim3(FT_NT), 0, s, x, maps, maps_stride, resid, g.lgH, g.lgW, g.lgR, C, Q);
+    GH_LAUNCH_CHECK("k_coils_rows_fwd");
+    hipLaunchKernelGGL((k_fourier_cols<FT_OBJECTIVE, true>), dim3(g.col_blocks), dim3(FT_NT), 0, s, (const float*)resid, inter, g.lgH,
+                       g.lgW, g.lgTC, g.scale, target, weight, inv_wsum, C * Q, inv_default, resid, partials, Q);
+    GH_LAUNCH_CHECK("k_fourier_cols (coils)");
+    hipLaunchKernelGGL(k_coils_rows_adj, dim3(adj_blocks), dim3(FT_NT), 0, s, (const float*)inter, maps, maps_stride, grad_x, g.lgH,
+                       g.lgW, g.lgR, g.scale, inv_wsum, C, Q, inv_default, (const double*)partials, g.col_tiles, loss_out);
+    GH_LAUNCH_CHECK("k_coils_rows_adj");
+    return GLOWHIP_OK;
+}
+
+extern "C" int glowhip_coils2d(const float* in, const float* maps, long maps_stride, float* out, int N, int C, int Q, int H, int W,
+                               int adjoint, glowhip_stream_t stream) {
+    GH_REQUIRE(in && maps && out, "coils2d: null argument");
+    GH_REQUIRE(adjoint == 0 || adjoint == 1, "coils2d: adjoint = %d (0: real to complex, 1: complex to real)", adjoint);
+    FtGeo g;
+    const char* why = coils_geo(N, C, Q, H, W, maps_stride, true, g);
+    GH_REQUIRE(!why, "coils2d: %s (N %d, C %d, Q %d, H %d, W %d, maps_stride %ld)", why, N, C, Q, H, W, maps_stride);
+    if (N == 0) return GLOWHIP_OK;
+    const size_t real_bytes = (size_t)N * (size_t)C * (size_t)H * (size_t)W * 4, cplx_bytes = (size_t)g.planes * (size_t)H * (size_t)W * 8;
+    const size_t maps_bytes = (maps_stride ? (size_t)N : (size_t)1) * (size_t)Q * (size_t)H * (size_t)W * 8;
+    const size_t in_bytes = adjoint ? cplx_bytes : real_bytes, out_bytes = adjoint ? real_bytes : cplx_bytes;
+    GH_REQUIRE(!ft_overlap(in, in_bytes, out, out_bytes) && !ft_overlap(maps, maps_bytes, out, out_bytes),
+               "coils2d: in, maps and out must not overlap");
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned adj_blocks = g.row_blocks / (unsigned)Q;
+    if (!adjoint) {
+        hipLaunchKernelGGL(k_coils_rows_fwd, dim3(g.row_blocks), dim3(FT_NT), 0, s, in, maps, maps_stride, out, g.lgH, g.lgW, g.lgR, C, Q);
+        GH_LAUNCH_CHECK("k_coils_rows_fwd");
+        hipLaunchKernelGGL(k_fourier_cols<FT_FORWARD>, dim3(g.col_blocks), dim3(FT_NT), 0, s, (const float*)out, out, g.lgH, g.lgW,
+                           g.lgTC, g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr, 1);
+        GH_LAUNCH_CHECK("k_fourier_cols");
+        return GLOWHIP_OK;
+    }
+    // as glowhip_fourier2d's adjoint: the complex intermediate comes from the stream's memory pool (not for a captured region)
+    void* inter = nullptr;
+    hipError_t e = hipMallocAsync(&inter, cplx_bytes, s);
+    if (e != hipSuccess || !inter) {
+        set_error("coils2d: hipMallocAsync of %zu bytes: %s", cplx_bytes, hipGetErrorString(e));
+        return GLOWHIP_ELAUNCH;
+    }
+    hipLaunchKernelGGL(k_fourier_cols<FT_ADJOINT>, dim3(g.col_blocks), dim3(FT_NT), 0, s, in, (float*)inter, g.lgH, g.lgW, g.lgTC,
+                       g.scale, nullptr, nullptr, nullptr, 1, 0.f, nullptr, nullptr, 1);
+    hipError_t e1 = hipGetLastError();
+    if (e1 == hipSuccess) {
+        hipLaunchKernelGGL(k_coils_rows_adj, dim3(adj_blocks), dim3(FT_NT), 0, s, (const float*)inter, maps, maps_stride, out, g.lgH,
+                           g.lgW, g.lgR, g.scale, nullptr, C, Q, 0.f, nullptr, 0, nullptr);
+        e1 = hipGetLastError();
+    }
+    (void)hipFreeAsync(inter, s);
+    if (e1 != hipSuccess) {
+        set_error("coils2d (adjoint): %s", hipGetErrorString(e1));
         return GLOWHIP_ELAUNCH;
     }
     return GLOWHIP_OK;

@@ -8,8 +8,9 @@ from .evaluate import EvalResult, Evaluator
 from .inferer import Inferer
 from .latents import Latents
 from .posterior import LatentMALA, PosteriorInfo
-from .restore import (LatentFit, PsfFit, RestoreInfo, check_fourier_shape, fourier2d, fourier2d_adjoint, fourier_mask, fourier_scratch,
-                      gaussian_operator, psf_from_logits, psf_gradient, restore_objective)
+from .restore import (COILS_MAX, LatentFit, PsfFit, RestoreInfo, check_coil_maps, check_fourier_shape, coil_maps, coils2d, coils2d_adjoint,
+                      coils_scratch, fourier2d, fourier2d_adjoint, fourier_mask, fourier_scratch, gaussian_operator, psf_from_logits,
+                      psf_gradient, restore_objective)
 from .trainer import Trainer
 
 _LAYERS = ("ActNorm", "LinearZeros", "Conv2d", "Conv2dZeros", "CouplingNet", "f", "Invertible1x1Conv", "Invertible1x1ConvLU",
@@ -23,4 +24,4 @@ for _n in _MODELS:
 
 __all__ = _MODELS + _LAYERS + ("Builder", "Trainer", "Inferer", "Evaluator", "EvalResult", "Latents", "LatentMALA", "PosteriorInfo", "LatentFit", "RestoreInfo", "restore_objective", "gaussian_operator",
                                "PsfFit", "psf_from_logits", "psf_gradient", "fourier2d", "fourier2d_adjoint", "fourier_mask", "fourier_scratch",
-                               "check_fourier_shape")
+                               "check_fourier_shape", "COILS_MAX", "check_coil_maps", "coil_maps", "coils2d", "coils2d_adjoint", "coils_scratch")

@@ -178,6 +178,57 @@ class Inferer:
             init = Latents(rep(init.z), [rep(e) for e in init.eps])
         return meas, weight, 1, init, None
 
+    def _coils_problem(self, measurement, weight, pool, init, chains, psf, operator, estimate_psf, coils):
+        """`_problem` with ``fourier=True, coils=maps``: the measurement is complex64 (N,C,Q,H,W) -- (C,Q,H,W) for one problem -- or
+        fp32 with a trailing 2, and comes back as the latter; ``maps`` are the Q complex sensitivity maps, (Q,H,W) or (N,Q,H,W); the
+        weight is the real k-space mask, shared by the coils, broadcast to (N,C,H,W); ``init`` None =
+        ``encode_full(clamp(coils2d_adjoint(w t, maps), 0, 1))``, with normalised maps the coil-combined zero-filled image;
+        ``chains`` > 1 repeats a single measurement (and per-sample maps of one sample).  Returns the maps as the sixth value.  Every
+        refusal is a ValueError raised before any device work."""
+        from .restore import as_kspace, check_coil_maps, check_fourier_shape, coils2d_adjoint
+        if psf is not None or operator is not None or estimate_psf is not None or int(pool) != 1:
+            raise ValueError("coils: multi-coil measurements exclude psf, operator and estimate_psf, and pool must be 1")
+        real = as_kspace(measurement)
+        if real.dim() not in (5, 6):
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)}: expected complex (C, Q, H, W) or (N, C, Q, H, W), or fp32 with a trailing 2")
+        c, q, h, w = (int(v) for v in real.shape[-5:-1])
+        check_fourier_shape((h, w), "measurement")
+        chw = (c, h, w)
+        if chw != tuple(int(v) for v in self.graph.flow.in_chw):
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)} is not the coil spectra of this model's images {tuple(self.graph.flow.in_chw)}")
+        n = 1 if real.dim() == 5 else int(real.shape[0])
+        maps, qs, per_sample = check_coil_maps(coils, n, (h, w))
+        if qs != q:
+            raise ValueError(f"measurement of shape {tuple(measurement.shape)} holds {q} coils, the maps {qs}")
+        if weight is not None:
+            weight = torch.as_tensor(weight, dtype=torch.float32)
+            try:
+                torch.broadcast_shapes(tuple(weight.shape), (n,) + chw)
+                ok = weight.dim() <= 4
+            except RuntimeError:
+                ok = False
+            if not ok:
+                raise ValueError(f"weight of shape {tuple(weight.shape)} does not broadcast to the k-space of {(n,) + chw}")
+            if bool((weight < 0).any()):
+                raise ValueError("weight: a k-space weight must be >= 0")
+        if chains < 1 or (chains > 1 and n != 1):
+            raise ValueError(f"chains = {chains}: several chains run on ONE measurement (a batch of {n} runs one chain each)")
+        meas = real.reshape((n, c, q, h, w, 2)).to(self.device).contiguous()
+        maps = maps.to(self.device).contiguous()
+        if weight is not None:
+            weight = weight.to(self.device).expand((n,) + chw).contiguous()
+        if init is None:
+            start = meas if weight is None else meas * weight.view(n, c, 1, h, w, 1)
+            init = self.encode_full(coils2d_adjoint(start.contiguous(), maps).clamp_(0.0, 1.0))
+        if chains > 1:
+            rep = lambda t: t.expand(chains, *t.shape[1:]).contiguous()
+            meas, weight = rep(meas), None if weight is None else rep(weight)
+            if per_sample:
+                maps = rep(maps)
+            if len(init) == 1:
+                init = Latents(rep(init.z), [rep(e) for e in init.eps])
+        return meas, weight, 1, init, None, maps
+
     def _fourier_problem(self, measurement, weight, pool, init, chains, psf, operator, estimate_psf):
         """`_problem` with ``fourier=True``: the measurement is complex64 (N,C,H,W) -- (C,H,W) for one problem -- or fp32 with a
         trailing 2, and comes back as the latter; the weight is the real k-space mask, broadcast to (N,C,H,W); ``init`` None =
@@ -274,7 +325,8 @@ class Inferer:
         return meas, weight, pool, init, psf
 
     def restore(self, measurement, weight=None, pool=1, steps=100, lr=0.05, prior_weight=0.0, init=None, max_grad_norm=0.0,
-                graph=True, exact=False, psf=None, border="valid", operator=None, estimate_psf=None, psf_lr=0.2, fourier=False):
+                graph=True, exact=False, psf=None, border="valid", operator=None, estimate_psf=None, psf_lr=0.2, fourier=False,
+                coils=None):
         """Latents whose decode explains ``measurement`` -- in-painting, denoising, projection (``pool=1``: ``measurement`` is an
         image (C,H,W) or a batch, ``weight`` its mask or per-pixel confidence, broadcast to it; None = everywhere) and
         super-resolution (``pool>1``: ``measurement`` is the LOW-resolution image, the decode is compared after a pool x pool average
@@ -335,9 +387,28 @@ class Inferer:
         ``encode_full(clamp(fourier2d_adjoint(w * measurement), 0, 1))``, the zero-filled reconstruction.  ``fourier`` together with
         ``psf``, ``operator``, ``estimate_psf`` or ``pool != 1``, a side that is not a power of two or is above 256, a measurement
         that is not the spectrum of the model's image shape, and a negative weight raise ValueError before any device work.
-        ``fourier=False`` is every call above, unchanged."""
+        ``fourier=False`` is every call above, unchanged.
+
+        ``coils=maps`` (with ``fourier=True``): multi-coil k-space, parallel imaging as SENSE states it -- Q receive coils each see
+        the image through a complex sensitivity map, Y[c,q] = F (S_q x_c) (include/glowhip.h, glowhip_restore_objective_coils).
+        ``measurement`` is complex64 (C,Q,H,W) or (N,C,Q,H,W), or fp32 with a trailing 2; ``maps`` complex64 (Q,H,W), shared by the
+        batch, or (N,Q,H,W), 1 <= Q <= 32, the same for every channel and not normalised here
+        (`network.restore.coil_maps` makes smooth synthetic ones with sum_q |S_q|^2 = 1); ``weight`` stays the real (N,C,H,W) mask,
+        shared by the coils, and ``inv_wsum[n] = 1 / max(Q sum w[n], 1)``.  ``init=None`` starts from
+        ``encode_full(clamp(coils2d_adjoint(w * measurement, maps), 0, 1))``, with normalised maps the usual coil-combined
+        zero-filled image.  ``coils`` without ``fourier=True``, with ``psf``, ``operator``, ``estimate_psf`` or ``pool != 1``, maps of
+        another plane, batch or coil count than the measurement's, and Q outside 1..32 raise ValueError before any device work.
+        ``coils=None`` is every call above, unchanged."""
         from .restore import LatentFit, check_prior_weight
         check_prior_weight(self.graph, prior_weight)
+        if coils is not None:
+            if not fourier:
+                raise ValueError("coils needs fourier=True (the maps multiply the image in front of the transform)")
+            meas, weight, pool, init, psf, coils = self._coils_problem(measurement, weight, pool, init, 1, psf, operator, estimate_psf, coils)
+            fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
+                            max_grad_norm=max_grad_norm, graph=graph, fourier=True, coils=coils)
+            info = fit.run(exact=exact)
+            return fit.latents(), info
         meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, psf=psf, border=border, operator=operator,
                                                       estimate_psf=estimate_psf, fourier=fourier)
         fit = LatentFit(self.graph, meas, weight=weight, pool=pool, init=init, steps=steps, lr=lr, prior_weight=prior_weight,
@@ -385,7 +456,7 @@ class Inferer:
         return info.psf, info
 
     def posterior(self, measurement, weight=None, pool=1, noise_std=0.1, chains=1, steps=200, burn_in=None, thin=1, step_size=1e-3,
-                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None, fourier=False):
+                  seed=None, init=None, graph=True, adapt_rate=0.5, psf=None, border="valid", operator=None, fourier=False, coils=None):
         """Draws from the posterior of the latents given ``measurement`` -- what else is consistent with it, and how sure the model
         is of each pixel -- by a Metropolis-adjusted Langevin chain on the device (`network.posterior.LatentMALA`):
 
@@ -412,13 +483,21 @@ class Inferer:
         all-zero latents.  ``fourier=True``: the measurement is the decode's unitary 2-D DFT and ``weight`` the k-space mask, as for
         `restore`; ``noise_std`` is then the standard deviation of EACH of the real and imaginary parts, the energy
         sum w |F x - measurement|^2 / (2 noise_std^2); ``chains=K`` repeats the one measurement and ``init=None`` starts every chain
-        from the zero-filled reconstruction."""
+        from the zero-filled reconstruction.  ``coils=maps`` (with ``fourier=True``): multi-coil k-space as for `restore`, the
+        measurement (C,Q,H,W) or (N,C,Q,H,W); ``noise_std`` is the standard deviation of each of the real and imaginary parts of each
+        coil's coefficient, the energy sum_{c,q,k} w |F (S_q x) - measurement|^2 / (2 noise_std^2); ``chains=K`` repeats the one
+        measurement and ``init=None`` starts every chain from the coil-combined zero-filled image."""
         from .model import sampler_position
         from .posterior import LatentMALA
         from .restore import check_prior_weight
         check_prior_weight(self.graph, 1.0)
-        meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border,
-                                                      operator=operator, fourier=fourier)
+        if coils is not None:
+            if not fourier:
+                raise ValueError("coils needs fourier=True (the maps multiply the image in front of the transform)")
+            meas, weight, pool, init, psf, coils = self._coils_problem(measurement, weight, pool, init, int(chains), psf, operator, None, coils)
+        else:
+            meas, weight, pool, init, psf = self._problem(measurement, weight, pool, init, chains=int(chains), psf=psf, border=border,
+                                                          operator=operator, fourier=fourier)
         if seed is None:
             seed, call = sampler_position(advance=True)
             call = call << 32      # (the chain's call is call + iteration: runs at successive positions share no counter)
@@ -426,7 +505,7 @@ class Inferer:
             seed, call = int(seed) & (2 ** 64 - 1), 0
         chain = LatentMALA(self.graph, meas, weight=weight, pool=pool, noise_std=noise_std, init=init, steps=steps, burn_in=burn_in,
                            thin=thin, step_size=step_size, adapt_rate=adapt_rate, seed=seed, graph=graph, call=call, psf=psf,
-                           operator=operator, fourier=fourier)
+                           operator=operator, fourier=fourier, coils=coils)
         info = chain.run()
         return chain.latents(), info
 

@@ -69,16 +69,18 @@ class LatentMALA(LatentLoop):
     (`restore.LatentLoop`); both evaluations of an iteration share the loop's one residual buffer.  ``operator`` (M,C,H,W): the
     measurement (N, M) is the decode seen through that dense matrix, held by reference (`restore.LatentLoop`).  ``fourier=True``: the
     measurement is the decode's unitary 2-D DFT, complex (N,C,H,W), ``weight`` the k-space mask, and ``noise_std`` the standard
-    deviation of each of the real and imaginary parts: the energy is sum w |F x - t|^2 / (2 noise_std^2)."""
+    deviation of each of the real and imaginary parts: the energy is sum w |F x - t|^2 / (2 noise_std^2).  ``coils=maps``: multi-coil
+    k-space (`restore.LatentLoop`), the measurement complex (N,C,Q,H,W); ``noise_std`` is the standard deviation of each of the real and
+    imaginary parts of each coil's coefficient, the energy sum_{c,q,k} w |F (S_q x) - t|^2 / (2 noise_std^2)."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, noise_std=0.1, init=None, steps=100, burn_in=None, thin=1,
                  step_size=1e-3, adapt_rate=0.5, seed=0, graph=True, call=0, step_clamp=(1e-10, 1.0), psf=None, operator=None,
-                 fourier=False):
+                 fourier=False, coils=None):
         check_prior_weight(glow, 1.0)
         burn_in = int(steps) // 2 if burn_in is None else int(burn_in)
         if init is None or steps < 1 or burn_in < 0 or thin < 1:
             raise ValueError("LatentMALA needs start latents (init), steps >= 1, burn_in >= 0 and thin >= 1")
-        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator, fourier=fourier)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator, fourier=fourier, coils=coils)
         self.burn_in, self.thin = burn_in, int(thin)
         self.noise_std, self.step_size, self.adapt_rate = float(noise_std), float(step_size), float(adapt_rate)
         self.step_min, self.step_max = (float(v) for v in step_clamp)

@@ -27,7 +27,11 @@ fused Adam step; `LatentFit` runs it inside the same captured iteration, `PsfFit
 Fourier-domain measurements: with ``fourier=True`` the measurement is the unitary 2-D DFT of each channel's plane, complex
 (N,C,H,W), and ``weight`` the k-space mask (glowhip_restore_objective_fourier, csrc/restore_fourier.hip: a separable radix-2 FFT in
 LDS; sides are powers of two up to 256).  `fourier2d` / `fourier2d_adjoint` are the transform alone, `fourier_mask` the usual
-undersampling masks.  Again only `LatentLoop._evaluate` knows."""
+undersampling masks.  Again only `LatentLoop._evaluate` knows.
+
+Multi-coil k-space: with ``fourier=True, coils=maps`` the measurement is complex (N,C,Q,H,W), the decode seen by Q receive coils
+through complex sensitivity maps, Y[c,q] = F (S_q x_c) (glowhip_restore_objective_coils, the same file).  `coils2d` /
+`coils2d_adjoint` are the operator alone, `coil_maps` smooth synthetic maps."""
 import contextlib
 import math
 from dataclasses import dataclass
@@ -193,8 +197,106 @@ def fourier2d_adjoint(k, out=None):
     return x
 
 
+COILS_MAX = 32      # the most receive coils of a multi-coil k-space problem (csrc/restore_fourier.hip)
+
+
+def check_coil_maps(maps, n, hw):
+    """The coil sensitivity maps of a multi-coil problem as their fp32 view: ``maps`` is complex64 (Q,H,W) -- shared by the batch --
+    or (N,Q,H,W) -- per sample -- or fp32 with a trailing 2; returns ``(fp32 view (..., Q, H, W, 2), Q, per_sample)``.  ValueError for
+    another dtype or rank, a plane other than ``hw``, a batch other than ``n``, Q outside 1..`COILS_MAX`.  No device work."""
+    real = as_kspace(maps, "coils")
+    h, w = (int(v) for v in tuple(hw)[-2:])
+    if real.dim() not in (4, 5) or tuple(real.shape[-3:-1]) != (h, w):
+        raise ValueError(f"coils of shape {tuple(maps.shape)}: expected complex (Q, {h}, {w}) or (N, Q, {h}, {w}), or fp32 with a trailing 2")
+    q, per_sample = int(real.shape[-4]), real.dim() == 5
+    if not 1 <= q <= COILS_MAX:
+        raise ValueError(f"coils: {q} coils; from 1 to {COILS_MAX}")
+    if per_sample and int(real.shape[0]) != int(n):
+        raise ValueError(f"coils of shape {tuple(maps.shape)}: per-sample maps for a batch of {n}")
+    return real, q, per_sample
+
+
+def coil_maps(hw, q, width=0.6, seed=0):
+    """Smooth synthetic coil sensitivities, complex64 (Q,H,W), made on the host.  Pixel (i, j) has the coordinates
+    y = (i + 0.5) / H - 0.5 and x = (j + 0.5) / W - 0.5; coil k sits at angle a_k = 2 pi (k + r) / Q on the circle of radius 0.6
+    around the field of view, centre (cy, cx) = 0.6 (sin a_k, cos a_k), with r one uniform draw in [0, 1) from a generator seeded
+    with ``seed``.  Its magnitude is the Gaussian exp(-((y - cy)^2 + (x - cx)^2) / (2 width^2)) and its phase the linear
+    2 pi (f_k y + g_k x) + p_k with f_k, g_k uniform in [-0.5, 0.5) and p_k uniform in [0, 2 pi), drawn in the order
+    r, f (Q values), g (Q values), p (Q values), all in fp64.  The maps are divided by sqrt(sum_q |S_q|^2) at every pixel, so that
+    sum_q |S_q|^2 = 1, and rounded to complex64."""
+    h, w = (int(v) for v in hw)
+    q = int(q)
+    if h < 1 or w < 1 or not 1 <= q <= COILS_MAX or not float(width) > 0.0:
+        raise ValueError(f"coil_maps: hw {tuple(hw)}, q {q!r} from 1 to {COILS_MAX}, width {width!r} > 0")
+    gen = torch.Generator().manual_seed(int(seed))
+    draw = lambda k: torch.rand(k, generator=gen, dtype=torch.float64)
+    r, f, g, p = draw(1), draw(q) - 0.5, draw(q) - 0.5, 2.0 * math.pi * draw(q)
+    a = 2.0 * math.pi * (torch.arange(q, dtype=torch.float64) + r) / q
+    cy, cx = (0.6 * torch.sin(a)).view(q, 1, 1), (0.6 * torch.cos(a)).view(q, 1, 1)
+    y = ((torch.arange(h, dtype=torch.float64) + 0.5) / h - 0.5).view(1, h, 1)
+    x = ((torch.arange(w, dtype=torch.float64) + 0.5) / w - 0.5).view(1, 1, w)
+    mag = torch.exp(-((y - cy) ** 2 + (x - cx) ** 2) / (2.0 * float(width) ** 2))
+    s = torch.polar(mag, 2.0 * math.pi * (f.view(q, 1, 1) * y + g.view(q, 1, 1) * x) + p.view(q, 1, 1))
+    s = s / (s.abs() ** 2).sum(dim=0, keepdim=True).sqrt()
+    return s.to(torch.complex64).contiguous()
+
+
+def coils_scratch(n, c, q, h, w, device):
+    """The scratch of glowhip_restore_objective_coils for a batch of ``n`` images (c, h, w) seen by ``q`` coils: a uint8 device
+    tensor of glowhip_restore_coils_scratch_bytes(n, c, q, h, w) bytes."""
+    need = int(_lib.lib().glowhip_restore_coils_scratch_bytes(int(n), int(c), int(q), int(h), int(w)))
+    if need == 0:
+        _lib.check(-1)
+    return torch.empty(need, dtype=torch.uint8, device=device)
+
+
+def _device_maps(maps, n, hw, device):
+    """(contiguous fp32 device view of the maps, Q, maps_stride in floats) for the C calls."""
+    real, q, per_sample = check_coil_maps(maps, n, hw)
+    real = _lib.require_device_tensor(real, "coils")
+    if real.device != device:
+        raise _lib.GlowHipError("coils must be on the device of the image")
+    real = real.contiguous()
+    return real, q, (q * int(hw[0]) * int(hw[1]) * 2 if per_sample else 0)
+
+
+def coils2d(x, maps, out=None):
+    """The multi-coil forward operator ``F (S x)``: real fp32 device ``x`` (N,C,H,W) to complex64 (N,C,Q,H,W) by glowhip_coils2d;
+    ``maps`` as `check_coil_maps` takes them, on the device of x.  ``out``: an fp32 buffer (N,C,Q,H,W,2) to write."""
+    x = _lib.require_device_tensor(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"coils2d: x of shape {tuple(x.shape)}: expected (N, C, H, W)")
+    n, c, h, w = (int(v) for v in x.shape)
+    check_fourier_shape((h, w), "coils2d")
+    s, q, stride = _device_maps(maps, n, (h, w), x.device)
+    real = torch.empty((n, c, q, h, w, 2), dtype=torch.float32, device=x.device) if out is None else out
+    if not (real.is_cuda and real.dtype == torch.float32 and real.is_contiguous() and tuple(real.shape) == (n, c, q, h, w, 2)):
+        raise _lib.GlowHipError("coils2d: out must be a contiguous fp32 device tensor (N, C, Q, H, W, 2)")
+    _lib.check(_lib.lib().glowhip_coils2d(_lib.ptr(x), _lib.ptr(s), stride, _lib.ptr(real), n, c, q, h, w, 0, _lib.stream_ptr(x.device)))
+    return torch.view_as_complex(real)
+
+
+def coils2d_adjoint(k, maps, out=None):
+    """``sum_q Re(conj(S_q) F^H k_q)``, real fp32 (N,C,H,W), of a device tensor ``k``, complex64 (N,C,Q,H,W) or fp32 with a trailing
+    2: the adjoint of `coils2d` as a map from real images (glowhip_coils2d with adjoint = 1) -- with normalised maps and a masked
+    measurement, the coil-combined zero-filled reconstruction.  ``out``: the fp32 buffer to write."""
+    real = _lib.require_device_tensor(as_kspace(k, "k"), "k")
+    if real.dim() != 6:
+        raise ValueError(f"coils2d_adjoint: k of shape {tuple(k.shape)}: expected complex (N, C, Q, H, W)")
+    n, c, q, h, w = (int(v) for v in real.shape[:5])
+    check_fourier_shape((h, w), "coils2d_adjoint")
+    s, qs, stride = _device_maps(maps, n, (h, w), real.device)
+    if qs != q:
+        raise ValueError(f"coils2d_adjoint: k holds {q} coils, the maps {qs}")
+    x = torch.empty((n, c, h, w), dtype=torch.float32, device=real.device) if out is None else out
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and tuple(x.shape) == (n, c, h, w)):
+        raise _lib.GlowHipError("coils2d_adjoint: out must be a contiguous fp32 device tensor (N, C, H, W)")
+    _lib.check(_lib.lib().glowhip_coils2d(_lib.ptr(real), _lib.ptr(s), stride, _lib.ptr(x), n, c, q, h, w, 1, _lib.stream_ptr(x.device)))
+    return x
+
+
 def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out=None, loss_out=None, psf=None, resid_out=None,
-                      operator=None, scratch=None, fourier=False):
+                      operator=None, scratch=None, fourier=False, coils=None):
     """``(loss (N,), grad_x)`` of the data term for images ``x`` (N,C,H,W): glowhip_restore_objective.  ``target`` / ``weight``
     (N,C,H/pool,W/pool; weight None = ones), ``inv_wsum`` (N,; None = 1 / elements of one measurement).  Contiguous fp32 device
     tensors, read where they are (a contiguous view at any offset is fine).  ``grad_out`` / ``loss_out``: buffers to write.
@@ -214,13 +316,23 @@ def restore_objective(x, target, weight=None, inv_wsum=None, pool=1, *, grad_out
     (glowhip_restore_objective_fourier); ``target`` / ``resid_out`` are then fp32 (N,C,H,W,2) -- `torch.view_as_real` of a
     complex64 (N,C,H,W) -- ``weight`` the real (N,C,H,W) k-space mask or weight, ``psf`` and ``operator`` must be None and ``pool``
     1.  ``scratch``: a uint8 device tensor of at least glowhip_restore_fourier_scratch_bytes(N, C, H, W) bytes (`fourier_scratch`),
-    allocated when None.  ``fourier=False`` is every call above, unchanged."""
+    allocated when None.  ``fourier=False`` is every call above, unchanged.
+
+    ``coils=maps`` (with ``fourier=True``; ValueError without): multi-coil k-space, glowhip_restore_objective_coils -- the image is
+    seen by Q coils through the complex sensitivity ``maps`` (Q,H,W), shared by the batch, or (N,Q,H,W), complex64 or fp32 with a
+    trailing 2 (`check_coil_maps`); ``target`` / ``resid_out`` are then fp32 (N,C,Q,H,W,2), ``weight`` stays (N,C,H,W), shared by
+    the coils, and ``inv_wsum=None`` is 1 / (C Q H W).  ``scratch``: at least glowhip_restore_coils_scratch_bytes(N, C, Q, H, W) bytes
+    (`coils_scratch`).  ``coils=None`` is every call above, unchanged."""
+    if coils is not None and not fourier:
+        raise ValueError("restore_objective: coils needs fourier=True (the maps multiply the image in front of the transform)")
     for name, t in (("x", x), ("target", target), ("weight", weight), ("inv_wsum", inv_wsum), ("grad_out", grad_out), ("loss_out", loss_out),
                     ("psf", psf), ("resid_out", resid_out), ("operator", operator)):
         if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == x.device):
             raise _lib.GlowHipError(f"restore_objective: {name} must be a contiguous fp32 tensor on the device of x")
     n, c, h, w = x.shape
     pool = int(pool)
+    if fourier and coils is not None:
+        return _restore_objective_coils(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch, coils)
     if fourier:
         return _restore_objective_fourier(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch)
     if operator is not None:
@@ -309,6 +421,35 @@ def _restore_objective_fourier(x, target, weight, inv_wsum, pool, grad_out, loss
     _lib.check(_lib.lib().glowhip_restore_objective_fourier(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), n, c, h, w,
                                                             _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss), _lib.ptr(scratch),
                                                             scratch.numel(), _lib.stream_ptr(x.device)))
+    return loss, grad
+
+
+def _restore_objective_coils(x, target, weight, inv_wsum, pool, grad_out, loss_out, psf, resid_out, operator, scratch, coils):
+    """`restore_objective` with ``fourier=True, coils=maps`` (its fp32 tensors are already known to be contiguous on the device of x)."""
+    n, c, h, w = x.shape
+    if psf is not None or operator is not None or pool != 1:
+        raise _lib.GlowHipError("restore_objective: fourier excludes psf and operator, and pool must be 1")
+    maps, q, stride = _device_maps(coils, n, (h, w), x.device)
+    for name, t, shape in (("target", target, (n, c, q, h, w, 2)), ("resid_out", resid_out, (n, c, q, h, w, 2)), ("weight", weight, (n, c, h, w))):
+        if t is not None and tuple(t.shape) != shape:
+            raise _lib.GlowHipError(f"restore_objective: {name} must have shape {shape} with {q} coils")
+    if inv_wsum is not None and inv_wsum.numel() != n:
+        raise _lib.GlowHipError(f"restore_objective: inv_wsum holds {inv_wsum.numel()} values for a batch of {n}")
+    grad = torch.empty_like(x) if grad_out is None else grad_out
+    loss = torch.empty(n, dtype=torch.float32, device=x.device) if loss_out is None else loss_out
+    if tuple(grad.shape) != tuple(x.shape) or loss.numel() != n:
+        raise _lib.GlowHipError("restore_objective: grad_out must have the shape of x, loss_out one value per sample")
+    resid = torch.empty_like(target) if resid_out is None else resid_out
+    if scratch is None:
+        if not (2 <= h <= FOURIER_MAX and 2 <= w <= FOURIER_MAX and h & (h - 1) == 0 and w & (w - 1) == 0):      # (let the C call say why)
+            scratch = torch.empty(16, dtype=torch.uint8, device=x.device)
+        else:
+            scratch = coils_scratch(n, c, q, h, w, x.device)
+    elif not (scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous() and scratch.device == x.device):
+        raise _lib.GlowHipError("restore_objective: scratch must be a contiguous uint8 tensor on the device of x")
+    _lib.check(_lib.lib().glowhip_restore_objective_coils(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), _lib.ptr(inv_wsum), _lib.ptr(maps),
+                                                          stride, n, c, q, h, w, _lib.ptr(resid), _lib.ptr(grad), _lib.ptr(loss),
+                                                          _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(x.device)))
     return loss, grad
 
 
@@ -447,12 +588,30 @@ class LatentLoop:
 
     ``fourier=True``: the measurement is the unitary 2-D DFT of the decode, complex64 (N,C,H,W) or fp32 with a trailing 2 (kept as
     the latter); ``weight`` is the real k-space mask or weight, broadcast to (N,C,H,W); sides are powers of two up to 256.  It
-    excludes ``psf``, ``operator`` and ``pool != 1`` (ValueError).  ``resid`` and ``op_scratch`` are static buffers as above."""
+    excludes ``psf``, ``operator`` and ``pool != 1`` (ValueError).  ``resid`` and ``op_scratch`` are static buffers as above.
 
-    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None, operator=None, fourier=False):
+    ``coils=maps`` (with ``fourier=True``; ValueError without): multi-coil k-space -- the measurement is complex64 (N,C,Q,H,W) or
+    fp32 with a trailing 2, the image shape (C,H,W) is taken from it, ``maps`` are the Q complex sensitivity maps (Q,H,W) or
+    (N,Q,H,W) (`check_coil_maps`) and ``weight`` stays (N,C,H,W), shared by the coils.  The maps are CLONED into a static buffer of
+    the loop (they are small, unlike the dense operator); ``resid`` and ``op_scratch`` are sized for the coil call."""
+
+    def __init__(self, glow, measurement, weight, pool, init, steps, graph, psf=None, operator=None, fourier=False, coils=None):
         self.glow, self.pool, self.steps, self.want_graph = glow, int(pool), int(steps), bool(graph)
         self.fourier = bool(fourier)
-        if self.fourier:
+        self.coils, self.n_coils = None, 0
+        if coils is not None and not self.fourier:
+            raise ValueError("coils needs fourier=True (the maps multiply the image in front of the transform)")
+        if coils is not None:
+            if psf is not None or operator is not None or self.pool != 1:
+                raise ValueError("coils excludes psf, operator and estimate_psf, and pool must be 1")
+            measurement = as_kspace(measurement)
+            if measurement.dim() != 6:
+                raise ValueError(f"measurement of shape {tuple(measurement.shape)}: expected complex (N, C, Q, H, W) or fp32 (N, C, Q, H, W, 2) with coils")
+            check_fourier_shape(measurement.shape[3:5], "measurement")
+            maps, self.n_coils, _ = check_coil_maps(coils, measurement.shape[0], measurement.shape[3:5])
+            if self.n_coils != int(measurement.shape[2]):
+                raise ValueError(f"measurement of shape {tuple(measurement.shape)} holds {int(measurement.shape[2])} coils, the maps {self.n_coils}")
+        elif self.fourier:
             if psf is not None or operator is not None or self.pool != 1:
                 raise ValueError("fourier excludes psf, operator and estimate_psf, and pool must be 1")
             measurement = as_kspace(measurement)
@@ -473,6 +632,8 @@ class LatentLoop:
             if meas.dim() != 2 or meas.shape[1] != m:
                 raise ValueError(f"measurement of shape {tuple(meas.shape)}: expected (N, {m}) with this operator")
             n, image_chw = meas.shape[0], tuple(op.shape[1:])
+        elif coils is not None:
+            n, image_chw = meas.shape[0], (int(meas.shape[1]),) + tuple(meas.shape[3:5])
         elif self.fourier:
             n, image_chw = meas.shape[0], tuple(meas.shape[1:4])
         else:
@@ -484,6 +645,8 @@ class LatentLoop:
         self.n = n
         self.target = meas.clone()
         wshape = meas.shape[:4] if self.fourier else meas.shape      # (the k-space weight is real: one value per coefficient)
+        if coils is not None:
+            wshape = (n,) + image_chw                                # (and shared by the coils)
         self.weight = None if weight is None else _lib.require_device_tensor(weight, "weight").expand(wshape).contiguous()
         self._start = [t.float().contiguous().clone() for t in init.to(dev).detach().tensors()]
         self.image = torch.empty((n,) + plan.in_chw, dtype=torch.float32, device=dev)
@@ -504,7 +667,9 @@ class LatentLoop:
         # Fourier-domain measurements: the residual (the forward pass's intermediate too) and the call's scratch, static as above
         if self.fourier:
             self.resid = torch.empty_like(self.target)
-            self.op_scratch = fourier_scratch(n, *image_chw, dev)
+            self.op_scratch = fourier_scratch(n, *image_chw, dev) if coils is None else coils_scratch(n, image_chw[0], self.n_coils, *image_chw[1:], dev)
+        if coils is not None:      # the maps: the loop's own fp32 copy (..., Q, H, W, 2)
+            self.coils = _lib.require_device_tensor(maps, "coils").to(dev).clone()
         self._capture = None
         self.graph_error = None
         self._iterations = 0         # run since construction (a reset does not take the lazy allocations back)
@@ -517,7 +682,8 @@ class LatentLoop:
         plan = self.plan
         plan.decode(leaves[0], leaves[1:], out=image)
         restore_objective(image, self.target, self.weight, self.inv_wsum, self.pool, grad_out=self.grad_x, loss_out=loss,
-                          psf=self.psf, resid_out=self.resid, operator=self.operator, scratch=self.op_scratch, fourier=self.fourier)
+                          psf=self.psf, resid_out=self.resid, operator=self.operator, scratch=self.op_scratch, fourier=self.fourier,
+                          coils=self.coils)
         plan.decode_vjp(image, self.grad_x, out=(grads[0], grads[1:]))
 
     def _capturing(self):            # the context of a recording (the fit: its optimiser's)
@@ -533,6 +699,8 @@ class LatentLoop:
         once in the constructor and never rebound, so a recorded launch always reaches them; ``operator`` is the caller's tensor,
         held here for the loop's life, which the caller must leave alone (`LatentLoop`)."""
         sig = self.plan.capture_signature(versions=True, family=True, buffers=("packed", "_ws", "_vjp_tape", "_vjp_ws"))
+        if self.coils is not None:
+            return {**sig, "fourier": True, "coils": self.n_coils}
         return {**sig, "fourier": True} if self.fourier else sig      # (which objective the recording holds)
 
     @torch.no_grad()
@@ -668,10 +836,11 @@ class LatentFit(LatentLoop):
     ambiguity between PSF and image; the translation ambiguity stays, and the centre of the start and the valid-band weights select
     the solution.
 
-    ``fourier=True``: the measurement is the decode's unitary 2-D DFT and ``weight`` the k-space mask (`LatentLoop`)."""
+    ``fourier=True``: the measurement is the decode's unitary 2-D DFT and ``weight`` the k-space mask (`LatentLoop`).
+    ``coils=maps``: multi-coil k-space, the measurement complex (N,C,Q,H,W) (`LatentLoop`)."""
 
     def __init__(self, glow, measurement, weight=None, pool=1, init=None, steps=100, lr=0.05, prior_weight=0.0, max_grad_norm=0.0,
-                 graph=True, psf=None, operator=None, estimate_psf=None, psf_lr=0.2, fourier=False):
+                 graph=True, psf=None, operator=None, estimate_psf=None, psf_lr=0.2, fourier=False, coils=None):
         check_prior_weight(glow, prior_weight)
         if init is None or steps < 1:
             raise ValueError("LatentFit needs start latents (init) and steps >= 1")
@@ -681,11 +850,13 @@ class LatentFit(LatentLoop):
         if estimate_psf is not None:
             start = blind_start(psf, estimate_psf, len(measurement), operator)
             psf = start.to(measurement.device)
-        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator, fourier=fourier)
+        super().__init__(glow, measurement, weight, pool, init, steps, graph, psf=psf, operator=operator, fourier=fourier, coils=coils)
         self.lr, self.max_grad_norm = float(lr), float(max_grad_norm or 0.0)
         n, dev = self.n, self.device
         # per sample: every image of the batch is its own problem (None: the kernel's 1 / elements, the all-ones weight's)
         self.inv_wsum = None if self.weight is None else 1.0 / self.weight.sum(dim=tuple(range(1, self.weight.dim()))).clamp(min=1.0)
+        if self.coils is not None and self.weight is not None:      # every coil's coefficient is a measurement: Q sum w of them
+            self.inv_wsum = 1.0 / (float(self.n_coils) * self.weight.sum(dim=(1, 2, 3))).clamp(min=1.0)
         self.loss = torch.zeros(n, dtype=torch.float32, device=dev)
         self.norm = torch.zeros(1, dtype=torch.float32, device=dev)
         self.loss_hist = torch.zeros((self.steps, n), dtype=torch.float32, device=dev)
